@@ -6,15 +6,18 @@ Workload (``config.workload``), default = the north-star cell: fcc silicon 5 x 5
 ``compute_fft_size`` (192^3), fp64 -- BASELINE configs[4]'s "~1000 electrons" cell, which fits one GPU
 (``--supercell 4`` = configs[1]).
 
-What is timed: ONE WHOLE ``self_consistent_field`` in the sense of the reference's own ``scf_full`` benchmark
-(benchmark/cases/common.jl:70-71): from ``guess_density`` (Gaussian superposition) to ``tol = 1e-6`` in the
+What is timed: ``self_consistent_field`` in the sense of the reference's own ``scf_full`` benchmark
+(benchmark/cases/common.jl:70-71): from ``guess_density`` (Gaussian superposition) towards ``tol = 1e-6`` in the
 density change, ScfAndersonDensitySolver, damping 0.8, AdaptiveDiagtol / AdaptiveBands defaults, random start
 orbitals.  One "step" = one SCF iteration (build V = V_loc + V_H + V_xc, LOBPCG with H psi on the device,
 ``compute_density`` + all-reduce, energies, Anderson mixing).  ``--warmup W`` runs W SCF steps on a THROW-AWAY
 stepper first (allocator, plan caches, lazy initialisation); the timed run then starts again from the guess
-density.  ``--steps K`` caps the timed run: it stops at convergence or after K steps, and ``steps`` in the
-JSON line is the number of steps actually run.  ``value`` = steps run / wall time, ``hpsi_applies_per_s`` =
-n_matvec / wall time.
+density.  ``--steps K`` times exactly K steps: convergence does not end the run, the steps after it carry on
+iterating (Anderson mixing down to the parity tolerance 1e-8, then the fixed point itself).  Without ``--steps``
+the timed run is one whole SCF that stops at convergence (at most 100 steps).  ``steps`` in the JSON line is the
+number of steps run, ``value`` = steps run / wall time, ``ms_per_step`` = wall time / steps run,
+``hpsi_applies_per_s`` = n_matvec / wall time.  ``--dump-outputs DIR`` writes what the last timed step computed
+(``step_outputs``) as DIR/<name>.npy.
 
 N > 1 (``--gpus N``, one process per GPU, launched by torch.distributed.run):
   --mode gamma   (default) the SAME Gamma-only workload, plane waves of the single k-block sharded over the
@@ -25,8 +28,11 @@ N > 1 (``--gpus N``, one process per GPU, launched by torch.distributed.run):
                  strong scaling (9 k-points per GPU at N = 8).
   --mode weak    one k-point of the Si supercell per GPU (weak scaling; the round-1 behaviour).
 
-Prints ONE JSON line on rank 0 with ``roofline`` (dominant kernel family, HIP-event timed inside the library
-on its own stream) and ``cpu_baseline`` (the CPU oracle timed on this host's cores).
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set-up, warm-up, the timed
+steps, the dump, the line.  ``--full`` adds everything else to the same line: ``roofline`` (dominant kernel family,
+HIP-event timed inside the library on its own stream, per-phase timers), the parity legs, the random-start and
+complex-orbital legs, the golden-fixture leg, the ``amdahl`` model, ``cpu_baseline`` (the CPU oracle timed on this
+host's cores) and, for N > 1, the start-up self-checks of the collectives.
 """
 from __future__ import annotations
 
@@ -70,10 +76,74 @@ def one_rank_energy(workload_key):
         return None
 
 
+# ------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BUDGET_BYTES = 64_000_000   # everything --dump-outputs writes, .npy headers included
+DM_SAMPLE_G = 128                # plane waves per k-block in the density-matrix sample
+
+
+def seeded_indices(n, k, seed):
+    """k distinct indices of range(n), sorted, drawn from a fixed seed (all of them when k >= n)."""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def step_outputs(info, budget=DUMP_BUDGET_BYTES):
+    """What a caller of self_consistent_field receives from the last step, as float64 host arrays {name: array}.
+    Eigenvalues and occupations are those of the converged bands (n_bands_converge of every k-block on this rank).
+    The orbitals enter through P[k, s, t] = sum_n f_n psi_n(G_s) conj(psi_n(G_t)) on a seeded sample of plane waves
+    (last axis: real, imaginary part): unlike the orbitals themselves it does not depend on the basis chosen inside a
+    degenerate set of bands.  The density is written whole ("rho") when it fits in what is left of ``budget``, else as
+    a seeded sample of its entries ("rho_sample")."""
+    import torch
+    n_conv = int(info["n_bands_converge"])
+    E = info["energies"]
+    out = {"eigenvalues": np.array([np.asarray(l_, dtype=np.float64)[:n_conv] for l_ in info["eigenvalues"]]),
+           "occupation": np.array([np.asarray(f_, dtype=np.float64)[:n_conv] for f_ in info["occupation"]]),
+           "energies": np.array([E.total] + [float(E[k_]) for k_ in E], dtype=np.float64)}
+    if info.get("eF") is not None:
+        out["fermi_level"] = np.asarray(info["eF"], dtype=np.float64).reshape(-1)
+    n_s = min(DM_SAMPLE_G, int(np.sqrt(budget / 4 / 16 / len(info["psi"]))),     # (at most a quarter of the budget)
+              min(int(X.shape[1]) for X in info["psi"]))
+    dm = []
+    for ik, (X, f_) in enumerate(zip(info["psi"], info["occupation"])):
+        idx = torch.as_tensor(seeded_indices(int(X.shape[1]), n_s, seed=ik), device=X.device)
+        f = np.asarray(f_, dtype=np.float64)[:X.shape[0]]
+        A = X[:len(f), idx]                                             # (bands, sampled G)
+        f = torch.as_tensor(f, device=X.device)
+        dm.append(torch.view_as_real((A.T * f) @ A.conj()).cpu().numpy())
+    out["density_matrix_sample"] = np.array(dm, dtype=np.float64)
+    rho = info["rho"].detach().cpu().numpy().astype(np.float64, copy=False)
+    left = budget - sum(a_.nbytes for a_ in out.values()) - 128 * (len(out) + 1)
+    if rho.nbytes <= left:
+        out["rho"] = rho
+    else:
+        out["rho_sample"] = rho.reshape(-1)[seeded_indices(rho.size, max(0, left) // 8, seed=0)]
+    return out
+
+
+def dump_outputs(outdir, arrays):
+    os.makedirs(outdir, exist_ok=True)
+    for name, a_ in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a_)
+    total = sum(os.path.getsize(os.path.join(outdir, name + ".npy")) for name in arrays)
+    print(f"bench.py: wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {outdir}", file=sys.stderr, flush=True)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100, help="cap on the timed SCF steps (stops earlier at convergence)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed SCF steps: exactly this many (steps after convergence carry on iterating the fixed point); "
+                         "omitted: one whole self_consistent_field that stops at convergence, at most 100 steps")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-family kernel timings and roofline, phase timers, "
+                         "parity legs, random-start and complex legs, golden fixture, Amdahl model, CPU baseline, N > 1 "
+                         "self-checks (the --no-* options switch single legs of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all): "
+                         "density, converged eigenvalues and occupations, energies, Fermi level, and a seeded sample of "
+                         "the occupied orbitals' density matrix")
     ap.add_argument("--warmup", type=int, default=3,
                     help="SCF steps on a throw-away stepper before the timed run (3: the Anderson / mixing paths of the second and "
                          "third step are warm as well -- their first-use cost is 50 ms, visible on the 0.4 s k-point SCFs)")
@@ -107,7 +177,13 @@ def parse():
                          "(what the N > 1 runs of the same workload are compared with)")
     ap.add_argument("--no-amdahl-probe", action="store_true",
                     help="--mode kpoints, N = 1: skip the timed SCF steps on one rank's share of the k-points (Amdahl model)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    for flag, on in (("--prof-all", args.prof_all), ("--write-reference-energy", args.write_reference_energy)):
+        if on and not args.full:
+            ap.error(f"{flag} needs --full")
+    return args
 
 
 def prof_get(lib, basis, fam):
@@ -470,21 +546,22 @@ def device_late_step(dftk, basis, info, tol, diagtol):
 
 # ------------------------------------------------------------------------------------------ the timed SCF
 def run_scf(dftk, lib, basis, args, barrier, world, dist, torch, coarse_start=True):
-    """--warmup steps on a throw-away stepper, then ONE whole self_consistent_field capped at --steps, HIP-event
-    family timings switched on for the timed part.  Returns the numbers of the JSON line."""
+    """--warmup steps on a throw-away stepper, then the timed self_consistent_field: exactly --steps steps, or (no
+    --steps) one whole SCF to convergence.  With --full the HIP-event family timings and the phase timers are switched
+    on for the timed part.  Returns the numbers of the JSON line."""
     from dftk_jl_amd._lib import check
     if args.prof_all:
         check(lib.dftk_mi_prof_enable(basis.handle, 1))
     if args.warmup > 0:
         warm = dftk.ScfStepper(basis, tol=args.tol, coarse_start=coarse_start)
         for _ in range(args.warmup):
-            if warm.step()["converged"]:
-                break
+            warm.step()
         del warm
     barrier()
-    if not args.prof_all:
+    if args.full and not args.prof_all:
         check(lib.dftk_mi_prof_enable(basis.handle, 3))        # 3: families + the per-shape zgemm table (slab replay)
     iters, diagtols, step_s, nmv_steps = [], [], [], []
+    steps_to_tol = None
     host_timers = {}
     counts0 = library_counts(lib)
     t0 = time.time()
@@ -493,10 +570,10 @@ def run_scf(dftk, lib, basis, args, barrier, world, dist, torch, coarse_start=Tr
     # self_consistent_field would (the only difference: the last timed step also mixes, ~4 ms inside the timed region)
     ptol = min(PARITY_SCF_TOL, args.tol)
     stepper = dftk.ScfStepper(basis, tol=args.tol, is_converged=lambda info_: info_["history_drho"][-1] < ptol,
-                              phase_timers=(args.mode != "kpoints"), coarse_start=coarse_start)
+                              phase_timers=(args.full and args.mode != "kpoints"), coarse_start=coarse_start)
     info = None
     nmv_coarse = 0
-    for _ in range(max(args.steps, 1)):
+    for _ in range(args.steps or 100):
         ts = time.time()
         info = stepper.step()
         step_s.append(time.time() - ts)
@@ -510,18 +587,26 @@ def run_scf(dftk, lib, basis, args, barrier, world, dist, torch, coarse_start=Tr
             if int(os.environ.get("RANK", "0")) == 0:
                 print(f"[step {len(step_s)}] {step_s[-1] * 1e3:.1f} ms: "
                       + ", ".join(f"{k_} {v_ * 1e3:.1f}" for k_, v_ in info["timers"].items()), file=sys.stderr)
-        if info["history_drho"][-1] < args.tol:
-            break
+        if steps_to_tol is None and info["history_drho"][-1] < args.tol:
+            steps_to_tol = len(step_s)
+            if args.steps is None:
+                break
     info = dict(stepper.finalize())                          # energies + Hamiltonian of the final state, as the reference
     info["converged"] = bool(info["history_drho"][-1] < args.tol)
     barrier()
     elapsed = time.time() - t0
     counts1 = library_counts(lib)
-    check(lib.dftk_mi_prof_enable(basis.handle, 0))
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    run = dict(info=info, elapsed=elapsed, iters=iters, diagtols=diagtols, step_s=step_s, nmv_steps=nmv_steps,
+               steps_to_tol=steps_to_tol or len(step_s), host_timers=host_timers, stepper=stepper,
+               n_matvec_coarse=nmv_coarse, library_launches=counts1[0] - counts0[0],
+               library_host_syncs=counts1[1] - counts0[1])
+    if not args.full:
+        return run
+    check(lib.dftk_mi_prof_enable(basis.handle, 0))
     fam = {f: prof_get(lib, basis, f) for f in list(FAMILIES) + [10, 12, 14, 17, 18]}
     shapes = []
     try:
@@ -534,9 +619,8 @@ def run_scf(dftk, lib, basis, args, barrier, world, dist, torch, coarse_start=Tr
                        flags=int(rows[6 * i + 4]), calls=int(rows[6 * i + 5]), ms=float(sms[i])) for i in range(min(cnt.value, cap))]
     except Exception:
         shapes = []
-    return dict(zgemm_shapes=shapes, info=info, elapsed=elapsed, iters=iters, diagtols=diagtols, step_s=step_s, nmv_steps=nmv_steps,
-                host_timers=host_timers, fam=fam, stepper=stepper, n_matvec_coarse=nmv_coarse,
-                library_launches=counts1[0] - counts0[0], library_host_syncs=counts1[1] - counts0[1])
+    run.update(zgemm_shapes=shapes, fam=fam)
+    return run
 
 
 def continue_to_parity(stepper, max_extra=80):
@@ -874,7 +958,8 @@ def amdahl_kpoints(dftk, basis, model, ecut, device, run, steps, args):
     first ceil(n_k / N) irreducible k-points (weights renormalised: a legitimate, smaller k-mesh problem that does all
     the replicated cube work of a step: PBE potential, LDOS pass over its k-points, Fermi level, mixing, energies) --
     so that the latency-bound lock-step batching is priced at the local k-point count, not divided by N."""
-    wall = 1e3 * float(np.median(run["step_s"][2:] or run["step_s"]))
+    to_tol = run["step_s"][:run["steps_to_tol"]]           # (steps past convergence: not a typical step)
+    wall = 1e3 * float(np.median(to_tol[2:] or to_tol))
     n_k = len(basis.kcoords_global)
     n_cube = basis.N
     saved = os.environ.get("DFTK_MI_KBATCH")
@@ -1018,19 +1103,71 @@ def main():
     if int(comm_info.get("n_ranks", -1)) != world:
         raise SystemExit(f"rank {rank}: the library's communicator reports {comm_info} but WORLD_SIZE is {world}")
     self_check = None
-    if world > 1 and args.mode == "gamma":
+    if args.full and world > 1 and args.mode == "gamma":
         self_check = sharded_self_check(dftk, basis, world)
         bad = [k_ for k_, v_ in self_check.items() if not (v_ < 1e-10)]
         if bad:
             raise SystemExit(f"sharded self-check failed on rank {rank}: {self_check}")
 
-    if world > 1 and args.mode in ("kpoints", "weak"):
+    if args.full and world > 1 and args.mode in ("kpoints", "weak"):
         self_check = kpoints_self_check(basis, comm, world)
         if not (self_check["allreduce_rank_stamped_cube_max_abs_error"] == 0.0):
             raise SystemExit(f"k-point self-check failed on rank {rank}: {self_check}")
 
     run = run_scf(dftk, lib, basis, args, barrier, world, dist, torch)
-    info, elapsed, fam = run["info"], run["elapsed"], run["fam"]
+    info, elapsed = run["info"], run["elapsed"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(info))
+    steps_run = info["n_iter"]
+    n_matvec = info["n_matvec"]                  # already summed over the k-point ranks
+    kblocks = n_gpus if (args.mode == "weak" and n_gpus > 1) else 1
+    value = kblocks * steps_run / elapsed
+    if args.steps is None:
+        timed = f"whole self_consistent_field (scf_full): guess_density -> tol={args.tol:g}, at most 100 steps"
+    else:
+        timed = (f"{args.steps} steps of self_consistent_field from guess_density (tol={args.tol:g} does not end them: "
+                 f"converged steps carry on iterating the fixed point)")
+    if rank == 0:
+        gamma_real = bool(getattr(basis.kpoints[0], "gamma_real", False))
+        kp0 = basis.kpoints[0]
+        out = {
+            "metric": "SCF iterations/sec (Hψ applies/sec) at fixed Ecut·atoms",
+            "value": value, "unit": "SCF iterations/s", "n_gpus": n_gpus, "steps": steps_run,
+            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / steps_run, "higher_is_better": True,
+            "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "hpsi_applies_per_s": n_matvec / elapsed,
+            "config": {"workload": workload, "timed": timed,
+                       "converged": bool(info["converged"]), "scf_wall_s": round(elapsed, 3),
+                       "scf_wall_s_to_convergence": (round(elapsed, 3) if info["converged"] and run["steps_to_tol"] == steps_run
+                                                     else None),
+                       "steps_to_convergence": run["steps_to_tol"] if info["converged"] else None,
+                       "n_G": kp0.n_G, "n_bands": int(info["psi"][0].shape[0]),
+                       "n_proj": int(basis.terms.D.shape[0]) if basis.terms.D is not None else 0,
+                       "parallelism": parallelism, "rccl": comm_info,
+                       "setup_s": round(t_setup, 2),
+                       "orbitals": ("real-symmetric at Gamma (psi(-G) = conj psi(G)): half-sphere real GEMMs, two bands "
+                                    "per FFT pass; same eigenvalues / density / energies as the reference's complex "
+                                    "iteration, which --full times in the same run: config.complex_iteration")
+                       if gamma_real else "general complex",
+                       "n_matvec": int(n_matvec), "lobpcg_iters_per_step": run["iters"],
+                       "n_matvec_per_step": run["nmv_steps"],
+                       "diagtol_per_step": [float(f"{d:.3g}") for d in run["diagtols"]],
+                       "step_wall_s": [round(s_, 3) for s_ in run["step_s"]],
+                       "lib_hash": library_source_hash(),
+                       "E_total": info["energies"].total, "drho": info["history_drho"][-1],
+                       "library_launches_per_step": round(run["library_launches"] / steps_run, 1),
+                       "library_host_syncs_per_step": round(run["library_host_syncs"] / steps_run, 1)},
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything beyond the headline figure
+    fam = run["fam"]
     n_atoms = len(model.positions)
     parity, late_info = None, info
     if not args.no_parity:
@@ -1041,49 +1178,18 @@ def main():
         parity = {"tolerance_Ha_per_atom": PARITY_TOL_HA_PER_ATOM, "scf_tol": min(PARITY_SCF_TOL, args.tol), "n_atoms": n_atoms,
                   "timed_leg": {k_: par[k_] for k_ in ("converged", "E_total", "extra_steps", "steps_total", "drho", "wall_s")}}
     amdahl = None
-    steps_run = info["n_iter"]
-    n_matvec = info["n_matvec"]                  # already summed over the k-point ranks
-    kblocks = n_gpus if (args.mode == "weak" and n_gpus > 1) else 1
-    value = kblocks * steps_run / elapsed
 
     if rank == 0:
-        gamma_real = bool(getattr(basis.kpoints[0], "gamma_real", False))
         roof = roofline_of(fam, n_gpus, workload)
         if args.mode == "kpoints":
             roof = latency_roofline(run, steps_run, roof)
         booked = sum(fam[f][0] for f in (0, 11, 1, 2, 3, 4, 5, 6, 7, 8, 13))
-        kp0 = basis.kpoints[0]
-        out = {
-            "metric": "SCF iterations/sec (Hψ applies/sec) at fixed Ecut·atoms",
-            "value": value, "unit": "SCF iterations/s", "n_gpus": n_gpus, "steps": steps_run,
-            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / steps_run, "higher_is_better": True,
-            "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "hpsi_applies_per_s": n_matvec / elapsed,
-            "config": {"workload": workload, "timed": "whole self_consistent_field (scf_full): guess_density -> "
-                                                      f"tol={args.tol:g}, capped at --steps={args.steps}",
-                       "converged": bool(info["converged"]), "scf_wall_s": round(elapsed, 3),
-                       "scf_wall_s_to_convergence": round(elapsed, 3) if info["converged"] else None,
-                       "n_G": kp0.n_G, "n_bands": int(info["psi"][0].shape[0]),
-                       "n_proj": int(basis.terms.D.shape[0]) if basis.terms.D is not None else 0,
-                       "parallelism": parallelism, "rccl": comm_info, "sharded_self_check": self_check,
-                       "setup_s": round(t_setup, 2),
-                       "orbitals": ("real-symmetric at Gamma (psi(-G) = conj psi(G)): half-sphere real GEMMs, two bands "
-                                    "per FFT pass; same eigenvalues / density / energies as the reference's complex "
-                                    "iteration, which is timed in the same run: config.complex_iteration")
-                       if gamma_real else "general complex",
-                       "n_matvec": int(n_matvec), "lobpcg_iters_per_step": run["iters"],
-                       "n_matvec_per_step": run["nmv_steps"],
-                       "diagtol_per_step": [float(f"{d:.3g}") for d in run["diagtols"]],
-                       "step_wall_s": [round(s_, 3) for s_ in run["step_s"]],
-                       "host_timers_ms_per_step": {k_: round(1e3 * v_ / steps_run, 2)
-                                                   for k_, v_ in run["host_timers"].items()},
-                       "host_timers_synced": args.mode != "kpoints",   # (k-point steps: no per-phase device synchronisation)
-                       "library_booked_ms": round(booked, 1), "lib_hash": library_source_hash(),
-                       "E_total": info["energies"].total, "drho": info["history_drho"][-1],
-                       "library_launches_per_step": round(run["library_launches"] / steps_run, 1),
-                       "library_host_syncs_per_step": round(run["library_host_syncs"] / steps_run, 1)},
-            "roofline": roof,
-        }
+        out["config"].update({"sharded_self_check": self_check,
+                              "host_timers_ms_per_step": {k_: round(1e3 * v_ / steps_run, 2)
+                                                          for k_, v_ in run["host_timers"].items()},
+                              "host_timers_synced": args.mode != "kpoints",   # (k-point steps: no per-phase device synchronisation)
+                              "library_booked_ms": round(booked, 1)})
+        out["roofline"] = roof
         # flat scalars (the driver's BENCH record keeps scalars of `config`, not nested objects)
         out["config"].update(step_roofline(fam, elapsed, steps_run, run["step_s"], run["iters"]))
         out["config"]["roofline_frac_zgemm"] = round(roof["frac"], 4) if roof.get("bound") == "mfma" else None
@@ -1204,7 +1310,7 @@ def main():
             elif n_gpus > 1:
                 parity["one_rank_reference"] = "MISSING"
                 print(f"bench.py: WARNING: no one-rank reference energy for workload key {wkey!r} in {ONE_RANK_ENERGIES}: the "
-                      f"N = {n_gpus} run is NOT compared with the one-rank run (write it with --gpus 1 --write-reference-energy)",
+                      f"N = {n_gpus} run is NOT compared with the one-rank run (write it with --gpus 1 --full --write-reference-energy)",
                       file=sys.stderr, flush=True)
             elif n_gpus == 1 and args.write_reference_energy and parity["timed_leg"]["converged"]:
                 try:
@@ -1255,7 +1361,8 @@ def main():
                     # a REAL timed step when the sampled model says it fits the budget
                     # tolerance of a TYPICAL late step: the median diagtol of the timed run (from the converged
                     # orbitals LOBPCG then needs the one iteration that most steps of this SCF take)
-                    tol_mid = float(np.median(run["diagtols"][2:] or run["diagtols"]))
+                    tols = run["diagtols"][:run["steps_to_tol"]]        # (steps past convergence: not a typical step)
+                    tol_mid = float(np.median(tols[2:] or tols))
                     t_dev, dinfo = device_late_step(dftk, basis, late_info, args.tol, tol_mid)
                     late_model = (2 * late_info["psi"][0].shape[0] / model_leg["hpsi_applies_per_s"]
                                   + model_leg["model_terms"]["density_s_per_band"] * (basis.model.n_electrons // 2)

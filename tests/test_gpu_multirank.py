@@ -118,8 +118,8 @@ def _run_bench(extra, port_base):
 
 def test_bench_two_ranks_one_gpu_weak_kpoints():
     """bench.py --mode weak, N = 2 (torch.distributed.run env contract, one k-point per rank, max-over-ranks
-    timing, whole-job value) on a tiny cell; both ranks on cuda:0 over gloo; --steps caps the SCF."""
-    out = _run_bench(["--mode", "weak", "--steps", "2", "--warmup", "1", "--supercell", "1", "--ecut", "10"], 33000)
+    timing, whole-job value) on a tiny cell; both ranks on cuda:0 over gloo; --steps sets the timed SCF steps."""
+    out = _run_bench(["--full", "--mode", "weak", "--steps", "2", "--warmup", "1", "--supercell", "1", "--ecut", "10"], 33000)
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["warmup"] == 1 and out["scaling"] == "weak"
     assert out["config"]["parallelism"] == "kpt2" and not out["config"]["converged"]
     assert abs(out["value"] - 2 * 2 / (out["ms_per_step"] * 2 / 1e3)) < 1e-6 * out["value"]   # 2 k-blocks x steps / time
@@ -130,7 +130,7 @@ def test_bench_two_ranks_one_gpu_kpoints_strong_equals_single_rank():
     """bench.py --mode kpoints (BASELINE configs[2] class: Al PBE, symmetry-reduced Monkhorst-Pack mesh, LDOS mixing,
     k-points split over the ranks, one density all-reduce per step + one for the LDOS): the 2-rank run does the SAME
     fixed workload as the 1-rank run (strong scaling) and converges to the same energy."""
-    args = ["--mode", "kpoints", "--kgrid", "4", "--ecut", "12", "--steps", "40", "--warmup", "0", "--tol", "1e-8"]
+    args = ["--full", "--mode", "kpoints", "--kgrid", "4", "--ecut", "12", "--warmup", "0", "--tol", "1e-8"]  # (to convergence)
     out = _run_bench(args, 39000)
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["config"]["converged"]
     assert out["config"]["parallelism"] == "kpt2" and "8 k-points (4 on rank 0" in out["config"]["workload"]
@@ -147,7 +147,7 @@ def test_bench_two_ranks_one_gpu_kpoints_strong_equals_single_rank():
 def test_bench_two_ranks_one_gpu_gamma_sharded_equals_single_rank():
     """bench.py's DEFAULT N > 1 path: the Gamma-only cell with its plane waves sharded over the ranks (strong
     scaling, whole SCF to convergence); same converged energy and SCF length class as the one-rank run."""
-    args = ["--steps", "40", "--warmup", "0", "--supercell", "1", "--ecut", "12", "--tol", "1e-8"]
+    args = ["--full", "--warmup", "0", "--supercell", "1", "--ecut", "12", "--tol", "1e-8"]     # (no --steps: to convergence)
     out = _run_bench(args, 35000)
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["config"]["converged"]
     assert out["config"]["parallelism"].startswith("pw2") and out["steps"] < 40

@@ -804,13 +804,56 @@ def test_bench_cli_contract_without_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     h = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True)
     assert h.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--mode", "--supercell", "--no-cpu-baseline"):
+    for flag in ("--gpus", "--steps", "--warmup", "--mode", "--supercell", "--no-cpu-baseline", "--full", "--dump-outputs"):
         assert flag in h.stdout
+    # options that only mean something next to --full are refused without it (before any GPU work)
+    for extra in (["--prof-all"], ["--write-reference-energy"], ["--steps", "0"]):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + extra, capture_output=True, text=True)
+        assert r.returncode == 2 and "error" in r.stderr, extra
     import torch
     if not torch.cuda.is_available():
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
                            capture_output=True, text=True)
         assert r.returncode != 0 and "needs a GPU" in (r.stdout + r.stderr)
+
+
+def test_bench_step_outputs_are_float64_within_budget_and_basis_free(tmp_path):
+    """bench.py --dump-outputs (step_outputs / dump_outputs) on a made-up last step held in host tensors: float64 arrays,
+    the same arrays for the same step, the density whole when it fits and a seeded sample within the byte budget on
+    disk when not, and a density-matrix sample that stays put when the orbitals of a degenerate set are rotated."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    M, n_G = 6, 300
+    X = torch.tensor(rng.standard_normal((M, n_G)) + 1j * rng.standard_normal((M, n_G)))
+    U = torch.linalg.qr(torch.tensor(rng.standard_normal((3, 3)) + 1j * rng.standard_normal((3, 3))))[0]
+    X_rot = X.clone()
+    X_rot[1:4] = U @ X[1:4]                                 # bands 1..3 share one eigenvalue and one occupation
+    from dftk_jl_amd.terms import Energies
+    energies = Energies(Kinetic=3.0, Hartree=1.5, Xc=-2.25)
+    info = dict(n_bands_converge=5, energies=energies, eF=0.1, psi=[X], rho=torch.tensor(rng.random((24, 20, 16))),
+                eigenvalues=[np.array([-1.0, -0.5, -0.5, -0.5, 0.3, 0.4])], occupation=[np.array([2.0, 2, 2, 2, 0, 0])])
+    a = bench.step_outputs(info)
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["eigenvalues"].shape == (1, 5) and a["occupation"].shape == (1, 5) and a["fermi_level"].tolist() == [0.1]
+    assert a["energies"].tolist() == [energies.total, 3.0, 1.5, -2.25]
+    np.testing.assert_array_equal(a["rho"], info["rho"].numpy())
+    assert a["density_matrix_sample"].shape == (1, 128, 128, 2)
+    b = bench.step_outputs(dict(info, psi=[X_rot]))
+    np.testing.assert_allclose(b["density_matrix_sample"], a["density_matrix_sample"], rtol=0, atol=1e-12)
+    budget = 150_000                                        # less than the 512 kB of this density
+    big = dict(info, rho=torch.tensor(rng.random((40, 40, 40))))
+    small = bench.step_outputs(big, budget=budget)
+    assert "rho" not in small and 0 < small["rho_sample"].size < 40 ** 3
+    again = bench.step_outputs(big, budget=budget)
+    assert all(np.array_equal(again[k_], v_) for k_, v_ in small.items())
+    bench.dump_outputs(str(tmp_path), small)
+    files = sorted(os.listdir(tmp_path))
+    assert files == sorted(k_ + ".npy" for k_ in small)
+    assert sum(os.path.getsize(tmp_path / f_) for f_ in files) <= budget
+    np.testing.assert_array_equal(np.load(tmp_path / "density_matrix_sample.npy"), small["density_matrix_sample"])
 
 
 def test_shard_plan_transposes_slabs_to_bands_and_back():

@@ -16,8 +16,8 @@ cp $R/gpurun_out/r04_pmc_traffic.json $R/gpurun_out/r04_pmc_fetch_size.txt $R/gp
 mkdir -p $R/profiles && cp $R/gpurun_out/r04_pmc_traffic.json $R/profiles/ 2>/dev/null
 tail -3 $O/pmc.log | cut -c1-300
 cd $R
-( time timeout 1500 python bench.py --steps 20 --warmup 5 > $O/r04_bench_cfg5_driver_args.json 2> $O/bench_driver.err ) 2> $O/bench_driver.time
-( time timeout 1500 python bench.py > $O/r04_bench_cfg5.json 2> $O/bench_cfg5.err ) 2> $O/bench_cfg5.time
+( time timeout 1500 python bench.py --full --steps 20 --warmup 5 > $O/r04_bench_cfg5_driver_args.json 2> $O/bench_driver.err ) 2> $O/bench_driver.time
+( time timeout 1500 python bench.py --full > $O/r04_bench_cfg5.json 2> $O/bench_cfg5.err ) 2> $O/bench_cfg5.time
 python - <<'PY'
 import json
 for f in ("r04_bench_cfg5_driver_args", "r04_bench_cfg5"):
@@ -26,17 +26,17 @@ for f in ("r04_bench_cfg5_driver_args", "r04_bench_cfg5"):
     print(f, round(d["value"], 3), d["steps"], c["scf_wall_s"], c["converged"], round(r["frac"], 3), r["traffic"], c["complex_iteration"]["value"], d["cpu_baseline"]["kind"], d["cpu_baseline"]["value"], c["parity"]["pass"], d["amdahl"]["predicted_speedup"])
 PY
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o p -- python $R/bench.py --no-cpu-baseline --no-complex-leg --no-parity > /tmp/bench_kt.json 2>/tmp/bench_kt.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o p -- python $R/bench.py --full --no-cpu-baseline --no-complex-leg --no-parity > /tmp/bench_kt.json 2>/tmp/bench_kt.err
 python $R/tools/kernel_stats_txt.py /tmp/kt/p_kernel_stats.csv 40 > $O/r04_kernel_trace_cfg5.txt
 tail -1 /tmp/bench_kt.json >> $O/r04_kernel_trace_cfg5.txt
 python $R/tools/trace_gaps.py /tmp/kt/p_kernel_trace.csv 24 0.5 > $O/r04_trace_gaps_cfg5.txt
 head -12 $O/r04_kernel_trace_cfg5.txt; head -6 $O/r04_trace_gaps_cfg5.txt
 rm -rf /tmp/kt
 cd $R
-timeout 600 python bench.py --supercell 4 --no-cpu-baseline --no-complex-leg > $O/r04_bench_cfg2.json 2> $O/bench_cfg2.err
-timeout 900 python bench.py --mode kpoints --system al --no-cpu-baseline > $O/r04_bench_kpoints_al.json 2> $O/bench_kpoints_al.err
+timeout 600 python bench.py --full --supercell 4 --no-cpu-baseline --no-complex-leg > $O/r04_bench_cfg2.json 2> $O/bench_cfg2.err
+timeout 900 python bench.py --full --mode kpoints --system al --no-cpu-baseline > $O/r04_bench_kpoints_al.json 2> $O/bench_kpoints_al.err
 for S in si graphene; do
-  timeout 600 python bench.py --mode kpoints --system $S --no-cpu-baseline --no-amdahl-probe > $O/r04_bench_kpoints_$S.json 2> $O/bench_kpoints_$S.err
+  timeout 600 python bench.py --full --mode kpoints --system $S --no-cpu-baseline --no-amdahl-probe > $O/r04_bench_kpoints_$S.json 2> $O/bench_kpoints_$S.err
 done
 python - <<'PY'
 import json

@@ -20,8 +20,8 @@ ARGS="--no-cpu-baseline --no-complex-leg --no-random-start-leg --no-parity --no-
 export DFTK_MI_HEEV_PARTIAL=0
 export PMC_NOTE="; Rayleigh-Ritz by the full Jacobi in these passes (DFTK_MI_HEEV_PARTIAL=0) so that all k_zgemm dispatches are booked zgemm calls; read back from the rocpd database (tools/rocpd_export_csv.py)"
 rm -rf /tmp/pf /tmp/pw
-timeout -s KILL 420 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/pf -o pf -- python $R/bench.py $ARGS > /tmp/bench_f.json 2>/dev/null
-timeout -s KILL 420 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/pw -o pw -- python $R/bench.py $ARGS > /tmp/bench_w.json 2>/dev/null
+timeout -s KILL 420 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/pf -o pf -- python $R/bench.py --full $ARGS > /tmp/bench_f.json 2>/dev/null
+timeout -s KILL 420 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/pw -o pw -- python $R/bench.py --full $ARGS > /tmp/bench_w.json 2>/dev/null
 python $R/tools/rocpd_export_csv.py $(ls /tmp/pf/*results.db | head -1) counters /tmp/pf.csv
 python $R/tools/rocpd_export_csv.py $(ls /tmp/pw/*results.db | head -1) counters /tmp/pw.csv
 python $R/tools/pmc_to_traffic.py /tmp/pf.csv /tmp/pw.csv /tmp/bench_f.json $O/r06_pmc_traffic.json
@@ -32,8 +32,8 @@ unset DFTK_MI_HEEV_PARTIAL PMC_NOTE
 rm -rf /tmp/pf /tmp/pw /tmp/pf.csv /tmp/pw.csv
 fi
 cd $R
-( time timeout 1500 python bench.py --steps 20 --warmup 5 > $O/r06_bench_cfg5_driver_args.json 2> $O/bench_driver.err ) 2> $O/bench_driver.time
-( time timeout 1500 python bench.py --no-cpu-baseline > $O/r06_bench_cfg5.json 2> $O/bench_cfg5.err ) 2> $O/bench_cfg5.time
+( time timeout 1500 python bench.py --full --steps 20 --warmup 5 > $O/r06_bench_cfg5_driver_args.json 2> $O/bench_driver.err ) 2> $O/bench_driver.time
+( time timeout 1500 python bench.py --full --no-cpu-baseline > $O/r06_bench_cfg5.json 2> $O/bench_cfg5.err ) 2> $O/bench_cfg5.time
 python - <<'PY'
 import json
 for f in ("r06_bench_cfg5_driver_args", "r06_bench_cfg5"):
@@ -43,7 +43,7 @@ for f in ("r06_bench_cfg5_driver_args", "r06_bench_cfg5"):
 PY
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kt
-timeout -s KILL 420 rocprofv3 --kernel-trace -d /tmp/kt -o p -- python $R/bench.py --no-cpu-baseline --no-complex-leg --no-random-start-leg --no-parity --no-amdahl-probe > /tmp/bench_kt.json 2>/tmp/bench_kt.err
+timeout -s KILL 420 rocprofv3 --kernel-trace -d /tmp/kt -o p -- python $R/bench.py --full --no-cpu-baseline --no-complex-leg --no-random-start-leg --no-parity --no-amdahl-probe > /tmp/bench_kt.json 2>/tmp/bench_kt.err
 DB=$(ls /tmp/kt/*results.db | head -1)
 python $R/tools/rocpd_stats.py $DB 44 > $O/r06_kernel_trace_cfg5.txt
 tail -1 /tmp/bench_kt.json >> $O/r06_kernel_trace_cfg5.txt
@@ -52,10 +52,10 @@ python $R/tools/trace_gaps.py /tmp/kt.csv 24 0.5 > $O/r06_trace_gaps_cfg5.txt
 head -14 $O/r06_kernel_trace_cfg5.txt; head -6 $O/r06_trace_gaps_cfg5.txt
 rm -rf /tmp/kt /tmp/kt.csv
 cd $R
-timeout 600 python bench.py --supercell 4 --no-cpu-baseline --no-complex-leg > $O/r06_bench_cfg2.json 2> $O/bench_cfg2.err
-timeout 900 python bench.py --mode kpoints --system al --no-cpu-baseline > $O/r06_bench_kpoints_al.json 2> $O/bench_kpoints_al.err
+timeout 600 python bench.py --full --supercell 4 --no-cpu-baseline --no-complex-leg > $O/r06_bench_cfg2.json 2> $O/bench_cfg2.err
+timeout 900 python bench.py --full --mode kpoints --system al --no-cpu-baseline > $O/r06_bench_kpoints_al.json 2> $O/bench_kpoints_al.err
 for S in si graphene; do
-  timeout 600 python bench.py --mode kpoints --system $S --no-cpu-baseline --no-amdahl-probe > $O/r06_bench_kpoints_$S.json 2> $O/bench_kpoints_$S.err
+  timeout 600 python bench.py --full --mode kpoints --system $S --no-cpu-baseline --no-amdahl-probe > $O/r06_bench_kpoints_$S.json 2> $O/bench_kpoints_$S.err
 done
 python - <<'PY'
 import json
