@@ -107,7 +107,7 @@ enum ProfFamily {
     PROF_ZGEMM_STRUCT = 11,  // structured calls (UPPER / B_UPPER), timed apart: work = flops of the part of the product
                              // that is mathematically needed (upper triangle of C; k <= j for triangular B)
     PROF_ZGEMM_EXEC = 12,    // no timing: real flops the launched tiles execute on the matrix pipe, all zgemm calls
-                             // (3M kernel: 6 per complex multiply-add, 4M: 8; full tiles incl. shifted/border recompute)
+                             // (3M kernel: 6 per complex multiply-add, REAL: 4; full tiles incl. shifted/border recompute)
     PROF_COMM = 13,          // collectives of a sharded k-block (work = bytes handed to the communicator)
     PROF_ZGEMM_CPLX = 14,    // no timing: useful flops of all zgemm calls as if none were REAL (a DFTK_MI_GEMM_REAL call
                              // stands for a complex product of twice its flops): what the general complex path needs

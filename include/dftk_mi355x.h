@@ -325,8 +325,9 @@ int dftk_mi_zgemm(dftk_mi_basis* basis, char transA, int64_t m, int64_t n, int64
                   dftk_mi_cplx* C_d, int64_t ldc);
 /* Structured variants used by the LOBPCG driver (lobpcg_hyper_impl.jl:141-145 Gram matrices that are
  * hermitised afterwards, :216-261 X*inv(R)); flags (may be combined):
- *   DFTK_MI_GEMM_UPPER     only the 128x64 tiles of C that intersect the upper triangle (i <= j) are
- *                          computed and written, the rest of C is left untouched;
+ *   DFTK_MI_GEMM_UPPER     only the tiles of C (128x32 for complex products, 128x64 with DFTK_MI_GEMM_REAL)
+ *                          that intersect the upper triangle (i <= j) are computed and written, the rest of C is
+ *                          left untouched;
  *   DFTK_MI_GEMM_B_UPPER   B is upper triangular (B[k][j] = 0 for k > j): the k loop stops at the diagonal;
  *   DFTK_MI_GEMM_REAL      the long operands are blocks of real-symmetric vectors in the half-sphere format of
  *                          dftk_mi_kblock_set_gamma_real, i.e. real matrices with two real rows per complex entry:

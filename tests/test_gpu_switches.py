@@ -3,7 +3,6 @@ diagnostic switch is checked to leave the results untouched (VERDICT r03 "weak" 
 the experiment switches of rounds 1-3 were deleted).  The switches are read once per process, so each case runs a small
 battery in a subprocess and compares it with the default process' results:
 
-  DFTK_MI_GEMM_4M=1        4-product complex kernel `k_zgemm_lds` instead of the 3M kernel (complex products only)
   DFTK_MI_GEMM=naive       the naive (non-MFMA) GEMM kernels
   DFTK_MI_FFT_REG=0        LDS-pass z kernels for axes that have a register-resident instantiation
   DFTK_MI_FFT_REG_MIN=256  the same through the length threshold
@@ -152,7 +151,6 @@ def test_default_paths_are_accurate(default_run):
 
 
 @pytest.mark.parametrize("tag,env", [
-    ("gemm_4m", {"DFTK_MI_GEMM_4M": "1"}),
     ("gemm_naive", {"DFTK_MI_GEMM": "naive"}),
     ("fft_lds_z", {"DFTK_MI_FFT_REG": "0"}),
     ("fft_reg_min", {"DFTK_MI_FFT_REG_MIN": "256"}),

@@ -6,7 +6,7 @@ usage: pmc_to_traffic.py fetch_counter_collection.csv write_counter_collection.c
 Kernels are grouped into the library's profiling families by name; bytes per launch = family bytes / launches the
 library counted in the SAME whole-process pass (bench.py --prof-all; a zgemm call = one launch).
 FETCH_SIZE is doubled (gfx950 under-reports 16 B/lane streaming reads by 2x: /opt/skills/guides/MI355X_MICROARCH.md
-"HBM", calibrated with a 1 GiB device copy by tools/pmc_traffic.sh); WRITE_SIZE is taken as is.  CSV units: KiB.
+"HBM", calibrated with a 1 GiB device copy); WRITE_SIZE is taken as is.  CSV units: KiB.
 The output carries the bench line's workload string and library source hash: bench.py only quotes it as
 ``roofline.traffic`` for exactly that build and workload."""
 import collections
