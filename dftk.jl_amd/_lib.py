@@ -53,6 +53,10 @@ _SIGNATURES = {
                                                C.POINTER(C.c_int)]),
     "dftk_mi_atomic_superposition": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
+    "dftk_mi_forces_local": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "dftk_mi_forces_nonlocal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_void_p]),
     "dftk_mi_xc_gga": (C.c_int, [C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
     "dftk_mi_ifft_sphere": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -514,6 +514,7 @@ extern "C" int dftk_mi_kblock_destroy(dftk_mi_kblock* kb) {
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (kb->sh_buf) hipFree(kb->sh_buf);
+    if (kb->d_G3) hipFree(kb->d_G3);
     delete kb->sh_rows;
     delete kb->lob_hist;
     delete kb->h_mapping;
@@ -1073,6 +1074,24 @@ extern "C" int dftk_mi_atomic_superposition(dftk_mi_kblock* cube_kb, int kind, c
     HIPCHK(hipSetDevice(cube_kb->basis->device));
     return atomic_superposition(cube_kb, kind, recip_lattice_h, n_species, params_h, n_atoms, species_of_atom_h,
                                 positions_h, out_d);
+}
+
+extern "C" int dftk_mi_forces_local(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species,
+                                    const double* params_h, int n_atoms, const int* species_of_atom_h,
+                                    const double* positions_h, const double* rho_d, double* forces_h) {
+    if (!cube_kb || !recip_lattice_h) return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(cube_kb->basis->device));
+    return forces_local(cube_kb, recip_lattice_h, n_species, params_h, n_atoms, species_of_atom_h, positions_h, rho_d,
+                        forces_h);
+}
+
+extern "C" int dftk_mi_forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int n_bands, const dftk_mi_cplx* psi_d,
+                                       int64_t ld_psi, const double* weight_h, int n_atoms, const int* col_start_h,
+                                       double* forces_h) {
+    if (!kb) return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(kb->basis->device));
+    return forces_nonlocal(kb, kcoord_h, n_bands, reinterpret_cast<const cd*>(psi_d), ld_psi, weight_h, n_atoms,
+                           col_start_h, forces_h);
 }
 
 extern "C" int dftk_mi_xc_gga(dftk_mi_basis* b, int64_t n, const double* rho_d, const double* sigma_d, int xc_functionals,

@@ -218,6 +218,7 @@ struct dftk_mi_kblock {
     std::vector<int64_t>* h_mapping;
     std::vector<double>* h_kin;
     GammaReal* gr;                   // owned; null until dftk_mi_kblock_set_gamma_real / density_accumulate_real
+    int32_t* d_G3;                   // [3 n_G] integer G of every sphere row (owned; built by the first forces call)
 };
 
 // ------------------------------------------------------------------------------------ internal API
@@ -350,6 +351,7 @@ int gamma_gather_P(dftk_mi_kblock* kb, int ncols, const cd* P, int64_t ldP, cd* 
 int gamma_density_bands(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho);
 int64_t gamma_local_rows(const dftk_mi_kblock* kb);     // half-format rows held by this rank
 int64_t gamma_row0(const dftk_mi_kblock* kb);
+int gamma_projectors(dftk_mi_kblock* kb);               // half-format projectors of this rank (built on first use)
 // api.cpp: the plane-wave sharded variants (slab <-> band all-to-alls around the local building blocks) and the
 // entry / exit conversions of dftk_mi_lobpcg (caller's full-sphere block <-> half-format block, sharded or not)
 int gamma_apply_H_sharded(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t ldpsi, cd* Hpsi, int64_t ldH);
@@ -361,6 +363,12 @@ int gamma_lobpcg_store(dftk_mi_kblock* kb, int M, const cd* Xh, int64_t ldh, cd*
 // into the two products (DFTK_MI_GEMM_REAL for half-format blocks); comm (nullable) all-reduces the projections
 int apply_nonlocal_rows(dftk_mi_kblock* kb, int nb, const cd* P, int64_t ldP, int64_t rows, const cd* psi,
                         int64_t ldpsi, cd* Hpsi, int64_t ldH, bool accumulate, int gemm_flags, dftk_mi_comm* comm);
+
+// force_kernels.hip: dftk_mi_forces_local / dftk_mi_forces_nonlocal
+int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, const double* par_h, int n_atoms,
+                 const int* species_of_atom_h, const double* positions_h, const double* rho_d, double* forces_h);
+int forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int nb, const cd* psi, int64_t ld_psi,
+                    const double* weight_h, int n_atoms, const int* col_start_h, double* forces_h);
 
 // lobpcg.cpp
 // ortho!(X) (Cholesky-QR with the reference's shift-and-retry and SVD fallback) on a stand-alone block;

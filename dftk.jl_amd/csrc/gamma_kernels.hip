@@ -488,6 +488,8 @@ static int gr_projectors(dftk_mi_kblock* kb) {
     return 0;
 }
 
+int gamma_projectors(dftk_mi_kblock* kb) { return gr_projectors(kb); }
+
 int gamma_pack_pairs(dftk_mi_kblock* kb, int nb, const cd* H, int64_t ldh, cd* Z, int64_t ldz) {
     if (nb <= 0) return 0;
     GammaReal* gr = kb->gr;

@@ -1,0 +1,163 @@
+"""Atomic forces after an SCF (src/postprocess/forces.jl): ``compute_forces`` sums ``compute_forces(term, ...)`` over the
+model's terms and returns REDUCED-coordinate forces, one row per atom in ``model.atoms`` order; ``compute_forces_cart``
+converts them with covector_red_to_cart, F_cart = inv(lattice') F_red (forces.jl:44-47).
+
+Device terms (the library's force kernels, force_kernels.hip): AtomicLocal (local.jl:142-177, the exact derivative of the
+local energy on the cube) and AtomicNonlocal (nonlocal.jl:49-98, one projector product per k-block, symmetrised as the
+reference does).  Ewald (ewald.jl:24-31) is analytic on the host.  Kinetic, Hartree, PspCorrection and Entropy have no
+explicit position dependence (terms.jl:85); Xc forces vanish without a non-linear core correction, which HGH
+pseudopotentials do not carry.  There is no torch fall-back: a basis without the library raises."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+from .symmetry import symmetrize_forces
+from .terms import energy_forces_ewald, total_density
+
+_NO_FORCES = ("Kinetic", "Hartree", "PspCorrection", "Entropy")
+
+
+def _group_order(model):
+    """Atoms in species-group order (the order of the projector columns and of the local-term species table)."""
+    return [ia for g in model.atom_groups for ia in g]
+
+
+def _forces_local(basis, rho):
+    model = basis.model
+    order = _group_order(model)
+    par = np.zeros((len(model.atom_groups), 8))
+    species = []
+    for s_idx, g in enumerate(model.atom_groups):
+        psp = model.atoms[g[0]].psp
+        vals = [psp.rloc, float(psp.Zion)] + list(psp.cloc)[:4]
+        par[s_idx, :len(vals)] = vals
+        species += [s_idx] * len(g)
+    species = np.asarray(species, dtype=np.int32)
+    positions = np.ascontiguousarray([np.asarray(model.positions[ia], dtype=float) for ia in order], dtype=np.float64)
+    Bh = np.asfortranarray(model.recip_lattice, dtype=np.float64)
+    rho_tot = total_density(rho).to(torch.float64).contiguous()
+    out = np.zeros((len(order), 3))
+    basis.pre_call()
+    _lib.check(basis.lib.dftk_mi_forces_local(basis._cube_handle, Bh.ctypes.data, par.shape[0], par.ctypes.data,
+                                              len(order), species.ctypes.data, positions.ctypes.data,
+                                              rho_tot.data_ptr(), out.ctypes.data))
+    F = np.zeros((len(model.atoms), 3))
+    F[order] = out
+    return F
+
+
+def _projector_col_start(model):
+    """Column offsets of every atom (group order) in P: groups without projectors own no columns."""
+    starts = [0]
+    for g in model.atom_groups:
+        n = model.atoms[g[0]].psp.count_n_proj()
+        for _ in g:
+            starts.append(starts[-1] + n)
+    return np.asarray(starts, dtype=np.int32)
+
+
+def _forces_nonlocal(basis, psi, occupation):
+    model = basis.model
+    n_atoms = len(model.atoms)
+    T = basis.terms
+    if T is None or T.P is None:
+        return np.zeros((n_atoms, 3))
+    order = _group_order(model)
+    col_start = _projector_col_start(model)
+
+    def one(ik, psik):
+        kpt = basis.kpoints[ik]
+        occ = np.asarray(occupation[ik], dtype=float)[:psik.shape[0]]
+        keep = np.nonzero(occ != 0)[0]
+        out = np.zeros((n_atoms, 3))
+        if len(keep) == 0:
+            return out
+        if len(keep) == keep[-1] + 1:
+            ps = psik[:len(keep)]
+        else:
+            ps = psik.index_select(0, torch.as_tensor(keep, device=psik.device))
+        if ps.stride(1) != 1:
+            ps = ps.contiguous()
+        w = np.ascontiguousarray(basis.kweights[ik] * occ[keep], dtype=np.float64)
+        kh = np.ascontiguousarray(kpt.coordinate, dtype=np.float64)
+        basis.pre_call()
+        _lib.check(basis.lib.dftk_mi_forces_nonlocal(kpt.handle, kh.ctypes.data, len(keep), ps.data_ptr(), ps.stride(0),
+                                                     w.ctypes.data, n_atoms, col_start.ctypes.data, out.ctypes.data))
+        return out
+
+    parts = basis.run_on_lanes(one, psi)
+    Fg = np.zeros((n_atoms, 3))
+    for p in parts:
+        Fg += p
+    if basis.comm_kpts.size > 1:
+        Fg = np.asarray(basis.comm_kpts.sum_scalars(Fg.reshape(-1).tolist())).reshape(n_atoms, 3)
+    F = np.zeros((n_atoms, 3))
+    F[order] = Fg
+    return symmetrize_forces(basis, F)
+
+
+def _check_nlcc(model):
+    """Xc forces are zero only without a non-linear core correction (xc.jl:200-); a pseudopotential that has one, or
+    that cannot say (no ``has_core_density``), is refused."""
+    for el in model.atoms:
+        has = getattr(el.psp, "has_core_density", None)
+        if has is None or has():
+            raise NotImplementedError(f"XC forces with a non-linear core correction ({el.symbol}) are not implemented")
+
+
+def compute_forces_term(name, basis, psi, occupation, rho=None):
+    """``compute_forces(term, basis, psi, occupation; rho)`` for the term named ``name``: an (n_atoms, 3) array of
+    reduced-coordinate forces, or None for terms without explicit position dependence."""
+    model = basis.model
+    if name not in model.term_types:
+        raise ValueError(f"term {name} is not part of the model")
+    if name in _NO_FORCES:
+        return None
+    if name == "Xc":
+        _check_nlcc(model)
+        return None
+    if name == "Ewald":
+        # computed on the first forces call (not at set-up: instantiate_terms and the SCF are unchanged), then kept
+        T = basis.terms
+        if getattr(T, "F_ewald", None) is None:
+            T.F_ewald = energy_forces_ewald(model.lattice, [a.charge_ionic for a in model.atoms], model.positions)[1]
+        return T.F_ewald.copy()
+    basis._require_gpu()
+    if name == "AtomicLocal":
+        if rho is None:
+            raise ValueError("AtomicLocal forces need the density")
+        with basis.on_library_stream():
+            return _forces_local(basis, rho)
+    if name == "AtomicNonlocal":
+        with basis.on_library_stream():
+            return _forces_nonlocal(basis, psi, occupation)
+    raise NotImplementedError(f"forces of term {name} are outside the MI355X hot path")
+
+
+def compute_forces(basis_or_scfres, psi=None, occupation=None, rho=None):
+    """``compute_forces(scfres)`` / ``compute_forces(basis, psi, occupation; rho)`` (forces.jl:23-36): the sum over the
+    model's terms, (n_atoms, 3) float64 in reduced coordinates, ``model.atoms`` order."""
+    if isinstance(basis_or_scfres, dict):
+        res = basis_or_scfres
+        basis, psi, occupation, rho = res["basis"], res["psi"], res["occupation"], res["rho"]
+    else:
+        basis = basis_or_scfres
+    total = np.zeros((len(basis.model.atoms), 3))
+    for name in basis.model.term_types:
+        f = compute_forces_term(name, basis, psi, occupation, rho=rho)
+        if f is not None:
+            total += f
+    return total
+
+
+def forces_red_to_cart(lattice, forces):
+    """covector_red_to_cart: F_cart = inv(lattice') F_red for every atom."""
+    return np.asarray(forces, dtype=float) @ np.linalg.inv(np.asarray(lattice, dtype=float))
+
+
+def compute_forces_cart(basis_or_scfres, psi=None, occupation=None, rho=None):
+    """``compute_forces_cart`` (forces.jl:44-47): Cartesian forces, (n_atoms, 3)."""
+    basis = basis_or_scfres["basis"] if isinstance(basis_or_scfres, dict) else basis_or_scfres
+    return forces_red_to_cart(basis.model.lattice, compute_forces(basis_or_scfres, psi, occupation, rho))

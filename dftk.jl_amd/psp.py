@@ -35,6 +35,10 @@ class PspHgh:
             return sum(self.count_n_proj(ll) for ll in range(self.lmax + 1))
         return self.count_n_proj_radial(l) * (2 * l + 1)
 
+    def has_core_density(self):
+        """PspHgh.jl:16: HGH pseudopotentials carry no non-linear core correction."""
+        return False
+
 
 def _psp(Zion, rloc, cloc, rp, hupper, identifier="", description=""):
     cloc = tuple(list(cloc) + [0.0] * (4 - len(cloc)))

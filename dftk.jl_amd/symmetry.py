@@ -320,3 +320,39 @@ def check_group(symmetries, tol=SYMMETRY_TOLERANCE):
             if not member(s.W @ t.W, s.w + s.W @ t.w):
                 raise ValueError("check_group: a product is missing")
     return symmetries
+
+
+def find_symmetry_preimage(positions_group, position, symop, tol_symmetry=SYMMETRY_TOLERANCE):
+    """symmetry.jl:379-399: index in ``positions_group`` of the atom that ``symop`` (r -> W r + w) maps onto
+    ``position`` (up to a lattice translation)."""
+    other = np.linalg.solve(np.asarray(symop.W, dtype=float), np.asarray(position, dtype=float) - symop.w)
+    dev = [float(np.max(np.abs((np.asarray(p, dtype=float) - other) - np.round(np.asarray(p, dtype=float) - other))))
+           for p in positions_group]
+    i = int(np.argmin(dev))
+    if not dev[i] < 10 * tol_symmetry:
+        raise ValueError(f"inconsistent symmetry operation: no preimage of atom at {position} (deviation {dev[i]:.3e})")
+    return i
+
+
+def symmetrize_forces(model_or_basis, forces, symmetries=None, tol_symmetry=SYMMETRY_TOLERANCE):
+    """``symmetrize_forces`` (symmetry.jl:401-423): reduced-coordinate forces (n_atoms, 3) averaged over the symmetry
+    operations, F_sym[a] = mean_S inv(W') F[preimage of a under S].  ``model_or_basis``: a Model (then ``symmetries``
+    is required) or a PlaneWaveBasis (default: ``basis.symmetries``)."""
+    model = getattr(model_or_basis, "model", model_or_basis)
+    if symmetries is None:
+        symmetries = model_or_basis.symmetries
+    forces = np.asarray(forces, dtype=float).reshape(-1, 3)
+    out = np.zeros_like(forces)
+    for group in model.atom_groups:
+        pg = np.asarray([np.asarray(model.positions[i], dtype=float) for i in group]).reshape(-1, 3)
+        for op in symmetries:
+            WtInv = np.linalg.inv(np.asarray(op.W, dtype=float).T)
+            # preimages of all atoms of the group at once (find_symmetry_preimage, vectorised)
+            other = np.linalg.solve(np.asarray(op.W, dtype=float), (pg - op.w).T).T
+            delta = pg[None, :, :] - other[:, None, :]
+            dev = np.max(np.abs(delta - np.round(delta)), axis=2)
+            j = np.argmin(dev, axis=1)
+            if not np.all(dev[np.arange(len(group)), j] < 10 * tol_symmetry):
+                raise ValueError("inconsistent symmetry operation: an atom has no preimage")
+            out[group] += forces[np.asarray(group)[j]] @ WtInv.T
+    return out / len(symmetries)

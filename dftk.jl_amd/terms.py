@@ -245,6 +245,70 @@ def energy_ewald(lattice, charges, positions, eta=None):
     return (s_recip + s_real) / 2
 
 
+def energy_forces_ewald(lattice, charges, positions, eta=None):
+    """``energy_forces_ewald`` (ewald.jl:64-168): the Ewald energy of ``energy_ewald`` (same sums, same cut-offs) and
+    the forces on the nuclei in REDUCED coordinates, F_i = -dE / dr_i, as an (n_atoms, 3) array (host, numpy)."""
+    from .basis import estimate_integer_lattice_bounds
+    lattice = np.asarray(lattice, dtype=float)
+    q = np.asarray(charges, dtype=float)
+    pos = np.asarray(positions, dtype=float).reshape(-1, 3)
+    forces = np.zeros((len(q), 3))
+    if q.size == 0:
+        return 0.0, forces
+    recip = TWO_PI * np.linalg.inv(lattice.T)
+    if eta is None:   # default_eta, ewald.jl:40-44
+        eta = math.sqrt(math.sqrt(1.69 * np.linalg.norm(recip / TWO_PI) / np.linalg.norm(lattice))) / 2
+    max_exp = -math.log(np.finfo(float).eps) + 5
+    max_erfc = math.sqrt(max_exp)
+    Glims = estimate_integer_lattice_bounds(recip, math.sqrt(max_exp) * 2 * eta)
+    poslims = [float(np.max(pos[:, i][:, None] - pos[:, i][None, :])) for i in range(3)]
+    Rlims = estimate_integer_lattice_bounds(lattice, max_erfc / eta, poslims)
+    vol = abs(np.linalg.det(lattice))
+    # reciprocal part: d|S(G)|^2 / dr_j = -4 pi q_j G Im(conj(S) e^{2 pi i G.r_j})
+    rng = [np.arange(-g, g + 1) for g in Glims]
+    G = np.stack(np.meshgrid(*rng, indexing="ij"), axis=-1).reshape(-1, 3)
+    G = G[np.any(G != 0, axis=1)]
+    Gsq = np.sum((G @ recip.T) ** 2, axis=1)
+    sel = Gsq / (4 * eta ** 2) < max_exp + 40
+    G, Gsq = G[sel], Gsq[sel]
+    s_recip = -(q.sum() ** 2) / (4 * eta ** 2)
+    f_recip = np.zeros_like(forces)
+    for c0 in range(0, len(G), 32768):
+        ph = TWO_PI * (G[c0:c0 + 32768] @ pos.T)
+        cs, sn = np.cos(ph), np.sin(ph)
+        Sc, Ss = cs @ q, sn @ q
+        sf2 = Sc ** 2 + Ss ** 2
+        fac = np.exp(-Gsq[c0:c0 + 32768] / (4 * eta ** 2)) / Gsq[c0:c0 + 32768]
+        s_recip += float(np.sum(sf2 * fac))
+        im = Sc[:, None] * sn - Ss[:, None] * cs                       # Im(conj(S) e^{i ph_j}), (n_G, n_atoms)
+        f_recip += ((fac[:, None] * im) * q[None, :]).T @ G[c0:c0 + 32768]
+    s_recip *= 4 * math.pi / vol
+    forces += (4 * math.pi / vol) * TWO_PI * f_recip                   # -1/2 * d/dr of the sum above
+    # real-space part: d/dr_i sum_{j,R} q_i q_j erfc(eta d) / d, d = |L (r_i - r_j - R)|
+    s_real = -2 * eta / math.sqrt(math.pi) * float(np.sum(q * q))
+    rr = [np.arange(-g, g + 1) for g in Rlims]
+    R = np.stack(np.meshgrid(*rr, indexing="ij"), axis=-1).reshape(-1, 3).astype(float)
+    qq = q[:, None] * q[None, :]
+    n = len(q)
+    eye = np.eye(n, dtype=bool)
+    LtL = lattice.T @ lattice
+    for Rv in R:
+        delta = pos[:, None, :] - pos[None, :, :] - Rv[None, None, :]
+        d = delta @ lattice.T
+        dist = np.linalg.norm(d, axis=-1)
+        if not Rv.any():
+            dist = np.where(eye, np.inf, dist)
+        m = dist * eta < max_erfc + 8
+        if m.any():
+            s_real += float(np.sum(qq[m] * erfc(eta * dist[m]) / dist[m]))
+            dm = dist[m]
+            dfd = -2 * eta / math.sqrt(math.pi) * np.exp(-(eta * dm) ** 2) / dm - erfc(eta * dm) / (dm * dm)
+            coef = np.zeros((n, n))
+            coef[m] = qq[m] * dfd / dm
+            forces -= np.einsum("ij,ijk->ik", coef, delta @ LtL)
+    return (s_recip + s_real) / 2, forces
+
+
 def energy_psp_correction(model):
     """psp_correction.jl:26-32."""
     corr = sum(len(g) * eval_psp_energy_correction(model.atoms[g[0]].psp) for g in model.atom_groups)

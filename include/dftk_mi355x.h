@@ -122,6 +122,25 @@ int dftk_mi_build_projectors_hgh(dftk_mi_basis* basis, int64_t n_rows, const int
 int dftk_mi_atomic_superposition(dftk_mi_kblock* cube_kb, int kind, const double* recip_lattice_h, int n_species,
                                  const double* params_h, int n_atoms, const int* species_of_atom_h,
                                  const double* positions_h, double* out_d);
+/* compute_forces(::TermAtomicLocal) (src/terms/local.jl:142-177): reduced-coordinate forces of the HGH local term,
+ * the exact derivative of the local energy this library evaluates (the cube of dftk_mi_atomic_superposition kind 0
+ * against the density, unpaired Nyquist entries dropped).  params / species / positions exactly as
+ * dftk_mi_atomic_superposition kind 0; rho_d = TOTAL density on the cube (nz x ny x nx, x fastest);
+ * forces_h[3 a + alpha] is overwritten.  Deterministic (fixed reduction order, no atomics). */
+int dftk_mi_forces_local(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species, const double* params_h,
+                         int n_atoms, const int* species_of_atom_h, const double* positions_h, const double* rho_d,
+                         double* forces_h);
+/* compute_forces(::TermAtomicNonlocal) (src/terms/nonlocal.jl:49-98) for ONE k-block, unsymmetrised: the block's P / D
+ * (dftk_mi_kblock_set_projectors); kcoord_h = the k-point (reduced); psi_d = n_bands orbitals in the caller's
+ * full-sphere layout (leading dimension ld_psi); weight_h[n] = kweight * occupation[n]; atom a owns projector columns
+ * col_start_h[a] .. col_start_h[a + 1] (D must not couple atoms: DFTK_MI_EINVAL); forces_h[3 n_atoms] is ACCUMULATED.
+ * One product P' [psi | i g_x psi | i g_y psi | i g_z psi] per band chunk (g = G + k reduced), then a per-atom
+ * contraction with D.  Gamma-real block: real half-format products.  Sharded block: psi is this rank's row slab, the
+ * projections are all-reduced over the block's communicator, every rank gets the full result.  Touches no LOBPCG
+ * state of the block (kept A X, start buffers). */
+int dftk_mi_forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int n_bands, const dftk_mi_cplx* psi_d,
+                            int64_t ld_psi, const double* weight_h, int n_atoms, const int* col_start_h,
+                            double* forces_h);
 
 /* ---- local-potential pipeline of energy_hamiltonian (src/terms/Hamiltonian.jl:200-227) on the cube ----------
  * Hartree (src/terms/hartree.jl:50-59: V_H = irfft(green .* fft(rho)), E_H = 1/2 Re<V_H(G), rho(G)>), LDA exchange-
