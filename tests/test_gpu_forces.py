@@ -277,3 +277,141 @@ def test_forces_between_scf_steps_leave_the_scf_bit_identical(blocks):
     assert torch.equal(got["rho"], ref["rho"])
     for a, b in zip(got["eigenvalues"], ref["eigenvalues"]):
         assert np.array_equal(np.asarray(a), np.asarray(b))
+
+
+# ------------------------------------------------------------------------------------------ 9. tile and chunk edges
+# k_forces_local tiles x by 64, y by FL_WAVES * FL_KY = 32 and z by FL_KZ = 2; k_rowsum loops above 256 waves.  The
+# cubes cross every tile edge (nx 63 / 64 / 65 / 129 / 130, ny off the multiple of 32), and every axis is even (the
+# Nyquist plane zeroed) and odd at least once.
+LOCAL_EDGE_CUBES = [(63, 33, 17), (64, 32, 10), (65, 45, 11), (130, 66, 20), (129, 40, 25)]
+
+
+def _local_waves(fft_size):
+    nx, ny, nz = fft_size
+    return -(-nx // 64) * -(-ny // 32) * -(-nz // 2) * 4
+
+
+def test_local_edge_cubes_cover_the_tiles():
+    assert {n % 64 for n, _, _ in LOCAL_EDGE_CUBES} >= {63, 0, 1}
+    assert any(ny % 32 for _, ny, _ in LOCAL_EDGE_CUBES)
+    for axis in range(3):
+        assert {c[axis] % 2 for c in LOCAL_EDGE_CUBES} == {0, 1}
+    assert max(_local_waves(c) for c in LOCAL_EDGE_CUBES) > 256
+
+
+@pytest.mark.parametrize("fft_size", LOCAL_EDGE_CUBES)
+def test_local_forces_on_tile_edges(fft_size):
+    lat, at, _ = dftk.silicon_cell()
+    from dftk_jl_amd.psp import load_psp
+    C_ = dftk.ElementPsp("C", load_psp("C", "lda"))
+    basis = _basis(DISPLACED, 1.5, dftk.ExplicitKpoints([[0.25, 0.0, 0.0]], [1.0]), fft_size=fft_size,
+                   atoms=[at[0], C_])
+    g = torch.Generator(device="cuda:0").manual_seed(sum(fft_size))
+    rho = dftk.guess_density(basis) * (1 + 0.1 * torch.rand(fft_size[::-1], dtype=torch.float64, device="cuda:0",
+                                                            generator=g))
+    F = dftk.compute_forces_term("AtomicLocal", basis, None, None, rho=rho)
+    F_ref = _numpy_local(basis, rho)
+    assert np.max(np.abs(F - F_ref)) <= 1e-11 * np.max(np.abs(F_ref)), (F, F_ref)
+
+
+def test_nonlocal_band_chunks_at_the_abi():
+    """dftk_mi_forces_nonlocal over several band chunks, against the closed formula
+    F_{a,alpha} = -4 pi sum_n w_n Re[p_n(a)' D_a q_{alpha,n}(a)], p = P' psi, q_alpha = P' (i g_alpha psi), g = G + k:
+    ~400k sphere rows, three atoms of 4 / 0 / 9 columns with banded D blocks, k != 0, ld_psi > rows (NaN padding) and a
+    different weight per band.  The chunk is cb = budget / (4 (rows + n_p) 16 B) bands, budget = max(T1, 512 MiB); a
+    fresh basis has run no FFT and no H application, so T1 is empty and the budget is the 512 MiB floor."""
+    from test_gpu_kernels import Basis, KBlock
+    lib = _lib.load()
+    n = 96
+    ax = dftk.basis.G_axis(n)
+    gz, gy, gx = np.meshgrid(ax, ax, ax, indexing="ij")
+    inside = (gx * gx + gy * gy + gz * gz <= 2090).reshape(-1)
+    mapping = np.nonzero(inside)[0]                                     # (z, y, x) index order, as a sphere
+    G = np.stack([gx.reshape(-1), gy.reshape(-1), gz.reshape(-1)], axis=1)[mapping].astype(float)
+    rows, nb = len(mapping), 64
+    col_start = np.array([0, 4, 4, 13], dtype=np.int32)
+    n_p = int(col_start[-1])
+    per_band = 4 * (rows + n_p) * 16
+    budget = 512 << 20
+    cb = budget // per_band
+    n_chunks = -(-nb // cb)
+    assert nb * per_band >= 3 * budget and n_chunks >= 3 and nb % cb != 0, (rows, cb, n_chunks)   # 20, 20, 20, 4
+    rng = np.random.default_rng(41)
+    P = rng.standard_normal((rows, n_p)) + 1j * rng.standard_normal((rows, n_p))
+    D = np.zeros((n_p, n_p))
+    for c0, c1, bw in ((0, 4, 1), (4, 13, 2)):
+        for i in range(c0, c1):
+            for j in range(i, min(c1, i + bw + 1)):
+                D[i, j] = D[j, i] = rng.uniform(-2, 2)
+    bs = Basis(lib, n, n, n)
+    kb = KBlock(lib, bs, mapping, np.zeros(rows))
+    kb.set_projectors(P, D)
+    psi = rng.standard_normal((rows, nb)) + 1j * rng.standard_normal((rows, nb))
+    ld = rows + 37
+    buf = torch.full((nb, ld), float("nan"), dtype=torch.complex128, device="cuda:0")
+    buf[:, :rows] = torch.from_numpy(np.ascontiguousarray(psi.T))
+    w = np.ascontiguousarray(rng.uniform(0.2, 2.0, nb))
+    kpt = np.array([0.13, -0.27, 0.41])
+    out = np.zeros(9)
+    _lib.check(lib.dftk_mi_forces_nonlocal(kb.h, kpt.ctypes.data, nb, buf.data_ptr(), ld, w.ctypes.data, 3,
+                                           col_start.ctypes.data, out.ctypes.data))
+    bs.sync()
+    g = G + kpt[None, :]
+    Ph = P.conj().T
+    p = Ph @ psi
+    q = [(Ph * (1j * g[:, al])[None, :]) @ psi for al in range(3)]
+    ref = np.zeros((3, 3))
+    for a in range(3):
+        c0, c1 = col_start[a], col_start[a + 1]
+        for al in range(3):
+            val = np.real(np.sum(p[c0:c1].conj() * (D[c0:c1, c0:c1] @ q[al][c0:c1]), axis=0))
+            ref[a, al] = -4 * np.pi * np.dot(w, val)
+    got = out.reshape(3, 3)
+    assert np.all(got[1] == 0)
+    assert np.max(np.abs(got - ref)) <= 1e-11 * np.max(np.abs(ref)), (got, ref)
+
+
+def _minus_G_index(G):
+    """Row of -G for every row G of a sphere (n, 3 integer)."""
+    off = int(np.abs(G).max()) + 1
+    M = 2 * off + 1
+    key = ((G[:, 0] + off) * M + (G[:, 1] + off)) * M + (G[:, 2] + off)
+    nkey = ((-G[:, 0] + off) * M + (-G[:, 1] + off)) * M + (-G[:, 2] + off)
+    order = np.argsort(key)
+    idx = order[np.searchsorted(key[order], nkey)]
+    assert np.array_equal(key[idx], nkey)
+    return idx
+
+
+def test_gamma_real_nonlocal_band_chunks():
+    """The Gamma-real branch (half-sphere rows, real product) over several band chunks against the complex block.
+    Chunks as in the ABI case with the half-sphere rows: this fresh basis has run no H application and no FFT; its T1
+    would stay below 512 MiB even then (fft_ensure_scratch: 32 bands x n_lines x nxp x 16 B with n_lines <= ny nz;
+    apply_nonlocal_rows: 2 n_p n_b 16 B), so the budget is the 512 MiB floor."""
+    lat, at, pos = dftk.silicon_cell(supercell=(2, 2, 2))
+    pos = [np.asarray(p) + (0.003 * np.array([1.0, -2.0, 3.0]) if i == 0 else 0) for i, p in enumerate(pos)]
+    kg = dftk.ExplicitKpoints([[0, 0, 0]], [1.0])
+    b_real = _basis(pos, 20, kg, lattice=lat, atoms=at, gamma_real=True)
+    assert b_real.kpoints[0].gamma_real
+    b_cplx = _basis(pos, 20, kg, lattice=lat, atoms=at, gamma_real=False, fft_size=b_real.fft_size)
+    kpt = b_real.kpoints[0]
+    n_G, n_p = kpt.n_G, b_real.terms.P[0].shape[0]
+    rows = (n_G + 1) // 2                                                # G = 0 and one row per (G, -G) pair
+    nx, ny, nz = b_real.fft_size
+    budget = 512 << 20
+    per_band = 4 * (rows + n_p) * 16
+    cb = budget // per_band
+    nb = 2 * cb + 7
+    assert max(32 * ny * nz * (-(-nx // 8) * 8) * 16, 2 * n_p * nb * 16) < budget
+    assert -(-nb // cb) == 3                                            # cb, cb, 7 bands
+    assert -(-nb // (budget // (4 * (n_G + n_p) * 16))) >= 3            # and the complex block chunks as well
+    G = kpt.G_vectors.cpu().numpy()
+    neg = torch.as_tensor(_minus_G_index(G), device="cuda:0")
+    gen = torch.Generator(device="cuda:0").manual_seed(43)
+    A = torch.randn((nb, n_G), dtype=torch.complex128, device="cuda:0", generator=gen)
+    psi = [((A + A[:, neg].conj()) / 2).contiguous()]                    # real-symmetric columns
+    del A
+    occ = [np.random.default_rng(47).uniform(0.1, 2.0, nb)]
+    Fr = dftk.compute_forces_term("AtomicNonlocal", b_real, psi, occ)
+    Fc = dftk.compute_forces_term("AtomicNonlocal", b_cplx, psi, occ)
+    assert np.max(np.abs(Fr - Fc)) <= 1e-12 * np.max(np.abs(Fc)), (Fr, Fc)
