@@ -31,4 +31,8 @@ from .symmetry import (SymOp, symmetry_operations, symmetrize_rho, irreducible_k
 from .symmetry import symmetrize_forces, find_symmetry_preimage  # noqa: F401,E402
 from .terms import energy_forces_ewald  # noqa: F401,E402
 from .forces import compute_forces, compute_forces_cart, compute_forces_term  # noqa: F401,E402
+from .symmetry import symmetrize_stresses  # noqa: F401,E402
+from .terms import stress_ewald  # noqa: F401,E402
+from .stresses import (compute_stresses_cart, compute_stresses_term, voigt_stress_to_full,  # noqa: F401,E402
+                       full_stress_to_voigt, voigt_strain_to_full, full_strain_to_voigt)
 from .memory_usage import estimate_memory_usage, plan_planewave_sharded, MemoryStatistics  # noqa: F401,E402

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libdftk_mi355x.so")
-SOURCES = ["api.cpp", "comm.cpp", "lobpcg.cpp", "batch.cpp", "batch_kernels.hip", "fft_kernels.hip", "gemm_kernels.hip", "dense_kernels.hip", "eig_kernels.hip", "xc_kernels.hip", "setup_kernels.hip", "gamma_kernels.hip", "cube_kernels.hip", "mix_kernels.hip", "force_kernels.hip"]
+SOURCES = ["api.cpp", "comm.cpp", "lobpcg.cpp", "batch.cpp", "batch_kernels.hip", "fft_kernels.hip", "gemm_kernels.hip", "dense_kernels.hip", "eig_kernels.hip", "xc_kernels.hip", "setup_kernels.hip", "gamma_kernels.hip", "cube_kernels.hip", "mix_kernels.hip", "force_kernels.hip", "stress_kernels.hip"]
 
 
 HASHPATH = LIBPATH + ".srchash"
@@ -141,7 +141,30 @@ def build_host_ortho_check(force: bool = False) -> str:
     return HOST_CHECK_BIN
 
 
+STRESS_CHECK_SRC = os.path.join(os.path.dirname(HERE), "tools", "host_stress_check.cpp")
+STRESS_CHECK_BIN = os.path.join(os.path.dirname(HERE), "tools", "bin", "host_stress_check")
+
+
+def build_host_stress_check(force: bool = False) -> str:
+    """tools/host_stress_check.cpp -> tools/bin/host_stress_check: the host-only check of the closed forms of
+    csrc/stress_kernels.hip (derivative projectors, local form-factor derivative) against finite differences.  The
+    translation unit includes the kernels' source with DFTK_STRESS_HOST_CHECK and calls no HIP runtime function: it runs
+    without a GPU."""
+    kern = os.path.join(CSRC, "stress_kernels.hip")
+    src_time = max(os.path.getmtime(p) for p in (STRESS_CHECK_SRC, kern, os.path.join(CSRC, "common.h")))
+    if not force and os.path.exists(STRESS_CHECK_BIN) and os.path.getmtime(STRESS_CHECK_BIN) >= src_time:
+        return STRESS_CHECK_BIN
+    os.makedirs(os.path.dirname(STRESS_CHECK_BIN), exist_ok=True)
+    cmd = [shutil.which("hipcc") or "/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-x", "hip", "--offload-arch=gfx950",
+           "-I", CSRC, STRESS_CHECK_SRC, "-o", STRESS_CHECK_BIN]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    if res.returncode != 0:
+        raise RuntimeError("hipcc failed on tools/host_stress_check.cpp:\n" + res.stdout + res.stderr)
+    return STRESS_CHECK_BIN
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     print(build_abi_check(force=True))
     print(build_host_ortho_check(force=True))
+    print(build_host_stress_check(force=True))

@@ -57,6 +57,13 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     "dftk_mi_forces_nonlocal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_void_p]),
+    "dftk_mi_stress_kinetic_nonlocal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p,
+                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+    "dftk_mi_stress_cube": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "dftk_mi_stress_xc": (C.c_int, [C.c_void_p, _i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "dftk_mi_xc_gga": (C.c_int, [C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
     "dftk_mi_ifft_sphere": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

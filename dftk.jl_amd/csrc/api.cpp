@@ -1094,6 +1094,36 @@ extern "C" int dftk_mi_forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_
                            col_start_h, forces_h);
 }
 
+extern "C" int dftk_mi_stress_kinetic_nonlocal(dftk_mi_kblock* kb, const double* recip_lattice_h, const double* kcoord_h,
+                                               int n_bands, const dftk_mi_cplx* psi_d, int64_t ld_psi,
+                                               const double* weight_h, int n_species, const double* rp_h,
+                                               const int* n_proj_h, int n_atoms, const int* species_of_atom_h,
+                                               const double* positions_h, const int* col_start_h, double* stress_h) {
+    if (!kb || !recip_lattice_h || !kcoord_h || !stress_h) return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(kb->basis->device));
+    return stress_kinetic_nonlocal(kb, recip_lattice_h, kcoord_h, n_bands, reinterpret_cast<const cd*>(psi_d), ld_psi,
+                                   weight_h, n_species, rp_h, n_proj_h, n_atoms, species_of_atom_h, positions_h,
+                                   col_start_h, stress_h);
+}
+
+extern "C" int dftk_mi_stress_cube(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species,
+                                   const double* params_h, int n_atoms, const int* species_of_atom_h,
+                                   const double* positions_h, const double* rho_d, double* out_h) {
+    if (!cube_kb || !recip_lattice_h || !rho_d || !out_h || cube_kb->sh_comm) return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(cube_kb->basis->device));
+    return stress_cube(cube_kb, recip_lattice_h, n_species, params_h, n_atoms, species_of_atom_h, positions_h, rho_d,
+                       out_h);
+}
+
+extern "C" int dftk_mi_stress_xc(dftk_mi_basis* b, int64_t n, int n_spin, const double* rho_d, const double* vrho_d,
+                                 const double* e_d, const double* vsigma_d, const double* grad_d, double* out_h) {
+    if (!b || n < 0 || (n_spin != 1 && n_spin != 2) || !rho_d || !vrho_d || !out_h || (vsigma_d && !grad_d) ||
+        (vsigma_d && n_spin != 1))
+        return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(b->device));
+    return stress_xc(b, n, n_spin, rho_d, vrho_d, e_d, vsigma_d, grad_d, out_h);
+}
+
 extern "C" int dftk_mi_xc_gga(dftk_mi_basis* b, int64_t n, const double* rho_d, const double* sigma_d, int xc_functionals,
                               double density_threshold, double* e_d, double* vrho_d, double* vsigma_d) {
     if (!b || n < 0 || !rho_d || !sigma_d || !e_d || !vrho_d || !vsigma_d || (xc_functionals & ~24) || !xc_functionals)

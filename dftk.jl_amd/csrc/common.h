@@ -369,6 +369,17 @@ int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, 
                  const int* species_of_atom_h, const double* positions_h, const double* rho_d, double* forces_h);
 int forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int nb, const cd* psi, int64_t ld_psi,
                     const double* weight_h, int n_atoms, const int* col_start_h, double* forces_h);
+int ensure_G3(dftk_mi_kblock* kb);       // kb->d_G3 (integer G of every sphere row), built on first use
+
+// stress_kernels.hip: dftk_mi_stress_kinetic_nonlocal / dftk_mi_stress_cube / dftk_mi_stress_xc
+int stress_kinetic_nonlocal(dftk_mi_kblock* kb, const double* recip_h, const double* kcoord_h, int nb, const cd* psi,
+                            int64_t ld_psi, const double* weight_h, int n_species, const double* rp_h, const int* nproj_h,
+                            int n_atoms, const int* species_of_atom_h, const double* positions_h, const int* col_start_h,
+                            double* stress_h);
+int stress_cube(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, const double* par_h, int n_atoms,
+                const int* species_of_atom_h, const double* positions_h, const double* rho_d, double* out_h);
+int stress_xc(dftk_mi_basis* b, int64_t n, int n_spin, const double* rho_d, const double* vrho_d, const double* e_d,
+              const double* vsigma_d, const double* grad_d, double* out_h);
 
 // lobpcg.cpp
 // ortho!(X) (Cholesky-QR with the reference's shift-and-retry and SVD fallback) on a stand-alone block;

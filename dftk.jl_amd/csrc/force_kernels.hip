@@ -337,7 +337,7 @@ __global__ __launch_bounds__(256) void k_nl_contract(int n_p, int nb, const cd* 
 }
 
 // integer G of every sphere row (3 per row), built from the block's host mapping on first use
-static int ensure_G3(dftk_mi_kblock* kb) {
+int ensure_G3(dftk_mi_kblock* kb) {
     if (kb->d_G3) return 0;
     dftk_mi_basis* b = kb->basis;
     if (!kb->h_mapping) return DFTK_MI_EINVAL;

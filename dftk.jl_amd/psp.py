@@ -127,6 +127,23 @@ def eval_psp_local_fourier(psp: PspHgh, p: torch.Tensor) -> torch.Tensor:
     return torch.where(t2 > 0, val, torch.zeros_like(val))
 
 
+def eval_psp_local_fourier_derivative(psp: PspHgh, p: torch.Tensor) -> torch.Tensor:
+    """d/dp of ``eval_psp_local_fourier`` (the local term of the stress tensor; the device kernel restates it).  With
+    t2 = (p rloc)^2 and ff = A e^{-t2/2} (-Z / t2 + B P(t2)):  dff/dt2 = A e^{-t2/2} (Z / t2^2 + B P' - ff-bracket / 2)
+    and dff/dp = 2 p rloc^2 dff/dt2; zero at p == 0 like the form factor itself."""
+    t2 = (p * psp.rloc) ** 2
+    c = psp.cloc
+    P = (c[0] + c[1] * (3 - t2) + c[2] * (15 - 10 * t2 + t2 * t2)
+         + c[3] * (105 - 105 * t2 + 21 * t2 * t2 - t2 ** 3))
+    dP = -c[1] + c[2] * (-10 + 2 * t2) + c[3] * (-105 + 42 * t2 - 3 * t2 * t2)
+    safe = torch.where(t2 > 0, t2, torch.ones_like(t2))
+    A = 4 * math.pi * psp.rloc ** 2 * torch.exp(-safe / 2)
+    B = math.sqrt(math.pi / 2) * psp.rloc
+    inner = -float(psp.Zion) / safe + B * P
+    val = A * (float(psp.Zion) / (safe * safe) + B * dP - inner / 2) * 2 * p * psp.rloc ** 2
+    return torch.where(t2 > 0, val, torch.zeros_like(val))
+
+
 def eval_psp_projector_fourier(psp: PspHgh, i: int, l: int, p: torch.Tensor) -> torch.Tensor:
     """PspHgh.jl:140-164 (i is 1-based; includes the division by p^l)."""
     rp = psp.rp[l]

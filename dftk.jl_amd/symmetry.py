@@ -356,3 +356,23 @@ def symmetrize_forces(model_or_basis, forces, symmetries=None, tol_symmetry=SYMM
                 raise ValueError("inconsistent symmetry operation: an atom has no preimage")
             out[group] += forces[np.asarray(group)[j]] @ WtInv.T
     return out / len(symmetries)
+
+
+def symmetrize_stresses(model_or_basis, stresses, symmetries=None):
+    """``symmetrize_stresses`` (symmetry.jl:362-374): the Cartesian stress tensor averaged over the symmetry operations,
+    mean_S W_cart sigma W_cart^-1 with W_cart = L W L^-1.  ``model_or_basis``: a Model (then ``symmetries`` is required)
+    or a PlaneWaveBasis (default: ``basis.symmetries``)."""
+    model = getattr(model_or_basis, "model", model_or_basis)
+    if symmetries is None:
+        symmetries = model_or_basis.symmetries
+    L = np.asarray(model.lattice, dtype=float)
+    Linv = np.linalg.inv(L)
+    stresses = np.asarray(stresses, dtype=float).reshape(3, 3)
+    out = np.zeros((3, 3))
+    for op in symmetries:
+        if np.array_equal(op.W, np.eye(3)):       # (exactly, not up to the round-off of L I L^-1)
+            out += stresses
+            continue
+        W_cart = L @ np.asarray(op.W, dtype=float) @ Linv
+        out += W_cart @ stresses @ np.linalg.inv(W_cart)
+    return out / len(symmetries)

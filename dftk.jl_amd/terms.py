@@ -309,6 +309,62 @@ def energy_forces_ewald(lattice, charges, positions, eta=None):
     return (s_recip + s_real) / 2, forces
 
 
+def stress_ewald(lattice, charges, positions, eta=None):
+    """Strain derivative of ``energy_ewald`` (same sums, same cut-offs), sigma = (1 / Omega) dE / d eps at eps = 0 for the
+    lattice (I + eps) L at fixed reduced positions: a symmetric (3, 3) array in Cartesian coordinates (host, numpy).
+    Reciprocal sum: G -> (I - eps) G and the 1 / Omega prefactor (which also multiplies -(sum q)^2 / 4 eta^2);
+    real-space sum: d -> (I + eps) d.  eta is held fixed (the energy does not depend on it)."""
+    from .basis import estimate_integer_lattice_bounds
+    lattice = np.asarray(lattice, dtype=float)
+    q = np.asarray(charges, dtype=float)
+    pos = np.asarray(positions, dtype=float).reshape(-1, 3)
+    if q.size == 0:
+        return np.zeros((3, 3))
+    recip = TWO_PI * np.linalg.inv(lattice.T)
+    if eta is None:   # default_eta, ewald.jl:40-44
+        eta = math.sqrt(math.sqrt(1.69 * np.linalg.norm(recip / TWO_PI) / np.linalg.norm(lattice))) / 2
+    max_exp = -math.log(np.finfo(float).eps) + 5
+    max_erfc = math.sqrt(max_exp)
+    Glims = estimate_integer_lattice_bounds(recip, math.sqrt(max_exp) * 2 * eta)
+    poslims = [float(np.max(pos[:, i][:, None] - pos[:, i][None, :])) for i in range(3)]
+    Rlims = estimate_integer_lattice_bounds(lattice, max_erfc / eta, poslims)
+    vol = abs(np.linalg.det(lattice))
+    rng = [np.arange(-g, g + 1) for g in Glims]
+    G = np.stack(np.meshgrid(*rng, indexing="ij"), axis=-1).reshape(-1, 3)
+    G = G[np.any(G != 0, axis=1)]
+    Gc = G @ recip.T
+    Gsq = np.sum(Gc ** 2, axis=1)
+    sel = Gsq / (4 * eta ** 2) < max_exp + 40
+    G, Gc, Gsq = G[sel], Gc[sel], Gsq[sel]
+    s_recip = -(q.sum() ** 2) / (4 * eta ** 2)
+    d_recip = np.zeros((3, 3))
+    for c0 in range(0, len(G), 32768):
+        ph = TWO_PI * (G[c0:c0 + 32768] @ pos.T)
+        sf2 = (np.cos(ph) @ q) ** 2 + (np.sin(ph) @ q) ** 2
+        g2 = Gsq[c0:c0 + 32768]
+        t = sf2 * np.exp(-g2 / (4 * eta ** 2)) / g2
+        s_recip += float(np.sum(t))
+        gc = Gc[c0:c0 + 32768]
+        d_recip += (gc * (2 * t * (1 / (4 * eta ** 2) + 1 / g2))[:, None]).T @ gc
+    dE = (2 * math.pi / vol) * (d_recip - s_recip * np.eye(3))
+    rr = [np.arange(-g, g + 1) for g in Rlims]
+    R = np.stack(np.meshgrid(*rr, indexing="ij"), axis=-1).reshape(-1, 3).astype(float)
+    qq = q[:, None] * q[None, :]
+    eye = np.eye(len(q), dtype=bool)
+    for Rv in R:
+        d = (pos[:, None, :] - pos[None, :, :] - Rv[None, None, :]) @ lattice.T
+        dist = np.linalg.norm(d, axis=-1)
+        if not Rv.any():
+            dist = np.where(eye, np.inf, dist)
+        m = dist * eta < max_erfc + 8
+        if m.any():
+            dm = dist[m]
+            dfd = -2 * eta / math.sqrt(math.pi) * np.exp(-(eta * dm) ** 2) / dm - erfc(eta * dm) / (dm * dm)
+            dv = d[m]
+            dE += 0.5 * (dv * (qq[m] * dfd / dm)[:, None]).T @ dv
+    return (dE + dE.T) / (2 * vol)      # (the matrix products above are symmetric up to round-off only)
+
+
 def energy_psp_correction(model):
     """psp_correction.jl:26-32."""
     corr = sum(len(g) * eval_psp_energy_correction(model.atoms[g[0]].psp) for g in model.atom_groups)

@@ -142,6 +142,42 @@ int dftk_mi_forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int n_ba
                             int64_t ld_psi, const double* weight_h, int n_atoms, const int* col_start_h,
                             double* forces_h);
 
+/* ---- stress tensor (src/postprocess/stresses.jl), term by term at fixed orbital coefficients (stress_kernels.hip) ----
+ * All results are Omega * sigma contributions in Cartesian coordinates, six numbers in the order xx, yy, zz, zy, zx, yx
+ * (the reference's Voigt order).  fp64, fixed reduction order, no atomics: two calls give bitwise identical results.
+ *
+ * Kinetic and AtomicNonlocal of ONE k-block, unsymmetrised, ACCUMULATED into stress_h[0..5] (kinetic) and
+ * stress_h[6..11] (nonlocal):
+ *   kinetic   -sum_n w_n sum_G q_a q_b |psi_n(G)|^2,                         q = B (G + k)
+ *   nonlocal   sum_n w_n 2 Re[ (P' psi_n)' D (dP_ab' psi_n) ],  dP_ab = -1/2 delta_ab P - 1/2 (q_a dP/dq_b + q_b dP/dq_a)
+ * psi_d / ld_psi / weight_h / col_start_h as dftk_mi_forces_nonlocal; species tables (rp_h, n_proj_h: 4 entries per
+ * species), species_of_atom_h and positions_h exactly as they were given to dftk_mi_build_projectors_hgh for this block
+ * (atoms WITH projectors only; col_start_h must be the column offsets that table implies and end at the block's n_p,
+ * else DFTK_MI_EINVAL).  The six derivative projectors are built on the fly for chunks of whole atoms and multiplied
+ * by the library's zgemm (Gamma-real block: real half-format products).  Extra workspace: at most
+ * max(512 MiB, 6 rows x the columns of one atom) for the derivative projectors plus (rows + 7 chunk columns) x band chunk
+ * complex numbers, never a multiple of the whole P.  A plane-wave sharded block is refused (DFTK_MI_EINVAL). */
+int dftk_mi_stress_kinetic_nonlocal(dftk_mi_kblock* kb, const double* recip_lattice_h, const double* kcoord_h,
+                                    int n_bands, const dftk_mi_cplx* psi_d, int64_t ld_psi, const double* weight_h,
+                                    int n_species, const double* rp_h, const int* n_proj_h, int n_atoms,
+                                    const int* species_of_atom_h, const double* positions_h, const int* col_start_h,
+                                    double* stress_h);
+/* AtomicLocal and Hartree sums over the cube from the TOTAL density rho_d (one forward FFT shared by both), written to
+ * out_h[14]; rho(G) in the normalisation of the energies, unpaired Nyquist entries and G = 0 dropped:
+ *   out[0..5]  = -sum_G Re[conj(rho(G)) sum_s S_s(G) ff_s'(|G|) / sqrt(Omega)] G_a G_b / |G|
+ *   out[6..11] =  sum_G 4 pi |rho(G)|^2 G_a G_b / |G|^4
+ *   out[12]    =  E_AtomicLocal,  out[13] = E_Hartree  (the -delta_ab E parts of both stresses)
+ * params / species / positions as dftk_mi_forces_local; n_atoms may be 0 (Hartree only). */
+int dftk_mi_stress_cube(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species, const double* params_h,
+                        int n_atoms, const int* species_of_atom_h, const double* positions_h, const double* rho_d,
+                        double* out_h);
+/* Exchange-correlation sums over n grid points (plain sums, the caller multiplies by the volume element):
+ *   out[0] = sum e  (0 when e_d is NULL),  out[1] = sum_s sum v_rho,s rho_s,
+ *   out[2..7] = sum v_sigma grad_a rho grad_b rho  (0 when vsigma_d is NULL)
+ * rho_d / vrho_d: n_spin (1 or 2) arrays of n values; grad_d: 3 arrays of n values (x, y, z; n_spin == 1 only). */
+int dftk_mi_stress_xc(dftk_mi_basis* basis, int64_t n, int n_spin, const double* rho_d, const double* vrho_d,
+                      const double* e_d, const double* vsigma_d, const double* grad_d, double* out_h);
+
 /* ---- local-potential pipeline of energy_hamiltonian (src/terms/Hamiltonian.jl:200-227) on the cube ----------
  * Hartree (src/terms/hartree.jl:50-59: V_H = irfft(green .* fft(rho)), E_H = 1/2 Re<V_H(G), rho(G)>), LDA exchange-
  * correlation (src/terms/xc.jl:84-160 with lda_x / lda_c_vwn / lda_c_pw, the functionals of `LDA()` and of the
