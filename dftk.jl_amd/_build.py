@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libdftk_mi355x.so")
 SOURCES = ["api.cpp", "comm.cpp", "lobpcg.cpp", "batch.cpp", "batch_kernels.hip", "fft_kernels.hip", "gemm_kernels.hip", "dense_kernels.hip", "eig_kernels.hip", "xc_kernels.hip", "setup_kernels.hip", "gamma_kernels.hip", "cube_kernels.hip", "mix_kernels.hip", "force_kernels.hip", "stress_kernels.hip"]
-
+HEADERS = ["common.h", "batch.h", "hgh_forms.h"]     # every header under csrc/: part of both hashes below
 
 HASHPATH = LIBPATH + ".srchash"
 
@@ -21,7 +21,7 @@ def source_hash() -> str:
     -- the .so is git-ignored but ships to the GPU box -- is never used silently, whatever its mtime says."""
     import hashlib
     h = hashlib.sha256()
-    deps = [os.path.join(CSRC, f) for f in sorted(SOURCES + ["common.h", "batch.h"])]
+    deps = [os.path.join(CSRC, f) for f in sorted(SOURCES + HEADERS)]
     deps.append(os.path.join(os.path.dirname(HERE), "include", "dftk_mi355x.h"))
     for d in deps:
         with open(d, "rb") as fh:
@@ -39,8 +39,8 @@ def needs_build() -> bool:
 def _tu_hash(path: str, flags: list[str]) -> str:
     import hashlib
     h = hashlib.sha256(" ".join(flags).encode())
-    for d in [path, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "batch.h"),
-              os.path.join(os.path.dirname(HERE), "include", "dftk_mi355x.h")]:
+    for d in [path] + [os.path.join(CSRC, f) for f in HEADERS] + [
+            os.path.join(os.path.dirname(HERE), "include", "dftk_mi355x.h")]:
         with open(d, "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
@@ -147,11 +147,9 @@ STRESS_CHECK_BIN = os.path.join(os.path.dirname(HERE), "tools", "bin", "host_str
 
 def build_host_stress_check(force: bool = False) -> str:
     """tools/host_stress_check.cpp -> tools/bin/host_stress_check: the host-only check of the closed forms of
-    csrc/stress_kernels.hip (derivative projectors, local form-factor derivative) against finite differences.  The
-    translation unit includes the kernels' source with DFTK_STRESS_HOST_CHECK and calls no HIP runtime function: it runs
-    without a GPU."""
-    kern = os.path.join(CSRC, "stress_kernels.hip")
-    src_time = max(os.path.getmtime(p) for p in (STRESS_CHECK_SRC, kern, os.path.join(CSRC, "common.h")))
+    csrc/hgh_forms.h (derivative projectors, local form-factor derivative) against finite differences.  The translation
+    unit includes that header alone and calls no HIP runtime function: it runs without a GPU."""
+    src_time = max(os.path.getmtime(p) for p in (STRESS_CHECK_SRC, os.path.join(CSRC, "hgh_forms.h")))
     if not force and os.path.exists(STRESS_CHECK_BIN) and os.path.getmtime(STRESS_CHECK_BIN) >= src_time:
         return STRESS_CHECK_BIN
     os.makedirs(os.path.dirname(STRESS_CHECK_BIN), exist_ok=True)

@@ -27,6 +27,16 @@ hipError_t dftk_scratch_malloc(void** p, size_t bytes) {
     if (e == hipSuccess && poison) e = hipMemset(*p, 0xFF, bytes);
     return e;
 }
+int scratch_grow(dftk_mi_basis* b, void** buf, size_t* have, size_t need) {
+    if (need <= *have) return 0;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (*buf) HIPCHK(hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
+    HIPCHK(dftk_scratch_malloc(buf, need));
+    *have = need;
+    return 0;
+}
 #ifndef DFTK_MI_SRC_HASH
 #define DFTK_MI_SRC_HASH "unknown"
 #endif
@@ -575,14 +585,7 @@ static int shard_buffers(dftk_mi_kblock* kb, int nb, cd** R1, cd** F, cd** G) {
     const size_t maxc = (size_t)(nb + p - 1) / p;
     const size_t each = (size_t)kb->n_G * (maxc ? maxc : 1);
     const size_t need = 3 * each * sizeof(cd);
-    if (need > kb->sh_bytes) {
-        HIPCHK(hipStreamSynchronize(kb->basis->stream));
-        if (kb->sh_buf) HIPCHK(hipFree(kb->sh_buf));
-        kb->sh_buf = nullptr;
-        kb->sh_bytes = 0;
-        HIPCHK(dftk_scratch_malloc((void**)&kb->sh_buf, need));
-        kb->sh_bytes = need;
-    }
+    CHK(scratch_grow(kb->basis, (void**)&kb->sh_buf, &kb->sh_bytes, need));
     *R1 = kb->sh_buf;
     *F = kb->sh_buf + each;
     *G = kb->sh_buf + 2 * each;
@@ -886,14 +889,7 @@ int apply_nonlocal_rows(dftk_mi_kblock* kb, int nb, const cd* P, int64_t ldP, in
     }
     // scratch for the two n_p x nb panels lives in T1 (free outside the FFT pipeline)
     const size_t need = 2 * (size_t)kb->n_p * nb * sizeof(cd);
-    if (need > b->T1_bytes) {
-        HIPCHK(hipStreamSynchronize(b->stream));
-        if (b->T1) HIPCHK(hipFree(b->T1));
-        b->T1 = nullptr;
-        b->T1_bytes = 0;
-        HIPCHK(dftk_scratch_malloc((void**)&b->T1, need));
-        b->T1_bytes = need;
-    }
+    CHK(scratch_grow(b, (void**)&b->T1, &b->T1_bytes, need));
     cd* Ppsi = b->T1;
     cd* DPpsi = b->T1 + (size_t)kb->n_p * nb;
     // (sharded block: P, psi, Hpsi are row slabs; the projections are partial sums -> one small all-reduce)

@@ -46,6 +46,43 @@ hipError_t dftk_scratch_malloc(void** p, size_t bytes);
         if (_s != 0) return _s;                   \
     } while (0)
 
+// 256-byte-aligned pieces of one workspace: take() every piece, grow the buffer to bytes(), then bind() sets the pointers
+struct WsCarver {
+    void** slot[16];
+    size_t at[16];
+    int n = 0;
+    size_t off = 0;
+    template <class T>
+    void take(T** p, size_t count) {
+        slot[n] = reinterpret_cast<void**>(p);
+        at[n++] = off;
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
+    }
+    size_t bytes() const { return off; }
+    void bind(void* base) const {
+        for (int i = 0; i < n; ++i) *slot[i] = static_cast<char*>(base) + at[i];
+    }
+};
+
+// sum of K values per thread over a workgroup of 256 (shared-memory tree, fixed order); on return v[0 .. K) of thread 0
+// holds the totals
+template <int K>
+__device__ inline void block_reduce(double* v) {
+    __shared__ double sh[K][256];
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h)
+#pragma unroll
+            for (int k = 0; k < K; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] = sh[k][0];
+}
+
 // ------------------------------------------------------------------------------------ 1-D plans
 #define DFTK_MAX_RADICES 32
 struct FftAxis {            // passed to kernels by value
@@ -242,6 +279,9 @@ int launch_kinetic_only(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi
 int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alpha, const cd* A,
           int64_t lda, const cd* B, int64_t ldb, cd beta, cd* C, int64_t ldc, int upper = 0);
 int ensure_ws(dftk_mi_basis* b, size_t bytes);
+// api.cpp: if *have < need: synchronise the stream, free *buf, dftk_scratch_malloc exactly `need` bytes, record them
+// (the contents are not kept)
+int scratch_grow(dftk_mi_basis* b, void** buf, size_t* have, size_t need);
 
 // dense_kernels.hip
 int dense_potrf_trtri(dftk_mi_basis* b, int n, cd* A, int64_t lda, cd* invR, int64_t ldi,
@@ -330,6 +370,16 @@ int build_projectors_hgh(dftk_mi_basis* b, int64_t n_rows, const int32_t* G_d, c
 
 int atomic_superposition(dftk_mi_kblock* cube_kb, int kind, const double* recip_h, int n_species, const double* par_h,
                          int n_atoms, const int* species_of_atom_h, const double* positions_h, double* out_d);
+// species indices in range and non-decreasing; `who` names the caller in the error text
+int check_species_grouped(const char* who, int n_species, int n_atoms, const int* species_of_atom_h);
+// per atom [t_x(nx) | t_y(ny) | t_z(nz)], t(i) = exp(-2 pi i g(i) r) with g the signed frequency of index i
+std::vector<cd> phase_tables_host(int nx, int ny, int nz, int n_atoms, const double* positions_h);
+// the columns of P: atom-major in the caller's order; within an atom (l, m, i): offset_l + n_l (m + l) + (i - 1)
+// (nonlocal.jl:205-244).  rp_h / nproj_h: 4 entries per species (l = 0..3).  col_start (optional): n_atoms + 1 offsets.
+struct ProjCol;
+int list_projector_columns(int n_species, const double* rp_h, const int* nproj_h, int n_atoms,
+                           const int* species_of_atom_h, const double* positions_h, std::vector<ProjCol>* cols,
+                           std::vector<int>* col_start = nullptr);
 
 // gamma_kernels.hip
 int gamma_tables_host(int nx, int ny, int nz, int64_t n_G, const int64_t* mapping, int64_t* n_half_out, int32_t* g,
@@ -370,6 +420,9 @@ int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, 
 int forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int nb, const cd* psi, int64_t ld_psi,
                     const double* weight_h, int n_atoms, const int* col_start_h, double* forces_h);
 int ensure_G3(dftk_mi_kblock* kb);       // kb->d_G3 (integer G of every sphere row), built on first use
+// out[r] = scale * sum_i in[r * n + i], one workgroup per row, fixed reduction order
+int launch_rowsum(dftk_mi_basis* b, int rows, int64_t n, const double* in, double scale, double* out);
+int launch_real_to_cplx(dftk_mi_basis* b, int64_t n, const double* x, cd* y);      // y = x + 0 i
 
 // stress_kernels.hip: dftk_mi_stress_kinetic_nonlocal / dftk_mi_stress_cube / dftk_mi_stress_xc
 int stress_kinetic_nonlocal(dftk_mi_kblock* kb, const double* recip_h, const double* kcoord_h, int nb, const cd* psi,

@@ -10,6 +10,7 @@
 // linear index (FFT order [0 .. (n-1)/2, -ceil((n-1)/2) .. -1], src/fft.jl:27-30) and, where needed, |B G|^2 from the
 // nine entries of the reciprocal lattice passed by value.
 #include "common.h"
+#include "hgh_forms.h"
 #include <cmath>
 #include <vector>
 
@@ -21,7 +22,6 @@ struct Lat9 {                 // recip_lattice, row-major: G_cart[a] = sum_j B[3
     double B[9];
 };
 
-__device__ __forceinline__ int signed_freq(int i, int n) { return i <= (n - 1) / 2 ? i : i - n; }
 __device__ __forceinline__ bool in_range(int g, int n) { return g >= -((n - 1) - (n - 1) / 2) && g <= (n - 1) / 2; }
 __device__ __forceinline__ int wrap(int g, int n) { return g < 0 ? g + n : g; }
 
@@ -117,9 +117,7 @@ __global__ __launch_bounds__(256) void k_multiplier(int nx, int ny, int nz, Lat9
         const double G2 = c0 * c0 + c1 * c1 + c2 * c2;
         double m;
         if (KIND == MULT_KERKER) {            // mixing.jl:61-72: G^2 / (kTF^2 + G^2), enforce_real!, DC copied from dF
-            const bool unpaired = ((nx % 2 == 0) && ix == nx / 2) || ((ny % 2 == 0) && iy == ny / 2) ||
-                                  ((nz % 2 == 0) && iz == nz / 2);
-            m = unpaired ? 0.0 : G2 / (p0 * p0 + G2);
+            m = unpaired_nyquist(ix, iy, iz, nx, ny, nz) ? 0.0 : G2 / (p0 * p0 + G2);
             if (i == 0) m = 1.0;              // d_rho .+= mean(dF) - mean(d_rho): the G = 0 coefficient of dF survives
         } else if (KIND == MULT_DIELECTRIC) { // mixing.jl:161-171 with C0 = 1 - eps_r
             const double C0 = 1.0 - p1;
@@ -165,17 +163,6 @@ Lat9 make_lat(const double* recip_h) {
 }
 }  // namespace dftk_cube
 using namespace dftk_cube;
-
-int cube_ws_ensure(dftk_mi_basis* b, size_t bytes) {
-    if (bytes <= b->dense_ws_bytes) return 0;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (b->dense_ws) HIPCHK(hipFree(b->dense_ws));
-    b->dense_ws = nullptr;
-    b->dense_ws_bytes = 0;
-    HIPCHK(dftk_scratch_malloc(&b->dense_ws, bytes));
-    b->dense_ws_bytes = bytes;
-    return 0;
-}
 
 // c_out = unnormalised forward FFT of the real cube f (* g); tmp: one complex cube of scratch
 int cube_forward_real(dftk_mi_kblock* cube_kb, const double* f, const double* g, cd* tmp, cd* c_out) {
@@ -279,7 +266,7 @@ int cube_symmetrize(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, cons
         b->symm_key = key;
         b->symm_n = n_sym;
     }
-    CHK(cube_ws_ensure(b, 2 * (size_t)N * sizeof(cd)));
+    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd)));
     cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
     cd* c2 = c1 + N;
     const double* d_tau = reinterpret_cast<const double*>(b->symm_tab);
@@ -299,7 +286,7 @@ int cube_fourier_filter(dftk_mi_kblock* cube_kb, int kind, const double* recip_h
     int64_t N;
     CHK(check_cube(cube_kb, &N));
     dftk_mi_basis* b = cube_kb->basis;
-    CHK(cube_ws_ensure(b, 2 * (size_t)N * sizeof(cd)));
+    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd)));
     cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
     cd* c2 = c1 + N;
     CHK(cube_forward_real(cube_kb, f, nullptr, c1, c2));

@@ -1337,17 +1337,6 @@ __global__ void k_gather_cols_real(int64_t n, const double* __restrict__ X, int6
 }
 
 // ======================================================================================== host side
-static int dws_ensure(dftk_mi_basis* b, void** buf, size_t* cur, size_t bytes) {
-    if (bytes <= *cur) return 0;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (*buf) HIPCHK(hipFree(*buf));
-    *buf = nullptr;
-    *cur = 0;
-    HIPCHK(dftk_scratch_malloc(buf, bytes));
-    *cur = bytes;
-    return 0;
-}
-
 // device -> pinned host words (host_fetch): the destination is host memory mapped into the device's address space
 __global__ void k_fetch_words(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t words) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x)
@@ -1444,7 +1433,7 @@ int dense_potrf_trtri(dftk_mi_basis* b, int n, cd* A, int64_t lda, cd* invR, int
     if (coop) {
         const int nb = (n + CCB - 1) / CCB, np = nb * CCB;
         const size_t need = ((size_t)nb * np * CCB + (size_t)nb * CCB * CCB) * sizeof(cd) + 64 * sizeof(int);
-        CHK(dws_ensure(b, &b->dense_ws, &b->dense_ws_bytes, need));
+        CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, need));
         cd* Lbuf = reinterpret_cast<cd*>(b->dense_ws);
         cd* Wbuf = Lbuf + (size_t)nb * np * CCB;
         int* flags = reinterpret_cast<int*>(Wbuf + (size_t)nb * CCB * CCB);
@@ -1555,7 +1544,7 @@ static int heev_impl(dftk_mi_basis* b, int n, cd* A, int64_t lda, double* W_h, c
     const size_t szW = (size_t)np * np * sizeof(cd);
     const size_t szU = (size_t)npairs * J2B * J2B * sizeof(cd);
     const size_t total = 3 * szW + 2 * szU + (size_t)np * (sizeof(double) + sizeof(int)) + 4096 * sizeof(double);
-    CHK(dws_ensure(b, &b->dense_ws, &b->dense_ws_bytes, total));   // per basis: one stream, one device
+    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, total));   // per basis: one stream, one device
     char* base = reinterpret_cast<char*>(b->dense_ws);
     ET* W = reinterpret_cast<ET*>(base);
     ET* Vw = reinterpret_cast<ET*>(base + szW);
@@ -1730,7 +1719,7 @@ static int heev_impl(dftk_mi_basis* b, int n, cd* A, int64_t lda, double* W_h, c
 
 int dense_input_norms(dftk_mi_basis* b, int n, const cd* A, int64_t lda, double* off2_out, double* dg2_out, double* im2_out) {
     const int redblocks = 64;
-    CHK(dws_ensure(b, &b->dense_ws, &b->dense_ws_bytes, 4096 * sizeof(double)));
+    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 4096 * sizeof(double)));
     double* d_red = reinterpret_cast<double*>(b->dense_ws);
     hipLaunchKernelGGL(k_offdiag_norm<cd>, dim3(redblocks), dim3(256), 0, b->stream, n, A, lda, d_red);
     std::vector<double> hred(3 * redblocks);

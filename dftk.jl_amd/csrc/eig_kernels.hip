@@ -186,14 +186,7 @@ __global__ __launch_bounds__(256) void k_eig_tall_to_cd(int n, const cd* __restr
 }
 
 int ws_ensure(dftk_mi_basis* b, size_t bytes) {
-    if (bytes <= b->eig_ws_bytes) return 0;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (b->eig_ws) HIPCHK(hipFree(b->eig_ws));
-    b->eig_ws = nullptr;
-    b->eig_ws_bytes = 0;
-    HIPCHK(dftk_scratch_malloc(&b->eig_ws, bytes));
-    b->eig_ws_bytes = bytes;
-    return 0;
+    return scratch_grow(b, &b->eig_ws, &b->eig_ws_bytes, bytes);
 }
 
 double a_of(double l) { return std::sqrt(3.0 / (1.0 + l + l * l)); }

@@ -18,6 +18,7 @@
 // block the REAL product over the half-sphere rows with the block's half-format projectors) and a small per-atom
 // contraction with the banded D.
 #include "common.h"
+#include "hgh_forms.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -27,22 +28,6 @@
 #define FL_KZ 2         // consecutive z planes per thread
 #define FL_WAVES 4      // waves per workgroup, stacked along y
 
-struct FMat3 {       // recip_lattice, column-major (B.b[3 j + i] = B_ij)
-    double b[9];
-};
-
-// the HGH local form factor of k_atomic_sum (setup_kernels.hip), same arithmetic; par = {rloc, Zion, c1..c4}
-__device__ inline double hgh_local_ff(const double* q, double p) {
-    const double rloc = q[0], Zion = q[1];
-    const double t2 = (p * rloc) * (p * rloc);
-    if (!(t2 > 0.0)) return 0.0;        // compensating background
-    const double P = q[2] + q[3] * (3.0 - t2) + q[4] * (15.0 - 10.0 * t2 + t2 * t2) +
-                     q[5] * (105.0 - 105.0 * t2 + 21.0 * t2 * t2 - t2 * t2 * t2);
-    return 4.0 * M_PI * rloc * rloc * (-Zion + sqrt(M_PI / 2.0) * rloc * t2 * P) * exp(-t2 / 2.0) / t2;
-}
-
-__device__ inline int fold(int i, int n) { return i <= (n - 1) / 2 ? i : i - n; }
-
 __device__ inline double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -50,22 +35,20 @@ __device__ inline double wave_sum(double v) {
 }
 
 // W_s(G) = ff_s(|G|) conj(R(G)) / N on the whole cube (one species), unpaired Nyquist entries zero
-__global__ __launch_bounds__(256) void k_forces_local_w(int nx, int ny, int nz, FMat3 B, const double* __restrict__ q,
+__global__ __launch_bounds__(256) void k_forces_local_w(int nx, int ny, int nz, Mat3 B, const double* __restrict__ q,
                                                         const cd* __restrict__ R, double inv_N, cd* __restrict__ W) {
     const int64_t N = (int64_t)nx * ny * nz;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= N) return;
     const int ix = (int)(idx % nx), iy = (int)((idx / nx) % ny), iz = (int)(idx / ((int64_t)nx * ny));
-    const bool unpaired = ((nx % 2 == 0) && ix == nx / 2) || ((ny % 2 == 0) && iy == ny / 2) || ((nz % 2 == 0) && iz == nz / 2);
-    if (unpaired) {
+    if (unpaired_nyquist(ix, iy, iz, nx, ny, nz)) {
         W[idx] = make_double2(0.0, 0.0);
         return;
     }
-    const double gx = (double)fold(ix, nx), gy = (double)fold(iy, ny), gz = (double)fold(iz, nz);
-    const double qx = gx * B.b[0] + gy * B.b[3] + gz * B.b[6];
-    const double qy = gx * B.b[1] + gy * B.b[4] + gz * B.b[7];
-    const double qz = gx * B.b[2] + gy * B.b[5] + gz * B.b[8];
-    const double ff = hgh_local_ff(q, sqrt(qx * qx + qy * qy + qz * qz)) * inv_N;
+    double qx, qy, qz;
+    recip_times(B, (double)signed_freq(ix, nx), (double)signed_freq(iy, ny), (double)signed_freq(iz, nz), &qx, &qy, &qz);
+    const double p = sqrt(qx * qx + qy * qy + qz * qz);
+    const double ff = hgh_local_ff(q, (p * q[0]) * (p * q[0])) * inv_N;
     const cd r = R[idx];
     W[idx] = make_double2(ff * r.x, -ff * r.y);
 }
@@ -82,7 +65,7 @@ __global__ __launch_bounds__(64 * FL_WAVES, 4) void k_forces_local(int nx, int n
     const int iz0 = blockIdx.z * FL_KZ;
     const int64_t wid = ((int64_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * FL_WAVES + wave;
     const int ixc = ix < nx ? ix : nx - 1;
-    const double gx = (double)fold(ixc, nx);
+    const double gx = (double)signed_freq(ixc, nx);
     const int64_t tstride = (int64_t)nx + ny + nz;
     cd w[FL_KZ][FL_KY];
 #pragma unroll
@@ -109,14 +92,14 @@ __global__ __launch_bounds__(64 * FL_WAVES, 4) void k_forces_local(int nx, int n
                 const cd t = ty[iy < ny ? iy : ny - 1];
                 const cd v = w[kz][ky];
                 const double ur = v.x * t.x - v.y * t.y, ui = v.x * t.y + v.y * t.x;
-                const double gy = (double)fold(iy < ny ? iy : ny - 1, ny);
+                const double gy = (double)signed_freq(iy < ny ? iy : ny - 1, ny);
                 s0r += ur;
                 s0i += ui;
                 syr += gy * ur;
                 syi += gy * ui;
             }
             const cd t = tz[iz < nz ? iz : nz - 1];
-            const double gz = (double)fold(iz < nz ? iz : nz - 1, nz);
+            const double gz = (double)signed_freq(iz < nz ? iz : nz - 1, nz);
             const double ar = s0r * t.x - s0i * t.y, ai = s0r * t.y + s0i * t.x;
             S0r += ar;
             S0i += ai;
@@ -141,32 +124,25 @@ __global__ __launch_bounds__(64 * FL_WAVES, 4) void k_forces_local(int nx, int n
 // out[r] = scale * sum_i in[r * n + i], one workgroup per row, fixed reduction order
 __global__ __launch_bounds__(256) void k_rowsum(int64_t n, const double* __restrict__ in, double scale,
                                                 double* __restrict__ out) {
-    __shared__ double sh[256];
     const double* x = in + (int64_t)blockIdx.x * n;
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 256) s += x[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = scale * sh[0];
+    block_reduce<1>(&s);
+    if (threadIdx.x == 0) out[blockIdx.x] = scale * s;
+}
+int launch_rowsum(dftk_mi_basis* b, int rows, int64_t n, const double* in, double scale, double* out) {
+    hipLaunchKernelGGL(k_rowsum, dim3((unsigned)rows), dim3(256), 0, b->stream, n, in, scale, out);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 __global__ __launch_bounds__(256) void k_real_to_cplx(int64_t n, const double* __restrict__ x, cd* __restrict__ y) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) y[i] = make_double2(x[i], 0.0);
 }
-
-static int grow(cd** buf, size_t* have, size_t need, hipStream_t s) {
-    if (need <= *have) return 0;
-    HIPCHK(hipStreamSynchronize(s));
-    if (*buf) HIPCHK(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    HIPCHK(dftk_scratch_malloc((void**)buf, need));
-    *have = need;
+int launch_real_to_cplx(dftk_mi_basis* b, int64_t n, const double* x, cd* y) {
+    hipLaunchKernelGGL(k_real_to_cplx, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, n, x, y);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -182,61 +158,30 @@ int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, 
     if (n_atoms < 0 || n_species < 0 || (n_atoms > 0 && (!species_of_atom_h || !positions_h || !par_h)) || !rho_d ||
         (n_atoms > 0 && !forces_h))
         return DFTK_MI_EINVAL;
-    for (int a = 0; a < n_atoms; ++a) {
-        if (species_of_atom_h[a] < 0 || species_of_atom_h[a] >= n_species) return DFTK_MI_EINVAL;
-        if (a > 0 && species_of_atom_h[a] < species_of_atom_h[a - 1]) {
-            dftk_set_error("forces_local: atoms must be grouped by species");
-            return DFTK_MI_EINVAL;
-        }
-    }
+    CHK(check_species_grouped("forces_local", n_species, n_atoms, species_of_atom_h));
     if (n_atoms == 0) return 0;
     // R(G): forward cube DFT of the total density (unnormalised), in the dense workspace as atomic_superposition uses it
-    const size_t need = 2 * (size_t)N * sizeof(cd);
-    if (need > b->dense_ws_bytes) {
-        HIPCHK(hipStreamSynchronize(b->stream));
-        if (b->dense_ws) HIPCHK(hipFree(b->dense_ws));
-        b->dense_ws = nullptr;
-        b->dense_ws_bytes = 0;
-        HIPCHK(dftk_scratch_malloc(&b->dense_ws, need));
-        b->dense_ws_bytes = need;
-    }
+    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd)));
     cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
     cd* c2 = c1 + N;
-    hipLaunchKernelGGL(k_real_to_cplx, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, N, rho_d, c1);
-    HIPCHK(hipGetLastError());
+    CHK(launch_real_to_cplx(b, N, rho_d, c1));
     CHK(launch_fft_from_cube(cube_kb, c1, c2));          // (c1 is overwritten by the transform)
-    // 1-D phase tables per atom: [t_x(nx) | t_y(ny) | t_z(nz)], t(i) = exp(-2 pi i g(i) r)
-    const int dims[3] = {nx, ny, nz};
-    const int64_t tstride = (int64_t)nx + ny + nz;
-    std::vector<cd> tab((size_t)n_atoms * tstride);
-    for (int a = 0; a < n_atoms; ++a) {
-        cd* t = tab.data() + (size_t)a * tstride;
-        for (int d = 0; d < 3; ++d) {
-            const int n = dims[d];
-            for (int i = 0; i < n; ++i) {
-                const int g = i <= (n - 1) / 2 ? i : i - n;
-                const double ph = -2.0 * M_PI * (double)g * positions_h[3 * a + d];
-                *t++ = make_double2(cos(ph), sin(ph));
-            }
-        }
-    }
+    const std::vector<cd> tab = phase_tables_host(nx, ny, nz, n_atoms, positions_h);
     const dim3 grid((unsigned)((nx + 63) / 64), (unsigned)((ny + FL_WAVES * FL_KY - 1) / (FL_WAVES * FL_KY)),
                     (unsigned)((nz + FL_KZ - 1) / FL_KZ));
     const int64_t n_waves = (int64_t)grid.x * grid.y * grid.z * FL_WAVES;
     // workspace: tables, per-wave partial sums, result (W_s goes into c1, free again after the transform)
-    const size_t b_tab = tab.size() * sizeof(cd), b_part = (size_t)3 * n_atoms * n_waves * sizeof(double),
-                 b_out = (size_t)3 * n_atoms * sizeof(double), b_par = (size_t)n_species * 8 * sizeof(double);
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    CHK(ensure_ws(b, up(b_tab) + up(b_part) + up(b_out) + up(b_par)));
-    char* ws = reinterpret_cast<char*>(b->ws);
-    cd* d_tab = reinterpret_cast<cd*>(ws);
-    double* d_part = reinterpret_cast<double*>(ws + up(b_tab));
-    double* d_out = reinterpret_cast<double*>(ws + up(b_tab) + up(b_part));
-    double* d_par = reinterpret_cast<double*>(ws + up(b_tab) + up(b_part) + up(b_out));
-    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), b_tab, hipMemcpyHostToDevice, b->stream));
+    const size_t b_out = (size_t)3 * n_atoms * sizeof(double), b_par = (size_t)n_species * 8 * sizeof(double);
+    cd* d_tab;
+    double *d_part, *d_out, *d_par;
+    WsCarver ws;
+    ws.take(&d_tab, tab.size()), ws.take(&d_part, (size_t)3 * n_atoms * n_waves);
+    ws.take(&d_out, (size_t)3 * n_atoms), ws.take(&d_par, (size_t)n_species * 8);
+    CHK(ensure_ws(b, ws.bytes()));
+    ws.bind(b->ws);
+    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(cd), hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemcpyAsync(d_par, par_h, b_par, hipMemcpyHostToDevice, b->stream));
-    FMat3 B;
-    for (int i = 0; i < 9; ++i) B.b[i] = recip_h[i];
+    const Mat3 B = make_mat3(recip_h);
     for (int a0 = 0; a0 < n_atoms;) {
         int a1 = a0 + 1;
         while (a1 < n_atoms && species_of_atom_h[a1] == species_of_atom_h[a0]) ++a1;
@@ -248,9 +193,7 @@ int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, 
         HIPCHK(hipGetLastError());
         a0 = a1;
     }
-    hipLaunchKernelGGL(k_rowsum, dim3((unsigned)(3 * n_atoms)), dim3(256), 0, b->stream, n_waves, (const double*)d_part,
-                       -2.0 * M_PI, d_out);
-    HIPCHK(hipGetLastError());
+    CHK(launch_rowsum(b, 3 * n_atoms, n_waves, d_part, -2.0 * M_PI, d_out));
     HIPCHK(hipMemcpyAsync(forces_h, d_out, b_out, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));     // (host tables and b->ws are free again)
     return 0;
@@ -296,7 +239,6 @@ __global__ __launch_bounds__(256) void k_nl_operands_half(int64_t rows, int nb, 
 __global__ __launch_bounds__(256) void k_nl_contract(int n_p, int nb, const cd* __restrict__ Q, const double* __restrict__ D,
                                                      int bw, const int* __restrict__ col_start, const double* __restrict__ w,
                                                      int n_atoms, double* __restrict__ acc) {
-    __shared__ double sh[3][256];
     const int a = blockIdx.x;
     const int c0 = col_start[a], c1 = col_start[a + 1], na = c1 - c0;
     double f[3] = {0.0, 0.0, 0.0};
@@ -321,18 +263,10 @@ __global__ __launch_bounds__(256) void k_nl_contract(int n_p, int nb, const cd* 
             }
         }
     }
-#pragma unroll
-    for (int al = 0; al < 3; ++al) sh[al][threadIdx.x] = f[al];
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h)
-#pragma unroll
-            for (int al = 0; al < 3; ++al) sh[al][threadIdx.x] += sh[al][threadIdx.x + h];
-        __syncthreads();
-    }
+    block_reduce<3>(f);
     if (threadIdx.x == 0)
 #pragma unroll
-        for (int al = 0; al < 3; ++al) acc[3 * a + al] += sh[al][0];
+        for (int al = 0; al < 3; ++al) acc[3 * a + al] += f[al];
     if (bad) acc[3 * n_atoms] = 1.0;     // (benign race: every writer stores the same value)
 }
 
@@ -346,9 +280,9 @@ int ensure_G3(dftk_mi_kblock* kb) {
     for (int64_t c = 0; c < kb->n_G; ++c) {
         const int64_t lin = (*kb->h_mapping)[c];
         const int ix = (int)(lin % nx), iy = (int)((lin / nx) % ny), iz = (int)(lin / ((int64_t)nx * ny));
-        G[3 * c + 0] = ix <= (nx - 1) / 2 ? ix : ix - nx;
-        G[3 * c + 1] = iy <= (ny - 1) / 2 ? iy : iy - ny;
-        G[3 * c + 2] = iz <= (nz - 1) / 2 ? iz : iz - nz;
+        G[3 * c + 0] = signed_freq(ix, nx);
+        G[3 * c + 1] = signed_freq(iy, ny);
+        G[3 * c + 2] = signed_freq(iz, nz);
     }
     HIPCHK(hipMalloc((void**)&kb->d_G3, G.size() * sizeof(int)));
     HIPCHK(hipMemcpy(kb->d_G3, G.data(), G.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -389,17 +323,14 @@ int forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int nb, const cd
     const size_t per_band = 4 * (size_t)(rows + n_p) * sizeof(cd);
     const size_t budget = std::max(b->T1_bytes, (size_t)512 << 20);
     const int cb = (int)std::max<size_t>(1, std::min<size_t>((size_t)nb, budget / per_band));
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_panel = up((size_t)rows * 4 * cb * sizeof(cd)), b_Q = up((size_t)n_p * 4 * cb * sizeof(cd)),
-                 b_w = up((size_t)nb * sizeof(double)), b_acc = up((size_t)(3 * n_atoms + 1) * sizeof(double)),
-                 b_cs = up((size_t)(n_atoms + 1) * sizeof(int));
-    CHK(grow(&b->T1, &b->T1_bytes, b_panel + b_Q + b_w + b_acc + b_cs, b->stream));
-    char* base = reinterpret_cast<char*>(b->T1);
-    cd* Z = reinterpret_cast<cd*>(base);
-    cd* Q = reinterpret_cast<cd*>(base + b_panel);
-    double* d_w = reinterpret_cast<double*>(base + b_panel + b_Q);
-    double* d_acc = reinterpret_cast<double*>(base + b_panel + b_Q + b_w);
-    int* d_cs = reinterpret_cast<int*>(base + b_panel + b_Q + b_w + b_acc);
+    cd *Z, *Q;
+    double *d_w, *d_acc;
+    int* d_cs;
+    WsCarver ws;
+    ws.take(&Z, (size_t)rows * 4 * cb), ws.take(&Q, (size_t)n_p * 4 * cb), ws.take(&d_w, (size_t)nb);
+    ws.take(&d_acc, (size_t)(3 * n_atoms + 1)), ws.take(&d_cs, (size_t)(n_atoms + 1));
+    CHK(scratch_grow(b, (void**)&b->T1, &b->T1_bytes, ws.bytes()));
+    ws.bind(b->T1);
     HIPCHK(hipMemcpyAsync(d_w, weight_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemcpyAsync(d_cs, col_start_h, (size_t)(n_atoms + 1) * sizeof(int), hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemsetAsync(d_acc, 0, (size_t)(3 * n_atoms + 1) * sizeof(double), b->stream));

@@ -407,15 +407,7 @@ void gamma_destroy(GammaReal* gr) {
 
 int gamma_ensure_buf(dftk_mi_kblock* kb, size_t elems) {
     GammaReal* gr = kb->gr;
-    const size_t need = elems * sizeof(cd);
-    if (need <= gr->buf_bytes) return 0;
-    HIPCHK(hipStreamSynchronize(kb->basis->stream));
-    if (gr->buf) HIPCHK(hipFree(gr->buf));
-    gr->buf = nullptr;
-    gr->buf_bytes = 0;
-    HIPCHK(dftk_scratch_malloc((void**)&gr->buf, need));
-    gr->buf_bytes = need;
-    return 0;
+    return scratch_grow(kb->basis, (void**)&gr->buf, &gr->buf_bytes, elems * sizeof(cd));
 }
 
 int gamma_compress(dftk_mi_kblock* kb, int m, const cd* X, int64_t ldx, cd* H, int64_t ldh) {

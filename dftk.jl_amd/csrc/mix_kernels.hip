@@ -11,12 +11,11 @@
 // device-visible landing zone (b->h_fetch) and summed on the host in block order -- deterministic, one stream
 // synchronisation per Krylov step / Anderson step, no device -> host blit.
 #include "common.h"
+#include "hgh_forms.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
-
-int cube_ws_ensure(dftk_mi_basis* b, size_t bytes);   // cube_kernels.hip
 
 namespace dftk_mix {
 const int MB = 128;          // blocks of every reduction kernel (partials are summed in block order)
@@ -56,7 +55,6 @@ __device__ __forceinline__ double m_sum_partials(const double* part, int stride,
     __syncthreads();
     return sh[7];
 }
-__device__ __forceinline__ int signed_freq(int i, int n) { return i <= (n - 1) / 2 ? i : i - n; }
 
 // c = sum over the components of x (as a complex cube): the total density the Hartree kernel acts on
 __global__ __launch_bounds__(MT) void k_total_r2c(int64_t N, int ncomp, const double* __restrict__ x, cd* __restrict__ c) {
@@ -640,7 +638,7 @@ extern "C" int dftk_mi_chi0_mix(dftk_mi_kblock* cube_kb, int n_comp, const doubl
     const size_t fixed = 3 * (size_t)N * sizeof(cd) + (size_t)N * sizeof(double) + 4 * MB * sizeof(double) + 256;
     int vcap = std::min(krylovdim + 1, 8);
     auto total_bytes = [&](int cap) { return fixed + (size_t)(3 + cap) * Nt * sizeof(double); };
-    CHK(cube_ws_ensure(b, total_bytes(vcap)));
+    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, total_bytes(vcap)));
     MixWork w;
     auto bind = [&]() {
         char* p = reinterpret_cast<char*>(b->dense_ws);

@@ -307,7 +307,6 @@ int xc_gga_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const doubl
 }
 
 // cube_kernels.hip
-int cube_ws_ensure(dftk_mi_basis* b, size_t bytes);
 int cube_forward_real(dftk_mi_kblock* cube_kb, const double* f, const double* g, cd* tmp, cd* c_out);
 int cube_gradient_multiply(dftk_mi_kblock* cube_kb, const double* recip_h, int alpha, const cd* c, cd* out, bool accumulate);
 int cube_backward_real(dftk_mi_kblock* cube_kb, const cd* c, cd* tmp, double scale, double* out);
@@ -330,7 +329,7 @@ int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const 
                        "(mask %d)", fun_mask);
         return DFTK_MI_EINVAL;
     }
-    CHK(cube_ws_ensure(b, 2 * (size_t)N * sizeof(cd) + 3 * XC_BLOCKS * sizeof(double)));
+    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd) + 3 * XC_BLOCKS * sizeof(double)));
     cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
     cd* c2 = c1 + N;
     double* partial = reinterpret_cast<double*>(c2 + N);
@@ -378,7 +377,7 @@ int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const do
     // complex cubes c1, c2 (+ three more and 7 real cubes for GGA) + reduction partials in the basis' dense workspace
     const size_t need = (gga_mask ? 5 : 2) * (size_t)N * sizeof(cd) + (gga_mask ? 7 : 0) * (size_t)N * sizeof(double) +
                         3 * XC_BLOCKS * sizeof(double);
-    CHK(cube_ws_ensure(b, need));
+    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, need));
     cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
     cd* c2 = c1 + N;
     cd* g3 = gga_mask ? c2 + N : nullptr;          // three cubes behind one another (one FFT pipeline for the three)

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .symmetry import symmetrize_forces
-from .terms import energy_forces_ewald, total_density
+from .terms import energy_forces_ewald, local_species_tables, occupied_block, total_density
 
 _NO_FORCES = ("Kinetic", "Hartree", "PspCorrection", "Entropy")
 
@@ -27,15 +27,7 @@ def _group_order(model):
 def _forces_local(basis, rho):
     model = basis.model
     order = _group_order(model)
-    par = np.zeros((len(model.atom_groups), 8))
-    species = []
-    for s_idx, g in enumerate(model.atom_groups):
-        psp = model.atoms[g[0]].psp
-        vals = [psp.rloc, float(psp.Zion)] + list(psp.cloc)[:4]
-        par[s_idx, :len(vals)] = vals
-        species += [s_idx] * len(g)
-    species = np.asarray(species, dtype=np.int32)
-    positions = np.ascontiguousarray([np.asarray(model.positions[ia], dtype=float) for ia in order], dtype=np.float64)
+    par, species, positions = local_species_tables(model)
     Bh = np.asfortranarray(model.recip_lattice, dtype=np.float64)
     rho_tot = total_density(rho).to(torch.float64).contiguous()
     out = np.zeros((len(order), 3))
@@ -69,21 +61,14 @@ def _forces_nonlocal(basis, psi, occupation):
 
     def one(ik, psik):
         kpt = basis.kpoints[ik]
-        occ = np.asarray(occupation[ik], dtype=float)[:psik.shape[0]]
-        keep = np.nonzero(occ != 0)[0]
         out = np.zeros((n_atoms, 3))
-        if len(keep) == 0:
+        block = occupied_block(basis, ik, psik, occupation)
+        if block is None:
             return out
-        if len(keep) == keep[-1] + 1:
-            ps = psik[:len(keep)]
-        else:
-            ps = psik.index_select(0, torch.as_tensor(keep, device=psik.device))
-        if ps.stride(1) != 1:
-            ps = ps.contiguous()
-        w = np.ascontiguousarray(basis.kweights[ik] * occ[keep], dtype=np.float64)
+        ps, w = block
         kh = np.ascontiguousarray(kpt.coordinate, dtype=np.float64)
         basis.pre_call()
-        _lib.check(basis.lib.dftk_mi_forces_nonlocal(kpt.handle, kh.ctypes.data, len(keep), ps.data_ptr(), ps.stride(0),
+        _lib.check(basis.lib.dftk_mi_forces_nonlocal(kpt.handle, kh.ctypes.data, len(w), ps.data_ptr(), ps.stride(0),
                                                      w.ctypes.data, n_atoms, col_start.ctypes.data, out.ctypes.data))
         return out
 

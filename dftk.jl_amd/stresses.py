@@ -13,9 +13,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .forces import _check_nlcc, _group_order
+from .forces import _check_nlcc
 from .symmetry import symmetrize_stresses
-from .terms import (_DENSITY_THRESHOLD, _GGA_BITS, _LDA_BITS, _SPIN_LDA, stress_ewald, total_density)
+from .terms import (_DENSITY_THRESHOLD, _GGA_BITS, _LDA_BITS, _SPIN_LDA, local_species_tables, occupied_block,
+                    projector_species_tables, stress_ewald, total_density)
 
 
 # ------------------------------------------------------------------------------------------ Voigt notation
@@ -44,29 +45,12 @@ def full_strain_to_voigt(e):
 
 
 # ------------------------------------------------------------------------------------------ device terms
+_projector_tables = projector_species_tables      # (the name this module had for it; tests import it from here)
+
+
 def _check_unsharded(basis):
     if basis.comm_pw.size > 1:
         raise NotImplementedError("stresses of a basis whose plane waves are sharded over comm_pw are not implemented")
-
-
-def _projector_tables(model):
-    """Species tables, species index and positions of the atoms WITH projectors, as build_projection_vectors_abi lists
-    them (the column order of P)."""
-    groups = [g for g in model.atom_groups if model.atoms[g[0]].psp.count_n_proj() > 0]
-    rp = np.zeros((max(len(groups), 1), 4))
-    nproj = np.zeros((max(len(groups), 1), 4), dtype=np.int32)
-    species, positions, starts = [], [], [0]
-    for s_idx, g in enumerate(groups):
-        psp = model.atoms[g[0]].psp
-        for l in range(psp.lmax + 1):
-            rp[s_idx, l] = psp.rp[l]
-            nproj[s_idx, l] = psp.count_n_proj_radial(l)
-        for ia in g:
-            species.append(s_idx)
-            positions.append(np.asarray(model.positions[ia], dtype=float))
-            starts.append(starts[-1] + psp.count_n_proj())
-    return (len(groups), rp, nproj, np.asarray(species, dtype=np.int32),
-            np.ascontiguousarray(np.asarray(positions, dtype=np.float64).reshape(-1, 3)), np.asarray(starts, dtype=np.int32))
 
 
 def _kinetic_nonlocal(basis, psi, occupation):
@@ -75,7 +59,7 @@ def _kinetic_nonlocal(basis, psi, occupation):
     model = basis.model
     T = basis.terms
     have_P = T is not None and T.P is not None
-    n_species, rp, nproj, species, positions, col_start = _projector_tables(model)
+    n_species, rp, nproj, species, positions, col_start = projector_species_tables(model)
     if not have_P:
         n_species, species, col_start = 0, species[:0], col_start[:1]
     n_atoms = len(species)
@@ -83,22 +67,15 @@ def _kinetic_nonlocal(basis, psi, occupation):
 
     def one(ik, psik):
         kpt = basis.kpoints[ik]
-        occ = np.asarray(occupation[ik], dtype=float)[:psik.shape[0]]
-        keep = np.nonzero(occ != 0)[0]
         out = np.zeros(12)
-        if len(keep) == 0:
+        block = occupied_block(basis, ik, psik, occupation)
+        if block is None:
             return out
-        if len(keep) == keep[-1] + 1:
-            ps = psik[:len(keep)]
-        else:
-            ps = psik.index_select(0, torch.as_tensor(keep, device=psik.device))
-        if ps.stride(1) != 1:
-            ps = ps.contiguous()
-        w = np.ascontiguousarray(basis.kweights[ik] * occ[keep], dtype=np.float64)
+        ps, w = block
         kh = np.ascontiguousarray(kpt.coordinate, dtype=np.float64)
         basis.pre_call()
         _lib.check(basis.lib.dftk_mi_stress_kinetic_nonlocal(
-            kpt.handle, Bh.ctypes.data, kh.ctypes.data, len(keep), ps.data_ptr(), ps.stride(0), w.ctypes.data, n_species,
+            kpt.handle, Bh.ctypes.data, kh.ctypes.data, len(w), ps.data_ptr(), ps.stride(0), w.ctypes.data, n_species,
             rp.ctypes.data, nproj.ctypes.data, n_atoms, species.ctypes.data if n_atoms else None,
             positions.ctypes.data if n_atoms else None, col_start.ctypes.data, out.ctypes.data))
         return out
@@ -116,17 +93,8 @@ def _kinetic_nonlocal(basis, psi, occupation):
 def _local_hartree(basis, rho):
     """(sigma_local, sigma_hartree) from one ``dftk_mi_stress_cube`` call."""
     model = basis.model
-    order = _group_order(model)
-    par = np.zeros((len(model.atom_groups), 8))
-    species = []
-    for s_idx, g in enumerate(model.atom_groups):
-        psp = model.atoms[g[0]].psp
-        vals = [psp.rloc, float(psp.Zion)] + list(psp.cloc)[:4]
-        par[s_idx, :len(vals)] = vals
-        species += [s_idx] * len(g)
-    species = np.asarray(species, dtype=np.int32)
-    positions = np.ascontiguousarray([np.asarray(model.positions[ia], dtype=float) for ia in order], dtype=np.float64)
-    n_atoms = len(order) if "AtomicLocal" in model.term_types else 0
+    par, species, positions = local_species_tables(model)
+    n_atoms = len(species) if "AtomicLocal" in model.term_types else 0
     Bh = np.asfortranarray(model.recip_lattice, dtype=np.float64)
     rho_tot = total_density(rho).to(torch.float64).contiguous()
     out = np.zeros(14)

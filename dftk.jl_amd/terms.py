@@ -36,29 +36,77 @@ def _structure_factor_cube(basis, r):
     return pz[:, None, None] * py[None, :, None] * px[None, None, :]
 
 
-def _atomic_superposition_abi(basis, kind, params_of, per_atom=False):
-    """One library call (``dftk_mi_atomic_superposition``) for sum_s ff_s(|G|) sum_a e^{-2 pi i G.r_a} -> real cube.
-    ``per_atom``: ``params_of(element, atom index)`` -- every atom is its own "species" (per-atom coefficients of the
-    spin-density guess, density_methods.jl:126-152)."""
-    model = basis.model
+def _hgh_local_params(el):
+    return [el.psp.rloc, float(el.psp.Zion)] + list(el.psp.cloc)[:4]
+
+
+def local_species_tables(model, params_of=_hgh_local_params):
+    """``(par, species, positions)`` of the local-term kernels, atoms in species-group order: one row of up to 8
+    parameters per group (``params_of(element)``, default the HGH local part {rloc, Zion, c1..c4}), the int32 group index
+    of every atom and the float64 (n_atoms, 3) reduced positions."""
+    par = np.zeros((len(model.atom_groups), 8))
     species, positions = [], []
-    if per_atom:
-        par = np.zeros((len(model.atoms), 8))
-        for ia, el in enumerate(model.atoms):
-            vals = params_of(el, ia)
-            par[ia, :len(vals)] = vals
-            species.append(ia)
-            positions.append(np.asarray(model.positions[ia], dtype=float))
-    else:
-        par = np.zeros((len(model.atom_groups), 8))
-    for s_idx, g in enumerate(model.atom_groups if not per_atom else []):
+    for s_idx, g in enumerate(model.atom_groups):
         vals = params_of(model.atoms[g[0]])
         par[s_idx, :len(vals)] = vals
         for ia in g:
             species.append(s_idx)
             positions.append(np.asarray(model.positions[ia], dtype=float))
-    species = np.asarray(species, dtype=np.int32)
-    positions = np.ascontiguousarray(np.asarray(positions, dtype=np.float64))
+    return (par, np.asarray(species, dtype=np.int32),
+            np.ascontiguousarray(np.asarray(positions, dtype=np.float64).reshape(-1, 3)))
+
+
+def projector_species_tables(model):
+    """``(n_species, rp, nproj, species, positions, col_start)`` of the atoms WITH projectors, in species-group order (the
+    column order of P): rp / nproj hold 4 entries (l = 0..3) per group, ``col_start`` the n_atoms + 1 column offsets."""
+    groups = [g for g in model.atom_groups if model.atoms[g[0]].psp.count_n_proj() > 0]
+    rp = np.zeros((max(len(groups), 1), 4))
+    nproj = np.zeros((max(len(groups), 1), 4), dtype=np.int32)
+    species, positions, starts = [], [], [0]
+    for s_idx, g in enumerate(groups):
+        psp = model.atoms[g[0]].psp
+        for l in range(psp.lmax + 1):
+            rp[s_idx, l] = psp.rp[l]
+            nproj[s_idx, l] = psp.count_n_proj_radial(l)
+        for ia in g:
+            species.append(s_idx)
+            positions.append(np.asarray(model.positions[ia], dtype=float))
+            starts.append(starts[-1] + psp.count_n_proj())
+    return (len(groups), rp, nproj, np.asarray(species, dtype=np.int32),
+            np.ascontiguousarray(np.asarray(positions, dtype=np.float64).reshape(-1, 3)), np.asarray(starts, dtype=np.int32))
+
+
+def occupied_block(basis, ik, psik, occupation):
+    """``(ps, weights)`` of the occupied bands of k-point ``ik``: the rows of ``psik`` with non-zero occupation (a view
+    when they are the leading rows), unit stride along the plane waves, and kweight * occupation as float64; None when
+    no band is occupied."""
+    occ = np.asarray(occupation[ik], dtype=float)[:psik.shape[0]]
+    keep = np.nonzero(occ != 0)[0]
+    if len(keep) == 0:
+        return None
+    if len(keep) == keep[-1] + 1:
+        ps = psik[:len(keep)]
+    else:
+        ps = psik.index_select(0, torch.as_tensor(keep, device=psik.device))
+    if ps.stride(1) != 1:
+        ps = ps.contiguous()
+    return ps, np.ascontiguousarray(basis.kweights[ik] * occ[keep], dtype=np.float64)
+
+
+def _atomic_superposition_abi(basis, kind, params_of, per_atom=False):
+    """One library call (``dftk_mi_atomic_superposition``) for sum_s ff_s(|G|) sum_a e^{-2 pi i G.r_a} -> real cube.
+    ``per_atom``: ``params_of(element, atom index)`` -- every atom is its own "species" (per-atom coefficients of the
+    spin-density guess, density_methods.jl:126-152)."""
+    model = basis.model
+    if per_atom:
+        par = np.zeros((len(model.atoms), 8))
+        for ia, el in enumerate(model.atoms):
+            vals = params_of(el, ia)
+            par[ia, :len(vals)] = vals
+        species = np.arange(len(model.atoms), dtype=np.int32)
+        positions = np.ascontiguousarray(np.asarray(model.positions, dtype=np.float64).reshape(-1, 3))
+    else:
+        par, species, positions = local_species_tables(model, params_of)
     Bh = np.asfortranarray(model.recip_lattice, dtype=np.float64)
     nx, ny, nz = basis.fft_size
     out = torch.empty((nz, ny, nx), dtype=torch.float64, device=basis.device)
@@ -77,7 +125,7 @@ def compute_local_potential(basis):
     """local.jl:108-138."""
     model = basis.model
     if _use_setup_abi(basis):
-        return _atomic_superposition_abi(basis, 0, lambda el: [el.psp.rloc, float(el.psp.Zion)] + list(el.psp.cloc)[:4])
+        return _atomic_superposition_abi(basis, 0, _hgh_local_params)
     Gnorm = torch.linalg.norm(basis.G_vectors_cart_cube(), dim=-1)
     pot = torch.zeros(Gnorm.shape, dtype=torch.complex128, device=basis.device)
     for group in model.atom_groups:
@@ -111,28 +159,15 @@ def build_projection_vectors_abi(basis, kpt):
     into P; same column order as the torch construction below (species groups, atoms, (l, m, i))."""
     import ctypes as C
     model = basis.model
-    groups = [g for g in model.atom_groups if model.atoms[g[0]].psp.count_n_proj() > 0]
-    if not groups:
+    n_species, rp, nproj, species, positions, _ = projector_species_tables(model)
+    if n_species == 0:
         return None
-    rp = np.zeros((len(groups), 4))
-    nproj = np.zeros((len(groups), 4), dtype=np.int32)
-    species, positions = [], []
-    for s_idx, g in enumerate(groups):
-        psp = model.atoms[g[0]].psp
-        for l in range(psp.lmax + 1):
-            rp[s_idx, l] = psp.rp[l]
-            nproj[s_idx, l] = psp.count_n_proj_radial(l)
-        for ia in g:
-            species.append(s_idx)
-            positions.append(np.asarray(model.positions[ia], dtype=float))
-    species = np.asarray(species, dtype=np.int32)
-    positions = np.ascontiguousarray(np.asarray(positions, dtype=np.float64))
     G32 = kpt.G_vectors[kpt.row0:kpt.row1].to(torch.int32).contiguous()
     Bh = np.asfortranarray(model.recip_lattice, dtype=np.float64)
     kh = np.ascontiguousarray(kpt.coordinate, dtype=np.float64)
     n_p = C.c_int()
     args = (basis.handle, kpt.n_loc, G32.data_ptr(), Bh.ctypes.data, kh.ctypes.data, model.unit_cell_volume,
-            len(groups), rp.ctypes.data, nproj.ctypes.data, len(species), species.ctypes.data, positions.ctypes.data)
+            n_species, rp.ctypes.data, nproj.ctypes.data, len(species), species.ctypes.data, positions.ctypes.data)
     _lib.check(basis.lib.dftk_mi_build_projectors_hgh(*args, None, kpt.n_loc, C.byref(n_p)))
     P = torch.empty((n_p.value, kpt.n_loc), dtype=torch.complex128, device=basis.device)
     basis.pre_call()
