@@ -36,3 +36,8 @@ from .terms import stress_ewald  # noqa: F401,E402
 from .stresses import (compute_stresses_cart, compute_stresses_term, voigt_stress_to_full,  # noqa: F401,E402
                        full_stress_to_voigt, voigt_strain_to_full, full_strain_to_voigt)
 from .memory_usage import estimate_memory_usage, plan_planewave_sharded, MemoryStatistics  # noqa: F401,E402
+from .response import (occupation_divided_difference, compute_alpha_mn, is_effective_insulator,  # noqa: F401,E402
+                       BandtolBalanced, BandtolGuaranteed, determine_band_tolerances, occupied_empty_masks,
+                       compute_delta_occ, sternheimer_solver, apply_chi0_4P, apply_chi0, compute_delta_rho,
+                       apply_kernel, solve_OmegaPlusK_split, solve_OmegaPlusK, compute_chi0,
+                       multiply_psi_by_potential)

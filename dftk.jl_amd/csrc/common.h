@@ -125,6 +125,9 @@ struct dftk_mi_basis {
     // device copy of the symmetry tables of the last cube_symmetrize call (owned; keyed by a hash of the operations: an SCF
     // symmetrises with the same group every step -- no upload and no host synchronisation after the first call)
     void* symm_tab; uint64_t symm_key; int symm_n;
+    // workspace of the Sternheimer solver (sternheimer.cpp): its blocks live across calls into the H apply (T1 / T2), the
+    // zgemm (ws) and nothing of a k-block's LOBPCG state, so it shares none of those buffers
+    void* resp_ws; size_t resp_ws_bytes;
 };
 
 // ------------------------------------------------------------------------------------ profiling
@@ -261,13 +264,16 @@ struct dftk_mi_kblock {
 // ------------------------------------------------------------------------------------ internal API
 // fft_kernels.hip
 int fft_ensure_scratch(dftk_mi_basis* b, dftk_mi_kblock* kb, int nb);
+// shift_d (nullable; needs add_kinetic and a bound local potential): out[:, n] -= shift_d[n] psi[:, n] in the gather pass
 int launch_local_apply(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, cd* out,
-                       int64_t ldout, bool add_kinetic, bool have_local);
+                       int64_t ldout, bool add_kinetic, bool have_local, const double* shift_d = nullptr);
 int launch_ifft_to_cube(dftk_mi_kblock* kb, const cd* c, cd* cube, int nb = 1);
 int launch_fft_from_cube(dftk_mi_kblock* kb, const cd* cube, cd* c, int nb = 1);
 // w_im_h (optional): separate weights for the squared IMAGINARY parts (two real bands packed into one transform)
 int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho,
                    const double* w_im_h = nullptr, const double* w2_h = nullptr, double* rho2 = nullptr);
+int launch_density_response(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const cd* dpsi, int64_t lddpsi,
+                            const double* wo_h, const double* wd_h, double* drho);
 int launch_pad_potential(dftk_mi_kblock* kb, const double* V);
 int launch_kinetic_only(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, cd* out,
                         int64_t ldout, bool accumulate, bool use_kin);
@@ -353,6 +359,10 @@ int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const 
 int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* vloc,
                         const double* green, int fun_mask, double threshold, double* V_out, double* energies_h);
 
+// dV = irfft(green fft(drho)) + f_xc(rho) drho, f_xc = d^2 (rho eps_xc) / d rho^2 of the LDA closed forms (fun_mask bits 1, 2, 4)
+int apply_kernel_lda(dftk_mi_kblock* cube_kb, const double* rho, const double* drho, const double* green, int fun_mask,
+                     double* dV_out);
+
 // cube_kernels.hip: density-sized operations of the SCF glue (symmetrisation, mixing multipliers) on a full-cube k-block
 int cube_symmetrize(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, const double* tau_h, int do_lowpass,
                     const double* rho_in, double* rho_out);
@@ -433,6 +443,27 @@ int stress_cube(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, c
                 const int* species_of_atom_h, const double* positions_h, const double* rho_d, double* out_h);
 int stress_xc(dftk_mi_basis* b, int64_t n, int n_spin, const double* rho_d, const double* vrho_d, const double* e_d,
               const double* vsigma_d, const double* grad_d, double* out_h);
+
+// response_kernels.hip: the n_G-sized element-wise kernels of the Sternheimer solver (all on b->stream; one launch for
+// all columns, scalars read from device memory)
+// x += p alpha, r -= c alpha with alpha[c] = gamma[c] / pc[c] (0 where pc[c] == 0)
+int resp_update_xr(dftk_mi_basis* b, int64_t n, int m, const double* gamma_d, const double* pc_d, const cd* p, int64_t ldp,
+                   const cd* c, int64_t ldc, cd* x, int64_t ldx, cd* r, int64_t ldr);
+// p = z + p beta with beta[c] = gamma_new[c] / gamma_old[c] (0 where gamma_old[c] == 0)
+int resp_update_p(dftk_mi_basis* b, int64_t n, int m, const double* gamma_new_d, const double* gamma_old_d, const cd* z,
+                  int64_t ldz, cd* p, int64_t ldp);
+// Y = a X + bcoef Y (bcoef == 0: Y is not read); sd (nullable): a is multiplied by sd[column]
+int resp_axpby(dftk_mi_basis* b, int64_t n, int m, double a, const double* sd, const cd* X, int64_t ldx, double bcoef, cd* Y,
+               int64_t ldy);
+// S[i, l] /= (ee[i] - e[l]) for the n_extra x m matrix S
+int resp_scale_inv(dftk_mi_basis* b, int n_extra, int m, cd* S, int64_t lds, const double* ee_d, const double* e_d);
+int resp_broadcast(dftk_mi_basis* b, int m, const double* src_d, double* dst_d);      // dst[0 .. m) = src[0]
+
+// sternheimer.cpp
+int sternheimer_run(dftk_mi_kblock* kb, int n_occ, const cd* psi_occ, int64_t ld_occ, const double* eps_h, int n_extra,
+                    const cd* psi_extra, int64_t ld_extra, const cd* rhs, int64_t ld_rhs, const double* tol_h, int miniter,
+                    int maxiter, const cd* dpsi0, int64_t ld_dpsi0, cd* dpsi, int64_t ld_dpsi, int* n_iter, double* resid_h,
+                    int* converged);
 
 // lobpcg.cpp
 // ortho!(X) (Cholesky-QR with the reference's shift-and-retry and SVD fallback) on a stand-alone block;

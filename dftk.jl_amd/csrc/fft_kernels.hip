@@ -877,7 +877,8 @@ __global__ __launch_bounds__(FFT_THREADS, YFWD_MIN_BLOCKS) void k_yfwd(FftAxis a
 }
 
 // ---------------------------------------------------------------------------------------- stage E
-// out[c] = FFT_x(line)[ix_c] (+ kin[c] * psi[c]) (+ out[c] if accumulate)
+// out[c] = FFT_x(line)[ix_c] (+ (kin[c] - shift[band]) * psi[c]); shift (nullable, with kin only): one value per band --
+// the (H - eps_n) psi_n of the Sternheimer solver leaves this pass finished (kin[c] - 0.0 is exact: H psi unchanged)
 template <bool GEN>
 __global__ __launch_bounds__(FFT_THREADS, YFWD_MIN_BLOCKS) void k_xfwd_gather(FftAxis ax, int nxp, int n_lines,
                                                              const int* __restrict__ line_start,
@@ -886,7 +887,8 @@ __global__ __launch_bounds__(FFT_THREADS, YFWD_MIN_BLOCKS) void k_xfwd_gather(Ff
                                                              const double* __restrict__ kin,
                                                              const cd* __restrict__ psi, int64_t ldpsi,
                                                              cd* __restrict__ out, int64_t ldout,
-                                                             const FftJob* __restrict__ jobs) {
+                                                             const FftJob* __restrict__ jobs,
+                                                             const double* __restrict__ shift) {
     constexpr int FFT_LS = FFT_LS_X;
     cd* buf = reinterpret_cast<cd*>(dftk_smem);
     cd* tw = buf + ax.n * FFT_LS;
@@ -917,12 +919,13 @@ __global__ __launch_bounds__(FFT_THREADS, YFWD_MIN_BLOCKS) void k_xfwd_gather(Ff
     __syncthreads();
     fft_tile<FFT_LS, true, GEN>(buf, tw, ax, -1.0, l, j);
     const int line = l0 + l;
+    const double sh = shift ? shift[band] : 0.0;
     if (line < n_lines) {
         const int c0 = line_start[line], c1 = line_start[line + 1];
         for (int c = c0 + j; c < c1; c += FFT_TPL) {
             cd v = buf[cpos[c] * FFT_LS + l];
             if (kin != nullptr) {
-                const double k = kin[c];
+                const double k = kin[c] - sh;
                 const cd q = p[c];
                 v.x = fma(k, q.x, v.x);
                 v.y = fma(k, q.y, v.y);
@@ -1009,6 +1012,73 @@ __global__ __launch_bounds__(FFT_THREADS, DENS_MIN_BLOCKS) void k_zdensity(FftAx
                     dst2[at] = part ? acc2[k] : dst2[at] + acc2[k];
                 }
             }
+        }
+    }
+}
+
+// drho[z,y,x] += sum_band 2 wo[band] Re(conj(psi) dpsi) + wd[band] |psi|^2 in real space: T2 holds the y-transformed
+// planes of the nb orbitals in slots 0 .. nb-1 and of their nb first-order changes in slots nb .. 2 nb - 1.  Two z
+// transforms per band (only one when wo[band] == 0); product and accumulation in the same pass, one workgroup owns an
+// (x-tile, y) column set -- every drho entry has exactly one writer (no atomics, fixed order over the bands).
+template <bool GEN>
+__global__ __launch_bounds__(FFT_THREADS, DENS_MIN_BLOCKS) void k_zdensity_response(FftAxis az, int nx, int nxp, int ny,
+                                                                   int nzx, const int* __restrict__ zpos, int nb,
+                                                                   const double* __restrict__ wo,
+                                                                   const double* __restrict__ wd,
+                                                                   const cd* __restrict__ T2, int64_t T2_stride,
+                                                                   double* __restrict__ drho) {
+    constexpr int FFT_LS = FFT_LS_YZ;
+    cd* buf = reinterpret_cast<cd*>(dftk_smem);
+    cd* tw = buf + az.n * FFT_LS;
+    const int tid = threadIdx.x, l = tid & (FFT_L - 1), j = tid >> 3;
+    const int x = blockIdx.x * FFT_L + l;
+    const int y = blockIdx.y;
+    const int nz = az.n;
+    const int64_t plane = (int64_t)ny * nxp;
+    double acc[DENS_MAXACC];
+    cd pv[DENS_MAXACC];
+#pragma unroll
+    for (int k = 0; k < DENS_MAXACC; ++k) acc[k] = 0.0;
+    for (int t = tid; t < nz; t += FFT_THREADS) tw[t] = az.tw[t];
+    const cd z0 = make_double2(0.0, 0.0);
+    for (int ib = 0; ib < nb; ++ib) {
+        const double w2 = 2.0 * wo[ib], w1 = wd[ib];
+        if (w2 == 0.0 && w1 == 0.0) continue;   // uniform across the block
+        for (int t = tid; t < nz * FFT_LS; t += FFT_THREADS) buf[t] = z0;
+        __syncthreads();
+        const cd* t2 = T2 + (int64_t)ib * T2_stride + (int64_t)y * nxp + x;
+        for (int zi = j; zi < nzx; zi += FFT_TPL) buf[zpos[zi] * FFT_LS + l] = t2[(int64_t)zi * plane];
+        __syncthreads();
+        fft_tile<FFT_LS, false, GEN>(buf, tw, az, +1.0, l, j);
+#pragma unroll
+        for (int k = 0; k < DENS_MAXACC; ++k) {
+            const int z = j + k * FFT_TPL;
+            pv[k] = z < nz ? buf[z * FFT_LS + l] : z0;
+            acc[k] = fma(w1, pv[k].x * pv[k].x + pv[k].y * pv[k].y, acc[k]);
+        }
+        __syncthreads();
+        if (w2 == 0.0) continue;
+        for (int t = tid; t < nz * FFT_LS; t += FFT_THREADS) buf[t] = z0;
+        __syncthreads();
+        const cd* d2 = T2 + (int64_t)(nb + ib) * T2_stride + (int64_t)y * nxp + x;
+        for (int zi = j; zi < nzx; zi += FFT_TPL) buf[zpos[zi] * FFT_LS + l] = d2[(int64_t)zi * plane];
+        __syncthreads();
+        fft_tile<FFT_LS, false, GEN>(buf, tw, az, +1.0, l, j);
+#pragma unroll
+        for (int k = 0; k < DENS_MAXACC; ++k) {
+            const int z = j + k * FFT_TPL;
+            if (z < nz) {
+                const cd v = buf[z * FFT_LS + l];
+                acc[k] = fma(w2, pv[k].x * v.x + pv[k].y * v.y, acc[k]);
+            }
+        }
+        __syncthreads();
+    }
+    if (x < nx) {
+#pragma unroll
+        for (int k = 0; k < DENS_MAXACC; ++k) {
+            const int z = j + k * FFT_TPL;
+            if (z < nz) drho[((int64_t)z * ny + y) * nx + x] += acc[k];
         }
     }
 }
@@ -1202,9 +1272,12 @@ static Strides strides(dftk_mi_kblock* kb) {
     return Strides{(int64_t)kb->n_lines * b->nxp, (int64_t)kb->nzx * b->ny * b->nxp};
 }
 
-static int run_AB(dftk_mi_kblock* kb, int nbb, const cd* psi, int64_t ldpsi) {
+// t_off: the first of the nbb scratch slots (bands) of T1 / T2 the launch group fills
+static int run_AB(dftk_mi_kblock* kb, int nbb, const cd* psi, int64_t ldpsi, int t_off = 0) {
     dftk_mi_basis* b = kb->basis;
     const Strides st = strides(kb);
+    cd* const T1 = b->T1 + (int64_t)t_off * st.s1;
+    cd* const T2 = b->T2 + (int64_t)t_off * st.s2;
     const int gl = (int)((kb->n_lines + FFT_L - 1) / FFT_L);
     const int nxt = b->nxp / FFT_L;
     const double Ncube = (double)b->nx * b->ny * b->nz;
@@ -1214,17 +1287,17 @@ static int run_AB(dftk_mi_kblock* kb, int nbb, const cd* psi, int64_t ldpsi) {
     (void)Ncube;
     int ps = prof_begin(b, PROF_FFT_A, (16.0 * kb->n_G + t1b) * nbb);
     LAUNCH_FFT(k_xbwd_scatter, b->ax[0], dim3(gl, nbb), lds_bytes(b->nx, FFT_LS_X), b->stream, b->ax[0],
-                       b->nxp, (int)kb->n_lines, kb->d_line_start, kb->d_cpos, psi, ldpsi, b->T1, st.s1, (const FftJob*)nullptr);
+                       b->nxp, (int)kb->n_lines, kb->d_line_start, kb->d_cpos, psi, ldpsi, T1, st.s1, (const FftJob*)nullptr);
     prof_end(b, ps);
     ps = prof_begin(b, PROF_FFT_B, (t1b + t2b) * nbb);
     LAUNCH_FFT(k_ybwd, b->ax[1], dim3(nxt, kb->nzx, nbb), lds_bytes(b->ny), b->stream, b->ax[1],
-                       b->nxp, b->ny, kb->d_zls, kb->d_line_ypos, b->T1, st.s1, b->T2, st.s2, (const FftJob*)nullptr);
+                       b->nxp, b->ny, kb->d_zls, kb->d_line_ypos, T1, st.s1, T2, st.s2, (const FftJob*)nullptr);
     prof_end(b, ps);
     return 0;
 }
 
 static int run_DE(dftk_mi_kblock* kb, int nbb, const double* kin, const cd* psi, int64_t ldpsi, cd* out,
-                  int64_t ldout) {
+                  int64_t ldout, const double* shift_d = nullptr) {
     dftk_mi_basis* b = kb->basis;
     const Strides st = strides(kb);
     const int gl = (int)((kb->n_lines + FFT_L - 1) / FFT_L);
@@ -1239,14 +1312,18 @@ static int run_DE(dftk_mi_kblock* kb, int nbb, const double* kin, const cd* psi,
     ps = prof_begin(b, PROF_FFT_E, (t1b + (kin ? 40.0 : 16.0) * kb->n_G) * nbb);
     LAUNCH_FFT(k_xfwd_gather, b->ax[0], dim3(gl, nbb), lds_bytes(b->nx, FFT_LS_X), b->stream, b->ax[0],
                        b->nxp, (int)kb->n_lines, kb->d_line_start, kb->d_cpos, b->T1, st.s1, kin, psi, ldpsi, out,
-                       ldout, (const FftJob*)nullptr);
+                       ldout, (const FftJob*)nullptr, shift_d);
     prof_end(b, ps);
     return 0;
 }
 
 int launch_local_apply(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, cd* out, int64_t ldout,
-                       bool add_kinetic, bool have_local) {
+                       bool add_kinetic, bool have_local, const double* shift_d) {
     dftk_mi_basis* b = kb->basis;
+    if (shift_d && (!add_kinetic || !have_local || kb->d_Vs == nullptr)) {
+        dftk_set_error("launch_local_apply: the per-band shift rides on the kinetic term of the gather pass");
+        return DFTK_MI_EINVAL;
+    }
     if (!have_local || kb->d_Vs == nullptr) {
         // no local potential: out = kinetic * psi (or zero)
         return launch_kinetic_only(kb, nb, psi, ldpsi, out, ldout, false, add_kinetic);
@@ -1271,7 +1348,8 @@ int launch_local_apply(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi,
         LAUNCH_ZPASS(0, b->ax[2], zpass_grid(b, nbb), lds_bytes(b->nz), b->stream, b->ax[2], b->nx, b->nxp, b->ny, kb->nzx, nbb, kb->d_zpos, kb->d_Vs, b->T2, st.s2,
                            (cd*)nullptr, (const FftJob*)nullptr);
         prof_end(b, pc);
-        CHK(run_DE(kb, nbb, add_kinetic ? kb->d_kin : nullptr, p, ldpsi, out + (int64_t)b0 * ldout, ldout));
+        CHK(run_DE(kb, nbb, add_kinetic ? kb->d_kin : nullptr, p, ldpsi, out + (int64_t)b0 * ldout, ldout,
+                   shift_d ? shift_d + b0 : nullptr));
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -1368,6 +1446,43 @@ int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, con
         if (rs == 1)
         LAUNCH_FFT(k_zdensity, b->ax[2], dim3(b->nxp / FFT_L, b->ny), lds_bytes(b->nz), b->stream, b->ax[2], b->nx, b->nxp, b->ny, kb->nzx, kb->d_zpos, nbb, w_d + b0,
                            wim_d ? wim_d + b0 : (const double*)nullptr, b->T2, st.s2, rho, (const FftJob*)nullptr, (double*)nullptr);
+        prof_end(b, pz);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// compute_drho's inner loop at q = 0 (src/densities.jl:60-108) for one k-block: the launch groups of launch_density with
+// two scratch slots per band (orbital and first-order change), the weights uploaded once
+int launch_density_response(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const cd* dpsi, int64_t lddpsi,
+                            const double* wo_h, const double* wd_h, double* drho) {
+    dftk_mi_basis* b = kb->basis;
+    CHK(check_lds(b));
+    if (b->nz > DENS_MAXACC * FFT_TPL) {
+        dftk_set_error("density kernel supports nz <= %d", DENS_MAXACC * FFT_TPL);
+        return DFTK_MI_EINVAL;
+    }
+    const int batch = b->fft_batch > 1 ? b->fft_batch / 2 : 1;
+    const int group = nb < batch ? nb : batch;
+    CHK(fft_ensure_scratch(b, kb, 2 * group));
+    const Strides st = strides(kb);
+    CHK(ensure_ws(b, 2 * (size_t)nb * sizeof(double)));
+    double* wo_d = reinterpret_cast<double*>(b->ws);
+    double* wd_d = wo_d + nb;
+    HIPCHK(hipMemcpyAsync(wo_d, wo_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(wd_d, wd_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    for (int b0 = 0; b0 < nb; b0 += batch) {
+        const int nbb = (nb - b0) < batch ? (nb - b0) : batch;
+        bool any = false;
+        for (int i = 0; i < nbb; ++i) any = any || wo_h[b0 + i] != 0.0 || wd_h[b0 + i] != 0.0;
+        if (!any) continue;
+        CHK(run_AB(kb, nbb, psi + (int64_t)b0 * ldpsi, ldpsi, 0));
+        CHK(run_AB(kb, nbb, dpsi + (int64_t)b0 * lddpsi, lddpsi, nbb));
+        const int pz = prof_begin(b, PROF_DENS_Z, 32.0 * (double)kb->nzx * b->ny * b->nxp * nbb +
+                                                      16.0 * (double)b->nx * b->ny * b->nz);
+        LAUNCH_FFT(k_zdensity_response, b->ax[2], dim3(b->nxp / FFT_L, b->ny), lds_bytes(b->nz), b->stream, b->ax[2], b->nx,
+                   b->nxp, b->ny, kb->nzx, kb->d_zpos, nbb, (const double*)(wo_d + b0), (const double*)(wd_d + b0),
+                   (const cd*)b->T2, st.s2, drho);
         prof_end(b, pz);
     }
     HIPCHK(hipGetLastError());
@@ -1477,7 +1592,7 @@ int batch_exec_apply_H(BatchCtx* ctx, hipStream_t stream, std::vector<BOp*>& ops
                            b->nxp, b->ny, (const int*)nullptr, (const int*)nullptr, (const cd*)T2, s2, T1, s1, dj);
         hipLaunchKernelGGL((k_xfwd_gather<false>), dim3(gl, nb), dim3(FFT_THREADS), lds_bytes(b->nx, FFT_LS_X), stream, b->ax[0],
                            b->nxp, 0, (const int*)nullptr, (const int*)nullptr, (const cd*)T1, s1, (const double*)nullptr,
-                           (const cd*)nullptr, (int64_t)0, (cd*)nullptr, (int64_t)0, dj);
+                           (const cd*)nullptr, (int64_t)0, (cd*)nullptr, (int64_t)0, dj, (const double*)nullptr);
     }
     HIPCHK(hipGetLastError());
     // nonlocal part: H psi += P (D (P' psi)) per k-block through the batched small products

@@ -280,6 +280,71 @@ __global__ __launch_bounds__(256) void k_xc_sum_spin(int64_t n, const double* __
         partial[XC_BLOCKS + blockIdx.x] = s1;
     }
 }
+// ---- second derivatives f_xc = d^2 (rho eps_xc) / d rho^2 of the three closed forms above (the XC kernel of
+// apply_kernel, src/terms/xc.jl:245-330).  With v = eps - (rs / 3) eps' (eps' = d eps / d rs) and d rs / d rho = -rs / (3 rho):
+//   f = d v / d rho = -rs / (3 rho) (2/3 eps' - rs / 3 eps'')
+__device__ __forceinline__ double lda_x_fxc(double rho) {
+    const double cx = -0.73855876638202240588;
+    const double r13 = cbrt(rho);
+    return (4.0 / 9.0) * cx / (r13 * r13);
+}
+__device__ __forceinline__ double fxc_from_rs(double rho, double rs, double d1, double d2) {
+    return -rs / (3.0 * rho) * ((2.0 / 3.0) * d1 - rs / 3.0 * d2);
+}
+__device__ __forceinline__ double lda_c_vwn_fxc(double rho) {
+    const double A = 0.0310907, b = 3.72744, c = 12.9352, x0 = -0.10498;
+    const double rs = cbrt(3.0 / (4.0 * M_PI * rho));
+    const double x = sqrt(rs);
+    const double X = x * x + b * x + c, X0 = x0 * x0 + b * x0 + c;
+    const double Q = sqrt(4.0 * c - b * b);
+    const double t = 2.0 * x + b;
+    const double dat = -Q / (2.0 * X);                 // d atan(Q / (2 x + b)) / dx  (Q^2 + (2 x + b)^2 = 4 X)
+    const double ddat = Q * t / (2.0 * X * X);
+    const double u1 = -t / X, u2 = -(2.0 / X - t * t / (X * X));      // d/dx, d2/dx2 of -log X
+    // eps = A (g(x) - b x0 / X0 h(x)),  g = log(x^2 / X) + 2 b / Q atan,  h = log((x - x0)^2 / X) + 2 (b + 2 x0) / Q atan
+    const double g1 = 2.0 / x + u1 + 2.0 * b / Q * dat;
+    const double g2 = -2.0 / (x * x) + u2 + 2.0 * b / Q * ddat;
+    const double h1 = 2.0 / (x - x0) + u1 + 2.0 * (b + 2.0 * x0) / Q * dat;
+    const double h2 = -2.0 / ((x - x0) * (x - x0)) + u2 + 2.0 * (b + 2.0 * x0) / Q * ddat;
+    const double E1 = A * (g1 - b * x0 / X0 * h1), E2 = A * (g2 - b * x0 / X0 * h2);   // d eps / dx, d2 eps / dx2
+    const double d1 = E1 / (2.0 * x);                                                  // x = sqrt(rs)
+    const double d2 = E2 / (4.0 * rs) - E1 / (4.0 * rs * x);
+    return fxc_from_rs(rho, rs, d1, d2);
+}
+__device__ __forceinline__ double lda_c_pw_fxc(double rho) {
+    const double a = 0.031091, a1 = 0.21370, b1 = 7.5957, b2 = 3.5876, b3 = 1.6382, b4 = 0.49294;
+    const double rs = cbrt(3.0 / (4.0 * M_PI * rho));
+    const double sq = sqrt(rs);
+    const double den = 2.0 * a * (b1 * sq + b2 * rs + b3 * rs * sq + b4 * rs * rs);
+    const double lg = log1p(1.0 / den);
+    const double dden = 2.0 * a * (b1 / (2.0 * sq) + b2 + 1.5 * b3 * sq + 2.0 * b4 * rs);
+    const double ddden = 2.0 * a * (-b1 / (4.0 * rs * sq) + 0.75 * b3 / sq + 2.0 * b4);
+    const double W = den * den + den;                  // d lg / d rs = -dden / W
+    const double pre = 2.0 * a * (1.0 + a1 * rs);
+    const double d1 = -2.0 * a * a1 * lg + pre * dden / W;
+    const double d2 = 4.0 * a * a1 * dden / W + pre * (ddden / W - (2.0 * den + 1.0) * dden * dden / (W * W));
+    return fxc_from_rs(rho, rs, d1, d2);
+}
+
+// dV = vh_scale Re(vh_cube) + f_xc(rho) drho
+__global__ __launch_bounds__(256) void k_fxc_sum(int64_t n, const double* __restrict__ rho, const double* __restrict__ drho,
+                                                 const cd* __restrict__ vh_cube, double vh_scale, int fun_mask,
+                                                 double* __restrict__ dV) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        double f = 0.0;
+        if (fun_mask != 0) {
+            const double r = rho[i];
+            if (r > 1e-300) {
+                if (fun_mask & 1) f += lda_x_fxc(r);
+                if (fun_mask & 2) f += lda_c_vwn_fxc(r);
+                if (fun_mask & 4) f += lda_c_pw_fxc(r);
+            }
+        }
+        double tot = f * drho[i];
+        if (vh_cube) tot += vh_scale * vh_cube[i].x;
+        dV[i] = tot;
+    }
+}
 }  // namespace dftk_xc
 using namespace dftk_xc;
 
@@ -438,5 +503,34 @@ int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const do
     energies_h[0] = green ? 0.5 * b->volume / ((double)N * (double)N) * s[2] : 0.0;   // Hartree
     energies_h[1] = s[0] * dvol;                                                        // Xc
     energies_h[2] = s[1] * dvol;                                                        // AtomicLocal
+    return 0;
+}
+
+// dV = v_c * drho + f_xc(rho) drho: the Hartree part through the Poisson multiplier between two cube FFTs (as the potential
+// pipeline above, hartree.jl:68-81), the XC part point by point in the final pass.  Asynchronous on the basis' stream.
+int apply_kernel_lda(dftk_mi_kblock* cube_kb, const double* rho, const double* drho, const double* green, int fun_mask,
+                     double* dV_out) {
+    dftk_mi_basis* b = cube_kb->basis;
+    const int64_t N = (int64_t)b->nx * b->ny * b->nz;
+    if (cube_kb->n_G != N) {
+        dftk_set_error("apply_kernel: the k-block must span the whole cube (n_G = %lld, N = %lld)", (long long)cube_kb->n_G,
+                       (long long)N);
+        return DFTK_MI_EINVAL;
+    }
+    const cd* vh = nullptr;
+    if (green) {
+        CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd) + XC_BLOCKS * sizeof(double)));
+        cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+        cd* c2 = c1 + N;
+        double* partial = reinterpret_cast<double*>(c2 + N);
+        hipLaunchKernelGGL(k_real_to_complex, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, drho, c1);
+        CHK(launch_fft_from_cube(cube_kb, c1, c2));
+        hipLaunchKernelGGL(k_poisson, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, c2, green, partial);
+        CHK(launch_ifft_to_cube(cube_kb, c2, c1));                        // c1 = N * dV_H(r)
+        vh = c1;
+    }
+    hipLaunchKernelGGL(k_fxc_sum, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, rho, drho, vh, 1.0 / (double)N, fun_mask & 7,
+                       dV_out);
+    HIPCHK(hipGetLastError());
     return 0;
 }

@@ -269,6 +269,40 @@ int dftk_mi_density_accumulate(dftk_mi_kblock* kb, int n_bands, const dftk_mi_cp
 int dftk_mi_density_accumulate_spin(dftk_mi_kblock* kb, int n_bands, const dftk_mi_cplx* psi_d, int64_t ld_psi,
                                     const double* weight_h, double* rho_d, int spin, int n_spin);
 
+/* ---- density response (src/response/chi0.jl, src/response/cg.jl, compute_drho of src/densities.jl:60-108; q = 0) --------
+ * sternheimer_solver (chi0.jl:115-232) for ONE k-block in one call: solves
+ *     Q (H - eps_n) Q dpsi_n = -Q rhs_n,   Q = 1 - psi_occ psi_occ',   n = 0 .. n_occ - 1
+ * by the reference's Schur split over the extra bands and its preconditioned block CG (cg.jl:30-128; projections after
+ * every update, TPA preconditioner with the mean kinetic energy of the FIRST occupied column, locking of converged columns
+ * on a contiguous active range; n_iter counts as the reference does).  psi_occ: n_occ orthonormal columns with
+ * psi_occ' H psi_occ = diag(eps_h); psi_extra: n_extra >= 0 further columns, orthonormal to them and Rayleigh-Ritz among
+ * themselves (H psi_extra and eps_extra are computed here); rhs: n_occ columns; tol_h[n_occ]: residual-norm tolerance of
+ * every column; dpsi0_d (nullable): start vector.  Outputs: dpsi_d (n_G x n_occ), *n_iter, resid_h[n_occ] (norms of the CG
+ * residual), *converged.  n_occ = 0 returns at once.  The H of the block's bound potential is applied in the general complex
+ * full-sphere layout (a Gamma-real block included).  ONE host synchronisation per CG iteration (the fetch of the residual
+ * norms); alpha and beta of the CG stay on the device.  Workspace: (8 n_occ + 2 n_extra) n_G complex numbers of the
+ * basis' response workspace; the k-block's LOBPCG state (kept A X, start buffers) is not touched.  A plane-wave sharded
+ * block is refused (DFTK_MI_EINVAL). */
+int dftk_mi_sternheimer(dftk_mi_kblock* kb, int n_occ, const dftk_mi_cplx* psi_occ_d, int64_t ld_occ, const double* eps_h,
+                        int n_extra, const dftk_mi_cplx* psi_extra_d, int64_t ld_extra, const dftk_mi_cplx* rhs_d,
+                        int64_t ld_rhs, const double* tol_h, int miniter, int maxiter, const dftk_mi_cplx* dpsi0_d,
+                        int64_t ld_dpsi0, dftk_mi_cplx* dpsi_d, int64_t ld_dpsi, int* n_iter, double* resid_h,
+                        int* converged);
+/* compute_drho's inner loop (densities.jl:86-103) for one k-block:
+ *     drho_d[nx*ny*nz] += sum_n 2 w_occ_h[n] Re(conj(psi_n(r)) dpsi_n(r)) + w_docc_h[n] |psi_n(r)|^2
+ * with psi_n(r) = BFFT(pad(psi[:, n])) unnormalised: the caller folds kweight * ifft_normalization^2 into both weights
+ * (w_occ = occupation * ..., w_docc = d occupation * ...).  Two pruned inverse transforms per band, the product and the
+ * accumulation in the last pass; bands with both weights 0 are skipped.  Unsharded blocks only. */
+int dftk_mi_density_response_accumulate(dftk_mi_kblock* kb, int n_bands, const dftk_mi_cplx* psi_d, int64_t ld_psi,
+                                        const dftk_mi_cplx* dpsi_d, int64_t ld_dpsi, const double* w_occ_h,
+                                        const double* w_docc_h, double* drho_d);
+/* apply_kernel of TermHartree + TermXc (hartree.jl:68-81, xc.jl:245-330; spin-unpolarised LDA) on the cube:
+ *     dV = irfft(poisson_green .* fft(drho)) + f_xc(rho) drho,   f_xc = d^2 (rho eps_xc) / d rho^2
+ * in closed form for DFTK_MI_XC_LDA_X, _LDA_C_VWN, _LDA_C_PW (other bits: DFTK_MI_EINVAL).  poisson_green_d NULL: no Hartree
+ * part; xc_functionals 0: no XC part (RPA; rho_d may then be NULL).  Asynchronous on the basis' stream. */
+int dftk_mi_apply_kernel(dftk_mi_kblock* cube_kb, const double* rho_d, const double* drho_d, const double* poisson_green_d,
+                         int xc_functionals, double* dV_d);
+
 /* ---- lobpcg_hyper(A, X0; prec=PreconditionerTPA, tol, miniter, maxiter, n_conv_check)
  *      (src/eigen/diag_lobpcg_hyper.jl:5-18 -> LOBPCG, src/eigen/lobpcg_hyper_impl.jl:354-582;
  *       PreconditionerTPA src/eigen/preconditioners.jl:27-78) ----------------------------------
