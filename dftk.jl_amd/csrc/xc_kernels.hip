@@ -80,7 +80,8 @@ __device__ __forceinline__ void lda_c_pw(double rho, double& e, double& v) {
     const double lg = log1p(1.0 / den);
     const double eps = -2.0 * a * (1.0 + a1 * rs) * lg;
     const double dden = 2.0 * a * (b1 / (2.0 * sq) + b2 + 1.5 * b3 * sq + 2.0 * b4 * rs);
-    const double deps = -2.0 * a * a1 * lg + 2.0 * a * (1.0 + a1 * rs) * dden / (den * den + den);
+    // d lg / d rs = -dden / (den^2 + den), as two quotients: den^2 overflows for rho < 2e-234 (den ~ rs^2)
+    const double deps = -2.0 * a * a1 * lg + 2.0 * a * (1.0 + a1 * rs) * (dden / den) / (den + 1.0);
     e = rho * eps;
     v = eps - rs / 3.0 * deps;
 }
@@ -88,6 +89,10 @@ __device__ __forceinline__ void lda_c_pw(double rho, double& e, double& v) {
 // ---- GGA (PBE): e(rho, sigma) with forward-mode derivatives d/d rho, d/d sigma carried through the closed forms
 // (libxc's gga_x_pbe / gga_c_pbe on lda_c_pw_mod; Perdew, Burke, Ernzerhof 1996).  A dual number (v, dr, ds) makes
 // the potential terms exact derivatives of exactly the energy expression -- no hand-derived formulas.
+// No fused multiply-adds from here to lda_spin_sum: the compiler folds the seeds (1, 0) and (0, 1) of the two derivative
+// slots and then contracts the two slots differently, which breaks the exchange symmetry V_up(a, b) = V_down(b, a) of the
+// collinear forms in the last bit.  With separate roundings every folding is exact and both slots round alike.
+#pragma clang fp contract(off)
 struct D3 {
     double v, dr, ds;
 };
@@ -202,6 +207,8 @@ __device__ __forceinline__ D3 lda_spin_sum(double rho_up, double rho_dn, int fun
     return acc;
 }
 
+#pragma clang fp contract(fast)
+
 // V = V_loc + V_H + v_xc ; partials: [0] sum e_xc, [1] sum rho V_loc
 __global__ __launch_bounds__(256) void k_xc_sum(int64_t n, const double* __restrict__ rho, const cd* __restrict__ vh_cube,
                                                 double vh_scale, const double* __restrict__ vloc, int fun_mask,
@@ -289,7 +296,7 @@ __device__ __forceinline__ double lda_x_fxc(double rho) {
     return (4.0 / 9.0) * cx / (r13 * r13);
 }
 __device__ __forceinline__ double fxc_from_rs(double rho, double rs, double d1, double d2) {
-    return -rs / (3.0 * rho) * ((2.0 / 3.0) * d1 - rs / 3.0 * d2);
+    return -(rs / 3.0) * (((2.0 / 3.0) * d1 - rs / 3.0 * d2) / rho);   // (rs / rho itself overflows for rho < 1e-231)
 }
 __device__ __forceinline__ double lda_c_vwn_fxc(double rho) {
     const double A = 0.0310907, b = 3.72744, c = 12.9352, x0 = -0.10498;
@@ -319,10 +326,14 @@ __device__ __forceinline__ double lda_c_pw_fxc(double rho) {
     const double lg = log1p(1.0 / den);
     const double dden = 2.0 * a * (b1 / (2.0 * sq) + b2 + 1.5 * b3 * sq + 2.0 * b4 * rs);
     const double ddden = 2.0 * a * (-b1 / (4.0 * rs * sq) + 0.75 * b3 / sq + 2.0 * b4);
-    const double W = den * den + den;                  // d lg / d rs = -dden / W
+    // d lg / d rs = -dden / W, W = den^2 + den; written with q = dden / den and iw = 1 / (den + 1) because W overflows for
+    // rho < 2e-234 (den ~ rs^2) and W^2 long before: dden / W = q iw, (2 den + 1) dden^2 / W^2 = (2 den + 1) iw q^2 iw
+    // (pre ~ rs is multiplied in before the last iw: q q iw alone underflows there, where the product is still 1e-299)
+    const double q = dden / den, iw = 1.0 / (den + 1.0);
     const double pre = 2.0 * a * (1.0 + a1 * rs);
-    const double d1 = -2.0 * a * a1 * lg + pre * dden / W;
-    const double d2 = 4.0 * a * a1 * dden / W + pre * (ddden / W - (2.0 * den + 1.0) * dden * dden / (W * W));
+    const double pq = pre * q;
+    const double d1 = -2.0 * a * a1 * lg + pq * iw;
+    const double d2 = 4.0 * a * a1 * q * iw + (pre * (ddden / den) - (2.0 * den + 1.0) * iw * q * pq) * iw;
     return fxc_from_rs(rho, rs, d1, d2);
 }
 

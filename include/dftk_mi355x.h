@@ -200,7 +200,11 @@ int dftk_mi_local_potential(dftk_mi_kblock* cube_kb, const double* rho_d, const 
  * (up, down) = rho[:, :, :, 1:2] of the reference.  V_out[s] = V_loc + V_H[rho_up + rho_down] + v_xc,s(rho_up, rho_down)
  * -- the potential of the k-blocks of spin s (ene_ops picks Vxc[:, :, :, kpt.spin], src/terms/xc.jl:163-175); the energies
  * are those of dftk_mi_local_potential with the total density in the Hartree and local terms.  Spin-polarised closed forms:
- * DFTK_MI_XC_LDA_X, DFTK_MI_XC_LDA_C_PW, DFTK_MI_XC_LDA_XC_TETER93 (anything else: DFTK_MI_EINVAL). */
+ * DFTK_MI_XC_LDA_X, DFTK_MI_XC_LDA_C_PW, DFTK_MI_XC_LDA_XC_TETER93 (anything else: DFTK_MI_EINVAL, nothing written).
+ * Density floor: each channel enters the closed forms as max(rho_s, 1e-20) (zero and negative channels included), v_xc,s is
+ * the derivative with respect to that clamped variable, and a point with rho_up + rho_down <= 2e-20 contributes e_xc = 0,
+ * v_xc,up = v_xc,down = 0.  The unpolarised DFTK_MI_XC_LDA_XC_TETER93 of dftk_mi_local_potential is this form at
+ * rho_up = rho_down = rho / 2 and so is zero for rho <= 2e-20; the other unpolarised forms are evaluated for rho > 1e-300. */
 int dftk_mi_local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho_d, const double* V_loc_d,
                                       const double* poisson_green_d, int xc_functionals, double* V_out_d,
                                       double* energies_h);

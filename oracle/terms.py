@@ -188,17 +188,35 @@ def energy_psp_correction(model):
 
 
 # ----------------------------------------------------------------------------- XC (closed forms)
+def _cbrt(z):
+    """Cube root that also takes the complex arguments of a complex-step derivative (np.cbrt is real only): one Newton
+    step from the cube root of the real part, exact to first order in the imaginary part."""
+    if not np.iscomplexobj(z):
+        return np.cbrt(z)
+    r = np.cbrt(np.real(z))
+    return r - (r * r * r - z) / (3 * r * r)
+
+
+def _log1p(z):
+    """log(1 + z), accurate for small |z| also for the complex arguments of a complex-step derivative (NumPy's complex
+    log1p is log(1 + z) and loses the real part once |z| < 1e-16): log|1 + z| = log1p(x) + 1/2 log1p((y / (1 + x))^2)."""
+    if not np.iscomplexobj(z):
+        return np.log1p(z)
+    x, y = np.real(z), np.imag(z)
+    return np.log1p(x) + 0.5 * np.log1p((y / (1 + x)) ** 2) + 1j * np.arctan2(y, 1 + x)
+
+
 def _lda_x(rho):
     """Slater exchange (libxc ``lda_x``): e = -3/4 (3/pi)^{1/3} rho^{4/3}."""
     cx = -0.75 * (3 / math.pi) ** (1 / 3)
-    r13 = np.cbrt(rho)
+    r13 = _cbrt(rho)
     return cx * rho * r13, (4 / 3) * cx * r13
 
 
 def _lda_c_vwn(rho):
     """VWN5 paramagnetic correlation (libxc ``lda_c_vwn``; Vosko, Wilk, Nusair 1980)."""
     A, b, c, x0 = 0.0310907, 3.72744, 12.9352, -0.10498
-    rs = np.cbrt(3 / (4 * math.pi * rho))
+    rs = _cbrt(3 / (4 * math.pi * rho))
     x = np.sqrt(rs)
     X = x * x + b * x + c
     X0 = x0 * x0 + b * x0 + c
@@ -216,15 +234,16 @@ def _lda_c_vwn(rho):
 
 def _lda_c_pw(rho):
     """Perdew-Wang 1992 unpolarised correlation (libxc ``lda_c_pw``, original parameters).
-    PARITY UNPINNED: the reference tests hold no numeric value for this functional."""
+    The reference tests hold no numeric value for this functional; tests/test_xc_reference.py pins e, v and f_xc to
+    60-digit values of the published form."""
     a, a1, b1, b2, b3, b4 = 0.031091, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294
-    rs = np.cbrt(3 / (4 * math.pi * rho))
+    rs = _cbrt(3 / (4 * math.pi * rho))
     sq = np.sqrt(rs)
     den = 2 * a * (b1 * sq + b2 * rs + b3 * rs * sq + b4 * rs * rs)
-    lg = np.log1p(1 / den)
+    lg = _log1p(1 / den)
     eps = -2 * a * (1 + a1 * rs) * lg
     dden = 2 * a * (b1 / (2 * sq) + b2 + 1.5 * b3 * sq + 2 * b4 * rs)
-    deps = -2 * a * a1 * lg + 2 * a * (1 + a1 * rs) * dden / (den * den + den)
+    deps = -2 * a * a1 * lg + 2 * a * (1 + a1 * rs) * dden / den / (den + 1)   # (den^2 overflows at rho ~ 1e-300)
     v = eps - rs / 3 * deps
     return rho * eps, v
 
@@ -246,15 +265,26 @@ def _teter_eps(rs, fz):
 
 
 def _lda_xc_teter93(rho):
-    """Unpolarised ``lda_xc_teter93``: (e, v) with v = d(rho eps)/d rho."""
+    """Unpolarised ``lda_xc_teter93``: (e, v) with v = d(rho eps)/d rho.  It is the collinear form at rho_up = rho_down =
+    rho / 2 and shares its threshold: zero when rho <= 2 _SPIN_FLOOR (the library evaluates it that way)."""
     rs = np.cbrt(3 / (4 * math.pi * rho))
     eps = _teter_eps(rs, 0.0)
     h = 1e-30
     deps = np.imag(_teter_eps(rs + 1j * h, 0.0)) / h
-    return rho * eps, eps - rs / 3 * deps
+    live = np.asarray(rho) > 2e-20
+    return np.where(live, rho * eps, 0.0), np.where(live, eps - rs / 3 * deps, 0.0)
 
 
 _FUNCTIONALS = {"lda_x": _lda_x, "lda_c_vwn": _lda_c_vwn, "lda_c_pw": _lda_c_pw, "lda_xc_teter93": _lda_xc_teter93}
+
+
+def lda_fxc(name, rho):
+    """f_xc = d^2 e / d rho^2 of ``lda_x``, ``lda_c_vwn`` or ``lda_c_pw`` (the XC kernel of apply_kernel, xc.jl:245-330) by a
+    complex step on the first derivative above: no second hand-derived formula.  The step is relative, 2^-30 rho (error of
+    the order 2^-60), and the quotient uses the step as stored, so that a subnormal step at rho ~ 1e-300 loses nothing."""
+    rho = np.asarray(rho, dtype=float)
+    h = rho * 2.0 ** -30
+    return np.imag(_FUNCTIONALS[name](rho + 1j * h)[1]) / h
 
 
 # ---- collinear spin (LDA): energy densities e(rho_up, rho_down) written with analytic primitives only; the potentials
@@ -276,12 +306,12 @@ def _lda_x_spin_e(ra, rb):
 
 def _pw92_G(rs, A, a1, b1, b2, b3, b4):
     sq = np.sqrt(rs)
-    return -2 * A * (1 + a1 * rs) * np.log(1 + 1 / (2 * A * (b1 * sq + b2 * rs + b3 * rs * sq + b4 * rs * rs)))
+    return -2 * A * (1 + a1 * rs) * _log1p(1 / (2 * A * (b1 * sq + b2 * rs + b3 * rs * sq + b4 * rs * rs)))
 
 
 def _lda_c_pw_spin_e(ra, rb):
     """Perdew-Wang 1992 with the spin interpolation of their eq. (8) (libxc ``lda_c_pw``, original parameters,
-    f''(0) = 1.709921).  PARITY UNPINNED like the unpolarised form."""
+    f''(0) = 1.709921).  Pinned like the unpolarised form (tests/test_xc_reference.py)."""
     rt, zeta, fz, rs = _zeta_terms(ra, rb)
     e0 = _pw92_G(rs, 0.031091, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294)
     e1 = _pw92_G(rs, 0.015545, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517)
@@ -343,12 +373,12 @@ def _gga_c_pbe_e(rho, sigma):
     a, a1, b1, b2, b3, b4 = 0.0310907, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294
     rs = (3 / (4 * math.pi * rho)) ** (1 / 3)
     sq = np.sqrt(rs)
-    eps = -2 * a * (1 + a1 * rs) * np.log1p(1 / (2 * a * (b1 * sq + b2 * rs + b3 * rs * sq + b4 * rs * rs)))
+    eps = -2 * a * (1 + a1 * rs) * _log1p(1 / (2 * a * (b1 * sq + b2 * rs + b3 * rs * sq + b4 * rs * rs)))
     kf = (3 * math.pi ** 2 * rho) ** (1 / 3)
     t2 = sigma * math.pi / (16 * kf * rho * rho)
     A = beta / gamma / np.expm1(-eps / gamma)
     f1 = t2 + A * t2 * t2
-    H = gamma * np.log1p(beta / gamma * f1 / (1 + A * f1))
+    H = gamma * _log1p(beta / gamma * f1 / (1 + A * f1))
     return rho * (eps + H)
 
 
@@ -357,8 +387,10 @@ _DENSITY_THRESHOLD = 1e-12   # below it a GGA contributes nothing (libxc-style d
 
 
 def _gga_terms(fun, rho, sigma):
-    """(e, de/drho, de/dsigma) by complex-step differentiation."""
-    h = 1e-30
+    """(e, de/drho, de/dsigma) by complex-step differentiation.  The step must be negligible against rho and against
+    sigma ~ (2 k_F rho)^2, which is 4e-31 at rho = 1e-12 and 8e-74 at rho = 1e-28; the imaginary parts (down to ~1e-110 for
+    rho >= 1e-28) stay far from underflow."""
+    h = 1e-100
     e = fun(rho, sigma)
     vrho = np.imag(fun(rho + 1j * h, sigma.astype(complex))) / h
     vsigma = np.imag(fun(rho.astype(complex), sigma + 1j * h)) / h
