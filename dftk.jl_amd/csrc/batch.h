@@ -1,8 +1,9 @@
 // batch.h -- lock-step batching of many small k-blocks ("must batch across k-points and bands
 // inside one launch to beat launch latency"; the reference's loop over k-points is sequential, src/eigen/diag.jl:24-48).
 //
-// The LOBPCG driver (lobpcg.cpp) stays the single statement of the algorithm.  dftk_mi_lobpcg_multi runs one instance
-// of it per k-block as a FIBER on the calling thread.  While a fiber runs, every device operation it issues (the
+// lobpcg.cpp stays the single statement of the algorithm: the steps of the iteration are written once (struct Lob) and
+// both of its drivers -- the host-driven one and the one-synchronisation-per-iteration one for small blocks -- call
+// them.  dftk_mi_lobpcg_multi runs one instance per k-block as a FIBER on the calling thread.  While a fiber runs, every device operation it issues (the
 // internal entry points zgemm, ew_*, dense_potrf_trtri, dense_heev, apply_H, host<->device copies) is RECORDED instead
 // of launched; when the fiber needs a result on the host it yields.  Once every fiber has yielded (or finished) the
 // recorded queues are merged position by position: operations of the same kind become ONE launch over all k-blocks
@@ -53,7 +54,7 @@ enum BOpType {
 //   ORTHO    n rows, m columns of X (C, ldc; m <= 8), k columns of Y (A, lda; k <= 16, 0 = ortho!(X) alone), W = column norms of X
 //            (optional), s0 = tol, host = double[4] {status, ortho!(X, Y) rounds, Cholesky count, growth factor} (after the round);
 //            status 0 = done, 1 = a rare branch is needed (drop_small!, SVD fallback: X is NOT usable), 2 = non-finite input
-// Extensions used by the small-block LOBPCG driver (lobpcg_run_small): RESIDUAL with W3 != null takes lam[c] = W[c] / W3[c];
+// Extensions used by the small-block LOBPCG driver (lobpcg.cpp: lobpcg_run_small): RESIDUAL with W3 != null takes lam[c] = W[c] / W3[c];
 // HEEV with E != null also leaves the eigenvalues in that DEVICE array (the residual pass of the same round reads them).
 struct BOp {
     int type = 0;

@@ -4,9 +4,11 @@
 // src/eigen/lobpcg_hyper_impl.jl:354-582 (B = I) including rayleigh_ritz (:141-171),
 // safe_cholesky (:190-210), ortho!(X) (:216-261), drop_small! (:264-268), ortho!(X,Y,BY)
 // (:271-323), final_retval (:325-338), compute_lambda (:341-344) and the TPA preconditioner of
-// src/eigen/preconditioners.jl:50-77.  Control flow (locking, active views, adaptive
-// orthogonalisation loops) runs on the host from a handful of reduced scalars per iteration;
-// every n_G-sized operation is a kernel on the basis' stream.
+// src/eigen/preconditioners.jl:50-77.  Control flow (locking, active views) runs on the host from a
+// handful of reduced scalars per iteration; every n_G-sized operation is a kernel on the basis' stream.
+// The iteration is stated once, as the steps of struct Lob.  Two drivers call them: lobpcg_run_general
+// (host-driven orthogonalisation loops and eigensolver; every block) and lobpcg_run_small (those as fused
+// recorded operations, one host synchronisation per iteration; small blocks of a batched call).
 #include "common.h"
 #include "batch.h"
 #include <cstdio>
@@ -25,6 +27,7 @@
 namespace {
 
 const double EPS = 2.220446049250313e-16;
+const double ORTHO_TOL = 2 * EPS;     // ortho_tol of LOBPCG (lobpcg_hyper_impl.jl:355)
 // ortho!(X, Y) on blocks up to this many elements lets its drop_small! fetch ride on the next Cholesky status (ortho_XY)
 const int64_t DEFER_FETCH_MAX_ELEMS = 1 << 16;
 const cd ONE = {1.0, 0.0}, ZERO = {0.0, 0.0}, MONE = {-1.0, 0.0};
@@ -277,11 +280,6 @@ bool contiguous(const std::vector<Mat>& Ys) {
             Ys[i].p + (int64_t)Ys[i].cols * Ys[i].ld != Ys[i + 1].p)
             return false;
     return !Ys.empty();
-}
-int total_cols(const std::vector<Mat>& Ys) {
-    int n = 0;
-    for (auto& Y : Ys) n += Y.cols;
-    return n;
 }
 
 // ortho!(X, Y, BY) with Y = hcat(Ys...), B = I
@@ -562,22 +560,10 @@ static int host_ortho_small_impl(std::vector<zd>& Xio, int n, int m, const zd* Y
 // largest coefficient block (elements) orthogonalised on the host: 32 KiB per k-block of a batched call
 const size_t HOST_CP_MAX_ELEMS = 2048;
 
-// C = sum_b Yb * coef[rows of b]   (LazyHcat * Matrix, lobpcg_hyper_impl.jl:124-132).  The active
-// blocks are kept adjacent in memory (see the workspace layout in lobpcg_run), so this is ONE GEMM
-// with k = sum of the block widths; the per-block loop only serves non-adjacent callers.
-int hcat_mul(Ctx& c, const std::vector<Mat>& Ys, const cd* coef, int64_t ldcoef, int ncols, Mat C) {
-    if (contiguous(Ys))
-        return c.mm('N', Ys[0].rows, ncols, total_cols(Ys), ONE, Ys[0].p, Ys[0].ld, coef, ldcoef, ZERO, C.p,
-                     C.ld);
-    int64_t off = 0;
-    bool first = true;
-    for (auto& Y : Ys) {
-        if (Y.cols == 0) continue;
-        CHK(c.mm('N', Y.rows, ncols, Y.cols, ONE, Y.p, Y.ld, coef + off, ldcoef, first ? ZERO : ONE, C.p, C.ld));
-        first = false;
-        off += Y.cols;
-    }
-    return 0;
+// C = hcat(Ys...) * coef   (LazyHcat * Matrix, lobpcg_hyper_impl.jl:124-132).  The active blocks are adjacent in memory
+// (see the workspace layout in Lob::bind), so Y is ONE matrix and this ONE GEMM with k = sum of the block widths.
+int hcat_mul(Ctx& c, const Mat& Y, const cd* coef, int64_t ldcoef, int ncols, Mat C) {
+    return c.mm('N', Y.rows, ncols, Y.cols, ONE, Y.p, Y.ld, coef, ldcoef, ZERO, C.p, C.ld);
 }
 
 // small replicated matrices (Ritz coefficients) are orthogonalised with the same routines: no reductions there
@@ -596,6 +582,356 @@ struct NoComm {
         c.replicated = false;
         c.small = false;
         c.rf = saved_rf;
+    }
+};
+
+// One LOBPCG call on one k-block: the workspace, the state of the iteration and every step that does not depend on HOW the
+// orthogonalisations, the Rayleigh-Ritz eigenproblem and the residual pass are issued.  The two drivers below
+// (lobpcg_run_general, lobpcg_run_small) issue those in their own way and call the steps in the reference's order:
+//   bind; [entry: ortho!(X), A X, Rayleigh quotients]; rayleigh_quotients;
+//   per iteration: views; [A R, Rayleigh-Ritz]; ritz_update; [residuals, fetch into hf]; lock; update_P; advance;
+//                  [ortho!(R, [X P])]; check_ortho
+//   sort_pairs; [copy-out]; report
+struct Lob {
+    Ctx c;
+    dftk_mi_kblock* kb = nullptr;
+    dftk_mi_basis* b = nullptr;
+    int M = 0;
+    int64_t N = 0;                  // rows of every n_G-sized block (this rank's slab / the half sphere / n_G)
+    const double* kin = nullptr;    // kinetic energies of those rows (TPA), or null
+    // ---- workspace (views into kb->lob_buf) ----
+    Mat Yb[2], AYb[2], newR;
+    cd *tmp = nullptr, *G = nullptr, *V = nullptr, *cP = nullptr;
+    // double slots, DS apart: [ d_a | d_b | d_norms | d_mk | d_xx ] (adjacent: what one fetch brings to hf), d_lam, d_rn, perm
+    int DS = 0;
+    double *dd = nullptr, *d_norms = nullptr, *d_mk = nullptr, *d_xx = nullptr, *d_lam = nullptr, *d_rn = nullptr;
+    int* d_perm = nullptr;
+    std::vector<double> hf;         // host image of the first five slots: the drivers fetch into it, the steps read it
+    // A X kept at the last exit of the general driver on this block, if the caller promised the same X and the shape fits
+    cd* kept_AX = nullptr;
+    int64_t kept_ld = 0;
+    // ---- state of the call ----
+    std::vector<double> resid_history, full_lam;
+    double& RH(int i, int it) { return resid_history[(size_t)i + (size_t)M * it]; }
+    int cur = 0;                    // the pair Yb[cur], AYb[cur] holds the current X, AX
+    int nlocked = 0, niter = 0, lo = 0, final_iter = 0;
+    bool finished = false;
+    int64_t n_matvec = 0;
+    // ---- views of iteration niter (views) ----
+    int nact = 0, nY = 0;
+    Mat X, AX, Xa, AXa, Ra, ARa, nX, nAX, nR;
+    Mat Y, AY;                      // hcat(X_active, [P,] R) and A times it: nY columns (from iteration 1 on)
+    std::vector<zd> h_cX;           // host copy of the Ritz coefficients (ritz_update)
+    bool host_cp = false;
+    int ncx = 0;
+    // ---- outcome of the locking decision (lock) ----
+    int newly_locked = 0, lenXn = 0, tgt = 0;
+    Mat nP, nAP, Rn;
+    std::vector<int> perm;          // final_retval's sort (sort_pairs)
+
+    Mat Pblk(const Mat& buf, int na) const { return buf.cols_from(M, na); }
+    Mat Rblk(const Mat& buf, int na, bool has_p) const { return buf.cols_from(M + (has_p ? na : 0), na); }
+
+    // Grow kb->lob_buf and carve it; seed the generators; empty history.  dstride: stride of the double slots (it sets the
+    // span of the drivers' reductions over adjacent slots, so each driver passes its own).
+    int bind(dftk_mi_kblock* kb_, int M_, int64_t N_, int dstride, dftk_mi_comm* comm, bool real_mode, const double* kin_,
+             uint64_t seed, int maxiter) {
+        kb = kb_;
+        b = kb->basis;
+        M = M_;
+        N = N_;
+        kin = kin_;
+        DS = dstride;
+        const size_t blk = (size_t)N * M;                   // elements of one n_G x M block
+        const size_t nbig = 14;                             // 2 x Y(3: X R P), 2 x AY(3), newR, tmp
+        const size_t m3 = 3 * (size_t)M;
+        const size_t small_elems = m3 * m3 * 2              // G, V
+                                   + m3 * M * 2             // cP, tmpS
+                                   + (size_t)M * M * 4      // O, Rw, invR, Vh
+                                   + (2 * (size_t)M + m3) * (M + 1);   // BYX (+1 scratch column)
+        const size_t dbl = 9 * (size_t)DS;
+        const size_t need = (nbig * blk + small_elems) * sizeof(cd) + dbl * sizeof(double) + m3 * sizeof(int) + 1024;
+        // The kept A X (dftk_mi_kblock_reuse_AX) lives in this buffer and every call overwrites it: whichever driver binds the
+        // workspace consumes the promise and drops what is kept
+        const bool reuse_asked = kb->ax_reuse_next;
+        kb->ax_reuse_next = false;
+        kept_AX = reuse_asked && kb->ax_M == M && kb->ax_rows == N ? kb->ax_keep : nullptr;
+        kept_ld = kb->ax_ld;
+        kb->ax_keep = nullptr;
+        if (need > kb->lob_bytes) {
+            CHK(host_wait(b));
+            if (kb->lob_buf) HIPCHK(hipFree(kb->lob_buf));
+            kb->lob_buf = nullptr;
+            kb->lob_bytes = 0;
+            kept_AX = nullptr;               // (it lived in the buffer that has just gone)
+            HIPCHK(dftk_scratch_malloc((void**)&kb->lob_buf, need));
+            kb->lob_bytes = need;
+        }
+        cd* w = kb->lob_buf;
+        auto take = [&](size_t n) {
+            cd* r = w;
+            w += n;
+            return r;
+        };
+        // Y = [X | P | R] and AY = [AX | AP | AR] live in n_G x 3M arrays.  X keeps columns [0, M);
+        // the ACTIVE search-direction block sits at columns [M, M + nact) and the active residual block
+        // right behind it at [M + nact, M + 2 nact), so that hcat(X_active, P, R) -- columns
+        // [lo, M + 2 nact) -- is one contiguous matrix: Rayleigh-Ritz is one Gram GEMM and the block
+        // updates one GEMM with k = 3 nact instead of per-block products; hcat(X, P) (all of X and the new P) is
+        // contiguous for ortho!(R, [X P]).  The block ORDER inside the hcat only permutes the rows of the Ritz
+        // coefficient matrix.  Until P exists (iterations 0, 1) R sits right after X.
+        // There are TWO such pairs of arrays: an iteration reads Y/AY of the current pair and writes the new
+        // X, AX, P, AP straight into the other one (no copy-back of n_G x M blocks); locked columns are kept
+        // identical in both, then the roles swap.
+        for (Mat& m : Yb) m = Mat{take(3 * blk), N, N, 3 * M};
+        for (Mat& m : AYb) m = Mat{take(3 * blk), N, N, 3 * M};
+        newR = Mat{take(blk), N, N, M};
+        tmp = take(blk);
+        G = take(m3 * m3);
+        V = take(m3 * m3);
+        cP = take(m3 * M);
+        c.kb = kb;
+        c.b = b;
+        c.comm = comm;
+        c.real_mode = real_mode;
+        c.holds_g0 = real_mode && gamma_row0(kb) == 0;
+        c.rf = real_mode ? DFTK_MI_GEMM_REAL : 0;
+        c.tmpS = take(m3 * M);
+        c.O = take((size_t)M * M);
+        c.Rw = take((size_t)M * M);
+        c.invR = take((size_t)M * M);
+        c.Vh = take((size_t)M * M);
+        c.BYX = take((2 * (size_t)M + m3) * (M + 1));
+        dd = reinterpret_cast<double*>(w);
+        c.d_a = dd;
+        c.d_b = dd + DS;
+        c.dstride = DS;
+        d_norms = dd + 2 * DS;
+        d_mk = dd + 3 * DS;
+        d_xx = dd + 4 * DS;
+        d_lam = dd + 5 * DS;
+        d_rn = dd + 6 * DS;
+        d_perm = reinterpret_cast<int*>(dd + 7 * DS);
+        hf.assign(5 * (size_t)DS, 0.0);
+        // every rank of a sharded block draws its own slab of a re-randomised column
+        c.rng.seed((seed ? seed : 0x9E3779B97F4A7C15ull) + 0x632BE59BD9B4E019ull * (uint64_t)comm_rank(comm));
+        c.rng_rep.seed((seed ? seed : 0x9E3779B97F4A7C15ull) ^ 0xD1B54A32D192ED03ull);
+        X = Yb[0].cols_from(0, M);
+        AX = AYb[0].cols_from(0, M);
+        kb->last_AX = real_mode ? nullptr : AX.p;   // (half-format blocks are not handed out)
+        resid_history.assign((size_t)M * (maxiter + 1), 0.0);
+        full_lam.assign(M, 0.0);
+        final_iter = maxiter;
+        n_matvec = M;
+        return 0;
+    }
+
+    // lambda = Re(X'AX)/(X'X) column-wise from the column dots in hf (slots d_a, d_b).  The reference's "any(!isfinite, AX)"
+    // check (:380) rides on them: a non-finite entry of AX makes its column's dot non-finite (0 * inf and x * nan are nan).
+    int rayleigh_quotients() {
+        for (int i = 0; i < M; ++i) {
+            if (!std::isfinite(hf[i])) {
+                dftk_set_error("non-finite values in H*X");
+                return DFTK_MI_NUM_NONFINITE;
+            }
+            full_lam[i] = hf[i] / hf[DS + i];
+        }
+        return 0;
+    }
+
+    // the blocks iteration niter reads and writes
+    void views() {
+        nact = M - lo;
+        Mat &Yc = Yb[cur], &AYc = AYb[cur], &Yn = Yb[cur ^ 1], &AYn = AYb[cur ^ 1];
+        X = Yc.cols_from(0, M);
+        AX = AYc.cols_from(0, M);
+        Xa = X.cols_from(lo);
+        AXa = AX.cols_from(lo);
+        Ra = Rblk(Yc, nact, niter > 1);
+        ARa = Rblk(AYc, nact, niter > 1);
+        // iteration 0 has no update: the "new" X is X itself; afterwards it is written into the other pair
+        nX = niter > 0 ? Yn.cols_from(lo, nact) : Xa;
+        nAX = niter > 0 ? AYn.cols_from(lo, nact) : AXa;
+        nR = newR.cols_from(0, nact);
+        nY = niter > 1 ? 3 * nact : niter > 0 ? 2 * nact : 0;   // [Xa | Pa | Ra], before P exists [Xa | Ra]
+        Y = Yc.cols_from(lo, nY);
+        AY = AYc.cols_from(lo, nY);
+    }
+
+    // new X = Y cX, new AX = AY cX with the Ritz coefficients cX = V[:, 1:nact] the eigensolver has left (or will leave, in
+    // stream order) on the device.  Small coefficient blocks are copied to the host as well: update_P orthogonalises cP there
+    // (the copy rides on the residual fetch).  join: the two products share a launch of a batched call.
+    int ritz_update(bool join) {
+        // No re-orthonormalisation of the Ritz coefficient block: the reference does that only for the
+        // CPU-LAPACK `syevr` of Julia < 1.12 (lobpcg_hyper_impl.jl:152-171); its GPU arrays take the generic
+        // method (:145-151) and Julia >= 1.12 `syevd`, both without it.  The Jacobi eigenvectors are an
+        // accumulated product of unitary rotations (||V'V - I|| ~ 1e-13, tests/test_gpu_kernels.py::test_heev).
+        ncx = nact;
+        host_cp = (size_t)nY * nact <= HOST_CP_MAX_ELEMS;
+        if (host_cp) {
+            h_cX.resize((size_t)nY * nact);
+            CHK(dev_d2h_async(b, h_cX.data(), V, h_cX.size() * sizeof(cd)));
+        }
+        CHK(hcat_mul(c, Y, V, nY, nact, nX));
+        if (join) batch_join_next();
+        return hcat_mul(c, AY, V, nY, nact, nAX);
+    }
+
+    // The residual norms of this iteration (hf, slot d_norms) go into the history; then the locking decision.  Either the
+    // call is finished (n_conv_check columns locked) or newly_locked, lenXn and tgt say what the rest of the iteration works on.
+    // (preconditioning -- precondprep!(new_X); ldiv!(precon, new_R) -- is applied in advance(), to the columns that stay
+    //  active only and straight into their place in the next iteration's Y)
+    int lock(double tol, int miniter, int n_conv_check) {
+        const double* h_norms = hf.data() + 2 * DS;
+        for (int i = 0; i < nact; ++i) {
+            if (!std::isfinite(h_norms[i])) {
+                dftk_set_error("non-finite residual norm in LOBPCG iteration %d", niter);
+                return DFTK_MI_NUM_NONFINITE;
+            }
+            RH(nlocked + i, niter) = h_norms[i];
+        }
+        const int prev_nlocked = nlocked;
+        if (niter >= miniter) {
+            for (int i = nlocked; i < M; ++i) {
+                if (RH(i, niter) < tol)
+                    nlocked += 1;
+                else
+                    break;
+            }
+        }
+        tgt = niter > 0 ? (cur ^ 1) : cur;   // the pair that now holds the up-to-date X, AX
+        if (nlocked >= n_conv_check) {
+            cur = tgt;     // locked columns [0, lo) are identical in both pairs, [lo, M) were just written
+            final_iter = niter;
+            finished = true;
+            return 0;
+        }
+        newly_locked = nlocked - prev_nlocked;
+        lenXn = nact - newly_locked;   // == M - nlocked
+        nP = Pblk(Yb[tgt], lenXn);     // next iteration's P, AP: written in place
+        nAP = Pblk(AYb[tgt], lenXn);
+        return 0;
+    }
+
+    // cP = (cX - e)[:, newly_locked:], orthogonalised against all of cX; P = Y cP, AP = AY cP.  (From iteration 1 on.)
+    int update_P(bool join) {
+        if (niter == 0) return 0;
+        cd* cX = V;
+        bool cp_done = false;
+        if (host_cp) {
+            // (h_cX is valid: the residual fetch was a synchronising call)
+            std::vector<zd> h_cP(h_cX.begin() + (size_t)newly_locked * nY, h_cX.begin() + (size_t)(newly_locked + lenXn) * nY);
+            for (int a = 0; a < lenXn - newly_locked; ++a)
+                if (2 * newly_locked + a < nY) h_cP[(size_t)(2 * newly_locked + a) + (size_t)a * nY] -= 1.0;
+            if (host_ortho_small(h_cP, nY, lenXn, h_cX.data(), ncx, ORTHO_TOL, &c.rng_rep, c.real_mode)) {
+                CHK(h2d(b, cP, h_cP.data(), h_cP.size() * sizeof(cd)));
+                cp_done = true;
+            }
+        }
+        if (!cp_done) {
+            CHK(ew_copy(b, nY, lenXn, cX + (int64_t)newly_locked * nY, nY, cP, nY));
+            CHK(ew_sub_identity_shifted(b, nY, lenXn - newly_locked, cP, nY, 2 * newly_locked));
+            std::vector<Mat> cXs = {Mat{cX, nY, nY, ncx}};
+            NoComm replicated(c);
+            CHK(ortho_XY(c, Mat{cP, nY, nY, lenXn}, cXs, c.tmpS, ORTHO_TOL));
+        }
+        CHK(hcat_mul(c, Y, cP, nY, lenXn, nP));
+        if (join) batch_join_next();
+        return hcat_mul(c, AY, cP, nY, lenXn, nAP);
+    }
+
+    // Normalisation check of the new X (hf, slot d_xx); newly locked columns mirrored into the other pair; restriction to the
+    // active columns; the preconditioned residuals of the columns that stay active go to their place Rn in the next
+    // iteration's Y (their norms to d_rn, local sums of a sharded block).  What follows is ortho!(Rn, [X P]).
+    int advance() {
+        const double* h_xx = hf.data() + 4 * DS;
+        // sanity: |<x,x> - 1| < sqrt(eps)
+        for (int i = 0; i < nact; ++i)
+            if (!(std::fabs(h_xx[i] - 1.0) < std::sqrt(EPS))) {
+                dftk_set_error("LOBPCG is badly failing to keep the vectors normalized (column %d: %g; iteration %d, "
+                               "%d locked, %d active, %d ranks)", lo + i, h_xx[i], niter, nlocked, nact, comm_size(c.comm));
+                return DFTK_MI_NUM_NORMALIZATION;
+            }
+        // newly locked columns never change again: keep them identical in both pairs
+        if (newly_locked > 0) {
+            CHK(ew_copy(b, N, newly_locked, Yb[tgt].p + (int64_t)lo * N, N, Yb[tgt ^ 1].p + (int64_t)lo * N, N));
+            CHK(ew_copy(b, N, newly_locked, AYb[tgt].p + (int64_t)lo * N, N, AYb[tgt ^ 1].p + (int64_t)lo * N, N));
+        }
+        // restrict to active
+        lo = nlocked;
+        cur = tgt;
+        X = Yb[cur].cols_from(0, M);
+        AX = AYb[cur].cols_from(0, M);
+        Rn = Rblk(Yb[cur], lenXn, niter > 0);   // next iteration's residual block (behind P once P exists)
+        return ew_tpa(b, N, lenXn, nR.p + (int64_t)newly_locked * nR.ld, nR.ld, Rn.p, Rn.ld, kin, d_mk + newly_locked, d_rn);
+    }
+
+    // DFTK_MI_LOBPCG_CHECK (debugging aid, costs a synchronisation): || [X P R]' [X P R] - I ||_max per pair of blocks after the
+    // orthogonalisations of this iteration.  ortho_status: status word of a fused orthogonalisation, where there is one.
+    int check_ortho(const double* ortho_status) {
+        static const bool dbg_check = getenv("DFTK_MI_LOBPCG_CHECK") != nullptr;
+        if (!dbg_check) return 0;
+        const int nc = M + (niter > 0 ? 2 : 1) * lenXn;
+        CHK(c.mm('C', nc, nc, N, ONE, Yb[cur].p, N, Yb[cur].p, N, ZERO, G, nc));
+        CHK(c.reduce_c(G, (size_t)nc * nc));
+        std::vector<double> hg(2 * (size_t)nc * nc);
+        CHK(d2h_sync(b, hg.data(), G, hg.size() * sizeof(double)));
+        double worst[3][3] = {{0}};
+        auto blk_of = [&](int j) { return j < M ? 0 : (niter > 0 && j < M + lenXn ? 1 : 2); };
+        for (int j = 0; j < nc; ++j)
+            for (int i = 0; i < nc; ++i) {
+                const double re = hg[2 * ((size_t)i + (size_t)j * nc)] - (i == j ? 1.0 : 0.0);
+                const double im = hg[2 * ((size_t)i + (size_t)j * nc) + 1];
+                double& w = worst[blk_of(i)][blk_of(j)];
+                w = std::max(w, std::sqrt(re * re + im * im));
+            }
+        char tail[48] = "";
+        if (ortho_status) snprintf(tail, sizeof tail, "  (ortho status %g)", *ortho_status);
+        fprintf(stderr, "[lobpcg-check rank %d] it %d locked %d act %d  XX %.1e XP %.1e XR %.1e PP %.1e PR %.1e RR %.1e%s\n",
+                comm_rank(c.comm), niter, nlocked, lenXn, worst[0][0], worst[0][1], worst[0][2], worst[1][1], worst[1][2],
+                worst[2][2], tail);
+        return 0;
+    }
+
+    // final_retval (:325-338), device part: X and AX of the current pair, sorted by lambda if needed.  Returns true in
+    // *permuted when columns had to move.
+    int sort_pairs(bool* permuted) {
+        X = Yb[cur].cols_from(0, M);
+        AX = AYb[cur].cols_from(0, M);
+        kb->last_AX = c.real_mode ? nullptr : AX.p;
+        perm.resize(M);
+        std::iota(perm.begin(), perm.end(), 0);
+        *permuted = !std::is_sorted(full_lam.begin(), full_lam.end());
+        if (*permuted) {
+            std::stable_sort(perm.begin(), perm.end(), [&](int a, int d) { return full_lam[a] < full_lam[d]; });
+            CHK(h2d(b, d_perm, perm.data(), M * sizeof(int)));
+            CHK(ew_gather_cols(b, N, M, X.p, X.ld, d_perm, tmp, N));
+            CHK(ew_copy(b, N, M, tmp, N, X.p, X.ld));
+            CHK(ew_gather_cols(b, N, M, AX.p, AX.ld, d_perm, tmp, N));
+            CHK(ew_copy(b, N, M, tmp, N, AX.p, AX.ld));
+        }
+        return 0;
+    }
+
+    // final_retval, host part: eigenvalues, residual norms and the history in the order of the returned eigenpairs
+    void report(double tol, int n_conv_check, double* lambda_h, double* resid_h, int* n_iter_out, int* converged_out,
+                int64_t* n_matvec_out) {
+        double maxres = 0.0;
+        for (int i = 0; i < M; ++i) {
+            lambda_h[i] = full_lam[perm[i]];
+            resid_h[i] = RH(perm[i], final_iter);
+        }
+        for (int i = 0; i < n_conv_check; ++i) maxres = std::max(maxres, resid_h[i]);
+        if (!kb->lob_hist) kb->lob_hist = new std::vector<double>();
+        kb->lob_hist->assign((size_t)M * (final_iter + 1), 0.0);
+        for (int it = 0; it <= final_iter; ++it)
+            for (int i = 0; i < M; ++i) (*kb->lob_hist)[(size_t)i + (size_t)M * it] = RH(perm[i], it);
+        kb->lob_hist_M = M;
+        kb->lob_hist_iters = final_iter;
+        kb->lob_n_svd = c.n_svd;
+        *converged_out = (maxres < tol) ? 1 : 0;
+        *n_iter_out = final_iter;
+        *n_matvec_out = n_matvec;
     }
 };
 
@@ -631,6 +967,9 @@ int lobpcg_ortho(dftk_mi_basis* b, int64_t n, int m, cd* X, int64_t ldx, int for
 }
 
 std::atomic<int64_t> g_ax_reuse_count{0};     // calls that started from the kept A X (dftk_mi_ax_reuse_count)
+
+// The host-driven driver: every block shape, plane-wave sharded and Gamma-real blocks.  Each orthogonalisation, the
+// eigensolver and the residual pass come back to the host by themselves (4-6 synchronisations per iteration).
 static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, double tol, int miniter, int maxiter,
                               int n_conv_check, int use_tpa, uint64_t seed, double* lambda_h, double* resid_h, int* n_iter_out,
                               int* converged_out, int64_t* n_matvec_out) {
@@ -657,123 +996,40 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
         return DFTK_MI_EINVAL;
     }
     if (n_conv_check <= 0 || n_conv_check > M) n_conv_check = M;
-    const double ortho_tol = 2 * EPS;
 
-    // ---- workspace -------------------------------------------------------------------------
-    const size_t blk = (size_t)N * M;                   // elements of one n_G x M block
-    const size_t nbig = 14;                             // 2 x Y(3: X R P), 2 x AY(3), newR, tmp
-    const size_t m3 = 3 * (size_t)M;
-    const size_t small_elems = m3 * m3 * 2              // G, V
-                               + m3 * M * 2             // cP, tmpS
-                               + (size_t)M * M * 4      // O, Rw, invR, Vh
-                               + (2 * (size_t)M + m3) * (M + 1);   // BYX (+1 scratch column)
-    const size_t dbl = 9 * (size_t)(M + 8);
-    const size_t need = (nbig * blk + small_elems) * sizeof(cd) + dbl * sizeof(double) + m3 * sizeof(int) + 1024;
-    // A X kept from the last exit of this driver on this block (dftk_mi_kblock_reuse_AX): consumed or dropped by this call
-    const bool reuse_asked = kb->ax_reuse_next;
-    kb->ax_reuse_next = false;
-    cd* ax_prev = kb->ax_keep;
-    const int64_t ax_prev_ld = kb->ax_ld;
-    const bool ax_shape_ok = ax_prev != nullptr && kb->ax_M == M && kb->ax_rows == N;
-    kb->ax_keep = nullptr;
-    if (need > kb->lob_bytes) {
-        CHK(host_wait(b));
-        if (kb->lob_buf) HIPCHK(hipFree(kb->lob_buf));
-        kb->lob_buf = nullptr;
-        kb->lob_bytes = 0;
-        ax_prev = nullptr;               // (it lived in the buffer that has just gone)
-        HIPCHK(dftk_scratch_malloc((void**)&kb->lob_buf, need));
-        kb->lob_bytes = need;
-    }
-    bool reuse_ax = reuse_asked && ax_shape_ok && ax_prev != nullptr && kb->d_Vs != nullptr && kb->d_Vs_ax != nullptr;
-    cd* w = kb->lob_buf;
-    auto take = [&](size_t n) {
-        cd* r = w;
-        w += n;
-        return r;
-    };
-    // Y = [X | R | P] and AY = [AX | AR | AP] live in n_G x 3M arrays.  X keeps columns [0, M);
-    // the ACTIVE residual block sits at columns [M, M + nact) and the active search-direction block
-    // right behind it at [M + nact, M + 2 nact), so that hcat(X_active, R, P) -- columns
-    // [lo, M + 2 nact) -- is one contiguous matrix: Rayleigh-Ritz is one Gram GEMM and the block
-    // updates one GEMM with k = 3 nact instead of per-block products.
-    // There are TWO such pairs of arrays: an iteration reads Y/AY of the current pair and writes the new
-    // X, AX, P, AP straight into the other one (no copy-back of n_G x M blocks); locked columns are kept
-    // identical in both, then the roles swap.
-    Mat Yb[2] = {Mat{take(3 * blk), N, N, 3 * M}, Mat{take(3 * blk), N, N, 3 * M}};
-    Mat AYb[2] = {Mat{take(3 * blk), N, N, 3 * M}, Mat{take(3 * blk), N, N, 3 * M}};
-    int cur = 0;
-    // memory order [X | P | R]: hcat(X_active, P, R) is contiguous for the Rayleigh-Ritz products and
-    // hcat(X, P) (all of X and the new P) for ortho!(R, [X P]); the block ORDER inside the hcat only
-    // permutes the rows of the Ritz coefficient matrix.  Until P exists (iterations 0, 1) R sits right after X.
-    auto Pblk = [&](const Mat& buf, int nact) { return buf.cols_from(M, nact); };
-    auto Rblk = [&](const Mat& buf, int nact, bool has_p) { return buf.cols_from(M + (has_p ? nact : 0), nact); };
-    Mat newR{take(blk), N, N, M};
-    cd* tmp = take(blk);
-    cd* G = take(m3 * m3);
-    cd* V = take(m3 * m3);
-    cd* cP = take(m3 * M);
-    Ctx c;
-    c.kb = kb;
-    c.b = b;
-    c.comm = comm;
-    c.real_mode = real_mode;
-    c.holds_g0 = real_mode && gamma_row0(kb) == 0;
-    c.rf = real_mode ? DFTK_MI_GEMM_REAL : 0;
-    c.tmpS = take(m3 * M);
-    c.O = take((size_t)M * M);
-    c.Rw = take((size_t)M * M);
-    c.invR = take((size_t)M * M);
-    c.Vh = take((size_t)M * M);
-    c.BYX = take((2 * (size_t)M + m3) * (M + 1));
-    double* dd = reinterpret_cast<double*>(w);
-    c.d_a = dd;
-    c.d_b = dd + (M + 8);
-    c.dstride = M + 8;
-    double* d_lam = dd + 2 * (M + 8);
-    double* d_norms = dd + 3 * (M + 8);
-    double* d_mk = dd + 4 * (M + 8);
-    double* d_xx = dd + 5 * (M + 8);
-    double* d_rn = dd + 6 * (M + 8);    // (slot 7 holds the final permutation)
-    // every rank of a sharded block draws its own slab of a re-randomised column
-    c.rng.seed((seed ? seed : 0x9E3779B97F4A7C15ull) + 0x632BE59BD9B4E019ull * (uint64_t)comm_rank(comm));
-    c.rng_rep.seed((seed ? seed : 0x9E3779B97F4A7C15ull) ^ 0xD1B54A32D192ED03ull);
-    Mat X = Yb[0].cols_from(0, M), AX = AYb[0].cols_from(0, M);   // views of the CURRENT pair (rebound on swap)
-    kb->last_AX = real_mode ? nullptr : AX.p;
-
-    Mat Xuser{Xp, ldX, N, M};
+    Lob s;
+    const int DS = M + 8;
+    CHK(s.bind(kb, M, N, DS, comm, real_mode, kin, seed, maxiter));
+    Ctx& c = s.c;
+    bool reuse_ax = s.kept_AX != nullptr && kb->d_Vs != nullptr && kb->d_Vs_ax != nullptr;
     if (real_mode)
-        CHK(gamma_lobpcg_load(kb, M, Xp, ldX, X.p, X.ld, /*align=*/true));
+        CHK(gamma_lobpcg_load(kb, M, Xp, ldX, s.X.p, s.X.ld, /*align=*/true));
     else
-        CHK(ew_copy(b, N, M, Xuser.p, Xuser.ld, X.p, X.ld));
-    std::vector<double> resid_history((size_t)M * (maxiter + 1), 0.0);
-    auto RH = [&](int i, int it) -> double& { return resid_history[(size_t)i + (size_t)M * it]; };
-    std::vector<double> full_lam(M, 0.0);
+        CHK(ew_copy(b, N, M, Xp, ldX, s.X.p, s.X.ld));
 
     // ---- X = ortho!(copy(X)); AX = A X --------------------------------------------------------
     {
         int nch;
         double gr;
-        CHK(ortho_X(c, X, tmp, ortho_tol, &nch, &gr));
+        CHK(ortho_X(c, s.X, s.tmp, ORTHO_TOL, &nch, &gr));
         // the kept A X follows X through ONE plain Cholesky-QR pass (X <- X inv(R), the common case: X comes back orthonormal
         // to round-off from the previous step); anything else (several passes, shifts, the SVD fallback) takes the full H X
         if (reuse_ax && !(nch == 1)) reuse_ax = false;
     }
-    int64_t n_matvec = M;
     if (reuse_ax) {
+        const Mat &X = s.X, &AX = s.AX, &newR = s.newR;
         g_ax_reuse_count.fetch_add(1);
         // A_new X = (A_old X) inv(R) + (V_new - V_old) X: kinetic and nonlocal parts are those of the last call.  Saves the two
         // projector products of an H X (P' psi and P (D P' psi): 11.5 of 131 ms per late SCF step of the 1000-electron cell)
         // for one triangular product, one local-only application and two element-wise passes.
-        dftk_mi_basis* bb = b;
-        const size_t cube = (size_t)bb->nz * bb->ny * bb->nxp;
+        const size_t cube = (size_t)b->nz * b->ny * b->nxp;
         if (!kb->d_dVs) HIPCHK(hipMalloc((void**)&kb->d_dVs, cube * sizeof(double)));
-        CHK(ew_sub_real(bb, (int64_t)cube, kb->d_Vs, kb->d_Vs_ax, kb->d_dVs));
+        CHK(ew_sub_real(b, (int64_t)cube, kb->d_Vs, kb->d_Vs_ax, kb->d_dVs));
         // (A_old X) inv(R) -> AX (straight into place unless the kept block IS AX's storage: through newR then)
-        if (ax_prev != AX.p) {
-            CHK(c.mm('N', N, M, M, ONE, ax_prev, ax_prev_ld, c.invR, M, ZERO, AX.p, AX.ld, /*B upper triangular=*/2));
+        if (s.kept_AX != AX.p) {
+            CHK(c.mm('N', N, M, M, ONE, s.kept_AX, s.kept_ld, c.invR, M, ZERO, AX.p, AX.ld, /*B upper triangular=*/2));
         } else {
-            CHK(c.mm('N', N, M, M, ONE, ax_prev, ax_prev_ld, c.invR, M, ZERO, newR.p, newR.ld, /*B upper triangular=*/2));
+            CHK(c.mm('N', N, M, M, ONE, s.kept_AX, s.kept_ld, c.invR, M, ZERO, newR.p, newR.ld, /*B upper triangular=*/2));
             CHK(ew_copy(b, N, M, newR.p, newR.ld, AX.p, AX.ld));
         }
         double* const Vs_bound = kb->d_Vs;
@@ -810,251 +1066,68 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
                     wc, nrm);
         }
     } else {
-        CHK(apply_H(M, X.p, X.ld, AX.p, AX.ld));
+        CHK(apply_H(M, s.X.p, s.X.ld, s.AX.p, s.AX.ld));
     }
     // (R is written at the end of iteration 0 and P at the end of iteration 1, before their first use)
-    // lambda = Re(X'AX)/(X'X) column-wise.  The reference's "any(!isfinite, AX)" check (:380) rides on the same
-    // pass: a non-finite entry of AX makes its column's dot non-finite (0 * inf and x * nan are nan).
-    CHK(ew_coldots(b, N, M, X.p, X.ld, AX.p, AX.ld, c.d_a));
-    CHK(ew_coldots(b, N, M, X.p, X.ld, X.p, X.ld, c.d_b));
-    CHK(c.reduce_d(c.d_a, 2 * (size_t)(M + 8)));
-    CHK(d2h(c, c.d_a, 2 * (M + 8)));
-    for (int i = 0; i < M; ++i) {
-        if (!std::isfinite(c.h[i])) {
-            dftk_set_error("non-finite values in H*X");
-            return DFTK_MI_NUM_NONFINITE;
-        }
-        full_lam[i] = c.h[i] / c.h[(M + 8) + i];
-    }
-
-    int nlocked = 0, niter = 0, lo = 0;
-    int status_final = 0;
-    bool finished = false;
-    int final_iter = maxiter;
-    int ncx = 0;   // columns of cX of the current iteration
+    CHK(ew_coldots(b, N, M, s.X.p, s.X.ld, s.AX.p, s.AX.ld, c.d_a));
+    CHK(ew_coldots(b, N, M, s.X.p, s.X.ld, s.X.p, s.X.ld, c.d_b));
+    CHK(c.reduce_d(c.d_a, 2 * (size_t)DS));
+    CHK(d2h_sync(b, s.hf.data(), c.d_a, 2 * (size_t)DS * sizeof(double)));
+    CHK(s.rayleigh_quotients());
 
     while (true) {
-        const int nact = M - lo;
-        Mat &Yc = Yb[cur], &AYc = AYb[cur], &Yn = Yb[cur ^ 1], &AYn = AYb[cur ^ 1];
-        X = Yc.cols_from(0, M);
-        AX = AYc.cols_from(0, M);
-        Mat Xa = X.cols_from(lo), AXa = AX.cols_from(lo);
-        Mat Ra = Rblk(Yc, nact, niter > 1), ARa = Rblk(AYc, nact, niter > 1), Pa = Pblk(Yc, nact), APa = Pblk(AYc, nact);
-        // iteration 0 has no update: the "new" X is X itself; afterwards it is written into the other pair
-        Mat nX = niter > 0 ? Yn.cols_from(lo, nact) : Xa, nAX = niter > 0 ? AYn.cols_from(lo, nact) : AXa;
-        Mat nR = newR.cols_from(0, nact);
-        std::vector<Mat> Ys, AYs;
-        int nY = 0;
-        cd* cX = V;
-        bool host_cp = false;
-        std::vector<zd> h_cX;
-        if (niter > 0) {
-            CHK(apply_H(nact, Ra.p, Ra.ld, ARa.p, ARa.ld));
-            n_matvec += nact;
-            if (niter > 1) {
-                Ys = {Xa, Pa, Ra};
-                AYs = {AXa, APa, ARa};
-            } else {
-                Ys = {Xa, Ra};
-                AYs = {AXa, ARa};
-            }
-            nY = (int)Ys.size() * nact;
+        s.views();
+        const int nact = s.nact, nY = s.nY;
+        if (s.niter > 0) {
+            CHK(apply_H(nact, s.Ra.p, s.Ra.ld, s.ARa.p, s.ARa.ld));
+            s.n_matvec += nact;
             // rayleigh_ritz: G = Y' AY (upper triangle), eigen, take the lowest nact
-            if (contiguous(Ys) && contiguous(AYs)) {
-                CHK(c.mm('C', nY, nY, N, ONE, Ys[0].p, Ys[0].ld, AYs[0].p, AYs[0].ld, ZERO, G, nY, /*upper=*/1));
-                CHK(c.reduce_c(G, (size_t)nY * nY));
-            } else {
-                for (size_t ib = 0; ib < Ys.size(); ++ib)
-                    for (size_t ia = 0; ia <= ib; ++ia)
-                        CHK(c.mm('C', nact, nact, N, ONE, Ys[ia].p, Ys[ia].ld, AYs[ib].p, AYs[ib].ld, ZERO,
-                                  G + (int64_t)ia * nact + (int64_t)ib * nact * nY, nY));
-                CHK(c.reduce_c(G, (size_t)nY * nY));
-            }
-            CHK(ew_hermitize_upper(b, nY, G, nY));
+            CHK(c.mm('C', nY, nY, N, ONE, s.Y.p, s.Y.ld, s.AY.p, s.AY.ld, ZERO, s.G, nY, /*upper=*/1));
+            CHK(c.reduce_c(s.G, (size_t)nY * nY));
+            CHK(ew_hermitize_upper(b, nY, s.G, nY));
             std::vector<double> wv(nY);
-            {
-                // only `vectors[:, 1:N]` and the N lowest values are used (lobpcg_hyper_impl.jl:146-150): the partial solver
-                int st = dense_heev_lowest(b, nY, nact, G, nY, wv.data(), V, nY);
-                if (st != 0) return st;
-            }
-            ncx = nact;
-            // No re-orthonormalisation of the Ritz coefficient block: the reference does that only for the
-            // CPU-LAPACK `syevr` of Julia < 1.12 (lobpcg_hyper_impl.jl:152-171); its GPU arrays take the generic
-            // method (:145-151) and Julia >= 1.12 `syevd`, both without it.  The Jacobi eigenvectors are an
-            // accumulated product of unitary rotations (||V'V - I|| ~ 1e-13, tests/test_gpu_kernels.py::test_heev).
-            for (int i = 0; i < nact; ++i) full_lam[lo + i] = wv[i];
-            // small coefficient blocks: cP is orthogonalised on the host further down (host_ortho_small); the copy of cX
-            // rides on the residual fetch below
-            host_cp = (size_t)nY * nact <= HOST_CP_MAX_ELEMS;
-            if (host_cp) {
-                h_cX.resize((size_t)nY * nact);
-                CHK(dev_d2h_async(b, h_cX.data(), cX, h_cX.size() * sizeof(cd)));
-            }
-            CHK(hcat_mul(c, Ys, cX, nY, nact, nX));
-            CHK(hcat_mul(c, AYs, cX, nY, nact, nAX));
+            // only `vectors[:, 1:N]` and the N lowest values are used (lobpcg_hyper_impl.jl:146-150): the partial solver
+            CHK(dense_heev_lowest(b, nY, nact, s.G, nY, wv.data(), s.V, nY));
+            for (int i = 0; i < nact; ++i) s.full_lam[s.lo + i] = wv[i];
+            CHK(s.ritz_update(/*join=*/false));
         }
-
-        // residuals
-        CHK(h2d(b, d_lam, full_lam.data() + lo, nact * sizeof(double)));
         // residuals; the same pass over the new X yields precondprep!'s mean kinetic energies and <x,x>
-        CHK(ew_residual(b, N, nact, nAX.p, nAX.ld, nX.p, nX.ld, d_lam, nR.p, nR.ld, d_norms, kin, d_mk, d_xx));
+        CHK(h2d(b, s.d_lam, s.full_lam.data() + s.lo, nact * sizeof(double)));
+        CHK(ew_residual(b, N, nact, s.nAX.p, s.nAX.ld, s.nX.p, s.nX.ld, s.d_lam, s.nR.p, s.nR.ld, s.d_norms, kin, s.d_mk, s.d_xx));
         // norms hold sqrt(local sums); mean_kin and <x,x> are plain sums (adjacent slots)   (no-ops for an unsharded block)
-        CHK(c.reduce_norms(d_norms, nact));
-        CHK(c.reduce_d(d_mk, (size_t)(M + 8) + nact));
-        // norms, mean kinetic energies and <x,x> sit (M + 8) apart: ONE fetch; <x,x> is checked further down
-        CHK(d2h(c, d_norms, 2 * (M + 8) + nact));
-        std::vector<double> h_xx(c.h.begin() + 2 * (M + 8), c.h.begin() + 2 * (M + 8) + nact);
-        for (int i = 0; i < nact; ++i) {
-            if (!std::isfinite(c.h[i])) {
-                dftk_set_error("non-finite residual norm in LOBPCG iteration %d", niter);
-                return DFTK_MI_NUM_NONFINITE;
-            }
-            RH(nlocked + i, niter) = c.h[i];
-        }
-        // (preconditioning -- precondprep!(new_X); ldiv!(precon, new_R) -- is applied further down, to the columns
-        //  that stay active only and straight into their place in the next iteration's Y)
-        // locking
-        const int prev_nlocked = nlocked;
-        if (niter >= miniter) {
-            for (int i = nlocked; i < M; ++i) {
-                if (RH(i, niter) < tol)
-                    nlocked += 1;
-                else
-                    break;
-            }
-        }
-        const int tgt = niter > 0 ? (cur ^ 1) : cur;   // the pair that now holds the up-to-date X, AX
-        if (nlocked >= n_conv_check) {
-            cur = tgt;     // locked columns [0, lo) are identical in both pairs, [lo, M) were just written
-            final_iter = niter;
-            finished = true;
-            break;
-        }
-        const int newly_locked = nlocked - prev_nlocked;
-        const int lenXn = nact - newly_locked;   // == M - nlocked
-
-        Mat nP = Pblk(Yb[tgt], lenXn), nAP = Pblk(AYb[tgt], lenXn);   // next iteration's P, AP: written in place
-        if (niter > 0) {
-            // cP = (cX - e)[:, newly_locked:], then orthogonalise against all of cX
-            Mat cPm{cP, nY, nY, lenXn};
-            bool cp_done = false;
-            if (host_cp) {
-                // (h_cX is valid: the residual fetch above was a synchronising call)
-                std::vector<zd> h_cP(h_cX.begin() + (size_t)newly_locked * nY, h_cX.begin() + (size_t)(newly_locked + lenXn) * nY);
-                for (int a = 0; a < lenXn - newly_locked; ++a)
-                    if (2 * newly_locked + a < nY) h_cP[(size_t)(2 * newly_locked + a) + (size_t)a * nY] -= 1.0;
-                if (host_ortho_small(h_cP, nY, lenXn, h_cX.data(), ncx, ortho_tol, &c.rng_rep, c.real_mode)) {
-                    CHK(h2d(b, cP, h_cP.data(), h_cP.size() * sizeof(cd)));
-                    cp_done = true;
-                }
-            }
-            if (!cp_done) {
-                CHK(ew_copy(b, nY, lenXn, cX + (int64_t)newly_locked * nY, nY, cP, nY));
-                CHK(ew_sub_identity_shifted(b, nY, lenXn - newly_locked, cP, nY, 2 * newly_locked));
-                std::vector<Mat> cXs = {Mat{cX, nY, nY, ncx}};
-                NoComm replicated(c);
-                CHK(ortho_XY(c, cPm, cXs, c.tmpS, ortho_tol));
-            }
-            CHK(hcat_mul(c, Ys, cP, nY, lenXn, nP));
-            CHK(hcat_mul(c, AYs, cP, nY, lenXn, nAP));
-        }
-        // sanity: |<x,x> - 1| < sqrt(eps)
-        for (int i = 0; i < nact; ++i)
-            if (!(std::fabs(h_xx[i] - 1.0) < std::sqrt(EPS))) {
-                dftk_set_error("LOBPCG is badly failing to keep the vectors normalized (column %d: %g; iteration %d, "
-                               "%d locked, %d active, %d ranks)", lo + i, h_xx[i], niter, nlocked, nact, comm_size(comm));
-                return DFTK_MI_NUM_NORMALIZATION;
-            }
-        // newly locked columns never change again: keep them identical in both pairs
-        if (newly_locked > 0) {
-            CHK(ew_copy(b, N, newly_locked, Yb[tgt].p + (int64_t)lo * N, N, Yb[tgt ^ 1].p + (int64_t)lo * N, N));
-            CHK(ew_copy(b, N, newly_locked, AYb[tgt].p + (int64_t)lo * N, N, AYb[tgt ^ 1].p + (int64_t)lo * N, N));
-        }
-        // restrict to active
-        lo = nlocked;
-        cur = tgt;
-        X = Yb[cur].cols_from(0, M);
-        AX = AYb[cur].cols_from(0, M);
-        Mat Rn = Rblk(Yb[cur], lenXn, niter > 0);   // next iteration's residual block (behind P once P exists)
-        CHK(ew_tpa(b, N, lenXn, nR.p + (int64_t)newly_locked * nR.ld, nR.ld, Rn.p, Rn.ld, kin, d_mk + newly_locked,
-                   d_rn));
-        CHK(c.reduce_norms(d_rn, lenXn));
-        std::vector<Mat> Zs = {X};
-        if (niter > 0) Zs.push_back(nP);
-        CHK(ortho_XY(c, Rn, Zs, tmp, ortho_tol, d_rn));
-        static const bool dbg_check = getenv("DFTK_MI_LOBPCG_CHECK") != nullptr;
-        if (dbg_check) {   // debugging aid: || [X P R]' [X P R] - I ||_max after the orthogonalisations of this iteration
-            const int nc = M + (niter > 0 ? 2 : 1) * lenXn;
-            CHK(c.mm('C', nc, nc, N, ONE, Yb[cur].p, N, Yb[cur].p, N, ZERO, G, nc));
-            CHK(c.reduce_c(G, (size_t)nc * nc));
-            std::vector<double> hg(2 * (size_t)nc * nc);
-            CHK(d2h_sync(b, hg.data(), G, hg.size() * sizeof(double)));
-            double worst[3][3] = {{0}};
-            auto blk_of = [&](int j) { return j < M ? 0 : (niter > 0 && j < M + lenXn ? 1 : 2); };
-            for (int j = 0; j < nc; ++j)
-                for (int i = 0; i < nc; ++i) {
-                    const double re = hg[2 * ((size_t)i + (size_t)j * nc)] - (i == j ? 1.0 : 0.0);
-                    const double im = hg[2 * ((size_t)i + (size_t)j * nc) + 1];
-                    double& w = worst[blk_of(i)][blk_of(j)];
-                    w = std::max(w, std::sqrt(re * re + im * im));
-                }
-            fprintf(stderr, "[lobpcg-check rank %d] it %d locked %d act %d  XX %.1e XP %.1e XR %.1e PP %.1e PR %.1e RR %.1e\n",
-                    comm_rank(comm), niter, nlocked, lenXn, worst[0][0], worst[0][1], worst[0][2], worst[1][1],
-                    worst[1][2], worst[2][2]);
-        }
-
-        if (niter >= maxiter) break;
-        niter += 1;
+        CHK(c.reduce_norms(s.d_norms, nact));
+        CHK(c.reduce_d(s.d_mk, (size_t)DS + nact));
+        // norms, mean kinetic energies and <x,x> sit DS apart: ONE fetch
+        CHK(d2h_sync(b, s.hf.data() + 2 * DS, s.d_norms, (2 * (size_t)DS + nact) * sizeof(double)));
+        CHK(s.lock(tol, miniter, n_conv_check));
+        if (s.finished) break;
+        CHK(s.update_P(/*join=*/false));
+        CHK(s.advance());
+        CHK(c.reduce_norms(s.d_rn, s.lenXn));
+        std::vector<Mat> Zs = {s.X};
+        if (s.niter > 0) Zs.push_back(s.nP);
+        CHK(ortho_XY(c, s.Rn, Zs, s.tmp, ORTHO_TOL, s.d_rn));
+        CHK(s.check_ortho(nullptr));
+        if (s.niter >= maxiter) break;
+        s.niter += 1;
     }
-    X = Yb[cur].cols_from(0, M);
-    AX = AYb[cur].cols_from(0, M);
-    kb->last_AX = real_mode ? nullptr : AX.p;   // (half-format blocks are not handed out)
-    if (!finished) final_iter = maxiter;
-    (void)status_final;
 
-    // final_retval: sort by lambda if needed
-    std::vector<int> perm(M);
-    std::iota(perm.begin(), perm.end(), 0);
-    bool sorted = std::is_sorted(full_lam.begin(), full_lam.end());
-    if (!sorted) {
-        std::stable_sort(perm.begin(), perm.end(), [&](int a, int d) { return full_lam[a] < full_lam[d]; });
-        int* d_perm = reinterpret_cast<int*>(dd + 7 * (M + 8));
-        CHK(h2d(b, d_perm, perm.data(), M * sizeof(int)));
-        CHK(ew_gather_cols(b, N, M, X.p, X.ld, d_perm, tmp, N));
-        CHK(ew_copy(b, N, M, tmp, N, X.p, X.ld));
-        CHK(ew_gather_cols(b, N, M, AX.p, AX.ld, d_perm, tmp, N));
-        CHK(ew_copy(b, N, M, tmp, N, AX.p, AX.ld));
-        CHK(stream_sync(b));
-    }
+    bool permuted = false;
+    CHK(s.sort_pairs(&permuted));
+    if (permuted) CHK(stream_sync(b));
     // hand the eigenvectors back to the caller's array
     if (real_mode)
-        CHK(gamma_lobpcg_store(kb, M, X.p, X.ld, Xp, ldX));
+        CHK(gamma_lobpcg_store(kb, M, s.X.p, s.X.ld, Xp, ldX));
     else
-        CHK(ew_copy(b, N, M, X.p, X.ld, Xuser.p, Xuser.ld));
-    double maxres = 0.0;
-    for (int i = 0; i < M; ++i) {
-        lambda_h[i] = full_lam[perm[i]];
-        resid_h[i] = RH(perm[i], final_iter);
-    }
-    for (int i = 0; i < n_conv_check; ++i) maxres = std::max(maxres, resid_h[i]);
-    // residual history of this call, rows permuted like the returned eigenpairs (final_retval :325-338)
-    if (!kb->lob_hist) kb->lob_hist = new std::vector<double>();
-    kb->lob_hist->assign((size_t)M * (final_iter + 1), 0.0);
-    for (int it = 0; it <= final_iter; ++it)
-        for (int i = 0; i < M; ++i) (*kb->lob_hist)[(size_t)i + (size_t)M * it] = RH(perm[i], it);
-    kb->lob_hist_M = M;
-    kb->lob_hist_iters = final_iter;
-    kb->lob_n_svd = c.n_svd;
-    *converged_out = (maxres < tol) ? 1 : 0;
-    *n_iter_out = final_iter;
-    *n_matvec_out = n_matvec;
+        CHK(ew_copy(b, N, M, s.X.p, s.X.ld, Xp, ldX));
+    s.report(tol, n_conv_check, lambda_h, resid_h, n_iter_out, converged_out, n_matvec_out);
     // keep A X (sorted like the returned X) and the potential it belongs to for a dftk_mi_kblock_reuse_AX start of the next call
     if (kb->d_Vs != nullptr && !batching()) {
         const size_t cube = (size_t)b->nz * b->ny * b->nxp;
         if (!kb->d_Vs_ax) HIPCHK(hipMalloc((void**)&kb->d_Vs_ax, cube * sizeof(double)));
         HIPCHK(hipMemcpyAsync(kb->d_Vs_ax, kb->d_Vs, cube * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
-        kb->ax_keep = AX.p;
-        kb->ax_ld = AX.ld;
+        kb->ax_keep = s.AX.p;
+        kb->ax_ld = s.AX.ld;
         kb->ax_M = M;
         kb->ax_rows = N;
     }
@@ -1063,7 +1136,7 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Small blocks (the k-point workloads: n_G ~ 1e3, M <= 8) inside a batched multi-k call: the same algorithm with ONE host
+// Small blocks (the k-point workloads: n_G ~ 1e3, M <= 8) inside a batched multi-k call: the same iteration with ONE host
 // synchronisation per LOBPCG iteration.  The general driver above yields to the host 4-6 times per iteration (Cholesky
 // statuses of the ortho! loops, the Ritz values, drop_small!'s norms, the residual norms) -- each a whole scheduling
 // round of the lock-step batch (~0.2 ms whatever is in it; 27-31 rounds per SCF step of the
@@ -1076,7 +1149,8 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
 //   * what the device cannot finish by itself (a column for drop_small! to re-randomise, the SVD fallbacks, a failed
 //     eigensolver) is only DETECTED: the call then starts again on the general driver from the caller's start block,
 //     which is untouched until the end (counted: DFTK_MI_KBATCH_TRACE).
-// Control flow, tolerances, locking, the order of the blocks and every n_G-sized kernel are those of lobpcg_run_general.
+// Locking, the P update, the block order, tolerances and the tail are the steps of Lob, shared with lobpcg_run_general; only
+// how the four device parts above are issued, and when their results are read, is stated here.
 std::atomic<int64_t> g_small_calls{0}, g_small_restarts{0};
 
 bool lobpcg_small_eligible(const dftk_mi_kblock* kb, int M) {
@@ -1112,68 +1186,11 @@ static int lobpcg_run_small(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, doub
     const int64_t N = kb->n_G;
     const double* kin = use_tpa ? kb->d_kin : nullptr;
     if (n_conv_check <= 0 || n_conv_check > M) n_conv_check = M;
-    const double ortho_tol = 2 * EPS;
-    // ---- workspace (the general driver's layout; the double scratch holds the Ritz values as well) ----
-    const size_t blk = (size_t)N * M;
-    const size_t nbig = 14;
-    const size_t m3 = 3 * (size_t)M;
-    const size_t small_elems = m3 * m3 * 2 + m3 * M * 2 + (size_t)M * M * 4 + (2 * (size_t)M + m3) * (M + 1);
-    const int DS = (int)m3 + 8;                              // stride of the double slots
-    const size_t dbl = 9 * (size_t)DS;
-    const size_t need = (nbig * blk + small_elems) * sizeof(cd) + dbl * sizeof(double) + m3 * sizeof(int) + 1024;
-    if (need > kb->lob_bytes) {
-        CHK(host_wait(b));
-        if (kb->lob_buf) HIPCHK(hipFree(kb->lob_buf));
-        kb->lob_buf = nullptr;
-        kb->lob_bytes = 0;
-        HIPCHK(dftk_scratch_malloc((void**)&kb->lob_buf, need));
-        kb->lob_bytes = need;
-    }
-    cd* w = kb->lob_buf;
-    auto take = [&](size_t n) {
-        cd* r = w;
-        w += n;
-        return r;
-    };
-    Mat Yb[2] = {Mat{take(3 * blk), N, N, 3 * M}, Mat{take(3 * blk), N, N, 3 * M}};
-    Mat AYb[2] = {Mat{take(3 * blk), N, N, 3 * M}, Mat{take(3 * blk), N, N, 3 * M}};
-    int cur = 0;
-    auto Pblk = [&](const Mat& buf, int nact) { return buf.cols_from(M, nact); };
-    auto Rblk = [&](const Mat& buf, int nact, bool has_p) { return buf.cols_from(M + (has_p ? nact : 0), nact); };
-    Mat newR{take(blk), N, N, M};
-    cd* tmp = take(blk);
-    cd* G = take(m3 * m3);
-    cd* V = take(m3 * m3);
-    cd* cP = take(m3 * M);
-    Ctx c;
-    c.kb = kb;
-    c.b = b;
-    c.tmpS = take(m3 * M);
-    c.O = take((size_t)M * M);
-    c.Rw = take((size_t)M * M);
-    c.invR = take((size_t)M * M);
-    c.Vh = take((size_t)M * M);
-    c.BYX = take((2 * (size_t)M + m3) * (M + 1));
-    double* dd = reinterpret_cast<double*>(w);
-    // [ d_a | d_b | d_norms | d_mk | d_xx ] are fetched together (5 slots); d_ev, d_rn, perm follow
-    c.d_a = dd;
-    c.d_b = dd + DS;
-    c.dstride = DS;
-    double* d_norms = dd + 2 * DS;
-    double* d_mk = dd + 3 * DS;
-    double* d_xx = dd + 4 * DS;
-    double* d_ev = dd + 5 * DS;
-    double* d_rn = dd + 6 * DS;
-    c.rng.seed((seed ? seed : 0x9E3779B97F4A7C15ull));
-    c.rng_rep.seed((seed ? seed : 0x9E3779B97F4A7C15ull) ^ 0xD1B54A32D192ED03ull);
-    Mat X = Yb[0].cols_from(0, M), AX = AYb[0].cols_from(0, M);
-    kb->last_AX = AX.p;
-    Mat Xuser{Xp, ldX, N, M};
-    CHK(ew_copy(b, N, M, Xuser.p, Xuser.ld, X.p, X.ld));
-    std::vector<double> resid_history((size_t)M * (maxiter + 1), 0.0);
-    auto RH = [&](int i, int it) -> double& { return resid_history[(size_t)i + (size_t)M * it]; };
-    std::vector<double> full_lam(M, 0.0);
-    std::vector<double> hf(5 * (size_t)DS);              // landing zone of the per-iteration fetch
+    Lob s;
+    // (the slots are wide enough for the Ritz values of the 3M x 3M eigenproblem, which stay on the device in d_lam)
+    CHK(s.bind(kb, M, N, 3 * M + 8, nullptr, false, kin, seed, maxiter));
+    Ctx& c = s.c;
+    CHK(ew_copy(b, N, M, Xp, ldX, s.X.p, s.X.ld));
     double o_res[4] = {0.0, 0.0, 0.0, 1.0};              // result of the orthogonalisation in flight
     bool o_pending = false;
     auto give_up = [&]() -> int {                         // a rare branch: the general driver takes the whole call
@@ -1182,77 +1199,44 @@ static int lobpcg_run_small(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, doub
     };
 
     // ---- X = ortho!(copy(X)); AX = A X; Rayleigh quotients; residuals of iteration 0: ONE round ----
-    CHK(rec_ortho(b, X, nullptr, 0, 0, nullptr, ortho_tol, o_res));
+    CHK(rec_ortho(b, s.X, nullptr, 0, 0, nullptr, ORTHO_TOL, o_res));
     o_pending = true;
-    int64_t n_matvec = M;
-    CHK(dftk_mi_apply_H(kb, M, reinterpret_cast<const dftk_mi_cplx*>(X.p), X.ld, reinterpret_cast<dftk_mi_cplx*>(AX.p), AX.ld));
-    CHK(ew_coldots(b, N, M, X.p, X.ld, AX.p, AX.ld, c.d_a));
+    CHK(dftk_mi_apply_H(kb, M, reinterpret_cast<const dftk_mi_cplx*>(s.X.p), s.X.ld, reinterpret_cast<dftk_mi_cplx*>(s.AX.p),
+                        s.AX.ld));
+    CHK(ew_coldots(b, N, M, s.X.p, s.X.ld, s.AX.p, s.AX.ld, c.d_a));
     batch_join_next();
-    CHK(ew_coldots(b, N, M, X.p, X.ld, X.p, X.ld, c.d_b));
+    CHK(ew_coldots(b, N, M, s.X.p, s.X.ld, s.X.p, s.X.ld, c.d_b));
 
-    int nlocked = 0, niter = 0, lo = 0;
-    bool finished = false;
-    int final_iter = maxiter;
-    int ncx = 0;
-    // state of the iteration whose device part is in flight (set by `head`, consumed after the fetch)
-    int nY = 0;
-    std::vector<Mat> Ys, AYs;
-    std::vector<zd> h_cX;
-    std::vector<double> wv(m3);
+    // results of the eigensolver in flight (set by `head`, read after the fetch)
+    std::vector<double> wv(3 * (size_t)M);
     int heev_st = 0;
     bool heev_pending = false;
-    cd* cX = V;
 
-    // device part of iteration `niter` up to the residuals (everything the general driver does before its locking decision)
+    // device part of iteration s.niter up to the residuals, and THE synchronisation of the iteration
     auto head = [&]() -> int {
-        const int nact = M - lo;
-        Mat &Yc = Yb[cur], &AYc = AYb[cur], &Yn = Yb[cur ^ 1], &AYn = AYb[cur ^ 1];
-        X = Yc.cols_from(0, M);
-        AX = AYc.cols_from(0, M);
-        Mat Xa = X.cols_from(lo), AXa = AX.cols_from(lo);
-        Mat Ra = Rblk(Yc, nact, niter > 1), ARa = Rblk(AYc, nact, niter > 1), Pa = Pblk(Yc, nact), APa = Pblk(AYc, nact);
-        Mat nX = niter > 0 ? Yn.cols_from(lo, nact) : Xa, nAX = niter > 0 ? AYn.cols_from(lo, nact) : AXa;
-        Mat nR = newR.cols_from(0, nact);
-        Ys.clear();
-        AYs.clear();
-        nY = 0;
-        if (niter > 0) {
-            CHK(dftk_mi_apply_H(kb, nact, reinterpret_cast<const dftk_mi_cplx*>(Ra.p), Ra.ld, reinterpret_cast<dftk_mi_cplx*>(ARa.p),
-                                ARa.ld));
-            n_matvec += nact;
-            if (niter > 1) {
-                Ys = {Xa, Pa, Ra};
-                AYs = {AXa, APa, ARa};
-            } else {
-                Ys = {Xa, Ra};
-                AYs = {AXa, ARa};
-            }
-            nY = (int)Ys.size() * nact;
-            // (the blocks are adjacent by construction of the layout: one Gram product)
-            CHK(c.mm('C', nY, nY, N, ONE, Ys[0].p, Ys[0].ld, AYs[0].p, AYs[0].ld, ZERO, G, nY, /*upper=*/1));
-            CHK(ew_hermitize_upper(b, nY, G, nY));
-            {
-                BOp o;
-                o.b = b;
-                o.type = BOP_HEEV;
-                o.m = nY;
-                o.C = G;
-                o.ldc = nY;
-                o.D = V;
-                o.ldb = nY;
-                o.host = wv.data();
-                o.E = d_ev;
-                o.status_out = &heev_st;
-                heev_st = 0;
-                heev_pending = true;
-                CHK(batch_record(std::move(o)));
-            }
-            ncx = nact;
-            h_cX.resize((size_t)nY * nact);
-            CHK(dev_d2h_async(b, h_cX.data(), cX, h_cX.size() * sizeof(cd)));
-            CHK(hcat_mul(c, Ys, cX, nY, nact, nX));
-            batch_join_next();                               // X = Y cX and AX = AY cX: one launch
-            CHK(hcat_mul(c, AYs, cX, nY, nact, nAX));
+        s.views();
+        const int nact = s.nact, nY = s.nY;
+        if (s.niter > 0) {
+            CHK(dftk_mi_apply_H(kb, nact, reinterpret_cast<const dftk_mi_cplx*>(s.Ra.p), s.Ra.ld,
+                                reinterpret_cast<dftk_mi_cplx*>(s.ARa.p), s.ARa.ld));
+            s.n_matvec += nact;
+            CHK(c.mm('C', nY, nY, N, ONE, s.Y.p, s.Y.ld, s.AY.p, s.AY.ld, ZERO, s.G, nY, /*upper=*/1));
+            CHK(ew_hermitize_upper(b, nY, s.G, nY));
+            BOp o;
+            o.b = b;
+            o.type = BOP_HEEV;
+            o.m = nY;
+            o.C = s.G;
+            o.ldc = nY;
+            o.D = s.V;
+            o.ldb = nY;
+            o.host = wv.data();
+            o.E = s.d_lam;
+            o.status_out = &heev_st;
+            heev_st = 0;
+            heev_pending = true;
+            CHK(batch_record(std::move(o)));
+            CHK(s.ritz_update(/*join=*/true));
         }
         // residuals with the Ritz values as the device holds them (iteration 0: the Rayleigh quotients d_a / d_b)
         BOp r;
@@ -1260,35 +1244,25 @@ static int lobpcg_run_small(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, doub
         r.type = BOP_RESIDUAL;
         r.n = N;
         r.m = nact;
-        r.A = nAX.p;
-        r.lda = nAX.ld;
-        r.B = nX.p;
-        r.ldb = nX.ld;
-        r.W = niter > 0 ? d_ev : c.d_a;
-        r.W3 = niter > 0 ? nullptr : c.d_b;
-        r.C = nR.p;
-        r.ldc = nR.ld;
-        r.D = d_norms;
+        r.A = s.nAX.p;
+        r.lda = s.nAX.ld;
+        r.B = s.nX.p;
+        r.ldb = s.nX.ld;
+        r.W = s.niter > 0 ? s.d_lam : c.d_a;
+        r.W3 = s.niter > 0 ? nullptr : c.d_b;
+        r.C = s.nR.p;
+        r.ldc = s.nR.ld;
+        r.D = s.d_norms;
         r.W2 = kin;
-        r.E = d_mk;
-        r.F = d_xx;
+        r.E = s.d_mk;
+        r.F = s.d_xx;
         CHK(batch_record(std::move(r)));
-        // THE synchronisation of the iteration
-        CHK(d2h_sync(b, hf.data(), dd, hf.size() * sizeof(double)));
-        return 0;
+        return d2h_sync(b, s.hf.data(), s.dd, s.hf.size() * sizeof(double));
     };
 
     CHK(head());
-    for (int i = 0; i < M; ++i) {
-        if (!std::isfinite(hf[i])) {
-            dftk_set_error("non-finite values in H*X");
-            return DFTK_MI_NUM_NONFINITE;
-        }
-        full_lam[i] = hf[i] / hf[DS + i];
-    }
-
+    CHK(s.rayleigh_quotients());
     while (true) {
-        const int nact = M - lo;
         // ---- what came back with the fetch ----
         if (o_pending) {
             o_pending = false;
@@ -1299,137 +1273,25 @@ static int lobpcg_run_small(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, doub
             heev_pending = false;
             if (heev_st == DFTK_MI_NUM_NONFINITE) return heev_st;
             if (heev_st != 0) return give_up();
-            for (int i = 0; i < nact; ++i) full_lam[lo + i] = wv[i];
+            for (int i = 0; i < s.nact; ++i) s.full_lam[s.lo + i] = wv[i];
         }
-        Mat nR = newR.cols_from(0, nact);
-        const double* h_norms = hf.data() + 2 * DS;
-        const double* h_xx = hf.data() + 4 * DS;
-        for (int i = 0; i < nact; ++i) {
-            if (!std::isfinite(h_norms[i])) {
-                dftk_set_error("non-finite residual norm in LOBPCG iteration %d", niter);
-                return DFTK_MI_NUM_NONFINITE;
-            }
-            RH(nlocked + i, niter) = h_norms[i];
-        }
-        // locking
-        const int prev_nlocked = nlocked;
-        if (niter >= miniter) {
-            for (int i = nlocked; i < M; ++i) {
-                if (RH(i, niter) < tol)
-                    nlocked += 1;
-                else
-                    break;
-            }
-        }
-        const int tgt = niter > 0 ? (cur ^ 1) : cur;
-        if (nlocked >= n_conv_check) {
-            cur = tgt;
-            final_iter = niter;
-            finished = true;
-            break;
-        }
-        const int newly_locked = nlocked - prev_nlocked;
-        const int lenXn = nact - newly_locked;
-        Mat nP = Pblk(Yb[tgt], lenXn), nAP = Pblk(AYb[tgt], lenXn);
-        if (niter > 0) {
-            Mat cPm{cP, nY, nY, lenXn};
-            bool cp_done = false;
-            {
-                std::vector<zd> h_cP(h_cX.begin() + (size_t)newly_locked * nY, h_cX.begin() + (size_t)(newly_locked + lenXn) * nY);
-                for (int a = 0; a < lenXn - newly_locked; ++a)
-                    if (2 * newly_locked + a < nY) h_cP[(size_t)(2 * newly_locked + a) + (size_t)a * nY] -= 1.0;
-                if (host_ortho_small(h_cP, nY, lenXn, h_cX.data(), ncx, ortho_tol, &c.rng_rep, c.real_mode)) {
-                    CHK(h2d(b, cP, h_cP.data(), h_cP.size() * sizeof(cd)));
-                    cp_done = true;
-                }
-            }
-            if (!cp_done) {
-                CHK(ew_copy(b, nY, lenXn, cX + (int64_t)newly_locked * nY, nY, cP, nY));
-                CHK(ew_sub_identity_shifted(b, nY, lenXn - newly_locked, cP, nY, 2 * newly_locked));
-                std::vector<Mat> cXs = {Mat{cX, nY, nY, ncx}};
-                NoComm replicated(c);
-                CHK(ortho_XY(c, cPm, cXs, c.tmpS, ortho_tol));
-            }
-            CHK(hcat_mul(c, Ys, cP, nY, lenXn, nP));
-            batch_join_next();                               // P = Y cP and AP = AY cP: one launch
-            CHK(hcat_mul(c, AYs, cP, nY, lenXn, nAP));
-        }
-        for (int i = 0; i < nact; ++i)
-            if (!(std::fabs(h_xx[i] - 1.0) < std::sqrt(EPS))) {
-                dftk_set_error("LOBPCG is badly failing to keep the vectors normalized (column %d: %g; iteration %d, "
-                               "%d locked, %d active, small-block driver)", lo + i, h_xx[i], niter, nlocked, nact);
-                return DFTK_MI_NUM_NORMALIZATION;
-            }
-        if (newly_locked > 0) {
-            CHK(ew_copy(b, N, newly_locked, Yb[tgt].p + (int64_t)lo * N, N, Yb[tgt ^ 1].p + (int64_t)lo * N, N));
-            CHK(ew_copy(b, N, newly_locked, AYb[tgt].p + (int64_t)lo * N, N, AYb[tgt ^ 1].p + (int64_t)lo * N, N));
-        }
-        lo = nlocked;
-        cur = tgt;
-        X = Yb[cur].cols_from(0, M);
-        AX = AYb[cur].cols_from(0, M);
-        Mat Rn = Rblk(Yb[cur], lenXn, niter > 0);
-        CHK(ew_tpa(b, N, lenXn, nR.p + (int64_t)newly_locked * nR.ld, nR.ld, Rn.p, Rn.ld, kin, d_mk + newly_locked, d_rn));
+        CHK(s.lock(tol, miniter, n_conv_check));
+        if (s.finished) break;
+        CHK(s.update_P(/*join=*/true));
+        CHK(s.advance());
         // ortho!(R, [X P]): X (all M columns) and the new P are adjacent in the layout -- one kernel, status with the next fetch
-        CHK(rec_ortho(b, Rn, X.p, X.ld, M + (niter > 0 ? lenXn : 0), d_rn, ortho_tol, o_res));
+        // (at the iteration limit there is no next fetch: the result is not used)
+        CHK(rec_ortho(b, s.Rn, s.X.p, s.X.ld, M + (s.niter > 0 ? s.lenXn : 0), s.d_rn, ORTHO_TOL, o_res));
         o_pending = true;
-        static const bool dbg_check = getenv("DFTK_MI_LOBPCG_CHECK") != nullptr;
-        if (dbg_check) {   // (a diagnostic: costs a synchronisation of its own)
-            const int nc = M + (niter > 0 ? 2 : 1) * lenXn;
-            CHK(c.mm('C', nc, nc, N, ONE, Yb[cur].p, N, Yb[cur].p, N, ZERO, G, nc));
-            std::vector<double> hg(2 * (size_t)nc * nc);
-            CHK(d2h_sync(b, hg.data(), G, hg.size() * sizeof(double)));
-            double worst = 0.0;
-            for (int j = 0; j < nc; ++j)
-                for (int i = 0; i < nc; ++i) {
-                    const double re = hg[2 * ((size_t)i + (size_t)j * nc)] - (i == j ? 1.0 : 0.0);
-                    const double im = hg[2 * ((size_t)i + (size_t)j * nc) + 1];
-                    worst = std::max(worst, std::sqrt(re * re + im * im));
-                }
-            fprintf(stderr, "[lobpcg-check small] it %d locked %d act %d  ||[X P R]'[X P R] - I||_max %.1e (ortho status %g)\n", niter,
-                    nlocked, lenXn, worst, o_res[0]);
-        }
-        if (niter >= maxiter) break;
-        niter += 1;
+        CHK(s.check_ortho(&o_res[0]));
+        if (s.niter >= maxiter) break;
+        s.niter += 1;
         CHK(head());
     }
-    if (o_pending && !finished) {
-        // (maxiter reached with an orthogonalisation in flight whose result is never used)
-        o_pending = false;
-    }
-    X = Yb[cur].cols_from(0, M);
-    AX = AYb[cur].cols_from(0, M);
-    kb->last_AX = AX.p;
-    if (!finished) final_iter = maxiter;
-    std::vector<int> perm(M);
-    std::iota(perm.begin(), perm.end(), 0);
-    const bool sorted = std::is_sorted(full_lam.begin(), full_lam.end());
-    if (!sorted) {
-        std::stable_sort(perm.begin(), perm.end(), [&](int a, int d) { return full_lam[a] < full_lam[d]; });
-        int* d_perm = reinterpret_cast<int*>(dd + 7 * DS);
-        CHK(h2d(b, d_perm, perm.data(), M * sizeof(int)));
-        CHK(ew_gather_cols(b, N, M, X.p, X.ld, d_perm, tmp, N));
-        CHK(ew_copy(b, N, M, tmp, N, X.p, X.ld));
-        CHK(ew_gather_cols(b, N, M, AX.p, AX.ld, d_perm, tmp, N));
-        CHK(ew_copy(b, N, M, tmp, N, AX.p, AX.ld));
-    }
-    CHK(ew_copy(b, N, M, X.p, X.ld, Xuser.p, Xuser.ld));
-    double maxres = 0.0;
-    for (int i = 0; i < M; ++i) {
-        lambda_h[i] = full_lam[perm[i]];
-        resid_h[i] = RH(perm[i], final_iter);
-    }
-    for (int i = 0; i < n_conv_check; ++i) maxres = std::max(maxres, resid_h[i]);
-    if (!kb->lob_hist) kb->lob_hist = new std::vector<double>();
-    kb->lob_hist->assign((size_t)M * (final_iter + 1), 0.0);
-    for (int it = 0; it <= final_iter; ++it)
-        for (int i = 0; i < M; ++i) (*kb->lob_hist)[(size_t)i + (size_t)M * it] = RH(perm[i], it);
-    kb->lob_hist_M = M;
-    kb->lob_hist_iters = final_iter;
-    kb->lob_n_svd = c.n_svd;
-    *converged_out = (maxres < tol) ? 1 : 0;
-    *n_iter_out = final_iter;
-    *n_matvec_out = n_matvec;
+    bool permuted = false;
+    CHK(s.sort_pairs(&permuted));
+    CHK(ew_copy(b, N, M, s.X.p, s.X.ld, Xp, ldX));
+    s.report(tol, n_conv_check, lambda_h, resid_h, n_iter_out, converged_out, n_matvec_out);
     // (no synchronisation of its own: the copies above are queued on the fiber and run in the batch's closing round; the
     //  batched call returns only after the stream has drained)
     return 0;

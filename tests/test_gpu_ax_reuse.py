@@ -1,7 +1,8 @@
 """A X kept between the LOBPCG calls of consecutive SCF steps (lobpcg.cpp: lobpcg_run_general, dftk_mi_kblock_reuse_AX): the
 next call starts from A_new X = (A_old X) inv(R) + (V_new - V_old) X instead of a full H X -- the kinetic and nonlocal parts of
 H do not change between SCF steps (src/scf/self_consistent_field.jl:80-129).  Same eigenpairs and the same SCF as with the full
-application, for real-symmetric Gamma orbitals and for a general complex k-point."""
+application, for real-symmetric Gamma orbitals and for a general complex k-point.  The kept block lives in the k-block's LOBPCG
+workspace, which every call binds anew (lobpcg.cpp: Lob::bind): a call through the small-block driver in between drops it."""
 import ctypes as C
 
 import numpy as np
@@ -72,6 +73,43 @@ def test_second_call_from_the_kept_AX_equals_the_full_application(kcoord):
     HX = ham2[0] @ a.X
     true = torch.linalg.norm(HX - a.X * torch.as_tensor(a.λ, device="cuda")[:, None], dim=1).cpu().numpy()
     assert true[:32].max() < 1.05e-7, true[:32].max()
+
+
+def test_small_driver_call_in_between_drops_the_kept_AX(monkeypatch):
+    """general driver (keeps A X) -> small-block driver on the same block (overwrites the workspace) -> general driver with the
+    promise: nothing is reused.  DFTK_MI_KBATCH_SEQUENTIAL is read per call and sends this 6-band block to the general driver."""
+    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
+    basis = _basis([0.25, 0.0, 0.125])
+    lib = basis.lib
+    _, ham = dftk.energy_hamiltonian(basis, None, None, rho=dftk.guess_density(basis))
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    X0 = dftk.random_orbitals(basis, basis.kpoints[0], 6, gen)
+
+    def small_calls():
+        a, b = C.c_int64(), C.c_int64()
+        assert lib.dftk_mi_lobpcg_small_stats(C.byref(a), C.byref(b)) == 0
+        return a.value
+
+    def call(X, general, reuse):
+        if general:
+            monkeypatch.setenv("DFTK_MI_KBATCH_SEQUENTIAL", "1")
+        else:
+            monkeypatch.delenv("DFTK_MI_KBATCH_SEQUENTIAL", raising=False)
+        s0, c0 = small_calls(), _count(lib)
+        r = dftk.lobpcg_hyper(ham[0], X, prec=dftk.PreconditionerTPA(ham[0]), tol=1e-7, reuse_AX=reuse)
+        monkeypatch.delenv("DFTK_MI_KBATCH_SEQUENTIAL", raising=False)
+        assert small_calls() - s0 == (0 if general else 1)
+        return r, _count(lib) - c0
+
+    r0, _ = call(X0, True, False)
+    r1, reused = call(r0.X, True, True)
+    assert reused == 1, "the general driver keeps A X of this block (otherwise the rest of the test shows nothing)"
+    r2, _ = call(r1.X, False, False)
+    r3, reused = call(r2.X, True, True)
+    assert reused == 0 and r3.converged
+    r4, reused = call(r2.X, True, False)
+    assert reused == 0 and r4.converged
+    np.testing.assert_allclose(r3.λ, r4.λ, rtol=0, atol=1e-9)
 
 
 def test_scf_with_and_without_the_kept_AX(monkeypatch):

@@ -1,6 +1,9 @@
 """The small-block LOBPCG driver (lobpcg.cpp: lobpcg_run_small -- ONE host synchronisation per iteration; k_b_ortho: the
 whole ortho!(X) / ortho!(X, Y) loops of lobpcg_hyper_impl.jl:216-323 in one kernel) against NumPy, the oracle's LOBPCG
-trajectory and the general driver (``DFTK_MI_LOBPCG_SMALL=0`` in a subprocess: the switch is read once per process)."""
+trajectory and the general driver.  Both drivers walk the same iteration steps (lobpcg.cpp: struct Lob) and work in the same
+workspace of a k-block, so they are also run one after the other on ONE block in ONE process (``DFTK_MI_KBATCH_SEQUENTIAL``
+is read per call and sends a small block to the general driver); ``DFTK_MI_LOBPCG_SMALL=0`` is read once per process and
+takes a subprocess."""
 import ctypes as C
 import json
 import os
@@ -84,46 +87,99 @@ def test_fused_ortho_reports_the_branches_it_does_not_take(lib):
     assert res[0] == 2.0, res
 
 
-@pytest.mark.parametrize("use_tpa,M,ncc", [(1, 8, 5), (0, 6, 6), (1, 3, 3)])
-def test_small_driver_walks_the_oracle_trajectory(lib, use_tpa, M, ncc):
-    """tests/test_gpu_lobpcg_blocks.py::test_lobpcg_residual_history_matches_oracle for a block the small-block driver
-    takes (M <= 8): same locking pattern, residual norms per iteration, eigenvalues; no restart on the general driver."""
-    _, H, bs, kb = _tpa_setup(lib, Ecut=12, fft=(24, 24, 24))
-    rng = np.random.default_rng(21 + M)
-    tol = 1e-7
-    X0 = np.linalg.qr(_block(rng, H.n_G, M))[0]
-    calls0, restarts0 = _small_stats(lib)
-    lam, res, nit, conv, nmv, X = run_lobpcg(lib, kb, X0, tol, n_conv_check=ncc, use_tpa=use_tpa, maxiter=200)
-    calls1, restarts1 = _small_stats(lib)
-    assert calls1 == calls0 + 1 and restarts1 == restarts0, "the block must take the small-block driver without a restart"
+def _history(lib, kb):
     Mo, nio, nsvd = C.c_int(), C.c_int(), C.c_int()
     check(lib.dftk_mi_lobpcg_history(kb.h, C.byref(Mo), C.byref(nio), None, 0, C.byref(nsvd)))
     hist = np.zeros((nio.value + 1, Mo.value))
     check(lib.dftk_mi_lobpcg_history(kb.h, C.byref(Mo), C.byref(nio), hist.ctypes.data, hist.size, C.byref(nsvd)))
-    hist = hist.T
-    assert (Mo.value, nio.value) == (M, nit)
-    np.testing.assert_array_equal(hist[:, -1], res)
+    return hist.T, Mo.value, nio.value
+
+
+def _same_trajectory(hist, ref, what):
+    """Residual histories (bands x iterations) over the iterations both have, at most nine: the same columns locked (a
+    locked column's norm is recorded as 0), relative deviation < 1e-9 over the first four iterations and < 1e-4 overall."""
+    ncmp = min(hist.shape[1], ref.shape[1], 9)
+    dev_rel = np.abs(hist[:, :ncmp] - ref[:, :ncmp]) / np.maximum(ref[:, :ncmp], 1e-300)
+    print(f"max relative deviation of the residual norms per iteration ({what}):", np.array2string(dev_rel.max(axis=0), precision=2))
+    np.testing.assert_array_equal(hist[:, :ncmp] == 0.0, ref[:, :ncmp] == 0.0)
+    assert dev_rel[:, :4].max() < 1e-9, what
+    assert dev_rel.max() < 1e-4, what
+
+
+@pytest.fixture(scope="module")
+def block12(lib):
+    """ONE k-block (and its LOBPCG workspace) for every call of the tests below, whichever driver takes it."""
+    return _tpa_setup(lib, Ecut=12, fft=(24, 24, 24))
+
+
+def _run(lib, kb, monkeypatch, driver, X0, tol, **kw):
+    """run_lobpcg through the named driver; asserts with the library's counters that it was that driver."""
+    if driver == "general":
+        monkeypatch.setenv("DFTK_MI_KBATCH_SEQUENTIAL", "1")
+    else:
+        monkeypatch.delenv("DFTK_MI_KBATCH_SEQUENTIAL", raising=False)
+    calls0, restarts0 = _small_stats(lib)
+    out = run_lobpcg(lib, kb, X0, tol, **kw)
+    calls1, restarts1 = _small_stats(lib)
+    monkeypatch.delenv("DFTK_MI_KBATCH_SEQUENTIAL", raising=False)
+    assert restarts1 == restarts0, "no restart expected"
+    assert calls1 - calls0 == (1 if driver == "small" else 0), f"the block must take the {driver} driver"
+    return out
+
+
+@pytest.mark.parametrize("use_tpa,M,ncc", [(1, 8, 5), (0, 6, 6), (1, 3, 3)])
+def test_small_driver_walks_the_oracle_trajectory(lib, block12, monkeypatch, use_tpa, M, ncc):
+    """tests/test_gpu_lobpcg_blocks.py::test_lobpcg_residual_history_matches_oracle for a block the small-block driver
+    takes (M <= 8): same locking pattern, residual norms per iteration, eigenvalues; no restart on the general driver.
+    Then the same start block on the same k-block through the general driver: the same bounds against the oracle, and the two
+    device trajectories against each other."""
+    _, H, bs, kb = block12
+    rng = np.random.default_rng(21 + M)
+    tol = 1e-7
+    X0 = np.linalg.qr(_block(rng, H.n_G, M))[0]
     prec = PreconditionerTPA(H.kinetic) if use_tpa else None
     ores = LOBPCG(H.mul, X0, prec, tol, 200, miniter=1, n_conv_check=ncc)
     ohist = ores["residual_history"]
-    assert conv == 1
-    np.testing.assert_allclose(lam[:ncc], ores["λ"][:ncc], atol=1e-10)
     nit_o = ohist.shape[1] - 1
-    ncmp = min(nit, nit_o, 8) + 1
-    dev_rel = np.abs(hist[:, :ncmp] - ohist[:, :ncmp]) / np.maximum(ohist[:, :ncmp], 1e-300)
-    print("max relative deviation of the residual norms per iteration:", np.array2string(dev_rel.max(axis=0), precision=2))
-    np.testing.assert_array_equal(hist[:, :ncmp] == 0.0, ohist[:, :ncmp] == 0.0)
-    assert dev_rel[:, :4].max() < 1e-9
-    assert dev_rel.max() < 1e-4
-    assert abs(nit - nit_o) <= 2 + nit_o // 10, (nit, nit_o)
     dense = np.linalg.eigvalsh(H.to_dense())[:ncc]
-    np.testing.assert_allclose(lam[:ncc], dense, atol=1e-9)
+    hists = {}
+    for driver in ("small", "general"):
+        lam, res, nit, conv, nmv, X = _run(lib, kb, monkeypatch, driver, X0, tol, n_conv_check=ncc, use_tpa=use_tpa, maxiter=200)
+        hist, Mo, nio = _history(lib, kb)
+        hists[driver] = hist
+        assert (Mo, nio) == (M, nit)
+        np.testing.assert_array_equal(hist[:, -1], res)
+        assert conv == 1
+        np.testing.assert_allclose(lam[:ncc], ores["λ"][:ncc], atol=1e-10)
+        _same_trajectory(hist, ohist, f"{driver} driver against the oracle")
+        assert abs(nit - nit_o) <= 2 + nit_o // 10, (driver, nit, nit_o)
+        np.testing.assert_allclose(lam[:ncc], dense, atol=1e-9)
+        assert np.linalg.norm(X.conj().T @ X - np.eye(M)) < 1e-11
+        # (the reported norm of a locked column is 0, as in the reference's history; the others are the true residual norms)
+        true_res = np.linalg.norm(H.mul(X) - X * lam, axis=0)
+        assert true_res[:ncc].max() < tol
+        live = res > 0
+        np.testing.assert_allclose(true_res[live], res[live], rtol=1e-6, atol=1e-12)
+    _same_trajectory(hists["general"], hists["small"], "general driver against small driver")
+
+
+@pytest.mark.parametrize("driver", ["small", "general"])
+def test_iteration_limit_ends_the_call(lib, block12, monkeypatch, driver):
+    """maxiter reached before anything converges (for the small driver: with a fused orthogonalisation still in flight):
+    the call returns the Ritz pairs of the last iteration -- orthonormal X, lambda ascending and equal to the Rayleigh
+    quotients, the last column of the history equal to the returned residual norms."""
+    _, H, bs, kb = block12
+    M = 6
+    X0 = np.linalg.qr(_block(np.random.default_rng(33), H.n_G, M))[0]
+    lam, res, nit, conv, nmv, X = _run(lib, kb, monkeypatch, driver, X0, 1e-12, n_conv_check=4, maxiter=2)
+    assert (nit, conv) == (2, 0)
+    hist, Mo, nio = _history(lib, kb)
+    assert hist.shape == (M, 3) and (Mo, nio) == (M, 2)
+    np.testing.assert_array_equal(hist[:, -1], res)
+    assert np.all(np.diff(lam) >= 0)
     assert np.linalg.norm(X.conj().T @ X - np.eye(M)) < 1e-11
-    # (the reported norm of a locked column is 0, as in the reference's history; the others are the true residual norms)
-    true_res = np.linalg.norm(H.mul(X) - X * lam, axis=0)
-    assert true_res[:ncc].max() < tol
-    live = res > 0
-    np.testing.assert_allclose(true_res[live], res[live], rtol=1e-6, atol=1e-12)
+    rq = np.real(np.sum(X.conj() * H.mul(X), axis=0))
+    np.testing.assert_allclose(lam, rq, rtol=0, atol=1e-10)
 
 
 def test_small_driver_restarts_on_a_rank_deficient_guess(lib):
