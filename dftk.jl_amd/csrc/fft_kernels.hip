@@ -1163,33 +1163,70 @@ static bool axis_generic(const FftAxis& ax) {
     return false;
 }
 
-// launch KERNEL<GEN> with GEN chosen from the axis plan (2-3-5-smooth => lean kernel)
-#define LAUNCH_FFT(KERNEL, AX, GRID, LDS, STREAM, ...)                                               \
-    do {                                                                                             \
-        if (axis_generic(AX)) {                                                                      \
-            CHK(set_lds_attr(KERNEL<true>, LDS));                                                    \
-            hipLaunchKernelGGL((KERNEL<true>), GRID, dim3(FFT_THREADS), LDS, STREAM, __VA_ARGS__);   \
-        } else {                                                                                     \
-            CHK(set_lds_attr(KERNEL<false>, LDS));                                                   \
-            hipLaunchKernelGGL((KERNEL<false>), GRID, dim3(FFT_THREADS), LDS, STREAM, __VA_ARGS__);  \
-        }                                                                                            \
+// launch KERNEL, whose template arguments name GEN, with GEN chosen from the axis plan (2-3-5-smooth => lean kernel).
+// set_lds_attr goes with every launch: it is one comparison unless the tile needs more than 64 KiB.
+#define LAUNCH_FFT(KERNEL, AX, GRID, LDS, STREAM, ...)                                       \
+    do {                                                                                     \
+        if (axis_generic(AX)) {                                                              \
+            constexpr bool GEN = true;                                                       \
+            CHK(set_lds_attr(KERNEL, LDS));                                                  \
+            hipLaunchKernelGGL(KERNEL, GRID, dim3(FFT_THREADS), LDS, STREAM, __VA_ARGS__);   \
+        } else {                                                                             \
+            constexpr bool GEN = false;                                                      \
+            CHK(set_lds_attr(KERNEL, LDS));                                                  \
+            hipLaunchKernelGGL(KERNEL, GRID, dim3(FFT_THREADS), LDS, STREAM, __VA_ARGS__);   \
+        }                                                                                    \
     } while (0)
-#define LAUNCH_ZPASS(MODE, AX, GRID, LDS, STREAM, ...)                                                      \
-    do {                                                                                                    \
-        if (axis_generic(AX)) {                                                                             \
-            CHK(set_lds_attr(k_zpass<MODE, true>, LDS));                                                    \
-            hipLaunchKernelGGL((k_zpass<MODE, true>), GRID, dim3(FFT_THREADS), LDS, STREAM, __VA_ARGS__);   \
-        } else {                                                                                            \
-            CHK(set_lds_attr(k_zpass<MODE, false>, LDS));                                                   \
-            hipLaunchKernelGGL((k_zpass<MODE, false>), GRID, dim3(FFT_THREADS), LDS, STREAM, __VA_ARGS__);  \
-        }                                                                                                   \
-    } while (0)
+
+// the sphere tables of a k-block as a job entry; the per-band fields stay zero
+static FftJob kblock_tables(const dftk_mi_kblock* kb) {
+    FftJob j{};
+    j.line_start = kb->d_line_start;
+    j.cpos = kb->d_cpos;
+    j.line_ypos = kb->d_line_ypos;
+    j.zls = kb->d_zls;
+    j.zpos = kb->d_zpos;
+    j.z_lo = kb->z_lo;
+    j.Vs = kb->d_Vs;
+    j.n_lines = (int)kb->n_lines;
+    j.nzx = kb->nzx;
+    return j;
+}
+
+// One launch group of the pipeline: nb bands, band i in slot i of T1 / T2.  The stage functions below are the only launch
+// sites of the stage kernels.  A kernel takes the sphere tables either as scalar arguments (`tab`, one k-block) or per
+// band from a device job table (`jobs`, multi-k; `tab` is then all null / 0, which is what the kernels expect beside a table).
+struct FftPipe {
+    dftk_mi_basis* b;
+    hipStream_t stream;
+    int nb;
+    cd *T1, *T2;
+    int64_t s1, s2;       // per-band strides of T1 / T2
+    int n_lines, nzx;     // grid extents: the k-block's, or the maxima over the job table
+    FftJob tab;
+    const FftJob* jobs;
+    bool reg_z;           // the sphere planes wrap around contiguously: the register-resident z kernels may be used
+    bool book;            // prof_begin / prof_end around every stage (never for the multi-k executors)
+    int64_t n_G;          // booked bytes of stages A / E
+};
+// t_off: the first of the nb scratch slots (bands) of T1 / T2 the launch group uses (after fft_ensure_scratch)
+static FftPipe kblock_pipe(dftk_mi_kblock* kb, int nb, int t_off = 0) {
+    dftk_mi_basis* b = kb->basis;
+    const int64_t s1 = (int64_t)kb->n_lines * b->nxp, s2 = (int64_t)kb->nzx * b->ny * b->nxp;
+    return FftPipe{b, b->stream, nb, b->T1 + t_off * s1, b->T2 + t_off * s2, s1, s2, (int)kb->n_lines, kb->nzx,
+                   kblock_tables(kb), nullptr, kb->z_lo >= 0, true, kb->n_G};
+}
+// nb bands of a staged slice of a multi-k job table: the tables ride in the jobs, the grids cover the largest k-block
+static FftPipe jobs_pipe(dftk_mi_basis* b, hipStream_t stream, int nb, const FftJob* jobs, cd* T1, cd* T2, int64_t s1,
+                         int64_t s2, int max_lines, int max_nzx, bool reg_z) {
+    return FftPipe{b, stream, nb, T1, T2, s1, s2, max_lines, max_nzx, FftJob{}, jobs, reg_z, false, 0};
+}
 
 // Register-resident z kernels (FourStep): used for the axis lengths with an instantiated factorisation n = R1 R2
 // (R1 = R1A R1B >= R2 = R2A R2B) when the sphere's z planes wrap around contiguously (kb->z_lo >= 0: always so for a sphere
 // of G vectors).  The y passes keep the LDS-pass kernels: they are HBM bound (4.9 / 3.9 TB/s at 192^3) and the
-// register-resident variants of stages B and D ran at exactly their speed (113.8 vs 112.9, 144.5 vs 141.4 us per launch).  DFTK_MI_FFT_REG=0 keeps the LDS-pass kernels everywhere, DFTK_MI_FFT_REG_MIN=n (default 64)
-// is the shortest axis they take (below that a tile has fewer than 64 threads).  The launchers return 1 if not applicable.
+// register-resident variants of stages B and D ran at exactly their speed (113.8 vs 112.9, 144.5 vs 141.4 us per launch).  DFTK_MI_FFT_REG=0 keeps the LDS-pass kernels everywhere, DFTK_MI_FFT_REG_MIN=n (default 24)
+// is the shortest axis they take.  reg_launch returns 1 if not applicable: the caller then takes the LDS-pass kernel.
 #define REG_SIZES(X)                                                                                                      \
     X(24, 2, 2, 3, 2) X(27, 3, 3, 3, 1) X(30, 5, 1, 3, 2) X(32, 2, 2, 4, 2) X(36, 3, 2, 3, 2) X(40, 2, 2, 5, 2) X(48, 3, 2, 4, 2) X(54, 3, 2, 3, 3)           \
     X(45, 3, 3, 5, 1) X(50, 5, 2, 5, 1) X(60, 3, 2, 5, 2)                                                                 \
@@ -1207,55 +1244,82 @@ static bool fft_reg_on(int n) {
 static bool fft_reg_fits(const dftk_mi_basis* b) {
     return (uint64_t)b->nz * (uint64_t)b->ny * (uint64_t)b->nxp * sizeof(cd) < (1ull << 32);
 }
-struct RegZ {   // arguments of the z kernels
-    dftk_mi_basis* b;
-    hipStream_t stream;
-    dim3 grid;
-    int nzx, z_lo, nbands;
-    const double* Vs;
-    cd* T2;
-    int64_t s2;
-    const double *w, *wim;
-    double* rho;
-    const FftJob* jobs;
-    double* part = nullptr;   // density: partial cubes of grid.z band groups (k_dens_reduce), or null
-    double* rho2 = nullptr;   // density: second accumulated cube (weights FftJob::w2), or null
-};
-template <int A, int B, int C, int D>
-static int reg_zpass_t(const RegZ& r) {
+// w ... rho2: the density's weights, cube, partial cubes of grid.z band groups (k_dens_reduce) and second cube (weights
+// FftJob::w2); all null for stage C
+template <bool DENS, int A, int B, int C, int D>
+static int reg_launch_t(const FftPipe& p, dim3 grid, const double* w, const double* wim, double* rho, double* part,
+                        double* rho2) {
     typedef FourStep<A, B, C, D> FS;
+    const dftk_mi_basis* b = p.b;
     const size_t lds = (size_t)FS::LDS_ELEMS * sizeof(cd);
-    CHK(set_lds_attr(k_zpass_reg<A, B, C, D>, lds));
-    hipLaunchKernelGGL((k_zpass_reg<A, B, C, D>), r.grid, dim3(FS::THREADS), lds, r.stream, r.b->ax[2], r.b->nx, r.b->nxp, r.b->ny,
-                       r.nzx, r.z_lo, r.nbands, r.Vs, r.T2, r.s2, r.jobs);
+    if constexpr (DENS) {
+        CHK(set_lds_attr(k_zdensity_reg<A, B, C, D>, lds));
+        hipLaunchKernelGGL((k_zdensity_reg<A, B, C, D>), grid, dim3(FS::THREADS), lds, p.stream, b->ax[2], b->nx, b->nxp, b->ny,
+                           p.tab.nzx, p.tab.z_lo, p.nb, w, wim, (const cd*)p.T2, p.s2, rho, p.jobs, part, rho2);
+    } else {
+        CHK(set_lds_attr(k_zpass_reg<A, B, C, D>, lds));
+        hipLaunchKernelGGL((k_zpass_reg<A, B, C, D>), grid, dim3(FS::THREADS), lds, p.stream, b->ax[2], b->nx, b->nxp, b->ny,
+                           p.tab.nzx, p.tab.z_lo, p.nb, p.tab.Vs, p.T2, p.s2, p.jobs);
+    }
     return 0;
 }
-template <int A, int B, int C, int D>
-static int reg_zdens_t(const RegZ& r) {
-    typedef FourStep<A, B, C, D> FS;
-    const size_t lds = (size_t)FS::LDS_ELEMS * sizeof(cd);
-    CHK(set_lds_attr(k_zdensity_reg<A, B, C, D>, lds));
-    hipLaunchKernelGGL((k_zdensity_reg<A, B, C, D>), r.grid, dim3(FS::THREADS), lds, r.stream, r.b->ax[2], r.b->nx, r.b->nxp,
-                       r.b->ny, r.nzx, r.z_lo, r.nbands, r.w, r.wim, (const cd*)r.T2, r.s2, r.rho, r.jobs, r.part, r.rho2);
-    return 0;
-}
-static int reg_zpass(const RegZ& r, bool tables_ok) {
-    if (!tables_ok || !fft_reg_on(r.b->nz) || !fft_reg_fits(r.b)) return 1;
-    switch (r.b->nz) {
-#define X(NN, A, B, C, D) case NN: return reg_zpass_t<A, B, C, D>(r);
+template <bool DENS>
+static int reg_launch(const FftPipe& p, dim3 grid, const double* w = nullptr, const double* wim = nullptr, double* rho = nullptr,
+                      double* part = nullptr, double* rho2 = nullptr) {
+    if (!p.reg_z || !fft_reg_on(p.b->nz) || !fft_reg_fits(p.b)) return 1;
+    switch (p.b->nz) {
+#define X(NN, A, B, C, D) case NN: return reg_launch_t<DENS, A, B, C, D>(p, grid, w, wim, rho, part, rho2);
         REG_SIZES(X)
 #undef X
         default: return 1;
     }
 }
-static int reg_zdens(const RegZ& r, bool tables_ok) {
-    if (!tables_ok || !fft_reg_on(r.b->nz) || !fft_reg_fits(r.b)) return 1;
-    switch (r.b->nz) {
-#define X(NN, A, B, C, D) case NN: return reg_zdens_t<A, B, C, D>(r);
-        REG_SIZES(X)
-#undef X
-        default: return 1;
-    }
+// Kernels are emitted in the order of their first use.  These two instantiations, the stage functions standing as A, B, D,
+// E, C, cube modes, density, response, and launch_ifft_to_cube / launch_fft_from_cube right behind stage_z_cube keep the
+// device code object byte-identical to earlier builds (a check, nothing else: any other order computes the same).
+template int reg_launch<false>(const FftPipe&, dim3, const double*, const double*, double*, double*, double*);
+template int reg_launch<true>(const FftPipe&, dim3, const double*, const double*, double*, double*, double*);
+
+// algorithmic HBM bytes of the PRUNED pipeline (what a perfect implementation must move), per band:
+//   T1 = n_lines x nxp, T2 = nzx x ny x nxp complex numbers
+static double t1_bytes(const FftPipe& p) { return 16.0 * (double)p.s1; }
+static double t2_bytes(const FftPipe& p) { return 16.0 * (double)p.s2; }
+static int book(const FftPipe& p, int fam, double bytes) { return p.book ? prof_begin(p.b, fam, bytes) : -1; }
+
+static int stage_A(const FftPipe& p, const cd* psi, int64_t ldpsi) {
+    const dftk_mi_basis* b = p.b;
+    const int ps = book(p, PROF_FFT_A, (16.0 * p.n_G + t1_bytes(p)) * p.nb);
+    LAUNCH_FFT((k_xbwd_scatter<GEN>), b->ax[0], dim3((p.n_lines + FFT_L - 1) / FFT_L, p.nb), lds_bytes(b->nx, FFT_LS_X),
+               p.stream, b->ax[0], b->nxp, p.tab.n_lines, p.tab.line_start, p.tab.cpos, psi, ldpsi, p.T1, p.s1, p.jobs);
+    prof_end(p.b, ps);
+    return 0;
+}
+static int stage_B(const FftPipe& p) {
+    const dftk_mi_basis* b = p.b;
+    const int ps = book(p, PROF_FFT_B, (t1_bytes(p) + t2_bytes(p)) * p.nb);
+    LAUNCH_FFT((k_ybwd<GEN>), b->ax[1], dim3(b->nxp / FFT_L, p.nzx, p.nb), lds_bytes(b->ny), p.stream, b->ax[1], b->nxp,
+               b->ny, p.tab.zls, p.tab.line_ypos, (const cd*)p.T1, p.s1, p.T2, p.s2, p.jobs);
+    prof_end(p.b, ps);
+    return 0;
+}
+static int stage_D(const FftPipe& p) {
+    const dftk_mi_basis* b = p.b;
+    const int ps = book(p, PROF_FFT_D, (t1_bytes(p) + t2_bytes(p)) * p.nb);
+    LAUNCH_FFT((k_yfwd<GEN>), b->ax[1], dim3(b->nxp / FFT_L, p.nzx, p.nb), lds_bytes(b->ny), p.stream, b->ax[1], b->nxp,
+               b->ny, p.tab.zls, p.tab.line_ypos, (const cd*)p.T2, p.s2, p.T1, p.s1, p.jobs);
+    prof_end(p.b, ps);
+    return 0;
+}
+// with a job table kin, psi and out come from the jobs (pass null / 0)
+static int stage_E(const FftPipe& p, const double* kin, const cd* psi, int64_t ldpsi, cd* out, int64_t ldout,
+                   const double* shift_d) {
+    const dftk_mi_basis* b = p.b;
+    const int ps = book(p, PROF_FFT_E, (t1_bytes(p) + (kin ? 40.0 : 16.0) * p.n_G) * p.nb);
+    LAUNCH_FFT((k_xfwd_gather<GEN>), b->ax[0], dim3((p.n_lines + FFT_L - 1) / FFT_L, p.nb), lds_bytes(b->nx, FFT_LS_X),
+               p.stream, b->ax[0], b->nxp, p.tab.n_lines, p.tab.line_start, p.tab.cpos, (const cd*)p.T1, p.s1, kin, psi,
+               ldpsi, out, ldout, p.jobs, shift_d);
+    prof_end(p.b, ps);
+    return 0;
 }
 
 // 1-D grid of k_zpass: (x tile, y) columns rounded up to a multiple of the 8 XCDs, times the bands of the launch
@@ -1264,56 +1328,104 @@ static dim3 zpass_grid(const dftk_mi_basis* b, int nbands) {
     return dim3((unsigned)(((groups + 7) / 8) * 8 * nbands));
 }
 
-struct Strides {
-    int64_t s1, s2;
-};
-static Strides strides(dftk_mi_kblock* kb) {
-    dftk_mi_basis* b = kb->basis;
-    return Strides{(int64_t)kb->n_lines * b->nxp, (int64_t)kb->nzx * b->ny * b->nxp};
+// stage C: T2 read + written per band, the potential once per launch
+static int stage_C(const FftPipe& p) {
+    const dftk_mi_basis* b = p.b;
+    const dim3 grid = zpass_grid(b, p.nb);
+    const int ps = book(p, PROF_FFT_C, 2.0 * t2_bytes(p) * p.nb + 8.0 * (double)b->nz * b->ny * b->nxp);
+    const int rs = reg_launch<false>(p, grid);
+    if (rs < 0) return rs;
+    if (rs == 1)
+        LAUNCH_FFT((k_zpass<0, GEN>), b->ax[2], grid, lds_bytes(b->nz), p.stream, b->ax[2], b->nx, b->nxp, b->ny, p.tab.nzx,
+                   p.nb, p.tab.zpos, p.tab.Vs, p.T2, p.s2, (cd*)nullptr, p.jobs);
+    prof_end(p.b, ps);
+    return 0;
 }
-
-// t_off: the first of the nbb scratch slots (bands) of T1 / T2 the launch group fills
-static int run_AB(dftk_mi_kblock* kb, int nbb, const cd* psi, int64_t ldpsi, int t_off = 0) {
+// The cube modes of the z pass (1: T2 -> full cubes, 2: full cubes -> T2) take the LDS-pass kernel only: the
+// register-resident kernels work in place on the sphere planes of T2 and have no cube mode.  Not booked.
+template <int MODE>
+static int stage_z_cube(const FftPipe& p, cd* cube) {
+    const dftk_mi_basis* b = p.b;
+    LAUNCH_FFT((k_zpass<MODE, GEN>), b->ax[2], zpass_grid(b, p.nb), lds_bytes(b->nz), p.stream, b->ax[2], b->nx, b->nxp,
+               b->ny, p.tab.nzx, p.nb, p.tab.zpos, (const double*)nullptr, p.T2, p.s2, cube, p.jobs);
+    return 0;
+}
+// nb coefficient vectors (n_G apart) <-> nb cubes (nx ny nz apart) through ONE pipeline; in place is fine (the destination
+// is written by the last stage only, the source is consumed by the first)
+int launch_ifft_to_cube(dftk_mi_kblock* kb, const cd* c, cd* cube, int nb) {
     dftk_mi_basis* b = kb->basis;
-    const Strides st = strides(kb);
-    cd* const T1 = b->T1 + (int64_t)t_off * st.s1;
-    cd* const T2 = b->T2 + (int64_t)t_off * st.s2;
-    const int gl = (int)((kb->n_lines + FFT_L - 1) / FFT_L);
-    const int nxt = b->nxp / FFT_L;
-    const double Ncube = (double)b->nx * b->ny * b->nz;
-    // algorithmic HBM bytes of the PRUNED pipeline (what a perfect implementation must move):
-    //   T1 = n_lines x nxp, T2 = nzx x ny x nxp complex numbers per band
-    const double t1b = 16.0 * (double)kb->n_lines * b->nxp, t2b = 16.0 * (double)kb->nzx * b->ny * b->nxp;
-    (void)Ncube;
-    int ps = prof_begin(b, PROF_FFT_A, (16.0 * kb->n_G + t1b) * nbb);
-    LAUNCH_FFT(k_xbwd_scatter, b->ax[0], dim3(gl, nbb), lds_bytes(b->nx, FFT_LS_X), b->stream, b->ax[0],
-                       b->nxp, (int)kb->n_lines, kb->d_line_start, kb->d_cpos, psi, ldpsi, T1, st.s1, (const FftJob*)nullptr);
-    prof_end(b, ps);
-    ps = prof_begin(b, PROF_FFT_B, (t1b + t2b) * nbb);
-    LAUNCH_FFT(k_ybwd, b->ax[1], dim3(nxt, kb->nzx, nbb), lds_bytes(b->ny), b->stream, b->ax[1],
-                       b->nxp, b->ny, kb->d_zls, kb->d_line_ypos, T1, st.s1, T2, st.s2, (const FftJob*)nullptr);
-    prof_end(b, ps);
+    CHK(check_lds(b));
+    CHK(fft_ensure_scratch(b, kb, nb));
+    const FftPipe p = kblock_pipe(kb, nb);
+    CHK(stage_A(p, c, kb->n_G));
+    CHK(stage_B(p));
+    CHK(stage_z_cube<1>(p, cube));
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
-static int run_DE(dftk_mi_kblock* kb, int nbb, const double* kin, const cd* psi, int64_t ldpsi, cd* out,
-                  int64_t ldout, const double* shift_d = nullptr) {
+int launch_fft_from_cube(dftk_mi_kblock* kb, const cd* cube, cd* c, int nb) {
     dftk_mi_basis* b = kb->basis;
-    const Strides st = strides(kb);
-    const int gl = (int)((kb->n_lines + FFT_L - 1) / FFT_L);
-    const int nxt = b->nxp / FFT_L;
-    const double Ncube = (double)b->nx * b->ny * b->nz;
-    const double t1b = 16.0 * (double)kb->n_lines * b->nxp, t2b = 16.0 * (double)kb->nzx * b->ny * b->nxp;
-    (void)Ncube;
-    int ps = prof_begin(b, PROF_FFT_D, (t1b + t2b) * nbb);
-    LAUNCH_FFT(k_yfwd, b->ax[1], dim3(nxt, kb->nzx, nbb), lds_bytes(b->ny), b->stream, b->ax[1],
-                       b->nxp, b->ny, kb->d_zls, kb->d_line_ypos, b->T2, st.s2, b->T1, st.s1, (const FftJob*)nullptr);
-    prof_end(b, ps);
-    ps = prof_begin(b, PROF_FFT_E, (t1b + (kin ? 40.0 : 16.0) * kb->n_G) * nbb);
-    LAUNCH_FFT(k_xfwd_gather, b->ax[0], dim3(gl, nbb), lds_bytes(b->nx, FFT_LS_X), b->stream, b->ax[0],
-                       b->nxp, (int)kb->n_lines, kb->d_line_start, kb->d_cpos, b->T1, st.s1, kin, psi, ldpsi, out,
-                       ldout, (const FftJob*)nullptr, shift_d);
-    prof_end(b, ps);
+    CHK(check_lds(b));
+    CHK(fft_ensure_scratch(b, kb, nb));
+    const FftPipe p = kblock_pipe(kb, nb);
+    CHK(stage_z_cube<2>(p, const_cast<cd*>(cube)));
+    CHK(stage_D(p));
+    CHK(stage_E(p, nullptr, c, kb->n_G, c, kb->n_G, nullptr));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// density z pass: T2 per band + rho read-modify-write.  With a job table the weights come from the jobs (w, wim null);
+// groups > 1 deals the bands to that many partial cubes (part)
+static int stage_density(const FftPipe& p, const double* w, const double* wim, double* rho, int groups = 1,
+                         double* part = nullptr, double* rho2 = nullptr) {
+    const dftk_mi_basis* b = p.b;
+    const dim3 grid(b->nxp / FFT_L, b->ny, groups);
+    const int ps = book(p, PROF_DENS_Z, t2_bytes(p) * p.nb + 16.0 * (double)b->nx * b->ny * b->nz);
+    const int rs = reg_launch<true>(p, grid, w, wim, rho, part, rho2);
+    if (rs < 0) return rs;
+    if (rs == 1)
+        LAUNCH_FFT((k_zdensity<GEN>), b->ax[2], grid, lds_bytes(b->nz), p.stream, b->ax[2], b->nx, b->nxp, b->ny, p.tab.nzx,
+                   p.tab.zpos, p.nb, w, wim, (const cd*)p.T2, p.s2, rho, p.jobs, part, rho2);
+    prof_end(p.b, ps);
+    return 0;
+}
+// response density z pass: slots [0, nb) hold the orbitals, [nb, 2 nb) their first-order changes
+static int stage_density_response(const FftPipe& p, const double* wo, const double* wd, double* drho) {
+    const dftk_mi_basis* b = p.b;
+    const int ps = book(p, PROF_DENS_Z, 2.0 * t2_bytes(p) * p.nb + 16.0 * (double)b->nx * b->ny * b->nz);
+    LAUNCH_FFT((k_zdensity_response<GEN>), b->ax[2], dim3(b->nxp / FFT_L, b->ny), lds_bytes(b->nz), p.stream, b->ax[2], b->nx,
+               b->nxp, b->ny, p.tab.nzx, p.tab.zpos, p.nb, wo, wd, (const cd*)p.T2, p.s2, drho);
+    prof_end(p.b, ps);
+    return 0;
+}
+
+// The launch groups of one k-block: fft_batch / slots bands each, `slots` scratch slots of T1 / T2 per band.  With
+// weights, they go to the device once (general workspace; the copy from the caller's pageable arrays is staged by the
+// runtime before the call returns: no host synchronisation between the groups) and a group whose weights are all zero
+// is skipped.  wa_h, wb_h: nb host weights each, or null.  body(b0, nbb, wa_d, wb_d) launches the stages of bands
+// [b0, b0 + nbb); wa_d, wb_d are the device copies of that group's weights (null where there are none).
+template <class F>
+static int band_groups(dftk_mi_kblock* kb, int nb, int slots, const double* wa_h, const double* wb_h, F&& body) {
+    dftk_mi_basis* b = kb->basis;
+    const int group = std::max(1, b->fft_batch / slots);
+    CHK(fft_ensure_scratch(b, kb, slots * std::min(nb, group)));
+    double* d = nullptr;
+    if (wa_h) {
+        CHK(ensure_ws(b, 2 * (size_t)nb * sizeof(double)));
+        d = reinterpret_cast<double*>(b->ws);
+        HIPCHK(hipMemcpyAsync(d, wa_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (wb_h) HIPCHK(hipMemcpyAsync(d + nb, wb_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    }
+    for (int b0 = 0; b0 < nb; b0 += group) {
+        const int nbb = std::min(group, nb - b0);
+        bool any = !wa_h;
+        for (int i = 0; i < nbb && !any; ++i) any = wa_h[b0 + i] != 0.0 || (wb_h && wb_h[b0 + i] != 0.0);
+        if (!any) continue;
+        CHK(body(b0, nbb, d ? d + b0 : nullptr, wb_h ? d + nb + b0 : nullptr));
+    }
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -1329,30 +1441,16 @@ int launch_local_apply(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi,
         return launch_kinetic_only(kb, nb, psi, ldpsi, out, ldout, false, add_kinetic);
     }
     CHK(check_lds(b));
-    const int batch = b->fft_batch;
-    CHK(fft_ensure_scratch(b, kb, nb < batch ? nb : batch));
-    const Strides st = strides(kb);
-    const int nxt = b->nxp / FFT_L;
-    for (int b0 = 0; b0 < nb; b0 += batch) {
-        const int nbb = (nb - b0) < batch ? (nb - b0) : batch;
-        const cd* p = psi + (int64_t)b0 * ldpsi;
-        CHK(run_AB(kb, nbb, p, ldpsi));
-        // stage C: T2 read + written per band, the potential once per launch
-        const int pc = prof_begin(b, PROF_FFT_C, 2.0 * 16.0 * (double)kb->nzx * b->ny * b->nxp * nbb +
-                                                     8.0 * (double)b->nz * b->ny * b->nxp);
-        const RegZ rz{b, b->stream, zpass_grid(b, nbb), kb->nzx, kb->z_lo, nbb, kb->d_Vs, b->T2, st.s2, nullptr, nullptr, nullptr,
-                      nullptr};
-        const int reg_st = reg_zpass(rz, kb->z_lo >= 0);
-        if (reg_st < 0) return reg_st;
-        if (reg_st != 0)
-        LAUNCH_ZPASS(0, b->ax[2], zpass_grid(b, nbb), lds_bytes(b->nz), b->stream, b->ax[2], b->nx, b->nxp, b->ny, kb->nzx, nbb, kb->d_zpos, kb->d_Vs, b->T2, st.s2,
-                           (cd*)nullptr, (const FftJob*)nullptr);
-        prof_end(b, pc);
-        CHK(run_DE(kb, nbb, add_kinetic ? kb->d_kin : nullptr, p, ldpsi, out + (int64_t)b0 * ldout, ldout,
-                   shift_d ? shift_d + b0 : nullptr));
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    return band_groups(kb, nb, 1, nullptr, nullptr, [&](int b0, int nbb, const double*, const double*) -> int {
+        const FftPipe p = kblock_pipe(kb, nbb);
+        const cd* in = psi + (int64_t)b0 * ldpsi;
+        CHK(stage_A(p, in, ldpsi));
+        CHK(stage_B(p));
+        CHK(stage_C(p));
+        CHK(stage_D(p));
+        return stage_E(p, add_kinetic ? kb->d_kin : nullptr, in, ldpsi, out + (int64_t)b0 * ldout, ldout,
+                       shift_d ? shift_d + b0 : nullptr);
+    });
 }
 
 int launch_kinetic_only(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, cd* out, int64_t ldout,
@@ -1366,29 +1464,11 @@ int launch_kinetic_only(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi
     return 0;
 }
 
-// nb coefficient vectors (n_G apart) <-> nb cubes (nx ny nz apart) through ONE pipeline; in place is fine (the destination
-// is written by the last stage only, the source is consumed by the first)
-int launch_ifft_to_cube(dftk_mi_kblock* kb, const cd* c, cd* cube, int nb) {
-    dftk_mi_basis* b = kb->basis;
-    CHK(check_lds(b));
-    CHK(fft_ensure_scratch(b, kb, nb));
-    const Strides st = strides(kb);
-    CHK(run_AB(kb, nb, c, kb->n_G));
-    LAUNCH_ZPASS(1, b->ax[2], zpass_grid(b, nb), lds_bytes(b->nz), b->stream, b->ax[2], b->nx, b->nxp, b->ny, kb->nzx, nb, kb->d_zpos, (const double*)nullptr, b->T2, st.s2,
-                       cube, (const FftJob*)nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int launch_fft_from_cube(dftk_mi_kblock* kb, const cd* cube, cd* c, int nb) {
-    dftk_mi_basis* b = kb->basis;
-    CHK(check_lds(b));
-    CHK(fft_ensure_scratch(b, kb, nb));
-    const Strides st = strides(kb);
-    LAUNCH_ZPASS(2, b->ax[2], zpass_grid(b, nb), lds_bytes(b->nz), b->stream, b->ax[2], b->nx, b->nxp, b->ny, kb->nzx, nb, kb->d_zpos, (const double*)nullptr, b->T2, st.s2,
-                       const_cast<cd*>(cube), (const FftJob*)nullptr);
-    CHK(run_DE(kb, nb, nullptr, c, kb->n_G, c, kb->n_G));
-    HIPCHK(hipGetLastError());
+static int check_density_nz(const dftk_mi_basis* b) {
+    if (b->nz > DENS_MAXACC * FFT_TPL) {
+        dftk_set_error("density kernel supports nz <= %d", DENS_MAXACC * FFT_TPL);
+        return DFTK_MI_EINVAL;
+    }
     return 0;
 }
 
@@ -1417,76 +1497,30 @@ int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, con
         return launch_density(kb, nb, psi, ldpsi, w2_h, rho2, nullptr, nullptr, nullptr);
     }
     CHK(check_lds(b));
-    if (b->nz > DENS_MAXACC * FFT_TPL) {
-        dftk_set_error("density kernel supports nz <= %d", DENS_MAXACC * FFT_TPL);
-        return DFTK_MI_EINVAL;
-    }
-    const int batch = b->fft_batch;
-    CHK(fft_ensure_scratch(b, kb, nb < batch ? nb : batch));
-    const Strides st = strides(kb);
-    // all weights go to the device once (general workspace; the copy from the caller's pageable array is
-    // staged by the runtime before the call returns) -- no host synchronisation between the band batches
-    CHK(ensure_ws(b, 2 * (size_t)nb * sizeof(double)));
-    double* w_d = reinterpret_cast<double*>(b->ws);
-    double* wim_d = w_im_h ? w_d + nb : nullptr;
-    HIPCHK(hipMemcpyAsync(w_d, w_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (w_im_h) HIPCHK(hipMemcpyAsync(wim_d, w_im_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    for (int b0 = 0; b0 < nb; b0 += batch) {
-        const int nbb = (nb - b0) < batch ? (nb - b0) : batch;
-        bool any = false;
-        for (int i = 0; i < nbb; ++i) any = any || (w_h[b0 + i] != 0.0) || (w_im_h && w_im_h[b0 + i] != 0.0);
-        if (!any) continue;
-        CHK(run_AB(kb, nbb, psi + (int64_t)b0 * ldpsi, ldpsi));
-        const int pz = prof_begin(b, PROF_DENS_Z, 16.0 * (double)kb->nzx * b->ny * b->nxp * nbb +
-                                                      16.0 * (double)b->nx * b->ny * b->nz);   // T2 per band + rho read-modify-write
-        const RegZ rz{b, b->stream, dim3(b->nxp / FFT_L, b->ny), kb->nzx, kb->z_lo, nbb, nullptr, b->T2, st.s2, w_d + b0,
-                      wim_d ? wim_d + b0 : (const double*)nullptr, rho, nullptr};
-        const int rs = reg_zdens(rz, kb->z_lo >= 0);
-        if (rs < 0) return rs;
-        if (rs == 1)
-        LAUNCH_FFT(k_zdensity, b->ax[2], dim3(b->nxp / FFT_L, b->ny), lds_bytes(b->nz), b->stream, b->ax[2], b->nx, b->nxp, b->ny, kb->nzx, kb->d_zpos, nbb, w_d + b0,
-                           wim_d ? wim_d + b0 : (const double*)nullptr, b->T2, st.s2, rho, (const FftJob*)nullptr, (double*)nullptr);
-        prof_end(b, pz);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    CHK(check_density_nz(b));
+    return band_groups(kb, nb, 1, w_h, w_im_h, [&](int b0, int nbb, const double* w_d, const double* wim_d) -> int {
+        const FftPipe p = kblock_pipe(kb, nbb);
+        CHK(stage_A(p, psi + (int64_t)b0 * ldpsi, ldpsi));
+        CHK(stage_B(p));
+        return stage_density(p, w_d, wim_d, rho);
+    });
 }
 
 // compute_drho's inner loop at q = 0 (src/densities.jl:60-108) for one k-block: the launch groups of launch_density with
-// two scratch slots per band (orbital and first-order change), the weights uploaded once
+// two scratch slots per band (orbital and first-order change), half as many bands per group
 int launch_density_response(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const cd* dpsi, int64_t lddpsi,
                             const double* wo_h, const double* wd_h, double* drho) {
     dftk_mi_basis* b = kb->basis;
     CHK(check_lds(b));
-    if (b->nz > DENS_MAXACC * FFT_TPL) {
-        dftk_set_error("density kernel supports nz <= %d", DENS_MAXACC * FFT_TPL);
-        return DFTK_MI_EINVAL;
-    }
-    const int batch = b->fft_batch > 1 ? b->fft_batch / 2 : 1;
-    const int group = nb < batch ? nb : batch;
-    CHK(fft_ensure_scratch(b, kb, 2 * group));
-    const Strides st = strides(kb);
-    CHK(ensure_ws(b, 2 * (size_t)nb * sizeof(double)));
-    double* wo_d = reinterpret_cast<double*>(b->ws);
-    double* wd_d = wo_d + nb;
-    HIPCHK(hipMemcpyAsync(wo_d, wo_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(wd_d, wd_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    for (int b0 = 0; b0 < nb; b0 += batch) {
-        const int nbb = (nb - b0) < batch ? (nb - b0) : batch;
-        bool any = false;
-        for (int i = 0; i < nbb; ++i) any = any || wo_h[b0 + i] != 0.0 || wd_h[b0 + i] != 0.0;
-        if (!any) continue;
-        CHK(run_AB(kb, nbb, psi + (int64_t)b0 * ldpsi, ldpsi, 0));
-        CHK(run_AB(kb, nbb, dpsi + (int64_t)b0 * lddpsi, lddpsi, nbb));
-        const int pz = prof_begin(b, PROF_DENS_Z, 32.0 * (double)kb->nzx * b->ny * b->nxp * nbb +
-                                                      16.0 * (double)b->nx * b->ny * b->nz);
-        LAUNCH_FFT(k_zdensity_response, b->ax[2], dim3(b->nxp / FFT_L, b->ny), lds_bytes(b->nz), b->stream, b->ax[2], b->nx,
-                   b->nxp, b->ny, kb->nzx, kb->d_zpos, nbb, (const double*)(wo_d + b0), (const double*)(wd_d + b0),
-                   (const cd*)b->T2, st.s2, drho);
-        prof_end(b, pz);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    CHK(check_density_nz(b));
+    return band_groups(kb, nb, 2, wo_h, wd_h, [&](int b0, int nbb, const double* wo_d, const double* wd_d) -> int {
+        const FftPipe p = kblock_pipe(kb, nbb), pd = kblock_pipe(kb, nbb, nbb);
+        CHK(stage_A(p, psi + (int64_t)b0 * ldpsi, ldpsi));
+        CHK(stage_B(p));
+        CHK(stage_A(pd, dpsi + (int64_t)b0 * lddpsi, lddpsi));
+        CHK(stage_B(pd));
+        return stage_density_response(p, wo_d, wd_d, drho);
+    });
 }
 
 int launch_pad_potential(dftk_mi_kblock* kb, const double* V) {
@@ -1513,19 +1547,10 @@ struct MultiPlan {
 void add_jobs(MultiPlan& mp, const dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, cd* out, int64_t ldout,
               bool kinetic, const double* w, const double* wim, const double* w2 = nullptr) {
     for (int i = 0; i < nb; ++i) {
-        FftJob j;
-        j.line_start = kb->d_line_start;
-        j.cpos = kb->d_cpos;
-        j.line_ypos = kb->d_line_ypos;
-        j.zls = kb->d_zls;
-        j.zpos = kb->d_zpos;
-        j.z_lo = kb->z_lo;
+        FftJob j = kblock_tables(kb);
         j.kin = kinetic ? kb->d_kin : nullptr;
-        j.Vs = kb->d_Vs;
         j.psi = psi + (int64_t)i * ldpsi;
         j.out = out ? out + (int64_t)i * ldout : nullptr;
-        j.n_lines = (int)kb->n_lines;
-        j.nzx = kb->nzx;
         j.w = w ? w[i] : 0.0;
         j.wim = wim ? wim[i] : j.w;
         j.w2 = w2 ? w2[i] : 0.0;
@@ -1534,6 +1559,30 @@ void add_jobs(MultiPlan& mp, const dftk_mi_kblock* kb, int nb, const cd* psi, in
     mp.max_lines = std::max(mp.max_lines, (int)kb->n_lines);
     mp.max_nzx = std::max(mp.max_nzx, kb->nzx);
     mp.reg_z = mp.reg_z && kb->z_lo >= 0;
+}
+// The chunks of a multi-k call: ONE scratch request holds T1 of a chunk of bands, T2 of the chunk and `extra_bytes`
+// behind them (*extra); a chunk is all jobs, what fits 2 GiB, or 4096 bands, whichever is least.  body(pipe) launches
+// the stages of one chunk, whose slice of the job table has been staged to the device.  The caller holds the
+// BatchScratchScope that the scratch lives in.
+template <class F>
+int multi_chunks(BatchCtx* ctx, hipStream_t stream, dftk_mi_basis* b, const MultiPlan& mp, size_t extra_bytes, void** extra,
+                 F&& body) {
+    const int64_t s1 = (int64_t)mp.max_lines * b->nxp, s2 = (int64_t)mp.max_nzx * b->ny * b->nxp;
+    const size_t per_band = (size_t)(s1 + s2) * sizeof(cd);
+    int chunk = (int)std::max<size_t>(1, std::min<size_t>(mp.jobs.size(), ((size_t)2 << 30) / per_band));
+    if (chunk > 4096) chunk = 4096;
+    cd* T1 = reinterpret_cast<cd*>(batch_scratch(ctx, per_band * chunk + extra_bytes));
+    if (!T1) return DFTK_MI_EHIP;
+    cd* T2 = T1 + (size_t)s1 * chunk;
+    if (extra) *extra = reinterpret_cast<char*>(T1) + per_band * chunk;
+    for (size_t j0 = 0; j0 < mp.jobs.size(); j0 += chunk) {
+        const int nb = (int)std::min<size_t>(chunk, mp.jobs.size() - j0);
+        const FftJob* dj = reinterpret_cast<const FftJob*>(batch_stage(ctx, mp.jobs.data() + j0, nb * sizeof(FftJob)));
+        if (!dj) return DFTK_MI_EHIP;
+        CHK(body(jobs_pipe(b, stream, nb, dj, T1, T2, s1, s2, mp.max_lines, mp.max_nzx, mp.reg_z)));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 }  // namespace
 
@@ -1550,51 +1599,19 @@ int batch_exec_apply_H(BatchCtx* ctx, hipStream_t stream, std::vector<BOp*>& ops
     for (BOp* o : ops)
         add_jobs(mp, o->kb, o->m, reinterpret_cast<const cd*>(o->A), o->lda, reinterpret_cast<cd*>(o->C), o->ldc, true, nullptr,
                  nullptr);
-    const int nxt = b->nxp / FFT_L;
-    const int64_t s1 = (int64_t)mp.max_lines * b->nxp, s2 = (int64_t)mp.max_nzx * b->ny * b->nxp;
-    const size_t per_band = (size_t)(s1 + s2) * sizeof(cd);
-    int chunk = (int)std::max<size_t>(1, std::min<size_t>(mp.jobs.size(), ((size_t)2 << 30) / per_band));
-    if (chunk > 4096) chunk = 4096;
     // one scratch request for the whole call: T1 / T2 of a chunk of bands, then the two projection panels of all k-blocks
     size_t np_total = 0;
     for (BOp* o : ops) np_total += (size_t)o->kb->n_p * o->m;
     BatchScratchScope scratch_scope(ctx);
-    cd* T1 = reinterpret_cast<cd*>(batch_scratch(ctx, per_band * chunk + 2 * np_total * sizeof(cd)));
-    if (!T1) return DFTK_MI_EHIP;
-    cd* T2 = T1 + (size_t)s1 * chunk;
-    cd* Pbuf = reinterpret_cast<cd*>(reinterpret_cast<char*>(T1) + per_band * chunk);
-    const int gl = (mp.max_lines + FFT_L - 1) / FFT_L;
-    for (size_t j0 = 0; j0 < mp.jobs.size(); j0 += chunk) {
-        const int nb = (int)std::min<size_t>(chunk, mp.jobs.size() - j0);
-        const FftJob* dj = reinterpret_cast<const FftJob*>(batch_stage(ctx, mp.jobs.data() + j0, nb * sizeof(FftJob)));
-        if (!dj) return DFTK_MI_EHIP;
-        CHK(set_lds_attr(k_xbwd_scatter<false>, lds_bytes(b->nx, FFT_LS_X)));
-        CHK(set_lds_attr(k_ybwd<false>, lds_bytes(b->ny)));
-        CHK(set_lds_attr(k_yfwd<false>, lds_bytes(b->ny)));
-        CHK(set_lds_attr(k_xfwd_gather<false>, lds_bytes(b->nx, FFT_LS_X)));
-        hipLaunchKernelGGL((k_xbwd_scatter<false>), dim3(gl, nb), dim3(FFT_THREADS), lds_bytes(b->nx, FFT_LS_X), stream, b->ax[0],
-                           b->nxp, 0, (const int*)nullptr, (const int*)nullptr, (const cd*)nullptr, (int64_t)0, T1, s1, dj);
-        hipLaunchKernelGGL((k_ybwd<false>), dim3(nxt, mp.max_nzx, nb), dim3(FFT_THREADS), lds_bytes(b->ny), stream, b->ax[1],
-                           b->nxp, b->ny, (const int*)nullptr, (const int*)nullptr, (const cd*)T1, s1, T2, s2, dj);
-        {
-            const int64_t groups = (int64_t)nxt * b->ny;
-            const dim3 grid((unsigned)(((groups + 7) / 8) * 8 * nb));
-            const RegZ rz{b, stream, grid, 0, 0, nb, nullptr, T2, s2, nullptr, nullptr, nullptr, dj};
-            const int rs = reg_zpass(rz, mp.reg_z);
-            if (rs < 0) return rs;
-            if (rs == 1) {
-                CHK(set_lds_attr(k_zpass<0, false>, lds_bytes(b->nz)));
-                hipLaunchKernelGGL((k_zpass<0, false>), grid, dim3(FFT_THREADS), lds_bytes(b->nz), stream, b->ax[2], b->nx, b->nxp,
-                                   b->ny, 0, nb, (const int*)nullptr, (const double*)nullptr, T2, s2, (cd*)nullptr, dj);
-            }
-        }
-        hipLaunchKernelGGL((k_yfwd<false>), dim3(nxt, mp.max_nzx, nb), dim3(FFT_THREADS), lds_bytes(b->ny), stream, b->ax[1],
-                           b->nxp, b->ny, (const int*)nullptr, (const int*)nullptr, (const cd*)T2, s2, T1, s1, dj);
-        hipLaunchKernelGGL((k_xfwd_gather<false>), dim3(gl, nb), dim3(FFT_THREADS), lds_bytes(b->nx, FFT_LS_X), stream, b->ax[0],
-                           b->nxp, 0, (const int*)nullptr, (const int*)nullptr, (const cd*)T1, s1, (const double*)nullptr,
-                           (const cd*)nullptr, (int64_t)0, (cd*)nullptr, (int64_t)0, dj, (const double*)nullptr);
-    }
-    HIPCHK(hipGetLastError());
+    void* panels = nullptr;
+    CHK(multi_chunks(ctx, stream, b, mp, 2 * np_total * sizeof(cd), &panels, [](const FftPipe& p) -> int {
+        CHK(stage_A(p, nullptr, 0));
+        CHK(stage_B(p));
+        CHK(stage_C(p));
+        CHK(stage_D(p));
+        return stage_E(p, nullptr, nullptr, 0, nullptr, 0, nullptr);
+    }));
+    cd* Pbuf = reinterpret_cast<cd*>(panels);
     // nonlocal part: H psi += P (D (P' psi)) per k-block through the batched small products
     if (np_total == 0) return 0;
     std::vector<BOp> g1, g2, g3;
@@ -1659,52 +1676,27 @@ int batch_exec_density(BatchCtx* ctx, hipStream_t stream, std::vector<BOp*>& ops
         }
     }
     if (mp.jobs.empty()) return 0;
-    const int nxt = b->nxp / FFT_L;
-    const int64_t s1 = (int64_t)mp.max_lines * b->nxp, s2 = (int64_t)mp.max_nzx * b->ny * b->nxp;
-    const size_t per_band = (size_t)(s1 + s2) * sizeof(cd);
-    int chunk = (int)std::max<size_t>(1, std::min<size_t>(mp.jobs.size(), ((size_t)2 << 30) / per_band));
-    if (chunk > 4096) chunk = 4096;
     BatchScratchScope scratch_scope(ctx);
-    cd* T1 = reinterpret_cast<cd*>(batch_scratch(ctx, per_band * chunk));
-    if (!T1) return DFTK_MI_EHIP;
-    cd* T2 = T1 + (size_t)s1 * chunk;
-    const int gl = (mp.max_lines + FFT_L - 1) / FFT_L;
-    for (size_t j0 = 0; j0 < mp.jobs.size(); j0 += chunk) {
-        const int nb = (int)std::min<size_t>(chunk, mp.jobs.size() - j0);
-        const FftJob* dj = reinterpret_cast<const FftJob*>(batch_stage(ctx, mp.jobs.data() + j0, nb * sizeof(FftJob)));
-        if (!dj) return DFTK_MI_EHIP;
-        hipLaunchKernelGGL((k_xbwd_scatter<false>), dim3(gl, nb), dim3(FFT_THREADS), lds_bytes(b->nx, FFT_LS_X), stream, b->ax[0],
-                           b->nxp, 0, (const int*)nullptr, (const int*)nullptr, (const cd*)nullptr, (int64_t)0, T1, s1, dj);
-        hipLaunchKernelGGL((k_ybwd<false>), dim3(nxt, mp.max_nzx, nb), dim3(FFT_THREADS), lds_bytes(b->ny), stream, b->ax[1],
-                           b->nxp, b->ny, (const int*)nullptr, (const int*)nullptr, (const cd*)T1, s1, T2, s2, dj);
+    return multi_chunks(ctx, stream, b, mp, 0, nullptr, [&](const FftPipe& p) -> int {
+        CHK(stage_A(p, nullptr, 0));
+        CHK(stage_B(p));
         // small cubes: (x tile, y) columns alone are 100-200 workgroups walking ALL bands one after the other (36^3, 54 bands:
         // 178 us); the bands are dealt to up to 32 groups with a partial cube each, summed in group order by k_dens_reduce
         const int64_t cube = (int64_t)b->nx * b->ny * b->nz;
         int groups = 1;
-        if ((int64_t)nxt * b->ny < 1024 && nb >= 16) groups = std::min(32, std::max(1, nb / 8));
+        if ((int64_t)(b->nxp / FFT_L) * b->ny < 1024 && p.nb >= 16) groups = std::min(32, std::max(1, p.nb / 8));
         double* part = nullptr;
         if (groups > 1) {
             part = reinterpret_cast<double*>(batch_scratch(ctx, (size_t)(rho2 ? 2 : 1) * groups * cube * sizeof(double)));
             if (!part) return DFTK_MI_EHIP;
         }
-        RegZ rz{b, stream, dim3(nxt, b->ny, groups), 0, 0, nb, nullptr, T2, s2, nullptr, nullptr, rho, dj};
-        rz.part = part;
-        rz.rho2 = rho2;
-        const int rs = reg_zdens(rz, mp.reg_z);
-        if (rs < 0) return rs;
-        if (rs == 1) {
-            CHK(set_lds_attr(k_zdensity<false>, lds_bytes(b->nz)));
-            hipLaunchKernelGGL((k_zdensity<false>), dim3(nxt, b->ny, groups), dim3(FFT_THREADS), lds_bytes(b->nz), stream, b->ax[2], b->nx,
-                               b->nxp, b->ny, 0, (const int*)nullptr, nb, (const double*)nullptr, (const double*)nullptr,
-                               (const cd*)T2, s2, rho, dj, part, rho2);
-        }
+        CHK(stage_density(p, nullptr, nullptr, rho, groups, part, rho2));
         if (part) {
             hipLaunchKernelGGL(k_dens_reduce, dim3((unsigned)((cube + 255) / 256)), dim3(256), 0, stream, cube, groups, (const double*)part, rho);
             if (rho2)
                 hipLaunchKernelGGL(k_dens_reduce, dim3((unsigned)((cube + 255) / 256)), dim3(256), 0, stream, cube, groups,
                                    (const double*)(part + (size_t)groups * cube), rho2);
         }
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+        return 0;
+    });
 }

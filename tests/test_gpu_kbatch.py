@@ -177,3 +177,84 @@ def test_gamma_point_of_a_batched_mesh_stays_in_the_batch():
         assert res["converged"]
         e.append(res["energies"].total)
     assert abs(e[0] - e[1]) < 1e-8
+
+
+@pytest.mark.parametrize("n,radius", [(24, 5.3), (20, 4.3)])
+def test_density_multi_across_the_4096_band_chunk(n, radius):
+    """``dftk_mi_density_accumulate_multi2`` over MORE jobs than one chunk of the multi-k pipeline holds (a chunk is
+    min(jobs, 2 GiB / per_band, 4096) bands).  3 k-blocks of 1640 random columns on one n^3 basis; every 7th band has
+    weight exactly 0 in BOTH weight sets and never enters the job table, so job indices run behind band indices: 1405
+    jobs per block, N = 4215 in all, the boundary falls inside the third block and the second round of the chunk loop
+    runs with 119 jobs.  (The columns per block are 1640 and not 1400 because the dropped bands must not take the job
+    count below the boundary.)  The spheres differ (Gamma and two generic k-points: the grids are sized for the
+    largest, surplus workgroups of the others leave); 24 is the shortest axis with a register-resident z kernel, 20 has
+    none (the LDS ``k_zdensity`` under a job table); two weight sets and two cubes, so that the 32 partial-cube band
+    groups (nxt ny = 72 < 1024, nb >= 16) carry both accumulators on both sides of the boundary.  Reference:
+    ``dftk_mi_density_accumulate`` per k-block and weight set on a second basis handle that never sees a batched call.
+    Both sides add the same non-negative terms w |psi|^2 per entry, from the same per-band transforms, in different
+    orders: recursive summation with two roundings per term errs by <= 2 N u relative per sum, two sums are compared =>
+    |d rho| <= 4 N u rho_ref entrywise, u = 2^-53; the cubes integrate to n^3 sum_b w_b |c_b|^2 (Parseval of the
+    unnormalised transform) to the same bound.
+    ``batch_exec_apply_H`` walks its chunks with the same planner; more than 4096 bands in one ``lobpcg_multi`` round cannot
+    be reached at a small shape, so this test is what covers its second chunk too."""
+    import ctypes as C
+    from dftk_jl_amd._lib import check
+    from test_gpu_kernels import Basis, KBlock
+    lib = dftk.load_library()
+    ax = dftk.basis.G_axis(n)
+    gz, gy, gx = np.meshgrid(ax, ax, ax, indexing="ij")
+    G = np.stack([gx.reshape(-1), gy.reshape(-1), gz.reshape(-1)], axis=1).astype(float)
+    maps = [np.nonzero((((G + np.array(k)) ** 2).sum(axis=1) <= radius ** 2))[0]
+            for k in ([0.0, 0.0, 0.0], [0.13, -0.27, 0.41], [-0.31, 0.22, 0.07])]
+    M = 1640
+    rng = np.random.default_rng(n)
+    w1, w2 = [], []
+    for _ in maps:
+        a, b = rng.uniform(0.1, 2.0, M), rng.uniform(0.1, 2.0, M)
+        a[0::7] = 0.0
+        b[0::7] = 0.0
+        w1.append(a)
+        w2.append(b)
+    wa, wb = np.concatenate(w1), np.concatenate(w2)
+    jobs = (wa != 0) | (wb != 0)                                       # a band is dropped when all its weights are zero
+    N = int(np.count_nonzero(jobs))
+    # the chunk of the pipeline, from the sphere tables: T1 = n_lines x nxp, T2 = nzx x ny x nxp complex numbers per band
+    nxp = (n + 7) // 8 * 8
+    n_lines = [len(np.unique(m // n)) for m in maps]
+    nzx = [len(np.unique(m // (n * n))) for m in maps]
+    assert len(set(n_lines)) > 1 and len(set(nzx)) > 1 and len({len(m) for m in maps}) == 3, (n_lines, nzx)
+    per_band = (max(n_lines) * nxp + max(nzx) * n * nxp) * 16
+    chunk = min(N, (2 << 30) // per_band, 4096)
+    assert N < 3 * M and N > chunk and N % chunk != 0 and chunk == 4096, (N, per_band, chunk)
+    first = int(np.nonzero(np.cumsum(jobs) == chunk + 1)[0][0])        # band index of the first job of the second chunk
+    assert first > chunk and 2 * M < first < 3 * M, first               # shifted by the dropped bands, inside the third block
+    multi, single = Basis(lib, n, n, n), Basis(lib, n, n, n)
+    psi, kbs = [], []
+    ref = torch.zeros((2, n, n, n), dtype=torch.float64, device="cuda")
+    expect = np.zeros(2)
+    rho = torch.zeros_like(ref)
+    for m, a, b in zip(maps, w1, w2):
+        c = rng.standard_normal((M, len(m))) + 1j * rng.standard_normal((M, len(m)))
+        psi.append(torch.from_numpy(c).cuda())
+        torch.cuda.synchronize()                                       # the library works on its own stream
+        kbs.append(KBlock(lib, multi, m, np.zeros(len(m))))
+        kb0 = KBlock(lib, single, m, np.zeros(len(m)))
+        for i, w in enumerate((a, b)):
+            check(lib.dftk_mi_density_accumulate(kb0.h, M, psi[-1].data_ptr(), len(m), w.ctypes.data, ref[i].data_ptr()))
+            expect[i] += n ** 3 * float(w @ (np.abs(c) ** 2).sum(axis=1))
+        single.sync()
+    check(lib.dftk_mi_density_accumulate_multi2(3, (C.c_void_p * 3)(*[k.h.value for k in kbs]), (C.c_int * 3)(*[M] * 3),
+                                                (C.c_void_p * 3)(*[p.data_ptr() for p in psi]),
+                                                (C.c_int64 * 3)(*[p.shape[1] for p in psi]), wa.ctypes.data,
+                                                rho[0].data_ptr(), wb.ctypes.data, rho[1].data_ptr()))
+    multi.sync()
+    got, want = rho.cpu().numpy(), ref.cpu().numpy()
+    bound = 4 * N * 2.0 ** -53
+    for i in range(2):
+        assert want[i].min() > 0.0
+        worst = float(np.max(np.abs(got[i] - want[i]) / want[i]))
+        print(f"n = {n}, cube {i}: max |d rho| / rho_ref = {worst:.3e} (bound {bound:.3e}); "
+              f"sums {got[i].sum():.15e} {want[i].sum():.15e} expected {expect[i]:.15e}")
+        assert np.all(np.abs(got[i] - want[i]) <= bound * want[i])
+        assert abs(got[i].sum() - expect[i]) <= bound * expect[i]
+        assert abs(want[i].sum() - expect[i]) <= bound * expect[i]

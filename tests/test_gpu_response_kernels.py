@@ -158,7 +158,7 @@ GROUP_CASES = {
 @pytest.mark.parametrize("Ecut,fft_size", [(6, (33, 16, 20)), (20, (32, 36, 40))])
 def test_density_response_band_groups_and_weights(lib, Ecut, fft_size, case):
     """Code paths of launch_density_response: a second and later launch group (``psi + b0 * ldpsi``, ``dpsi + b0 * lddpsi``,
-    ``wo_d + b0``, ``wd_d + b0`` with b0 > 0, the slot offset nbb of the second run_AB differing between groups), the
+    ``wo_d + b0``, ``wd_d + b0`` with b0 > 0, the slot offset nbb of the second stage A / B pair differing between groups), the
     skipped all-zero group, fft_batch = 1, and in the kernel the ``w2 == 0 && w1 == 0`` and ``w2 == 0`` branches.  One of
     the grids has nz = 40 > 32.  Two identical calls give bitwise identical results (one writer per drho entry)."""
     nb, batch, wo, wd = GROUP_CASES[case]
