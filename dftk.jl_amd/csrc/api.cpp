@@ -360,6 +360,7 @@ extern "C" int dftk_mi_basis_create(int nx, int ny, int nz, double unit_cell_vol
         FftAxis& ax = b->ax[a];
         ax.n = n;
         if (plan_radices(n, &ax.nrad, ax.rad) != 0) {
+            dftk_mi_basis_destroy(b);   // this path only: the Prof, the stream and the tables of the earlier axes
             dftk_set_error("cannot plan FFT axis of length %d", n);
             return DFTK_MI_EINVAL;
         }

@@ -94,7 +94,17 @@ def dif(buf, n, rad, sgn):
     return buf
 
 
-@pytest.mark.parametrize("n", [1, 2, 8, 12, 15, 17, 21, 27, 30, 33, 36, 40, 120, 150, 192])
+def largest_prime_factor(n):
+    p, big = 2, 1
+    while n > 1:
+        while n % p == 0:
+            big, n = p, n // p
+        p += 1
+    return big
+
+
+# every length up to 256 that the planner accepts: radices 2 ... 8 and the generic primes 7 ... 61
+@pytest.mark.parametrize("n", [n for n in range(1, 257) if largest_prime_factor(n) < 67])
 def test_fft_plan_tables(lib, n):
     rad, pos = get_plan(lib, n)
     assert int(np.prod(rad)) == n or (n == 1 and rad == [])
@@ -108,8 +118,13 @@ def test_fft_plan_tables(lib, n):
 
 
 def test_fft_plan_rejects_large_primes(lib):
-    nr, rad, pos = C.c_int(), (C.c_int * 32)(), (C.c_int * 67)()
-    assert lib.dftk_mi_fft_plan_host(67, C.byref(nr), rad, pos) == -1
+    """One rule for every length up to 256: the plan is rejected exactly when n has a prime factor >= 67."""
+    for n in range(1, 257):
+        nr, rad, pos = C.c_int(), (C.c_int * 32)(), (C.c_int * n)()
+        st = lib.dftk_mi_fft_plan_host(n, C.byref(nr), rad, pos)
+        assert st == (-1 if largest_prime_factor(n) >= 67 else 0), (n, st)
+        if st != 0:
+            assert b"cannot plan" in lib.dftk_mi_last_error()
 
 
 def test_pruned_pipeline_emulation(lib):
