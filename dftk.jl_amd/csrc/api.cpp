@@ -521,6 +521,8 @@ extern "C" int dftk_mi_kblock_destroy(dftk_mi_kblock* kb) {
     release_Vs(kb);
     if (kb->d_Vs_ax) hipFree(kb->d_Vs_ax);
     if (kb->d_dVs) hipFree(kb->d_dVs);
+    if (kb->planes) hipFree(kb->planes);
+    delete kb->planes_valid;
     void* ptrs[] = {kb->d_cpos, kb->d_cx, kb->d_line_start, kb->d_line_ypos, kb->d_line_yval, kb->d_zls,
                     kb->d_zpos, kb->d_zval, kb->d_kin, kb->d_D, kb->lob_buf};
     for (void* p : ptrs)
@@ -547,6 +549,7 @@ extern "C" int dftk_mi_kblock_set_shard(dftk_mi_kblock* kb, dftk_mi_comm* comm, 
     if (!kb) return DFTK_MI_EINVAL;
     HIPCHK(hipSetDevice(kb->basis->device));
     HIPCHK(hipStreamSynchronize(kb->basis->stream));
+    planes_drop(kb);
     if (!comm || comm_size(comm) == 1) {      // a one-rank communicator owns the whole sphere: nothing to shard
         kb->sh_comm = nullptr;
         return 0;
@@ -810,6 +813,7 @@ extern "C" int dftk_mi_kblock_set_projectors(dftk_mi_kblock* kb, int n_p, const 
     kb->P = nullptr;
     kb->ax_keep = nullptr;                  // (an A X kept by the LOBPCG driver belongs to the old nonlocal term)
     kb->ax_reuse_next = false;
+    planes_drop(kb);
     if (kb->gr) kb->gr->P_src = nullptr;   // the half-format copy is rebuilt on its next use
     if (n_p == 0) return 0;
     if (!P_d || !D_h || ldP < local_rows(kb)) return DFTK_MI_EINVAL;

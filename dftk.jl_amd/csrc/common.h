@@ -246,6 +246,15 @@ struct dftk_mi_kblock {
     double* d_Vs_ax;              // [nz*ny*nxp] snapshot of d_Vs at that exit (owned)
     double* d_dVs;                // [nz*ny*nxp] scratch: V_new - V_old (owned)
     bool ax_reuse_next;           // the caller's one-shot promise: X0 of the next call IS the X returned by the last one
+    // y-planes (stage-B output, the layout of T2) of the band pairs of the block the general driver returned last, written
+    // by the Gamma-real density pass over that block instead of into the recycled scratch: the kept-A X start of the next
+    // call applies (V_new - V_old) from stage C on.  Un-sharded, un-batched Gamma-real blocks only.
+    const cd* ret_X; int64_t ret_ld; int ret_M;   // where the last general-driver call left its X (null: none since, or not eligible)
+    cd* planes; size_t planes_bytes;              // pair p in slot p, nzx * ny * nxp elements each (owned, allocated on first use)
+    bool planes_on;                               // the slots belong to ret_X: planes_valid[p] tells which were written
+    bool planes_declined;                         // the device had no room for the buffer: the feature stays off for this block
+    int planes_batch;                             // basis->fft_batch of the density pass (the launch groups the valid bits follow)
+    std::vector<char>* planes_valid;              // [(ret_M + 1) / 2] (owned)
     // plane-wave (row-slab) sharding of this block over a communicator (dftk_mi_kblock_set_shard): orbital blocks
     // handed to apply_H / lobpcg / density_accumulate and the projector matrix are the rows
     // [sh_rows[rank], sh_rows[rank + 1]) of the sphere; the sphere tables / potential above stay complete
@@ -270,8 +279,17 @@ int launch_local_apply(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi,
 int launch_ifft_to_cube(dftk_mi_kblock* kb, const cd* c, cd* cube, int nb = 1);
 int launch_fft_from_cube(dftk_mi_kblock* kb, const cd* cube, cd* c, int nb = 1);
 // w_im_h (optional): separate weights for the squared IMAGINARY parts (two real bands packed into one transform)
+// keep_planes: stage B of band i writes slot i of kb->planes instead of the scratch, and kb->planes_valid[i] is set for the
+// bands of every launch group that ran (the caller has sized both; never inside a batched call)
 int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho,
-                   const double* w_im_h = nullptr, const double* w2_h = nullptr, double* rho2 = nullptr);
+                   const double* w_im_h = nullptr, const double* w2_h = nullptr, double* rho2 = nullptr,
+                   bool keep_planes = false);
+int fft_group_size(const dftk_mi_basis* b);      // bands per launch group of the one-slot pipelines
+// stages A and B of bands [b0, b0 + nbb) of psi (column 0 = band b0) into slots b0 ... of `planes`
+int launch_planes_fill(dftk_mi_kblock* kb, int b0, int nbb, const cd* psi, int64_t ldpsi, cd* planes);
+// out = V_loc psi for nb bands whose y-planes sit in `planes` (slot = band): stages C (in place: the planes are consumed), D
+// and E without the kinetic term; T1 stays scratch
+int launch_local_apply_from_planes(dftk_mi_kblock* kb, int nb, cd* planes, cd* out, int64_t ldout);
 int launch_density_response(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const cd* dpsi, int64_t lddpsi,
                             const double* wo_h, const double* wd_h, double* drho);
 int launch_pad_potential(dftk_mi_kblock* kb, const double* V);
@@ -409,6 +427,10 @@ int gamma_unpack_pairs(dftk_mi_kblock* kb, int nb, const cd* W, int64_t ldw, cd*
 int gamma_pack_full(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Z, int64_t ldz);
 int gamma_gather_P(dftk_mi_kblock* kb, int ncols, const cd* P, int64_t ldP, cd* Ph, int64_t ldh, double* asym_mag_h);
 int gamma_density_bands(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho);
+// y-planes kept by the density pass over the block the general LOBPCG driver returned (kb->planes)
+inline void planes_drop(dftk_mi_kblock* kb) { kb->planes_on = false; kb->ret_X = nullptr; }
+bool gamma_planes_ready(const dftk_mi_kblock* kb, int M);     // kept, for M bands, under today's launch-group size
+int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Hpsi, int64_t ldH);
 int64_t gamma_local_rows(const dftk_mi_kblock* kb);     // half-format rows held by this rank
 int64_t gamma_row0(const dftk_mi_kblock* kb);
 int gamma_projectors(dftk_mi_kblock* kb);               // half-format projectors of this rank (built on first use)

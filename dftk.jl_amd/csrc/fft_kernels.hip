@@ -1210,11 +1210,12 @@ struct FftPipe {
     int64_t n_G;          // booked bytes of stages A / E
 };
 // t_off: the first of the nb scratch slots (bands) of T1 / T2 the launch group uses (after fft_ensure_scratch)
-static FftPipe kblock_pipe(dftk_mi_kblock* kb, int nb, int t_off = 0) {
+// planes (nullable): the group's y-planes live there, band i in slot i, instead of in T2 (kb->planes: slot = band of the call)
+static FftPipe kblock_pipe(dftk_mi_kblock* kb, int nb, int t_off = 0, cd* planes = nullptr) {
     dftk_mi_basis* b = kb->basis;
     const int64_t s1 = (int64_t)kb->n_lines * b->nxp, s2 = (int64_t)kb->nzx * b->ny * b->nxp;
-    return FftPipe{b, b->stream, nb, b->T1 + t_off * s1, b->T2 + t_off * s2, s1, s2, (int)kb->n_lines, kb->nzx,
-                   kblock_tables(kb), nullptr, kb->z_lo >= 0, true, kb->n_G};
+    return FftPipe{b, b->stream, nb, b->T1 + t_off * s1, planes ? planes : b->T2 + t_off * s2, s1, s2, (int)kb->n_lines,
+                   kb->nzx, kblock_tables(kb), nullptr, kb->z_lo >= 0, true, kb->n_G};
 }
 // nb bands of a staged slice of a multi-k job table: the tables ride in the jobs, the grids cover the largest k-block
 static FftPipe jobs_pipe(dftk_mi_basis* b, hipStream_t stream, int nb, const FftJob* jobs, cd* T1, cd* T2, int64_t s1,
@@ -1406,6 +1407,8 @@ static int stage_density_response(const FftPipe& p, const double* wo, const doub
 // runtime before the call returns: no host synchronisation between the groups) and a group whose weights are all zero
 // is skipped.  wa_h, wb_h: nb host weights each, or null.  body(b0, nbb, wa_d, wb_d) launches the stages of bands
 // [b0, b0 + nbb); wa_d, wb_d are the device copies of that group's weights (null where there are none).
+int fft_group_size(const dftk_mi_basis* b) { return std::max(1, b->fft_batch); }
+
 template <class F>
 static int band_groups(dftk_mi_kblock* kb, int nb, int slots, const double* wa_h, const double* wb_h, F&& body) {
     dftk_mi_basis* b = kb->basis;
@@ -1453,6 +1456,35 @@ int launch_local_apply(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi,
     });
 }
 
+int launch_planes_fill(dftk_mi_kblock* kb, int b0, int nbb, const cd* psi, int64_t ldpsi, cd* planes) {
+    dftk_mi_basis* b = kb->basis;
+    CHK(check_lds(b));
+    CHK(fft_ensure_scratch(b, kb, nbb));
+    const int64_t s2 = (int64_t)kb->nzx * b->ny * b->nxp;
+    const FftPipe p = kblock_pipe(kb, nbb, 0, planes + (int64_t)b0 * s2);
+    CHK(stage_A(p, psi, ldpsi));
+    CHK(stage_B(p));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int launch_local_apply_from_planes(dftk_mi_kblock* kb, int nb, cd* planes, cd* out, int64_t ldout) {
+    dftk_mi_basis* b = kb->basis;
+    if (kb->d_Vs == nullptr) {
+        dftk_set_error("launch_local_apply_from_planes: no local potential is bound");
+        return DFTK_MI_EINVAL;
+    }
+    CHK(check_lds(b));
+    const int64_t s2 = (int64_t)kb->nzx * b->ny * b->nxp;
+    return band_groups(kb, nb, 1, nullptr, nullptr, [&](int b0, int nbb, const double*, const double*) -> int {
+        const FftPipe p = kblock_pipe(kb, nbb, 0, planes + (int64_t)b0 * s2);
+        cd* o = out + (int64_t)b0 * ldout;
+        CHK(stage_C(p));
+        CHK(stage_D(p));
+        return stage_E(p, nullptr, o, ldout, o, ldout, nullptr);
+    });
+}
+
 int launch_kinetic_only(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, cd* out, int64_t ldout,
                         bool accumulate, bool use_kin) {
     dftk_mi_basis* b = kb->basis;
@@ -1473,8 +1505,9 @@ static int check_density_nz(const dftk_mi_basis* b) {
 }
 
 int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho,
-                   const double* w_im_h, const double* w2_h, double* rho2) {
+                   const double* w_im_h, const double* w2_h, double* rho2, bool keep_planes) {
     dftk_mi_basis* b = kb->basis;
+    if (!keep_planes) kb->planes_on = false;   // planes kept by an earlier pass belong to another block or shape
     if (batching() && nb > 0) {   // part of a batched multi-k call: the bands of all k-blocks share one pipeline later
         // payload: [w | wim (flags & 1) | w2 (flags & 2)]; D = the second cube of a two-weight pass
         BOp o;
@@ -1498,10 +1531,12 @@ int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, con
     }
     CHK(check_lds(b));
     CHK(check_density_nz(b));
+    const int64_t s2 = (int64_t)kb->nzx * b->ny * b->nxp;
     return band_groups(kb, nb, 1, w_h, w_im_h, [&](int b0, int nbb, const double* w_d, const double* wim_d) -> int {
-        const FftPipe p = kblock_pipe(kb, nbb);
+        const FftPipe p = kblock_pipe(kb, nbb, 0, keep_planes ? kb->planes + (int64_t)b0 * s2 : nullptr);
         CHK(stage_A(p, psi + (int64_t)b0 * ldpsi, ldpsi));
         CHK(stage_B(p));
+        if (keep_planes) std::fill_n(kb->planes_valid->begin() + b0, nbb, (char)1);
         return stage_density(p, w_d, wim_d, rho);
     });
 }

@@ -18,9 +18,11 @@
 // (the local potential is real and the kinetic factor even in G, so H_loc (a + i b) = H_loc a + i H_loc b with both
 // parts real-symmetric) and are separated again by W(G) +/- conj(W(-G)).
 #include "common.h"
+#include "batch.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <unordered_map>
 #include <vector>
 
@@ -342,6 +344,7 @@ static dim3 gr_grid_unr(int64_t rows, int cols) { return dim3((unsigned)((rows +
 
 int gamma_enable(dftk_mi_kblock* kb, int on) {
     dftk_mi_basis* b = kb->basis;
+    planes_drop(kb);                      // (kept y-planes belong to the format that was on when the block was returned)
     if (!on) {
         if (kb->gr) kb->gr->on = false;
         return 0;
@@ -554,10 +557,51 @@ int gamma_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, cons
     return gamma_density_bands(kb, nb, psi, ldpsi, w_h, rho);
 }
 
+// DFTK_MI_PLANES_REUSE=0 (read per call) keeps the y-planes of the density pass in the recycled scratch: today's path
+static bool planes_wanted() {
+    const char* e = getenv("DFTK_MI_PLANES_REUSE");
+    return !(e && atoi(e) == 0);
+}
+
+// Does this density pass run over the very block the general LOBPCG driver returned last (un-sharded, un-batched
+// Gamma-real block)?  Then its y-planes are kept for the next call's start: the buffer is allocated on
+// first use, and only where the device has room for it twice over -- otherwise the block declines for good.
+static int planes_prepare(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, bool* keep) {
+    *keep = false;
+    dftk_mi_basis* b = kb->basis;
+    if (!planes_wanted() || !kb->gr->on || kb->sh_comm || batching() || kb->planes_declined || kb->ret_X == nullptr ||
+        kb->ret_X != psi || kb->ret_ld != ldpsi || kb->ret_M != nb)
+        return 0;
+    const size_t nb2 = (size_t)(nb + 1) / 2;
+    const size_t need = nb2 * (size_t)kb->nzx * b->ny * b->nxp * sizeof(cd);
+    if (need > kb->planes_bytes) {
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (kb->planes) HIPCHK(hipFree(kb->planes));
+        kb->planes = nullptr;
+        kb->planes_bytes = 0;
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        if (free_b < 2 * need + ((size_t)1 << 30) || hipMalloc((void**)&kb->planes, need) != hipSuccess) {
+            (void)hipGetLastError();
+            kb->planes = nullptr;
+            kb->planes_declined = true;
+            return 0;
+        }
+        kb->planes_bytes = need;
+    }
+    if (!kb->planes_valid) kb->planes_valid = new std::vector<char>();
+    kb->planes_valid->assign(nb2, 0);
+    kb->planes_batch = b->fft_batch;
+    *keep = true;
+    return 0;
+}
+
 // whole bands on this rank (full-sphere layout)
 int gamma_density_bands(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho) {
     if (nb <= 0) return 0;
     const int nb2 = (nb + 1) / 2;
+    bool keep = false;
+    CHK(planes_prepare(kb, nb, psi, ldpsi, &keep));
     CHK(gamma_ensure_buf(kb, (size_t)kb->n_G * nb2));
     CHK(gamma_pack_full(kb, nb, psi, ldpsi, kb->gr->buf, kb->n_G));
     std::vector<double> wre(nb2), wim(nb2);
@@ -565,5 +609,44 @@ int gamma_density_bands(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi
         wre[p] = w_h[2 * p];
         wim[p] = (2 * p + 1 < nb) ? w_h[2 * p + 1] : 0.0;
     }
-    return launch_density(kb, nb2, kb->gr->buf, kb->n_G, wre.data(), rho, wim.data());
+    kb->planes_on = keep;
+    return launch_density(kb, nb2, kb->gr->buf, kb->n_G, wre.data(), rho, wim.data(), nullptr, nullptr, keep);
+}
+
+bool gamma_planes_ready(const dftk_mi_kblock* kb, int M) {
+    return planes_wanted() && kb->planes_on && kb->planes != nullptr && kb->ret_M == M && kb->gr && kb->gr->on &&
+           !kb->sh_comm && !batching() && kb->planes_batch == kb->basis->fft_batch &&
+           kb->planes_valid->size() == (size_t)(M + 1) / 2;
+}
+
+// The local part of H psi (the bound potential) in the half-sphere format for the nb bands whose y-planes the density pass
+// kept: the pipeline starts at stage C.  A launch group the density pass skipped (all weights zero) gets its planes here
+// first, from the caller's full-format block X (the block those planes belong to).  The planes are consumed.
+int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Hpsi, int64_t ldH) {
+    if (nb <= 0) return 0;
+    GammaReal* gr = kb->gr;
+    dftk_mi_basis* b = kb->basis;
+    const int nb2 = (nb + 1) / 2;
+    kb->planes_on = false;
+    const int slot = prof_begin(b, PROF_APPLY_H, (double)nb);
+    struct G {
+        dftk_mi_basis* b;
+        int s;
+        ~G() { prof_end(b, s); }
+    } guard{b, slot};
+    CHK(gamma_ensure_buf(kb, 2 * (size_t)kb->n_G * nb2));
+    cd* Z = gr->buf;
+    cd* W = gr->buf + (size_t)kb->n_G * nb2;
+    prof_count(b, PROF_A2A_MODEL, 16.0 * (double)gr->n_half * nb);   // (as gamma_apply_H: what a sharded run of the call moves)
+    prof_count(b, PROF_A2A_MODEL, 16.0 * (double)gr->n_half * nb);
+    const std::vector<char>& valid = *kb->planes_valid;
+    const int group = fft_group_size(b);
+    for (int b0 = 0; b0 < nb2; b0 += group) {
+        const int nbb = std::min(group, nb2 - b0);
+        if (std::all_of(valid.begin() + b0, valid.begin() + b0 + nbb, [](char v) { return v != 0; })) continue;
+        CHK(gamma_pack_full(kb, std::min(2 * nbb, nb - 2 * b0), X + (int64_t)(2 * b0) * ldx, ldx, Z, kb->n_G));
+        CHK(launch_planes_fill(kb, b0, nbb, Z, kb->n_G, kb->planes));
+    }
+    CHK(launch_local_apply_from_planes(kb, nb2, kb->planes, W, kb->n_G));
+    return gamma_unpack_pairs(kb, nb, W, kb->n_G, Hpsi, ldH);
 }

@@ -610,6 +610,7 @@ struct Lob {
     // A X kept at the last exit of the general driver on this block, if the caller promised the same X and the shape fits
     cd* kept_AX = nullptr;
     int64_t kept_ld = 0;
+    bool kept_planes = false;       // ... and the density pass over that X has left its y-planes (gamma_planes_ready)
     // ---- state of the call ----
     std::vector<double> resid_history, full_lam;
     double& RH(int i, int it) { return resid_history[(size_t)i + (size_t)M * it]; }
@@ -658,6 +659,9 @@ struct Lob {
         kept_AX = reuse_asked && kb->ax_M == M && kb->ax_rows == N ? kb->ax_keep : nullptr;
         kept_ld = kb->ax_ld;
         kb->ax_keep = nullptr;
+        // the y-planes of the returned X go the same way: this call uses them at its start or not at all
+        kept_planes = kept_AX != nullptr && real_mode && comm == nullptr && gamma_planes_ready(kb, M);
+        planes_drop(kb);
         if (need > kb->lob_bytes) {
             CHK(host_wait(b));
             if (kb->lob_buf) HIPCHK(hipFree(kb->lob_buf));
@@ -967,6 +971,7 @@ int lobpcg_ortho(dftk_mi_basis* b, int64_t n, int m, cd* X, int64_t ldx, int for
 }
 
 std::atomic<int64_t> g_ax_reuse_count{0};     // calls that started from the kept A X (dftk_mi_ax_reuse_count)
+std::atomic<int64_t> g_planes_reuse_count{0}; // ... and applied V_new - V_old from the kept y-planes (dftk_mi_planes_reuse_count)
 
 // The host-driven driver: every block shape, plane-wave sharded and Gamma-real blocks.  Each orthogonalisation, the
 // eigensolver and the residual pass come back to the host by themselves (4-6 synchronisations per iteration).
@@ -1025,6 +1030,24 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
         const size_t cube = (size_t)b->nz * b->ny * b->nxp;
         if (!kb->d_dVs) HIPCHK(hipMalloc((void**)&kb->d_dVs, cube * sizeof(double)));
         CHK(ew_sub_real(b, (int64_t)cube, kb->d_Vs, kb->d_Vs_ax, kb->d_dVs));
+        double* const Vs_bound = kb->d_Vs;
+        if (s.kept_planes) {
+            // The density pass over the returned X left that block's y-planes (gamma_density_bands): (V_new - V_old) is applied
+            // to the RETURNED X from stage C on -- no pack, no stages A and B -- and follows the kept block through inv(R):
+            // A_new X = (A_old X_ret + (V_new - V_old) X_ret) inv(R), the same operator before the triangular factor.
+            g_planes_reuse_count.fetch_add(1);
+            kb->d_Vs = kb->d_dVs;
+            const int st_dv = gamma_apply_local_from_planes(kb, M, Xp, ldX, newR.p, newR.ld);
+            kb->d_Vs = Vs_bound;
+            CHK(st_dv);
+            CHK(ew_add(b, N, M, newR.p, newR.ld, s.kept_AX, s.kept_ld));
+            if (s.kept_AX != AX.p) {
+                CHK(c.mm('N', N, M, M, ONE, s.kept_AX, s.kept_ld, c.invR, M, ZERO, AX.p, AX.ld, /*B upper triangular=*/2));
+            } else {
+                CHK(c.mm('N', N, M, M, ONE, s.kept_AX, s.kept_ld, c.invR, M, ZERO, newR.p, newR.ld, /*B upper triangular=*/2));
+                CHK(ew_copy(b, N, M, newR.p, newR.ld, AX.p, AX.ld));
+            }
+        } else {
         // (A_old X) inv(R) -> AX (straight into place unless the kept block IS AX's storage: through newR then)
         if (s.kept_AX != AX.p) {
             CHK(c.mm('N', N, M, M, ONE, s.kept_AX, s.kept_ld, c.invR, M, ZERO, AX.p, AX.ld, /*B upper triangular=*/2));
@@ -1032,7 +1055,6 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
             CHK(c.mm('N', N, M, M, ONE, s.kept_AX, s.kept_ld, c.invR, M, ZERO, newR.p, newR.ld, /*B upper triangular=*/2));
             CHK(ew_copy(b, N, M, newR.p, newR.ld, AX.p, AX.ld));
         }
-        double* const Vs_bound = kb->d_Vs;
         kb->d_Vs = kb->d_dVs;                                  // (the kernels take the pointer at launch)
         const int st_dv = real_mode ? gamma_apply_H(kb, 1, M, X.p, X.ld, newR.p, newR.ld)
                                     : dftk_mi_apply_H_parts(kb, 1, M, reinterpret_cast<const dftk_mi_cplx*>(X.p), X.ld,
@@ -1040,6 +1062,7 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
         kb->d_Vs = Vs_bound;
         CHK(st_dv);
         CHK(ew_add(b, N, M, newR.p, newR.ld, AX.p, AX.ld));
+        }
         static const bool ax_check = getenv("DFTK_MI_AX_REUSE_CHECK") != nullptr;
         if (ax_check) {     // diagnostic: the full application beside it (costs what the path saves, and a synchronisation)
             CHK(apply_H(M, X.p, X.ld, newR.p, newR.ld));
@@ -1130,6 +1153,12 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
         kb->ax_ld = s.AX.ld;
         kb->ax_M = M;
         kb->ax_rows = N;
+        // where the returned X lives: a Gamma-real density pass over exactly this block keeps its y-planes (un-sharded only)
+        if (real_mode && !kb->sh_comm) {
+            kb->ret_X = Xp;
+            kb->ret_ld = ldX;
+            kb->ret_M = M;
+        }
     }
     return stream_sync(b);
 }
@@ -1334,6 +1363,11 @@ extern "C" int dftk_mi_ortho_small(dftk_mi_basis* b, int64_t n, int m, dftk_mi_c
 
 extern "C" int dftk_mi_ax_reuse_count(int64_t* calls) {
     if (calls) *calls = g_ax_reuse_count.load();
+    return 0;
+}
+
+extern "C" int dftk_mi_planes_reuse_count(int64_t* calls) {
+    if (calls) *calls = g_planes_reuse_count.load();
     return 0;
 }
 

@@ -97,6 +97,10 @@ def plan_planewave_sharded(model, Ecut, n_ranks, fft_size=None, gamma_real=True,
       fft_scratch       fft_batch x (T1 + T2)                 (fft_kernels.hip fft_ensure_scratch)
       gemm_split_k      <= 1 GiB of split-K slabs             (gemm_kernels.hip)
       cubes             rho, V and its parts, Anderson history of 10 (x, r) pairs: 26 real cubes
+    Optional (``optional_bytes_per_rank``, not in the total: the library allocates it only where the device has room for it
+    twice over, and runs the same without it):
+      kept_planes       ceil(M / 2) x T2: the y-planes the density pass keeps for the next LOBPCG start (un-sharded
+                        Gamma-real block only; gamma_kernels.hip planes_prepare)
     Also returned: the per-step communication volumes of one H psi sweep and one Rayleigh-Ritz Gram all-reduce."""
     from .scf import AdaptiveBands
     p = int(n_ranks)
@@ -129,6 +133,7 @@ def plan_planewave_sharded(model, Ecut, n_ranks, fft_size=None, gamma_real=True,
         "cubes": 26 * N * F64,
     }
     total = int(sum(items.values()))
+    optional = {"kept_planes": (-(-M // 2) * nzx * fft[1] * nxp * CPLX) if (gamma_real and p == 1) else 0}
     band_block = CPLX * (n_half if gamma_real else n_G) * M          # one block of all bands, iteration format
     comm = {
         "alltoall_bytes_sent_per_rank_per_Hpsi_sweep": int(2 * band_block / p * (p - 1) / p) if p > 1 else 0,
@@ -138,6 +143,7 @@ def plan_planewave_sharded(model, Ecut, n_ranks, fft_size=None, gamma_real=True,
     ref = estimate_memory_usage(model, Ecut, fft_size=fft)
     return {"n_ranks": p, "fft_size": fft, "n_G": n_G, "n_half": n_half, "n_bands": M, "n_projectors": n_p,
             "rows_per_rank": rows_fmt, "bytes_per_rank": {k: int(v) for k, v in items.items()}, "total_bytes_per_rank": total,
+            "optional_bytes_per_rank": {k: int(v) for k, v in optional.items()},
             "hbm_bytes": int(hbm_bytes), "fits": bool(total <= 0.92 * hbm_bytes), "headroom_fraction": 1.0 - total / hbm_bytes,
             "communication": comm,
             "reference_layout": {**asdict(ref), "note": "src/memory_usage.jl:74-81 rule of thumb, one process, dense complex "
@@ -153,6 +159,8 @@ def format_plan(plan: dict) -> str:
              f"{plan['n_bands']} bands, {plan['n_projectors']} projectors, {plan['rows_per_rank']} rows per rank"]
     for k, v in plan["bytes_per_rank"].items():
         lines.append(f"  {k:18s} {v / 1e9:9.2f} GB")
+    for k, v in plan.get("optional_bytes_per_rank", {}).items():
+        lines.append(f"  {k:18s} {v / 1e9:9.2f} GB (optional: allocated only where there is room, not in the total)")
     lines.append(f"  {'TOTAL':18s} {plan['total_bytes_per_rank'] / 1e9:9.2f} GB of {plan['hbm_bytes'] / 1e9:.0f} GB -> "
                  f"{'fits' if plan['fits'] else 'DOES NOT FIT'}")
     return "\n".join(lines)

@@ -379,6 +379,18 @@ int dftk_mi_lobpcg_history(dftk_mi_kblock* kb, int* M, int* n_iter, double* hist
 int dftk_mi_kblock_reuse_AX(dftk_mi_kblock* kb, int on);
 /* number of dftk_mi_lobpcg calls of this process that started from the kept A X (diagnostic / tests) */
 int dftk_mi_ax_reuse_count(int64_t* calls);
+/* src/densities.jl:39 (compute_density's loop over the bands) and src/scf/self_consistent_field.jl:80-129 (the next_density
+ * / diagonalisation hand-over of one SCF step): the density pass transforms the orbitals the last dftk_mi_lobpcg call
+ * returned to y-planes, and the kept-A X start of the next call would transform the same orbitals again.  On an un-sharded,
+ * un-batched Gamma-real block, dftk_mi_density_accumulate_real over exactly the block the last call returned (pointer,
+ * leading dimension, band count) keeps those planes, and a promised dftk_mi_kblock_reuse_AX start applies
+ * (V_new - V_old) from them: A_new X = (A_old X_ret + (V_new - V_old) X_ret) inv(R).  Nothing to call: binding a new
+ * potential keeps the planes; any other density call, any dftk_mi_lobpcg call, dftk_mi_kblock_set_projectors / _set_shard /
+ * _set_gamma_real and a change of dftk_mi_basis_set_fft_batch drop them.  The buffer (one T2 slab per band pair) is allocated
+ * on first use if the device has room for it twice over; otherwise the block declines and every call takes the path above.
+ * Environment DFTK_MI_PLANES_REUSE=0 (read per call) switches it off.
+ * calls = number of dftk_mi_lobpcg calls of this process that started from kept planes (diagnostic / tests) */
+int dftk_mi_planes_reuse_count(int64_t* calls);
 
 /* Optional: device pointer to H*X of the last dftk_mi_lobpcg call on this block (n_G x M,
  * leading dimension n_G; valid until the next lobpcg call on the block). */
