@@ -80,6 +80,10 @@ _SIGNATURES = {
                                  C.POINTER(C.c_int), C.POINTER(_i64)]),
     "dftk_mi_local_potential_gga": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_double, C.c_void_p, C.c_void_p]),
+    "dftk_mi_local_potential_collinear_gga": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                        C.c_double, C.c_void_p, C.c_void_p]),
+    "dftk_mi_xc_gga_spin": (C.c_int, [C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
     "dftk_mi_symmetrize_rho": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dftk_mi_mix_kerker": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "dftk_mi_mix_dielectric": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),

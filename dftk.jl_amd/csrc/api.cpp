@@ -1002,6 +1002,20 @@ extern "C" int dftk_mi_local_potential_gga(dftk_mi_kblock* cube_kb, const double
                                energies_h);
 }
 
+extern "C" int dftk_mi_local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_lattice_h,
+                                                     const double* rho_d, const double* V_loc_d,
+                                                     const double* poisson_green_d, int xc_functionals,
+                                                     double density_threshold, double* V_out_d, double* energies_h) {
+    if (!cube_kb || !rho_d || (!energies_h && !V_out_d) || (xc_functionals & ~(1 | 4 | 32 | 24)) || cube_kb->sh_comm)
+        return DFTK_MI_EINVAL;
+    if ((xc_functionals & 24) && !recip_lattice_h) return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(cube_kb->basis->device));
+    double B[9] = {0};
+    if (recip_lattice_h) rowmajor3(recip_lattice_h, B);
+    return local_potential_collinear_gga(cube_kb, B, rho_d, V_loc_d, poisson_green_d, xc_functionals, density_threshold,
+                                         V_out_d, energies_h);
+}
+
 extern "C" int dftk_mi_symmetrize_rho(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, const double* tau_h,
                                       int do_lowpass, const double* rho_in_d, double* rho_out_d) {
     if (!cube_kb || n_sym < 1 || !S_h || !tau_h || !rho_in_d || !rho_out_d || cube_kb->sh_comm) return DFTK_MI_EINVAL;
@@ -1133,6 +1147,16 @@ extern "C" int dftk_mi_xc_gga(dftk_mi_basis* b, int64_t n, const double* rho_d, 
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(b->device));
     return xc_gga_pointwise(b, n, rho_d, sigma_d, xc_functionals, density_threshold, e_d, vrho_d, vsigma_d);
+}
+
+extern "C" int dftk_mi_xc_gga_spin(dftk_mi_basis* b, int64_t n, const double* rho_d, const double* sigma_d,
+                                   int xc_functionals, double density_threshold, double* e_d, double* vrho_d,
+                                   double* vsigma_d) {
+    if (!b || n < 0 || !rho_d || !sigma_d || !e_d || !vrho_d || !vsigma_d || (xc_functionals & ~24) || !xc_functionals)
+        return DFTK_MI_EINVAL;
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(b->device));
+    return xc_gga_spin_pointwise(b, n, rho_d, sigma_d, xc_functionals, density_threshold, e_d, vrho_d, vsigma_d);
 }
 
 extern "C" int dftk_mi_ifft_sphere(dftk_mi_kblock* kb, const dftk_mi_cplx* c_d, dftk_mi_cplx* cube_d) {

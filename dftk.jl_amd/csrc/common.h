@@ -376,6 +376,10 @@ int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const 
                               int fun_mask, double* V_out, double* energies_h);
 int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* vloc,
                         const double* green, int fun_mask, double threshold, double* V_out, double* energies_h);
+int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* vloc,
+                                  const double* green, int fun_mask, double threshold, double* V_out, double* energies_h);
+int xc_gga_spin_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, int fun_mask,
+                          double threshold, double* e, double* vrho, double* vsigma);
 
 // dV = irfft(green fft(drho)) + f_xc(rho) drho, f_xc = d^2 (rho eps_xc) / d rho^2 of the LDA closed forms (fun_mask bits 1, 2, 4)
 int apply_kernel_lda(dftk_mi_kblock* cube_kb, const double* rho, const double* drho, const double* green, int fun_mask,

@@ -207,6 +207,109 @@ __device__ __forceinline__ D3 lda_spin_sum(double rho_up, double rho_dn, int fun
     return acc;
 }
 
+// ---- collinear spin, GGA (PBE): e(rho_up, rho_down, sigma_uu, sigma_ud, sigma_dd), sigma_st = grad rho_s . grad rho_t.
+// Exchange by the spin-scaling relation e_x = 1/2 [e_x0(2 rho_up, 4 sigma_uu) + e_x0(2 rho_down, 4 sigma_dd)] on the
+// unpolarised gga_x_pbe above: one D3 per channel, slots (d/d rho_s, d/d sigma_ss), and de/dsigma_ud = 0.
+// Correlation depends on (rho_up, rho_down, sigma_tot = sigma_uu + 2 sigma_ud + sigma_dd): D4 is D3 with one more slot,
+// de/dsigma_uu = de/dsigma_dd = de/dsigma_tot, de/dsigma_ud = 2 de/dsigma_tot.  Closed form as libxc's polarised gga_c_pbe:
+// eps_c(rs, zeta) is the PW92 interpolation with the lda_c_pw_mod parameters (the a = 0.0310907 of gga_c_pbe above, more
+// digits for the other two fits and f''(0)), phi = ((1 + zeta)^(2/3) + (1 - zeta)^(2/3)) / 2, t^2 = pi sigma_tot /
+// (16 phi^2 k_F rho^2), A = (beta / gamma) / expm1(-eps_c / (gamma phi^3)), H = gamma phi^3 log1p(...): gga_c_pbe
+// term by term where phi = 1.
+struct D4 {
+    double v, da, db, ds;
+};
+__device__ __forceinline__ D4 dc4(double c) { return D4{c, 0.0, 0.0, 0.0}; }
+__device__ __forceinline__ D4 operator+(D4 a, D4 b) { return D4{a.v + b.v, a.da + b.da, a.db + b.db, a.ds + b.ds}; }
+__device__ __forceinline__ D4 operator-(D4 a, D4 b) { return D4{a.v - b.v, a.da - b.da, a.db - b.db, a.ds - b.ds}; }
+__device__ __forceinline__ D4 operator*(D4 a, D4 b) {
+    return D4{a.v * b.v, a.da * b.v + a.v * b.da, a.db * b.v + a.v * b.db, a.ds * b.v + a.v * b.ds};
+}
+__device__ __forceinline__ D4 operator/(D4 a, D4 b) {
+    const double q = a.v / b.v;
+    return D4{q, (a.da - q * b.da) / b.v, (a.db - q * b.db) / b.v, (a.ds - q * b.ds) / b.v};
+}
+__device__ __forceinline__ D4 operator*(double c, D4 a) { return D4{c * a.v, c * a.da, c * a.db, c * a.ds}; }
+__device__ __forceinline__ D4 operator+(double c, D4 a) { return D4{c + a.v, a.da, a.db, a.ds}; }
+__device__ __forceinline__ D4 dchain(D4 a, double f, double df) { return D4{f, df * a.da, df * a.db, df * a.ds}; }
+__device__ __forceinline__ D4 dsqrt(D4 a) { const double r = sqrt(a.v); return dchain(a, r, 0.5 / r); }
+__device__ __forceinline__ D4 dcbrt(D4 a) { const double r = cbrt(a.v); return dchain(a, r, r / (3.0 * a.v)); }
+__device__ __forceinline__ D4 dlog1p(D4 a) { return dchain(a, log1p(a.v), 1.0 / (1.0 + a.v)); }
+__device__ __forceinline__ D4 dexpm1(D4 a) { const double e = expm1(a.v); return dchain(a, e, e + 1.0); }
+__device__ __forceinline__ D4 pw92_G(D4 rs, D4 sq, double A, double a1, double b1, double b2, double b3, double b4) {
+    const D4 den = 2.0 * A * (b1 * sq + b2 * rs + b3 * (rs * sq) + b4 * (rs * rs));
+    return (-2.0 * A) * ((1.0 + a1 * rs) * dlog1p(dc4(1.0) / den));
+}
+__device__ __forceinline__ D4 gga_c_pbe_spin(D4 ra, D4 rb, D4 sigma) {
+    const double beta = 0.06672455060314922, gamma = 0.031090690869654895;   // (1 - ln 2) / pi^2
+    const D4 rt = ra + rb;
+    const D4 xa = 2.0 * (ra / rt), xb = 2.0 * (rb / rt);                     // 1 + zeta, 1 - zeta
+    const D4 ca = dcbrt(xa), cb = dcbrt(xb);
+    const D4 fz = (1.0 / (2.5198420997897464 - 2.0)) * (xa * ca + xb * cb + dc4(-2.0));
+    const D4 phi = 0.5 * (ca * ca + cb * cb);
+    const D4 z = (ra - rb) / rt;
+    const D4 z2 = z * z, z4 = z2 * z2;
+    const D4 rs = dcbrt(dc4(3.0 / (4.0 * M_PI)) / rt);
+    const D4 sq = dsqrt(rs);
+    const D4 e0 = pw92_G(rs, sq, 0.0310907, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294);
+    const D4 e1 = pw92_G(rs, sq, 0.01554535, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517);
+    const D4 mac = pw92_G(rs, sq, 0.0168869, 0.11125, 10.357, 3.6231, 0.88026, 0.49671);   // = -alpha_c
+    const D4 eps = e0 - (1.0 / 1.709920934161365617563962776245) * (mac * fz * (dc4(1.0) - z4)) + (e1 - e0) * (fz * z4);
+    const D4 phi2 = phi * phi, phi3 = phi2 * phi;
+    const D4 kf = dcbrt(3.0 * M_PI * M_PI * rt);
+    const D4 t2 = (M_PI / 16.0) * (sigma / (phi2 * (kf * rt * rt)));
+    const D4 A = dc4(beta / gamma) / dexpm1((-1.0 / gamma) * (eps / phi3));
+    const D4 f1 = t2 + A * (t2 * t2);
+    const D4 H = gamma * (phi3 * dlog1p((beta / gamma) * (f1 / (1.0 + A * f1))));
+    return rt * (eps + H);
+}
+// Floors as lda_spin_sum: a channel enters as max(rho_s, 1e-20) and the derivatives are those of the clamped variables;
+// rho_up + rho_down <= max(threshold, 2e-20) gives zeros; sigma_uu, sigma_dd and sigma_tot enter as max(., 0).
+__global__ __launch_bounds__(256) void k_gga_spin(int64_t n, const double* __restrict__ up, const double* __restrict__ dn,
+                                                  const double* __restrict__ suu, const double* __restrict__ sud,
+                                                  const double* __restrict__ sdd, int fun_mask, double threshold,
+                                                  double* __restrict__ e, double* __restrict__ vup, double* __restrict__ vdn,
+                                                  double* __restrict__ vsuu, double* __restrict__ vsud,
+                                                  double* __restrict__ vsdd) {
+    const double floor_ = 1e-20;
+    const double cut = threshold > 2.0 * floor_ ? threshold : 2.0 * floor_;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double a = up[i], b = dn[i];
+        double ev = 0.0, va = 0.0, vb = 0.0, wuu = 0.0, wud = 0.0, wdd = 0.0;
+        if (a + b > cut) {
+            const double ra = a > floor_ ? a : floor_, rb = b > floor_ ? b : floor_;
+            const double s_uu = suu[i], s_ud = sud[i], s_dd = sdd[i];
+            const double p_uu = s_uu > 0.0 ? s_uu : 0.0, p_dd = s_dd > 0.0 ? s_dd : 0.0;
+            if (fun_mask & 8) {
+                const D3 xu = 0.5 * gga_x_pbe(D3{2.0 * ra, 2.0, 0.0}, D3{4.0 * p_uu, 0.0, 4.0});
+                const D3 xd = 0.5 * gga_x_pbe(D3{2.0 * rb, 2.0, 0.0}, D3{4.0 * p_dd, 0.0, 4.0});
+                ev += xu.v + xd.v;
+                va += xu.dr;
+                vb += xd.dr;
+                wuu += xu.ds;
+                wdd += xd.ds;
+            }
+            if (fun_mask & 16) {
+                const double st = (s_uu + s_dd) + 2.0 * s_ud;      // (symmetric in the channels to the last bit)
+                const D4 c = gga_c_pbe_spin(D4{ra, 1.0, 0.0, 0.0}, D4{rb, 0.0, 1.0, 0.0},
+                                            D4{st > 0.0 ? st : 0.0, 0.0, 0.0, 1.0});
+                ev += c.v;
+                va += c.da;
+                vb += c.db;
+                wuu += c.ds;
+                wud += 2.0 * c.ds;
+                wdd += c.ds;
+            }
+        }
+        e[i] = ev;
+        vup[i] = va;
+        vdn[i] = vb;
+        vsuu[i] = wuu;
+        vsud[i] = wud;
+        vsdd[i] = wdd;
+    }
+}
+
 #pragma clang fp contract(fast)
 
 // V = V_loc + V_H + v_xc ; partials: [0] sum e_xc, [1] sum rho V_loc
@@ -260,13 +363,20 @@ __global__ __launch_bounds__(256) void k_total_to_complex(int64_t n, const doubl
 // V_s = V_loc + V_H[rho_tot] + v_xc,s(rho_up, rho_down), s = up, down ; partials: [0] sum e_xc, [1] sum rho_tot V_loc
 __global__ __launch_bounds__(256) void k_xc_sum_spin(int64_t n, const double* __restrict__ up, const double* __restrict__ dn,
                                                      const cd* __restrict__ vh_cube, double vh_scale,
-                                                     const double* __restrict__ vloc, int fun_mask, double* __restrict__ V_up,
-                                                     double* __restrict__ V_dn, double* __restrict__ partial) {
+                                                     const double* __restrict__ vloc, int fun_mask,
+                                                     const double* __restrict__ e_extra, const double* __restrict__ v_extra,
+                                                     double* __restrict__ V_up, double* __restrict__ V_dn,
+                                                     double* __restrict__ partial) {
     __shared__ double sh[4];
     double acc_xc = 0.0, acc_loc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double ra = up[i], rb = dn[i];
-        const D3 e = lda_spin_sum(ra, rb, fun_mask);
+        D3 e = lda_spin_sum(ra, rb, fun_mask);
+        if (e_extra) {                       // GGA part: e and v_rho,s - 2 div(...) of the two channels (v_extra: 2 cubes)
+            e.v += e_extra[i];
+            e.dr += v_extra[i];
+            e.ds += v_extra[n + i];
+        }
         acc_xc += e.v;
         double common = 0.0;
         if (vloc) {
@@ -373,6 +483,78 @@ __global__ __launch_bounds__(256) void k_product3_to_complex(int64_t n, const do
     }
 }
 
+// out = green * (a + b) ; partial[block] = sum green |a + b|^2   (the Poisson pass of a collinear density, from F[rho_s])
+__global__ __launch_bounds__(256) void k_poisson_sum(int64_t n, const cd* __restrict__ a, const cd* __restrict__ b,
+                                                     const double* __restrict__ green, cd* __restrict__ out,
+                                                     double* __restrict__ partial) {
+    __shared__ double sh[4];
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const cd va = a[i], vb = b[i];
+        const double x = va.x + vb.x, y = va.y + vb.y;
+        const double g = green[i];
+        acc += g * (x * x + y * y);
+        out[i] = make_double2(g * x, g * y);
+    }
+    const double s = block_sum(acc, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+// g: d_a rho_up (a = 0, 1, 2), then d_a rho_down; sigma: uu, ud, dd
+__global__ __launch_bounds__(256) void k_sigma_spin(int64_t n, const double* __restrict__ g, double* __restrict__ sigma) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        double uu = 0.0, ud = 0.0, dd = 0.0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double u = g[a * n + i], d = g[(3 + a) * n + i];
+            uu += u * u;
+            ud += u * d;
+            dd += d * d;
+        }
+        sigma[i] = uu;
+        sigma[n + i] = ud;
+        sigma[2 * n + i] = dd;
+    }
+}
+// out[(3 s + a) n + i] = v_sigma,ss d_a rho_s + 1/2 v_sigma,ud d_a rho_s'  (as complex numbers; v: uu, ud, dd)
+__global__ __launch_bounds__(256) void k_flux_spin_to_complex(int64_t n, const double* __restrict__ v, const double* __restrict__ g,
+                                                              cd* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double vuu = v[i], hud = 0.5 * v[n + i], vdd = v[2 * n + i];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double u = g[a * n + i], d = g[(3 + a) * n + i];
+            // explicit fma: left to the compiler, the two sums contract differently (fma(vuu, u, hud d) but fma(hud, u, vdd d))
+            // and rho_up = rho_down no longer gives V_up = V_down to the last bit
+            out[a * n + i] = make_double2(fma(vuu, u, hud * d), 0.0);
+            out[(3 + a) * n + i] = make_double2(fma(vdd, d, hud * u), 0.0);
+        }
+    }
+}
+
+// the three energies of a collinear pipeline from its reduction partials ([0] e_xc, [1] rho_tot V_loc, [2] Hartree)
+static int collinear_energies(dftk_mi_basis* b, int64_t N, const double* partial, bool hartree, double* energies_h) {
+    std::vector<double> hp(3 * XC_BLOCKS, 0.0);
+    CHK(host_fetch(b, hp.data(), partial, (hartree ? 3 : 2) * XC_BLOCKS * sizeof(double)));
+    double s3[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < 3; ++k)
+        for (int i = 0; i < XC_BLOCKS; ++i) s3[k] += hp[(size_t)k * XC_BLOCKS + i];
+    const double dvol = b->volume / (double)N;
+    energies_h[0] = hartree ? 0.5 * b->volume / ((double)N * (double)N) * s3[2] : 0.0;
+    energies_h[1] = s3[0] * dvol;
+    energies_h[2] = s3[1] * dvol;
+    return 0;
+}
+
+// rho: (up, down), sigma: (uu, ud, dd), vrho: (up, down), vsigma: (uu, ud, dd), n values each
+int xc_gga_spin_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, int fun_mask,
+                          double threshold, double* e, double* vrho, double* vsigma) {
+    hipLaunchKernelGGL(k_gga_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, n, rho, rho + n, sigma, sigma + n, sigma + 2 * n,
+                       fun_mask, threshold, e, vrho, vrho + n, vsigma, vsigma + n, vsigma + 2 * n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
 int xc_gga_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, int fun_mask,
                      double threshold, double* e, double* vrho, double* vsigma) {
     hipLaunchKernelGGL(k_gga, dim3(XC_BLOCKS), dim3(256), 0, b->stream, n, rho, sigma, fun_mask, threshold, e, vrho,
@@ -419,19 +601,80 @@ int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const 
         vh = c1;
     }
     hipLaunchKernelGGL(k_xc_sum_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, up, dn, vh, 1.0 / (double)N, vloc, fun_mask,
-                       V_out, V_out ? V_out + N : (double*)nullptr, partial);
+                       (const double*)nullptr, (const double*)nullptr, V_out, V_out ? V_out + N : (double*)nullptr, partial);
     HIPCHK(hipGetLastError());
     if (!energies_h) return 0;      // potential only: asynchronous, like every call that returns no host data
-    std::vector<double> hp(3 * XC_BLOCKS, 0.0);
-    CHK(host_fetch(b, hp.data(), partial, (green ? 3 : 2) * XC_BLOCKS * sizeof(double)));
-    double s3[3] = {0.0, 0.0, 0.0};
-    for (int k = 0; k < 3; ++k)
-        for (int i = 0; i < XC_BLOCKS; ++i) s3[k] += hp[(size_t)k * XC_BLOCKS + i];
-    const double dvol = b->volume / (double)N;
-    energies_h[0] = green ? 0.5 * b->volume / ((double)N * (double)N) * s3[2] : 0.0;
-    energies_h[1] = s3[0] * dvol;
-    energies_h[2] = s3[1] * dvol;
-    return 0;
+    return collinear_energies(b, N, partial, green != nullptr, energies_h);
+}
+
+// Collinear-spin GGA pipeline (xc.jl:120-137 with LibxcDensities for two spin components): as local_potential_collinear, plus
+//   grad rho_s = irfft(i G_a fft(rho_s)),  sigma_st = grad rho_s . grad rho_t,  point-wise PBE (k_gga_spin),
+//   V_s += v_rho,s - 2 div(v_sigma,ss grad rho_s + 1/2 v_sigma,ud grad rho_s')
+// F[rho_up], F[rho_down] are computed once (the Poisson pass works on their sum); the six gradient cubes and the six flux
+// cubes go through one transform pipeline each.  17 cube FFTs in 5 pipelines, 35 launches with Hartree.
+int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* vloc,
+                                  const double* green, int fun_mask, double threshold, double* V_out, double* energies_h) {
+    dftk_mi_basis* b = cube_kb->basis;
+    const int64_t N = (int64_t)b->nx * b->ny * b->nz;
+    if (cube_kb->n_G != N) {
+        dftk_set_error("local_potential_collinear_gga: the k-block must span the whole cube (n_G = %lld, N = %lld)",
+                       (long long)cube_kb->n_G, (long long)N);
+        return DFTK_MI_EINVAL;
+    }
+    if (fun_mask & ~(1 | 4 | 32 | 24)) {
+        dftk_set_error("local_potential_collinear_gga: spin-polarised forms exist for lda_x, lda_c_pw, lda_xc_teter93, "
+                       "gga_x_pbe, gga_c_pbe only (mask %d)", fun_mask);
+        return DFTK_MI_EINVAL;
+    }
+    const int gga_mask = fun_mask & 24;
+    if (!gga_mask) return local_potential_collinear(cube_kb, rho, vloc, green, fun_mask, V_out, energies_h);
+    // complex cubes: c1 | F[rho_up], F[rho_down] | six gradient / flux cubes; real cubes: 6 gradients, 3 sigma, e, 2 v_rho,
+    // 3 v_sigma; then the reduction partials
+    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes,
+                     9 * (size_t)N * sizeof(cd) + 15 * (size_t)N * sizeof(double) + 3 * XC_BLOCKS * sizeof(double)));
+    cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+    cd* f2 = c1 + N;                                   // F[rho_up], F[rho_down]; later the two divergences
+    cd* g6 = f2 + 2 * N;
+    double* grad = reinterpret_cast<double*>(g6 + 6 * N);   // d_a rho_up (a = 0, 1, 2), d_a rho_down
+    double* sigma = grad + 6 * N;                      // uu, ud, dd
+    double* e_g = sigma + 3 * N;
+    double* vrho = e_g + N;                            // up, down
+    double* vsig = vrho + 2 * N;                       // uu, ud, dd
+    double* partial = vsig + 3 * N;
+    const double *up = rho, *dn = rho + N;
+    const cd* vh = nullptr;
+    hipLaunchKernelGGL(k_real_to_complex, dim3(XC_BLOCKS), dim3(256), 0, b->stream, 2 * N, rho, g6);
+    CHK(launch_fft_from_cube(cube_kb, g6, f2, 2));                                     // f2[s] = F[rho_s] (unnormalised)
+    for (int s = 0; s < 2; ++s)
+        for (int a = 0; a < 3; ++a) CHK(cube_gradient_multiply(cube_kb, recip_h, a, f2 + s * N, g6 + (3 * s + a) * N, false));
+    if (green) {
+        hipLaunchKernelGGL(k_poisson_sum, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, (const cd*)f2, (const cd*)(f2 + N), green,
+                           c1, partial + 2 * XC_BLOCKS);
+        CHK(launch_ifft_to_cube(cube_kb, c1, c1));                                     // c1 = N * V_H(r): kept until the final sum
+        vh = c1;
+    }
+    CHK(launch_ifft_to_cube(cube_kb, g6, g6, 6));                                      // in place: N grad rho_s
+    hipLaunchKernelGGL(k_xc_real_part_scaled, dim3(XC_BLOCKS), dim3(256), 0, b->stream, 6 * N, (const cd*)g6, 1.0 / (double)N,
+                       grad);
+    hipLaunchKernelGGL(k_sigma_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, (const double*)grad, sigma);
+    hipLaunchKernelGGL(k_gga_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, up, dn, (const double*)sigma,
+                       (const double*)(sigma + N), (const double*)(sigma + 2 * N), gga_mask, threshold, e_g, vrho, vrho + N, vsig,
+                       vsig + N, vsig + 2 * N);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_flux_spin_to_complex, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, (const double*)vsig,
+                       (const double*)grad, g6);
+    CHK(launch_fft_from_cube(cube_kb, g6, g6, 6));                                     // in place
+    for (int s = 0; s < 2; ++s)
+        for (int a = 0; a < 3; ++a) CHK(cube_gradient_multiply(cube_kb, recip_h, a, g6 + (3 * s + a) * N, f2 + s * N, a > 0));
+    CHK(launch_ifft_to_cube(cube_kb, f2, g6, 2));                                      // g6[s] = N div(flux_s)
+    double* v_g = sigma;                                                               // (sigma is dead by now): two cubes
+    CHK(cube_axpy_real(b, 2 * N, vrho, -2.0 / (double)N, g6, v_g));
+    hipLaunchKernelGGL(k_xc_sum_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, up, dn, vh, 1.0 / (double)N, vloc,
+                       fun_mask & (1 | 4 | 32), (const double*)e_g, (const double*)v_g, V_out,
+                       V_out ? V_out + N : (double*)nullptr, partial);
+    HIPCHK(hipGetLastError());
+    if (!energies_h) return 0;      // potential only: asynchronous (no fetch, no synchronisation)
+    return collinear_energies(b, N, partial, green != nullptr, energies_h);
 }
 
 // cube_kb: a k-block whose "sphere" is the whole cube (mapping = 0 .. N-1), i.e. the library's cube FFT.

@@ -686,12 +686,14 @@ def _PH_psi(basis, Pt, psik):
 _LDA_BITS = {"lda_x": 1, "lda_c_vwn": 2, "lda_c_pw": 4, "lda_xc_teter93": 32}
 _SPIN_LDA = ("lda_x", "lda_c_pw", "lda_xc_teter93")      # functionals with a spin-polarised closed form in the library
 _GGA_BITS = {"gga_x_pbe": 8, "gga_c_pbe": 16}
+_SPIN_GGA = ("gga_x_pbe", "gga_c_pbe")                   # ... through dftk_mi_local_potential_collinear_gga
 
 
 def local_potential_fused(basis, rho, want_potential=True, want_energies=True):
     """Hartree + XC (LDA point-wise; PBE with its gradient / divergence Fourier passes) + V_loc summed into one
-    potential and their three energies by ONE library call (``dftk_mi_local_potential`` / ``_gga``: hartree.jl:50-59,
-    xc.jl:84-160,356-409,576-584, local.jl:15-16, operators.jl:213-222).  Returns None for functionals the library does
+    potential and their three energies by ONE library call (``dftk_mi_local_potential`` / ``_gga``; a collinear density
+    (rho.dim() == 4) goes to ``_collinear`` / ``_collinear_gga``: hartree.jl:50-59, xc.jl:84-160,356-409,576-584,
+    local.jl:15-16, operators.jl:213-222).  Returns None for functionals the library does
     not evaluate.  ``want_energies=False`` (potential only): the call does not synchronise, the three energies are NaN."""
     import ctypes as C
     T = basis.terms
@@ -713,11 +715,17 @@ def local_potential_fused(basis, rho, want_potential=True, want_energies=True):
     args = (vloc.data_ptr() if vloc is not None else None, green.data_ptr() if green is not None else None)
     if rho.dim() == 4:
         # collinear spin: (rho_up, rho_down) -> (V_up, V_down); Hartree and the local term see the total density
-        if "Xc" in T.names and any(f not in _SPIN_LDA for f in basis.model.functionals):
-            raise NotImplementedError(f"collinear spin: spin-polarised forms exist for {_SPIN_LDA} only, got "
+        if "Xc" in T.names and any(f not in _SPIN_LDA + _SPIN_GGA for f in basis.model.functionals):
+            raise NotImplementedError(f"collinear spin: spin-polarised forms exist for {_SPIN_LDA + _SPIN_GGA} only, got "
                                       f"{basis.model.functionals}")
-        _lib.check(basis.lib.dftk_mi_local_potential_collinear(basis._cube_handle, rho.data_ptr(), *args, mask,
-                                                               V.data_ptr() if V is not None else None, E3))
+        if mask & 24:
+            Bh = np.asfortranarray(basis.model.recip_lattice, dtype=np.float64)
+            _lib.check(basis.lib.dftk_mi_local_potential_collinear_gga(
+                basis._cube_handle, Bh.ctypes.data, rho.data_ptr(), *args, mask, _DENSITY_THRESHOLD,
+                V.data_ptr() if V is not None else None, E3))
+        else:
+            _lib.check(basis.lib.dftk_mi_local_potential_collinear(basis._cube_handle, rho.data_ptr(), *args, mask,
+                                                                   V.data_ptr() if V is not None else None, E3))
     elif mask & 24:
         Bh = np.asfortranarray(basis.model.recip_lattice, dtype=np.float64)
         _lib.check(basis.lib.dftk_mi_local_potential_gga(basis._cube_handle, Bh.ctypes.data, rho.data_ptr(), *args, mask,

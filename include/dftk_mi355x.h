@@ -219,6 +219,19 @@ int dftk_mi_local_potential_gga(dftk_mi_kblock* cube_kb, const double* recip_lat
                                 const double* V_loc_d, const double* poisson_green_d, int xc_functionals,
                                 double density_threshold, double* V_out_d, double* energies_h);
 
+/* Collinear spin with GGA functionals (PBE on a magnetic system, the reference's test/iron_pbe.jl): the semantics of
+ * dftk_mi_local_potential_collinear (two cubes in rho_d and V_out_d, Hartree and V_loc on the total density, three
+ * energies, energies_h == NULL: asynchronous) with the gradient terms of src/terms/xc.jl:120-137 for two spin components,
+ *   grad rho_s = irfft(i G_a fft(rho_s)),  sigma_st = grad rho_s . grad rho_t,
+ *   V_out[s] += de/drho_s - 2 div(de/dsigma_ss grad rho_s + 1/2 de/dsigma_ud grad rho_s'),   s' = the other channel,
+ * G cartesian from recip_lattice_h (3x3 column-major; required with a GGA bit).  xc_functionals: the spin-polarised LDA
+ * bits (LDA_X, LDA_C_PW, LDA_XC_TETER93) and DFTK_MI_XC_GGA_X_PBE, DFTK_MI_XC_GGA_C_PBE in any mix; anything else:
+ * DFTK_MI_EINVAL, nothing written.  Without a GGA bit the call is dftk_mi_local_potential_collinear.  Floors of the GGA
+ * part: see dftk_mi_xc_gga_spin. */
+int dftk_mi_local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, const double* rho_d,
+                                          const double* V_loc_d, const double* poisson_green_d, int xc_functionals,
+                                          double density_threshold, double* V_out_d, double* energies_h);
+
 /* ---- density-sized operations of the SCF glue ----------------------------------------------
  * symmetrize_rho(basis, rho; symmetries, do_lowpass) for one spin component (src/symmetry.jl:346-357): fft, then
  * accumulate_over_symmetries! (:282-319: out(G) = sum_s e^{-2 pi i G.tau_s} in(S_s^-1 G), terms whose S_s^-1 G leaves
@@ -253,6 +266,15 @@ int dftk_mi_cube_fourier_filter(dftk_mi_kblock* cube_kb, const double* multiplie
 #define DFTK_MI_XC_GGA_C_PBE 16
 int dftk_mi_xc_gga(dftk_mi_basis* basis, int64_t n, const double* rho_d, const double* sigma_d, int xc_functionals,
                    double density_threshold, double* e_d, double* vrho_d, double* vsigma_d);
+
+/* The same for two spin components (libxc's polarised gga_x_pbe / gga_c_pbe).  Planar arrays of n values per component:
+ * rho_d = (up, down), sigma_d = (uu, ud, dd) with sigma_st = grad rho_s . grad rho_t, e_d = energy density per volume,
+ * vrho_d = (de/drho_up, de/drho_down), vsigma_d = (de/dsigma_uu, de/dsigma_ud, de/dsigma_dd) -- the reference's packed
+ * order (DftFunctionals.spinindex_sigma).  Each channel enters as max(rho_s, 1e-20) and the derivatives are those of the
+ * clamped variables; a point with rho_up + rho_down <= max(density_threshold, 2e-20) gives zeros in all six outputs;
+ * sigma_uu, sigma_dd and sigma_uu + 2 sigma_ud + sigma_dd enter as max(., 0). */
+int dftk_mi_xc_gga_spin(dftk_mi_basis* basis, int64_t n, const double* rho_d, const double* sigma_d, int xc_functionals,
+                        double density_threshold, double* e_d, double* vrho_d, double* vsigma_d);
 
 /* ---- sphere <-> cube transforms  (src/fft.jl:110-122 ifft!, :162-172 fft!; normalize=false) --
  * cube_d is nx*ny*nz complex, x fastest.  Test/diagnostic entry points (the hot path never
