@@ -87,32 +87,60 @@ __device__ __forceinline__ void lda_c_pw(double rho, double& e, double& v) {
 }
 
 // ---- GGA (PBE): e(rho, sigma) with forward-mode derivatives d/d rho, d/d sigma carried through the closed forms
-// (libxc's gga_x_pbe / gga_c_pbe on lda_c_pw_mod; Perdew, Burke, Ernzerhof 1996).  A dual number (v, dr, ds) makes
+// (libxc's gga_x_pbe / gga_c_pbe on lda_c_pw_mod; Perdew, Burke, Ernzerhof 1996).  A dual number (v, d/d rho, d/d sigma) makes
 // the potential terms exact derivatives of exactly the energy expression -- no hand-derived formulas.
-// No fused multiply-adds from here to lda_spin_sum: the compiler folds the seeds (1, 0) and (0, 1) of the two derivative
+// Dual<N>: a value and N derivative slots, every slot through the same operations.  D3 carries (d/d rho, d/d sigma) or
+// (d/d rho_up, d/d rho_down), D4 (d/d rho_up, d/d rho_down, d/d sigma_tot).
+// No fused multiply-adds from here to k_gga_spin: the compiler folds the seeds (1, 0) and (0, 1) of two derivative
 // slots and then contracts the two slots differently, which breaks the exchange symmetry V_up(a, b) = V_down(b, a) of the
-// collinear forms in the last bit.  With separate roundings every folding is exact and both slots round alike.
+// collinear forms in the last bit.  With separate roundings every folding is exact and all slots round alike.
 #pragma clang fp contract(off)
-struct D3 {
-    double v, dr, ds;
+template <int N>
+struct Dual {
+    double v, d[N];
+    template <class F>
+    static __device__ __forceinline__ Dual make(double v, F slot) {      // value v, slot k = slot(k)
+        Dual r;
+        r.v = v;
+#pragma unroll
+        for (int k = 0; k < N; ++k) r.d[k] = slot(k);
+        return r;
+    }
+    friend __device__ __forceinline__ Dual operator+(Dual a, Dual b) {
+        return make(a.v + b.v, [&](int k) { return a.d[k] + b.d[k]; });
+    }
+    friend __device__ __forceinline__ Dual operator-(Dual a, Dual b) {
+        return make(a.v - b.v, [&](int k) { return a.d[k] - b.d[k]; });
+    }
+    friend __device__ __forceinline__ Dual operator*(Dual a, Dual b) {
+        return make(a.v * b.v, [&](int k) { return a.d[k] * b.v + a.v * b.d[k]; });
+    }
+    friend __device__ __forceinline__ Dual operator/(Dual a, Dual b) {
+        const double q = a.v / b.v;
+        return make(q, [&](int k) { return (a.d[k] - q * b.d[k]) / b.v; });
+    }
+    friend __device__ __forceinline__ Dual operator*(double c, Dual a) {
+        return make(c * a.v, [&](int k) { return c * a.d[k]; });
+    }
+    friend __device__ __forceinline__ Dual operator+(double c, Dual a) { a.v = c + a.v; return a; }
+    friend __device__ __forceinline__ Dual dchain(Dual a, double f, double df) {      // f(a) with f' = df
+        return make(f, [&](int k) { return df * a.d[k]; });
+    }
+    friend __device__ __forceinline__ Dual dsqrt(Dual a) { const double r = sqrt(a.v); return dchain(a, r, 0.5 / r); }
+    friend __device__ __forceinline__ Dual dcbrt(Dual a) { const double r = cbrt(a.v); return dchain(a, r, r / (3.0 * a.v)); }
+    friend __device__ __forceinline__ Dual dlog1p(Dual a) { return dchain(a, log1p(a.v), 1.0 / (1.0 + a.v)); }
+    friend __device__ __forceinline__ Dual dexpm1(Dual a) { const double e = expm1(a.v); return dchain(a, e, e + 1.0); }
 };
-__device__ __forceinline__ D3 dc(double c) { return D3{c, 0.0, 0.0}; }
-__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return D3{a.v + b.v, a.dr + b.dr, a.ds + b.ds}; }
-__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return D3{a.v - b.v, a.dr - b.dr, a.ds - b.ds}; }
-__device__ __forceinline__ D3 operator*(D3 a, D3 b) {
-    return D3{a.v * b.v, a.dr * b.v + a.v * b.dr, a.ds * b.v + a.v * b.ds};
+typedef Dual<2> D3;
+typedef Dual<3> D4;
+template <class T>
+__device__ __forceinline__ T dc(double c) { return T{c, {}}; }      // a constant
+// the PW92 fit G(rs; A, a1, b1 .. b4) = -2 A (1 + a1 rs) log1p(1 / (2 A (b1 sqrt(rs) + b2 rs + b3 rs^(3/2) + b4 rs^2)))
+template <class T>
+__device__ __forceinline__ T pw92_G(T rs, T sq, double A, double a1, double b1, double b2, double b3, double b4) {
+    const T den = 2.0 * A * (b1 * sq + b2 * rs + b3 * (rs * sq) + b4 * (rs * rs));
+    return (-2.0 * A) * ((1.0 + a1 * rs) * dlog1p(dc<T>(1.0) / den));
 }
-__device__ __forceinline__ D3 operator/(D3 a, D3 b) {
-    const double q = a.v / b.v;
-    return D3{q, (a.dr - q * b.dr) / b.v, (a.ds - q * b.ds) / b.v};
-}
-__device__ __forceinline__ D3 operator*(double c, D3 a) { return D3{c * a.v, c * a.dr, c * a.ds}; }
-__device__ __forceinline__ D3 operator+(double c, D3 a) { return D3{c + a.v, a.dr, a.ds}; }
-__device__ __forceinline__ D3 dchain(D3 a, double f, double df) { return D3{f, df * a.dr, df * a.ds}; }
-__device__ __forceinline__ D3 dsqrt(D3 a) { const double r = sqrt(a.v); return dchain(a, r, 0.5 / r); }
-__device__ __forceinline__ D3 dcbrt(D3 a) { const double r = cbrt(a.v); return dchain(a, r, r / (3.0 * a.v)); }
-__device__ __forceinline__ D3 dlog1p(D3 a) { return dchain(a, log1p(a.v), 1.0 / (1.0 + a.v)); }
-__device__ __forceinline__ D3 dexpm1(D3 a) { const double e = expm1(a.v); return dchain(a, e, e + 1.0); }
 
 __device__ __forceinline__ D3 gga_x_pbe(D3 rho, D3 sigma) {
     const double kappa = 0.8040, mu = 0.2195149727645171;
@@ -120,18 +148,16 @@ __device__ __forceinline__ D3 gga_x_pbe(D3 rho, D3 sigma) {
     const D3 kf = dcbrt(3.0 * M_PI * M_PI * rho);
     const D3 s2 = sigma / (4.0 * (kf * kf * rho * rho));
     const D3 r13 = dcbrt(rho);
-    return cx * (rho * r13) * ((1.0 + kappa) + (-kappa * kappa) * (dc(1.0) / (kappa + mu * s2)));
+    return cx * (rho * r13) * ((1.0 + kappa) + (-kappa * kappa) * (dc<D3>(1.0) / (kappa + mu * s2)));
 }
 __device__ __forceinline__ D3 gga_c_pbe(D3 rho, D3 sigma) {
     const double beta = 0.06672455060314922, gamma = 0.031090690869654895;   // (1 - ln 2) / pi^2
-    const double a = 0.0310907, a1 = 0.21370, b1 = 7.5957, b2 = 3.5876, b3 = 1.6382, b4 = 0.49294;
-    const D3 rs = dcbrt(dc(3.0 / (4.0 * M_PI)) / rho);
+    const D3 rs = dcbrt(dc<D3>(3.0 / (4.0 * M_PI)) / rho);
     const D3 sq = dsqrt(rs);
-    const D3 den = 2.0 * a * (b1 * sq + b2 * rs + b3 * (rs * sq) + b4 * (rs * rs));
-    const D3 eps = (-2.0 * a) * ((1.0 + a1 * rs) * dlog1p(dc(1.0) / den));
+    const D3 eps = pw92_G(rs, sq, 0.0310907, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294);   // lda_c_pw_mod
     const D3 kf = dcbrt(3.0 * M_PI * M_PI * rho);
     const D3 t2 = (M_PI / 16.0) * (sigma / (kf * rho * rho));
-    const D3 A = dc(beta / gamma) / dexpm1((-1.0 / gamma) * eps);
+    const D3 A = dc<D3>(beta / gamma) / dexpm1((-1.0 / gamma) * eps);
     const D3 f1 = t2 + A * (t2 * t2);
     const D3 H = gamma * dlog1p((beta / gamma) * (f1 / (1.0 + A * f1)));
     return rho * (eps + H);
@@ -142,16 +168,16 @@ __global__ __launch_bounds__(256) void k_gga(int64_t n, const double* __restrict
                                              int fun_mask, double threshold, double* __restrict__ e,
                                              double* __restrict__ vrho, double* __restrict__ vsigma) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        D3 acc = dc(0.0);
+        D3 acc = dc<D3>(0.0);
         const double r = rho[i];
         if (r > threshold) {
-            const D3 dr = D3{r, 1.0, 0.0}, dsg = D3{sigma[i], 0.0, 1.0};
-            if (fun_mask & 8) acc = acc + gga_x_pbe(dr, dsg);
-            if (fun_mask & 16) acc = acc + gga_c_pbe(dr, dsg);
+            const D3 dr = D3{r, {1.0, 0.0}}, dsg = D3{sigma[i], {0.0, 1.0}};
+            if (fun_mask & DFTK_MI_XC_GGA_X_PBE) acc = acc + gga_x_pbe(dr, dsg);
+            if (fun_mask & DFTK_MI_XC_GGA_C_PBE) acc = acc + gga_c_pbe(dr, dsg);
         }
         e[i] = acc.v;
-        vrho[i] = acc.dr;
-        vsigma[i] = acc.ds;
+        vrho[i] = acc.d[0];
+        vsigma[i] = acc.d[1];
     }
 }
 // ---- collinear spin, LDA: e(rho_up, rho_down) with forward-mode derivatives; the two derivative slots of D3 carry
@@ -161,11 +187,7 @@ __global__ __launch_bounds__(256) void k_gga(int64_t n, const double* __restrict
 __device__ __forceinline__ D3 dpow43(D3 a) { return a * dcbrt(a); }
 __device__ __forceinline__ D3 spin_fzeta(D3 ra, D3 rb, D3 rt) {
     const D3 xa = 2.0 * (ra / rt), xb = 2.0 * (rb / rt);
-    return (1.0 / (2.5198420997897464 - 2.0)) * (dpow43(xa) + dpow43(xb) + dc(-2.0));   // 2^(4/3) - 2
-}
-__device__ __forceinline__ D3 pw92_G(D3 rs, D3 sq, double A, double a1, double b1, double b2, double b3, double b4) {
-    const D3 den = 2.0 * A * (b1 * sq + b2 * rs + b3 * (rs * sq) + b4 * (rs * rs));
-    return (-2.0 * A) * ((1.0 + a1 * rs) * dlog1p(dc(1.0) / den));
+    return (1.0 / (2.5198420997897464 - 2.0)) * (dpow43(xa) + dpow43(xb) + dc<D3>(-2.0));   // 2^(4/3) - 2
 }
 __device__ __forceinline__ D3 lda_x_spin(D3 ra, D3 rb) {
     const double cx = -0.73855876638202240588 * 1.2599210498948732;   // -3/4 (3/pi)^(1/3) 2^(1/3)
@@ -176,12 +198,12 @@ __device__ __forceinline__ D3 lda_c_pw_spin(D3 ra, D3 rb) {
     const D3 fz = spin_fzeta(ra, rb, rt);
     const D3 z = (ra - rb) / rt;
     const D3 z2 = z * z, z4 = z2 * z2;
-    const D3 rs = dcbrt(dc(3.0 / (4.0 * M_PI)) / rt);
+    const D3 rs = dcbrt(dc<D3>(3.0 / (4.0 * M_PI)) / rt);
     const D3 sq = dsqrt(rs);
     const D3 e0 = pw92_G(rs, sq, 0.031091, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294);
     const D3 e1 = pw92_G(rs, sq, 0.015545, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517);
     const D3 mac = pw92_G(rs, sq, 0.016887, 0.11125, 10.357, 3.6231, 0.88026, 0.49671);   // = -alpha_c
-    return rt * (e0 - (1.0 / 1.709921) * (mac * fz * (dc(1.0) - z4)) + (e1 - e0) * (fz * z4));
+    return rt * (e0 - (1.0 / 1.709921) * (mac * fz * (dc<D3>(1.0) - z4)) + (e1 - e0) * (fz * z4));
 }
 __device__ __forceinline__ D3 lda_xc_teter93_spin(D3 ra, D3 rb) {
     const double a[4] = {0.4581652932831429, 2.217058676663745, 0.7405551735357053, 0.01968227878617998};
@@ -190,20 +212,19 @@ __device__ __forceinline__ D3 lda_xc_teter93_spin(D3 ra, D3 rb) {
     const double db[4] = {0.0, 0.2673612973836267, 0.2052004607777787, 0.004200005045691381};
     const D3 rt = ra + rb;
     const D3 fz = spin_fzeta(ra, rb, rt);
-    const D3 rs = dcbrt(dc(3.0 / (4.0 * M_PI)) / rt);
+    const D3 rs = dcbrt(dc<D3>(3.0 / (4.0 * M_PI)) / rt);
     const D3 num = (a[0] + da[0] * fz) + rs * ((a[1] + da[1] * fz) + rs * ((a[2] + da[2] * fz) + rs * (a[3] + da[3] * fz)));
     const D3 den = rs * ((bb[0] + db[0] * fz) + rs * ((bb[1] + db[1] * fz) + rs * ((bb[2] + db[2] * fz) + rs * (bb[3] + db[3] * fz))));
-    return dc(-1.0) * (rt * (num / den));
+    return dc<D3>(-1.0) * (rt * (num / den));
 }
-// fun_mask bits: 1 lda_x, 4 lda_c_pw, 32 lda_xc_teter93
 __device__ __forceinline__ D3 lda_spin_sum(double rho_up, double rho_dn, int fun_mask) {
     const double floor_ = 1e-20;                       // a spin channel is never evaluated below this density
-    const D3 ra = D3{rho_up > floor_ ? rho_up : floor_, 1.0, 0.0}, rb = D3{rho_dn > floor_ ? rho_dn : floor_, 0.0, 1.0};
-    D3 acc = dc(0.0);
+    const D3 ra = D3{rho_up > floor_ ? rho_up : floor_, {1.0, 0.0}}, rb = D3{rho_dn > floor_ ? rho_dn : floor_, {0.0, 1.0}};
+    D3 acc = dc<D3>(0.0);
     if (rho_up + rho_dn <= 2.0 * floor_) return acc;
-    if (fun_mask & 1) acc = acc + lda_x_spin(ra, rb);
-    if (fun_mask & 4) acc = acc + lda_c_pw_spin(ra, rb);
-    if (fun_mask & 32) acc = acc + lda_xc_teter93_spin(ra, rb);
+    if (fun_mask & DFTK_MI_XC_LDA_X) acc = acc + lda_x_spin(ra, rb);
+    if (fun_mask & DFTK_MI_XC_LDA_C_PW) acc = acc + lda_c_pw_spin(ra, rb);
+    if (fun_mask & DFTK_MI_XC_LDA_XC_TETER93) acc = acc + lda_xc_teter93_spin(ra, rb);
     return acc;
 }
 
@@ -216,49 +237,25 @@ __device__ __forceinline__ D3 lda_spin_sum(double rho_up, double rho_dn, int fun
 // digits for the other two fits and f''(0)), phi = ((1 + zeta)^(2/3) + (1 - zeta)^(2/3)) / 2, t^2 = pi sigma_tot /
 // (16 phi^2 k_F rho^2), A = (beta / gamma) / expm1(-eps_c / (gamma phi^3)), H = gamma phi^3 log1p(...): gga_c_pbe
 // term by term where phi = 1.
-struct D4 {
-    double v, da, db, ds;
-};
-__device__ __forceinline__ D4 dc4(double c) { return D4{c, 0.0, 0.0, 0.0}; }
-__device__ __forceinline__ D4 operator+(D4 a, D4 b) { return D4{a.v + b.v, a.da + b.da, a.db + b.db, a.ds + b.ds}; }
-__device__ __forceinline__ D4 operator-(D4 a, D4 b) { return D4{a.v - b.v, a.da - b.da, a.db - b.db, a.ds - b.ds}; }
-__device__ __forceinline__ D4 operator*(D4 a, D4 b) {
-    return D4{a.v * b.v, a.da * b.v + a.v * b.da, a.db * b.v + a.v * b.db, a.ds * b.v + a.v * b.ds};
-}
-__device__ __forceinline__ D4 operator/(D4 a, D4 b) {
-    const double q = a.v / b.v;
-    return D4{q, (a.da - q * b.da) / b.v, (a.db - q * b.db) / b.v, (a.ds - q * b.ds) / b.v};
-}
-__device__ __forceinline__ D4 operator*(double c, D4 a) { return D4{c * a.v, c * a.da, c * a.db, c * a.ds}; }
-__device__ __forceinline__ D4 operator+(double c, D4 a) { return D4{c + a.v, a.da, a.db, a.ds}; }
-__device__ __forceinline__ D4 dchain(D4 a, double f, double df) { return D4{f, df * a.da, df * a.db, df * a.ds}; }
-__device__ __forceinline__ D4 dsqrt(D4 a) { const double r = sqrt(a.v); return dchain(a, r, 0.5 / r); }
-__device__ __forceinline__ D4 dcbrt(D4 a) { const double r = cbrt(a.v); return dchain(a, r, r / (3.0 * a.v)); }
-__device__ __forceinline__ D4 dlog1p(D4 a) { return dchain(a, log1p(a.v), 1.0 / (1.0 + a.v)); }
-__device__ __forceinline__ D4 dexpm1(D4 a) { const double e = expm1(a.v); return dchain(a, e, e + 1.0); }
-__device__ __forceinline__ D4 pw92_G(D4 rs, D4 sq, double A, double a1, double b1, double b2, double b3, double b4) {
-    const D4 den = 2.0 * A * (b1 * sq + b2 * rs + b3 * (rs * sq) + b4 * (rs * rs));
-    return (-2.0 * A) * ((1.0 + a1 * rs) * dlog1p(dc4(1.0) / den));
-}
 __device__ __forceinline__ D4 gga_c_pbe_spin(D4 ra, D4 rb, D4 sigma) {
     const double beta = 0.06672455060314922, gamma = 0.031090690869654895;   // (1 - ln 2) / pi^2
     const D4 rt = ra + rb;
     const D4 xa = 2.0 * (ra / rt), xb = 2.0 * (rb / rt);                     // 1 + zeta, 1 - zeta
     const D4 ca = dcbrt(xa), cb = dcbrt(xb);
-    const D4 fz = (1.0 / (2.5198420997897464 - 2.0)) * (xa * ca + xb * cb + dc4(-2.0));
+    const D4 fz = (1.0 / (2.5198420997897464 - 2.0)) * (xa * ca + xb * cb + dc<D4>(-2.0));
     const D4 phi = 0.5 * (ca * ca + cb * cb);
     const D4 z = (ra - rb) / rt;
     const D4 z2 = z * z, z4 = z2 * z2;
-    const D4 rs = dcbrt(dc4(3.0 / (4.0 * M_PI)) / rt);
+    const D4 rs = dcbrt(dc<D4>(3.0 / (4.0 * M_PI)) / rt);
     const D4 sq = dsqrt(rs);
     const D4 e0 = pw92_G(rs, sq, 0.0310907, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294);
     const D4 e1 = pw92_G(rs, sq, 0.01554535, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517);
     const D4 mac = pw92_G(rs, sq, 0.0168869, 0.11125, 10.357, 3.6231, 0.88026, 0.49671);   // = -alpha_c
-    const D4 eps = e0 - (1.0 / 1.709920934161365617563962776245) * (mac * fz * (dc4(1.0) - z4)) + (e1 - e0) * (fz * z4);
+    const D4 eps = e0 - (1.0 / 1.709920934161365617563962776245) * (mac * fz * (dc<D4>(1.0) - z4)) + (e1 - e0) * (fz * z4);
     const D4 phi2 = phi * phi, phi3 = phi2 * phi;
     const D4 kf = dcbrt(3.0 * M_PI * M_PI * rt);
     const D4 t2 = (M_PI / 16.0) * (sigma / (phi2 * (kf * rt * rt)));
-    const D4 A = dc4(beta / gamma) / dexpm1((-1.0 / gamma) * (eps / phi3));
+    const D4 A = dc<D4>(beta / gamma) / dexpm1((-1.0 / gamma) * (eps / phi3));
     const D4 f1 = t2 + A * (t2 * t2);
     const D4 H = gamma * (phi3 * dlog1p((beta / gamma) * (f1 / (1.0 + A * f1))));
     return rt * (eps + H);
@@ -280,25 +277,25 @@ __global__ __launch_bounds__(256) void k_gga_spin(int64_t n, const double* __res
             const double ra = a > floor_ ? a : floor_, rb = b > floor_ ? b : floor_;
             const double s_uu = suu[i], s_ud = sud[i], s_dd = sdd[i];
             const double p_uu = s_uu > 0.0 ? s_uu : 0.0, p_dd = s_dd > 0.0 ? s_dd : 0.0;
-            if (fun_mask & 8) {
-                const D3 xu = 0.5 * gga_x_pbe(D3{2.0 * ra, 2.0, 0.0}, D3{4.0 * p_uu, 0.0, 4.0});
-                const D3 xd = 0.5 * gga_x_pbe(D3{2.0 * rb, 2.0, 0.0}, D3{4.0 * p_dd, 0.0, 4.0});
+            if (fun_mask & DFTK_MI_XC_GGA_X_PBE) {
+                const D3 xu = 0.5 * gga_x_pbe(D3{2.0 * ra, {2.0, 0.0}}, D3{4.0 * p_uu, {0.0, 4.0}});
+                const D3 xd = 0.5 * gga_x_pbe(D3{2.0 * rb, {2.0, 0.0}}, D3{4.0 * p_dd, {0.0, 4.0}});
                 ev += xu.v + xd.v;
-                va += xu.dr;
-                vb += xd.dr;
-                wuu += xu.ds;
-                wdd += xd.ds;
+                va += xu.d[0];
+                vb += xd.d[0];
+                wuu += xu.d[1];
+                wdd += xd.d[1];
             }
-            if (fun_mask & 16) {
+            if (fun_mask & DFTK_MI_XC_GGA_C_PBE) {
                 const double st = (s_uu + s_dd) + 2.0 * s_ud;      // (symmetric in the channels to the last bit)
-                const D4 c = gga_c_pbe_spin(D4{ra, 1.0, 0.0, 0.0}, D4{rb, 0.0, 1.0, 0.0},
-                                            D4{st > 0.0 ? st : 0.0, 0.0, 0.0, 1.0});
+                const D4 c = gga_c_pbe_spin(D4{ra, {1.0, 0.0, 0.0}}, D4{rb, {0.0, 1.0, 0.0}},
+                                            D4{st > 0.0 ? st : 0.0, {0.0, 0.0, 1.0}});
                 ev += c.v;
-                va += c.da;
-                vb += c.db;
-                wuu += c.ds;
-                wud += 2.0 * c.ds;
-                wdd += c.ds;
+                va += c.d[0];
+                vb += c.d[1];
+                wuu += c.d[2];
+                wud += 2.0 * c.d[2];
+                wdd += c.d[2];
             }
         }
         e[i] = ev;
@@ -324,13 +321,13 @@ __global__ __launch_bounds__(256) void k_xc_sum(int64_t n, const double* __restr
         double e = 0.0, v = 0.0;
         if (fun_mask != 0 && r > 1e-300) {
             double ei, vi;
-            if (fun_mask & 1) { lda_x(r, ei, vi); e += ei; v += vi; }
-            if (fun_mask & 2) { lda_c_vwn(r, ei, vi); e += ei; v += vi; }
-            if (fun_mask & 4) { lda_c_pw(r, ei, vi); e += ei; v += vi; }
-            if (fun_mask & 32) {               // lda_xc_teter93: the polarised form at rho_up = rho_down = rho / 2
-                const D3 t = lda_spin_sum(0.5 * r, 0.5 * r, 32);
+            if (fun_mask & DFTK_MI_XC_LDA_X) { lda_x(r, ei, vi); e += ei; v += vi; }
+            if (fun_mask & DFTK_MI_XC_LDA_C_VWN) { lda_c_vwn(r, ei, vi); e += ei; v += vi; }
+            if (fun_mask & DFTK_MI_XC_LDA_C_PW) { lda_c_pw(r, ei, vi); e += ei; v += vi; }
+            if (fun_mask & DFTK_MI_XC_LDA_XC_TETER93) {   // the polarised form at rho_up = rho_down = rho / 2
+                const D3 t = lda_spin_sum(0.5 * r, 0.5 * r, DFTK_MI_XC_LDA_XC_TETER93);
                 e += t.v;
-                v += t.dr;
+                v += t.d[0];
             }
         }
         if (e_extra) {                       // GGA part: e(rho, sigma) and v_rho - 2 div(v_sigma grad rho), precomputed
@@ -374,8 +371,8 @@ __global__ __launch_bounds__(256) void k_xc_sum_spin(int64_t n, const double* __
         D3 e = lda_spin_sum(ra, rb, fun_mask);
         if (e_extra) {                       // GGA part: e and v_rho,s - 2 div(...) of the two channels (v_extra: 2 cubes)
             e.v += e_extra[i];
-            e.dr += v_extra[i];
-            e.ds += v_extra[n + i];
+            e.d[0] += v_extra[i];
+            e.d[1] += v_extra[n + i];
         }
         acc_xc += e.v;
         double common = 0.0;
@@ -386,8 +383,8 @@ __global__ __launch_bounds__(256) void k_xc_sum_spin(int64_t n, const double* __
         }
         if (vh_cube) common += vh_scale * vh_cube[i].x;
         if (V_up) {
-            V_up[i] = common + e.dr;
-            V_dn[i] = common + e.ds;
+            V_up[i] = common + e.d[0];
+            V_dn[i] = common + e.d[1];
         }
     }
     const double s0 = block_sum(acc_xc, sh);
@@ -456,9 +453,9 @@ __global__ __launch_bounds__(256) void k_fxc_sum(int64_t n, const double* __rest
         if (fun_mask != 0) {
             const double r = rho[i];
             if (r > 1e-300) {
-                if (fun_mask & 1) f += lda_x_fxc(r);
-                if (fun_mask & 2) f += lda_c_vwn_fxc(r);
-                if (fun_mask & 4) f += lda_c_pw_fxc(r);
+                if (fun_mask & DFTK_MI_XC_LDA_X) f += lda_x_fxc(r);
+                if (fun_mask & DFTK_MI_XC_LDA_C_VWN) f += lda_c_vwn_fxc(r);
+                if (fun_mask & DFTK_MI_XC_LDA_C_PW) f += lda_c_pw_fxc(r);
             }
         }
         double tot = f * drho[i];
