@@ -19,6 +19,16 @@ class dftk_mi_cplx(C.Structure):
     _fields_ = [("re", C.c_double), ("im", C.c_double)]
 
 
+class dftk_mi_batch_op(C.Structure):
+    """One row of dftk_mi_batch_replay's table (include/dftk_mi355x.h)."""
+    _fields_ = ([(name, C.c_int32) for name in ("type", "fiber", "trans", "m", "k", "i0", "mode", "flags", "join_next",
+                                                 "sync_after", "status", "reserved")] +
+                [(name, _i64) for name in ("n", "gm", "gn", "gk", "lda", "ldb", "ldc")] +
+                [("alpha", dftk_mi_cplx), ("beta", dftk_mi_cplx), ("s0", C.c_double)] +
+                [(name, C.c_void_p) for name in ("A", "B", "W", "W2", "W3", "C", "D", "E", "F", "kb", "host")] +
+                [("bytes", C.c_uint64)])
+
+
 class DftkMiError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"dftk_mi355x status {status}: {msg}")
@@ -102,6 +112,7 @@ _SIGNATURES = {
     "dftk_mi_lobpcg_small_stats": (C.c_int, [C.POINTER(_i64), C.POINTER(_i64)]),
     "dftk_mi_ortho_small": (C.c_int, [C.c_void_p, _i64, C.c_int, C.c_void_p, _i64, C.c_int, C.c_void_p, _i64, C.c_void_p,
                                       C.c_double, C.c_void_p]),
+    "dftk_mi_batch_replay": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dftk_mi_lobpcg_last_AX": (C.c_void_p, [C.c_void_p]),
     "dftk_mi_lobpcg_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_size_t,
                                          C.POINTER(C.c_int)]),

@@ -169,7 +169,9 @@ int exec_one(BOp& o) {
                           (double*)o.D, o.s0);
         case BOP_SCALE: return ew_scale_cols(o.b, o.n, o.m, Cc, o.ldc, (const double*)o.W, o.flags != 0);
         case BOP_COPY: return ew_copy(o.b, o.n, o.m, (const cd*)o.A, o.lda, Cc, o.ldc);
-        case BOP_FILL0: return ew_fill_zero(o.b, Cc, o.bytes / sizeof(cd));
+        case BOP_FILL0:   // (ew_fill_zero's own form, for any byte count: the replay entry records sizes it cannot express)
+            HIPCHK(hipMemsetAsync(o.C, 0, o.bytes, o.b->stream));
+            return 0;
         case BOP_SUBID: return ew_sub_identity_shifted(o.b, (int)o.n, o.m, Cc, o.ldc, o.i0);
         case BOP_GATHER: return ew_gather_cols(o.b, o.n, o.m, (const cd*)o.A, o.lda, (const int*)o.W, Cc, o.ldc);
         case BOP_ADDDIAG: return ew_add_diag(o.b, o.m, Cc, o.ldc, o.s0);
@@ -361,6 +363,153 @@ extern "C" int dftk_mi_batch_stats(int64_t* rounds, int64_t* ops, int64_t* merge
     if (ops) *ops = g_last_stats[1];
     if (merged_launches) *merged_launches = g_last_stats[2];
     if (sequential_ops) *sequential_ops = g_last_stats[3];
+    return 0;
+}
+
+// ---- dftk_mi_batch_replay: a table of operations issued by fibers (tests; the general form of dftk_mi_ortho_small) ----
+static_assert(DFTK_MI_BOP_ZGEMM == BOP_ZGEMM && DFTK_MI_BOP_COLRED == BOP_COLRED && DFTK_MI_BOP_RESIDUAL == BOP_RESIDUAL &&
+              DFTK_MI_BOP_TPA == BOP_TPA && DFTK_MI_BOP_SCALE == BOP_SCALE && DFTK_MI_BOP_COPY == BOP_COPY &&
+              DFTK_MI_BOP_FILL0 == BOP_FILL0 && DFTK_MI_BOP_SUBID == BOP_SUBID && DFTK_MI_BOP_GATHER == BOP_GATHER &&
+              DFTK_MI_BOP_ADDDIAG == BOP_ADDDIAG && DFTK_MI_BOP_HERMIT == BOP_HERMIT && DFTK_MI_BOP_CTRANS == BOP_CTRANS &&
+              DFTK_MI_BOP_H2D == BOP_H2D && DFTK_MI_BOP_D2H == BOP_D2H && DFTK_MI_BOP_POTRF == BOP_POTRF &&
+              DFTK_MI_BOP_HEEV == BOP_HEEV && DFTK_MI_BOP_APPLYD == BOP_APPLYD && DFTK_MI_BOP_ORTHO == BOP_ORTHO,
+              "the operation types of include/dftk_mi355x.h are the BOpType values");
+
+namespace {
+BOp replay_bop(dftk_mi_basis* b, const dftk_mi_batch_op& r) {
+    BOp o;
+    o.type = r.type;
+    o.b = b;
+    o.kb = r.kb;
+    o.trans = (char)r.trans;
+    o.n = r.n; o.lda = r.lda; o.ldb = r.ldb; o.ldc = r.ldc;
+    o.gm = r.gm; o.gn = r.gn; o.gk = r.gk;
+    o.m = r.m; o.k = r.k; o.i0 = r.i0; o.mode = r.mode; o.flags = r.flags;
+    o.alpha = make_double2(r.alpha.re, r.alpha.im);
+    o.beta = make_double2(r.beta.re, r.beta.im);
+    o.s0 = r.s0;
+    o.A = r.A; o.B = r.B; o.W = r.W; o.W2 = r.W2; o.W3 = r.W3;
+    o.C = r.C; o.D = r.D; o.E = r.E; o.F = r.F;
+    o.host = r.host;
+    o.bytes = (size_t)r.bytes;
+    return o;
+}
+
+// what a row must satisfy before ANY row is issued (the entry points themselves would only refuse inside a running fiber)
+bool replay_row_ok(dftk_mi_basis* b, const dftk_mi_batch_op& r) {
+    const bool sq = r.m >= 1 && r.C && r.ldc >= r.m;                       // an m x m matrix in C
+    const bool cols = r.n >= 1 && r.m >= 1;                                // n rows, m columns
+    switch (r.type) {
+        case BOP_ZGEMM: {
+            if (r.trans != 'N' && r.trans != 'C') return false;
+            if (r.gm < 1 || r.gn < 1 || r.gk < 1 || r.gm > INT32_MAX || r.gn > INT32_MAX || r.gk > INT32_MAX) return false;
+            if (r.flags & ~(3 | DFTK_MI_GEMM_REAL)) return false;
+            return r.A && r.B && r.C && r.lda >= (r.trans == 'C' ? r.gk : r.gm) && r.ldb >= r.gk && r.ldc >= r.gm;
+        }
+        case BOP_COLRED:
+            if (!cols || r.mode < 0 || r.mode > 4 || !r.A || r.lda < r.n || !r.C) return false;
+            if ((r.mode == 1 || r.mode == 4) && (!r.B || r.ldb < r.n)) return false;
+            return r.mode != 2 || r.W != nullptr;
+        case BOP_RESIDUAL:
+            return cols && r.A && r.lda >= r.n && r.B && r.ldb >= r.n && r.W && r.C && r.ldc >= r.n && r.D && (!r.W2 || r.E);
+        case BOP_TPA: return cols && r.A && r.lda >= r.n && r.C && r.ldc >= r.n && r.D;
+        case BOP_SCALE: return cols && r.C && r.ldc >= r.n && r.W;
+        case BOP_COPY: return cols && r.A && r.lda >= r.n && r.C && r.ldc >= r.n;
+        case BOP_GATHER: return cols && r.A && r.lda >= r.n && r.C && r.ldc >= r.n && r.W;
+        case BOP_FILL0: return r.C && r.bytes >= 1;
+        case BOP_SUBID: return cols && r.n <= INT32_MAX && r.C && r.ldc >= r.n && r.i0 >= 0;
+        case BOP_ADDDIAG:
+        case BOP_HERMIT: return sq;
+        case BOP_CTRANS: return sq && r.A && r.lda >= r.m;
+        case BOP_H2D: return r.C && r.host && r.bytes >= 1;
+        case BOP_D2H: return r.A && r.host && r.bytes >= 1 && (r.flags & ~1) == 0;
+        case BOP_POTRF: return sq && r.D && r.ldb >= r.m && r.host;
+        case BOP_HEEV: return sq && r.D && r.ldb >= r.m && r.host;
+        case BOP_APPLYD: return r.kb && r.kb->basis == b && r.kb->n_p >= 1 && r.m >= 1 && r.A && r.C;
+        case BOP_ORTHO:
+            return r.n >= 1 && r.m >= 1 && r.m <= 8 && r.k >= 0 && r.k <= 16 && r.C && r.ldc >= r.n &&
+                   (r.k == 0 || (r.A && r.lda >= r.n)) && r.host;
+        default: return false;
+    }
+}
+
+// one row, issued by the running fiber
+int replay_issue(dftk_mi_basis* b, dftk_mi_batch_op& r) {
+    BOp o = replay_bop(b, r);
+    switch (r.type) {
+        case BOP_H2D: return dev_h2d(b, r.C, r.host, (size_t)r.bytes);
+        case BOP_D2H:
+            return (r.flags & 1) ? dev_d2h_sync(b, r.host, r.A, (size_t)r.bytes) : dev_d2h_async(b, r.host, r.A, (size_t)r.bytes);
+        case BOP_POTRF: {
+            double* out = reinterpret_cast<double*>(r.host);
+            const int st = dense_potrf_trtri(b, r.m, (cd*)r.C, r.ldc, (cd*)r.D, r.ldb, out, out + 1);
+            r.status = st > 0 ? st : 0;
+            return st < 0 ? st : 0;
+        }
+        case BOP_HEEV: {
+            if (r.E) {   // the small-block driver's form: the status arrives with the fiber's next synchronisation
+                o.status_out = &r.status;
+                return batch_record(std::move(o));
+            }
+            const int st = dense_heev(b, r.m, (cd*)r.C, r.ldc, (double*)r.host, (cd*)r.D, r.ldb);
+            r.status = st > 0 ? st : 0;
+            return st < 0 ? st : 0;
+        }
+        case BOP_RESIDUAL:
+            if (r.W3) return batch_record(std::move(o));
+            return exec_one(o);
+        case BOP_FILL0:   // ew_fill_zero counts complex numbers: other sizes are recorded as they are
+            if (r.bytes % sizeof(cd)) return batch_record(std::move(o));
+            return ew_fill_zero(b, (cd*)r.C, (size_t)r.bytes / sizeof(cd));
+        case BOP_APPLYD:
+        case BOP_ORTHO: return batch_record(std::move(o));
+        default: return exec_one(o);   // recording is on: the entry point records the row
+    }
+}
+}  // namespace
+
+extern "C" int dftk_mi_batch_replay(dftk_mi_basis* b, int n_fibers, int n_ops, dftk_mi_batch_op* ops) {
+    if (!b || n_fibers < 1 || n_ops < 1 || !ops) return DFTK_MI_EINVAL;
+    std::vector<std::vector<int>> rows((size_t)n_fibers);
+    for (int i = 0; i < n_ops; ++i) {
+        const dftk_mi_batch_op& r = ops[i];
+        if (r.fiber < 0 || r.fiber >= n_fibers || !replay_row_ok(b, r)) {
+            dftk_set_error("batch_replay: row %d is malformed (type %d, fiber %d)", i, r.type, r.fiber);
+            return DFTK_MI_EINVAL;
+        }
+        rows[(size_t)r.fiber].push_back(i);
+    }
+    for (auto& q : rows)
+        for (size_t j = 0; j < q.size(); ++j) {
+            const dftk_mi_batch_op& r = ops[q[j]];
+            if (!r.join_next) continue;
+            // a joined row must leave the fiber running (no waiting entry point) and have a partner of its own type
+            const bool waits = r.type == BOP_POTRF || (r.type == BOP_HEEV && !r.E) || (r.type == BOP_D2H && (r.flags & 1));
+            if (waits || r.sync_after || j + 1 == q.size() || ops[q[j + 1]].type != r.type) {
+                dftk_set_error("batch_replay: row %d cannot be joined with the fiber's next row", q[j]);
+                return DFTK_MI_EINVAL;
+            }
+        }
+    HIPCHK(hipSetDevice(b->device));
+    for (int i = 0; i < n_ops; ++i) ops[i].status = 0;
+    std::vector<std::function<int()>> bodies;
+    for (int f = 0; f < n_fibers; ++f)
+        bodies.push_back([&rows, ops, b, f]() -> int {
+            for (int i : rows[(size_t)f]) {
+                CHK(replay_issue(b, ops[i]));
+                if (ops[i].join_next) batch_join_next();
+                if (ops[i].sync_after) CHK(dev_stream_sync(b));
+            }
+            CHK(dev_stream_sync(b));
+            for (int i : rows[(size_t)f])
+                if (ops[i].type == BOP_ORTHO) ops[i].status = (int)reinterpret_cast<const double*>(ops[i].host)[0];
+            return 0;
+        });
+    std::vector<int> rets;
+    const int st = batch_run(b, bodies, rets);
+    if (st != 0) return st;
+    for (int r : rets)
+        if (r != 0) return r;
     return 0;
 }
 

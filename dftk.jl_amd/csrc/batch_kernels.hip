@@ -524,7 +524,23 @@ __global__ __launch_bounds__(256) void k_b_heev(const DenseItem* __restrict__ it
     __syncthreads();
     const double fro2 = s_red[0];
     const bool finite_in = isfinite(fro2);
-    const double fro = sqrt(fro2);
+    // A matrix whose norm is far from 1 is brought to norm ~ 1 by an exact power of two and the eigenvalues are scaled back
+    // on the way out: at |A| ~ 1e-150 every |S_pq|^2 falls under the absolute rotation threshold below (no pair would ever
+    // rotate), at 1e+150 the products S_pp S_qq overflow.  (The branch is uniform: fro comes from shared memory.)
+    double fro = sqrt(fro2), sc = 1.0;
+    if (finite_in && fro > 0.0 && (fro < 1e-100 || fro > 1e100)) {
+        sc = exp2(-(double)ilogb(fro));
+        for (int t = tid; t < np * np; t += nthr) {
+            const int j = t / np, i = t - j * np;
+            cd v = S[i * pitch + j];
+            v.x *= sc;
+            v.y *= sc;
+            S[i * pitch + j] = v;
+        }
+        fro *= sc;
+        __syncthreads();
+    }
+    const double inv_sc = 1.0 / sc;
     if (np > n && tid == 0) S[n * pitch + n] = make_double2(2.0 * fro + 1.0, 0.0);
     __syncthreads();
     const double tol = 1e-14;
@@ -617,8 +633,8 @@ __global__ __launch_bounds__(256) void k_b_heev(const DenseItem* __restrict__ it
             if (dj < di || (dj == di && j < tid)) rank += 1;
         }
         if (rank < n) {
-            res[rank] = di;
-            if (it.ev) it.ev[rank] = di;
+            res[rank] = di * inv_sc;
+            if (it.ev) it.ev[rank] = di * inv_sc;
             for (int i = 0; i < n; ++i) it.B[i + (int64_t)rank * it.ldb] = V[i * pitch + tid];
         }
     }

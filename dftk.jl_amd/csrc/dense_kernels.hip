@@ -1311,15 +1311,18 @@ __global__ void k_set_identity(int n, ET* __restrict__ V, int64_t ldv) {
 
 // copy A (n x n) into the padded work matrix W (np x np), padding diagonal with `big` values
 template <typename ET>
-__global__ void k_pad_matrix(int n, int np, const cd* __restrict__ A, int64_t lda, ET* __restrict__ W, double big) {
+__global__ void k_pad_matrix(int n, int np, const cd* __restrict__ A, int64_t lda, ET* __restrict__ W, double big, double sc) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)np * np) return;
     const int j = (int)(idx / np), i = (int)(idx - (int64_t)j * np);
     cd v = make_double2(0.0, 0.0);
-    if (i < n && j < n)
+    if (i < n && j < n) {
         v = A[i + (int64_t)j * lda];
-    else if (i == j)
+        v.x *= sc;      // (sc = 1 unless the norm of A is far from 1: heev_impl)
+        v.y *= sc;
+    } else if (i == j) {
         v = make_double2(big * (1.0 + 1e-3 * (i - n)), 0.0);
+    }
     jac_st(W[idx], v.x, v.y);
 }
 
@@ -1534,6 +1537,18 @@ template <bool REAL>
 static int heev_impl(dftk_mi_basis* b, int n, cd* A, int64_t lda, double* W_h, cd* V, int64_t ldv, double off2,
                      double dg2) {
     typedef typename JacEl<REAL>::T ET;
+    // A matrix whose norm is far from 1 enters the work matrix scaled to norm ~ 1 by an exact power of two, and the
+    // eigenvalues are scaled back: at |A| ~ 1e-150 every |W_pq|^2 falls under the absolute rotation threshold of
+    // k_jacobi_round (no pair would ever rotate), at 1e+150 the products W_pp W_qq overflow.
+    double sc = 1.0;
+    {
+        const double f = sqrt(off2 + dg2);
+        if (std::isfinite(f) && f > 0.0 && (f < 1e-100 || f > 1e100)) {
+            sc = std::exp2(-(double)std::ilogb(f));
+            off2 = (off2 * sc) * sc;
+            dg2 = (dg2 * sc) * sc;
+        }
+    }
     int nb = (n + JB - 1) / JB;
     if (nb % 2) nb += 1;
     if (nb < 2) nb = 2;
@@ -1560,7 +1575,7 @@ static int heev_impl(dftk_mi_basis* b, int n, cd* A, int64_t lda, double* W_h, c
     const double fro = sqrt(off2 + dg2);
     const double big = 2.0 * fro + 1.0;
     hipLaunchKernelGGL(k_pad_matrix<ET>, dim3((unsigned)(((size_t)np * np + 255) / 256)), dim3(256), 0, b->stream, n, np,
-                       A, lda, W, big);
+                       A, lda, W, big, sc);
     hipLaunchKernelGGL(k_set_identity<ET>, dim3((unsigned)(((size_t)np * np + 255) / 256)), dim3(256), 0, b->stream, np,
                        Vw, (int64_t)np);
     // off-diagonal Frobenius norm relative to ||A||_F; the round-off floor of the blocked sweeps
@@ -1704,7 +1719,7 @@ static int heev_impl(dftk_mi_basis* b, int n, cd* A, int64_t lda, double* W_h, c
     std::vector<int> perm(np);
     std::iota(perm.begin(), perm.end(), 0);
     std::stable_sort(perm.begin(), perm.end(), [&](int a, int c) { return diag[a] < diag[c]; });
-    for (int i = 0; i < n; ++i) W_h[i] = diag[perm[i]];
+    for (int i = 0; i < n; ++i) W_h[i] = diag[perm[i]] * (1.0 / sc);
     HIPCHK(hipMemcpyAsync(d_perm, perm.data(), n * sizeof(int), hipMemcpyHostToDevice, b->stream));
     if constexpr (REAL)
         hipLaunchKernelGGL(k_gather_cols_real, dim3((n + 255) / 256, n), dim3(256), 0, b->stream, (int64_t)n, Vw,

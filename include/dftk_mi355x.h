@@ -390,6 +390,51 @@ int dftk_mi_lobpcg_small_stats(int64_t* calls, int64_t* restarts);
  * Cholesky factorisations of the last ortho!(X), growth factor}. */
 int dftk_mi_ortho_small(dftk_mi_basis* basis, int64_t n, int m, dftk_mi_cplx* X_d, int64_t ldx, int ny, const dftk_mi_cplx* Y_d,
                         int64_t ldy, const double* norms_d, double tol, double* res4_h);
+/* The general form of dftk_mi_ortho_small (tests): a TABLE of device operations issued by n_fibers fibers of one batched
+ * call, exactly as the k-blocks of dftk_mi_lobpcg_multi issue theirs.  Fiber f issues the rows with fiber == f in table
+ * order through the internal entry points the LOBPCG drivers call (which record inside a fiber), and ends with a
+ * synchronisation; the recorded queues are merged position by position into the batched kernels.  Field use per type
+ * (device pointers unless named host; every leading dimension >= the rows it strides over):
+ *   ZGEMM    trans ('N' | 'C'), gm, gn, gk, alpha, A, lda, B, ldb, beta, C, ldc, flags (DFTK_MI_GEMM_*)
+ *   COLRED   mode 0 column norms | 1 Re <A, B> | 2 sum_i W[i] |A[i]|^2 | 3 sum |A|^2 | 4 Im <A, B>; n rows, m columns, A, lda,
+ *            (B, ldb,) (W,) C = m doubles out
+ *   RESIDUAL n, m, A = AX, lda, B = X, ldb, W = lambda (m doubles), C = R, ldc, D = norms out, W2 = kin (n doubles) or NULL,
+ *            E = sum kin |x|^2 out (with W2), F = <x, x> out or NULL; W3 != NULL: lambda[c] = W[c] / W3[c] (recorded directly:
+ *            the small-block driver's form, which has no one-by-one twin)
+ *   TPA      n, m, A = src, lda, C = dst, ldc, W = kin or NULL (plain copy), W2 = mean_kin or NULL (1 / (kin + s0)), D = norms out
+ *   SCALE    n, m, C, ldc, W = m factors, flags = 1: divide        COPY  n, m, A, lda, C, ldc        GATHER  the same + W = m ints
+ *   FILL0    C, bytes (not a multiple of 16: recorded directly)        SUBID  n rows, m columns, C, ldc, i0: C[i0 + a, a] -= 1 while i0 + a < n
+ *   ADDDIAG  m, C, ldc, s0        HERMIT  m, C, ldc        CTRANS  m, A, lda, C, ldc (C = A^H)
+ *   H2D      C = destination, host = source, bytes        D2H  A = source, host = destination, bytes; flags = 1: the fiber waits
+ *   POTRF    m, C = A in / R out, ldc, D = inv(R), ldb, host = double[2] normests; status = 0 | DFTK_MI_NUM_CHOLESKY
+ *   HEEV     m, C = A (destroyed), ldc, D = V, ldb, host = m eigenvalues; status = 0 | DFTK_MI_NUM_*; E != NULL: a device copy
+ *            of the eigenvalues as well (recorded directly, no one-by-one twin)
+ *   APPLYD   kb, m bands, A = X (n_p x m), C = Y = D X (recorded directly: internal to the batched apply_H)
+ *   ORTHO    n, m <= 8, k = ny <= 16, C = X, ldc, A = Y, lda, W = norms or NULL, s0 = tol, host = double[4] as res4_h of
+ *            dftk_mi_ortho_small; status = (int)host[0] (recorded directly, batched form only)
+ * join_next: the fiber's next row (same type, independent of this one) shares this row's launch.  sync_after: the fiber
+ * synchronises after this row, so later rows sit at earlier queue positions of a later round.  A malformed table returns
+ * DFTK_MI_EINVAL before anything is launched.  dftk_mi_batch_stats describes the call afterwards. */
+enum {
+    DFTK_MI_BOP_ZGEMM = 0, DFTK_MI_BOP_COLRED = 1, DFTK_MI_BOP_RESIDUAL = 2, DFTK_MI_BOP_TPA = 3, DFTK_MI_BOP_SCALE = 4,
+    DFTK_MI_BOP_COPY = 5, DFTK_MI_BOP_FILL0 = 6, DFTK_MI_BOP_SUBID = 7, DFTK_MI_BOP_GATHER = 8, DFTK_MI_BOP_ADDDIAG = 9,
+    DFTK_MI_BOP_HERMIT = 10, DFTK_MI_BOP_CTRANS = 11, DFTK_MI_BOP_H2D = 12, DFTK_MI_BOP_D2H = 13, DFTK_MI_BOP_POTRF = 14,
+    DFTK_MI_BOP_HEEV = 15, DFTK_MI_BOP_APPLYD = 18, DFTK_MI_BOP_ORTHO = 19
+};
+typedef struct dftk_mi_batch_op {
+    int32_t type, fiber, trans, m, k, i0, mode, flags, join_next, sync_after;
+    int32_t status;                  /* out */
+    int32_t reserved;
+    int64_t n, gm, gn, gk, lda, ldb, ldc;
+    dftk_mi_cplx alpha, beta;
+    double s0;
+    const void *A, *B, *W, *W2, *W3;
+    void *C, *D, *E, *F;
+    dftk_mi_kblock* kb;
+    void* host;
+    uint64_t bytes;
+} dftk_mi_batch_op;
+int dftk_mi_batch_replay(dftk_mi_basis* basis, int n_fibers, int n_ops, dftk_mi_batch_op* ops);
 int dftk_mi_lobpcg_history(dftk_mi_kblock* kb, int* M, int* n_iter, double* hist_h, size_t cap, int* n_svd);
 /* One-shot promise for the NEXT dftk_mi_lobpcg call on this block: its X0 IS the X the last call returned (an SCF step
  * hands the orbitals of the previous step back; same number of bands).  The driver then starts from

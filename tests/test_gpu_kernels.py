@@ -124,6 +124,45 @@ def test_zgemm(lib, trans, m, n, k):
     assert relerr(Cn.cpu().numpy().T, opA @ B) < 1e-13
 
 
+def padded(a, pad=5):
+    """A (rows x cols) as a column-major device buffer with ld = rows + pad and one column more, NaN wherever a is not."""
+    h = np.full((a.shape[1] + 1, a.shape[0] + pad), complex(np.nan, np.nan))
+    h[:a.shape[1], :a.shape[0]] = a.T
+    return h, torch.from_numpy(h.copy()).cuda()
+
+
+def padding_untouched(h, t, rows, cols):
+    """Everything outside the rows x cols window of the buffer is bitwise what it was."""
+    keep = np.ones(h.shape, dtype=bool)
+    keep[:cols, :rows] = False
+    after = np.ascontiguousarray(t.cpu().numpy()).view(np.uint64).reshape(h.shape + (2,))
+    return np.array_equal(after[keep], h.view(np.uint64).reshape(h.shape + (2,))[keep])
+
+
+@pytest.mark.parametrize("trans,m,n,k,flags", [("C", 37, 50, 1000, 0), ("N", 1000, 37, 50, 0), ("C", 259, 259, 3000, 1),
+                                               ("N", 700, 64, 64, 2)])
+def test_zgemm_padded_ld(lib, trans, m, n, k, flags):
+    """The drivers call zgemm on sub-blocks of wider buffers: lda, ldb, ldc larger than the rows, NaN in every padding
+    row and in a column beyond the last one.  The padding is neither read (the result is finite) nor written."""
+    rng = np.random.default_rng(m + n + k)
+    bs = Basis(lib, 8, 8, 8)
+    A = rng.standard_normal((m, k) if trans == "N" else (k, m)) + 1j * rng.standard_normal((m, k) if trans == "N" else (k, m))
+    B = rng.standard_normal((k, n)) + 1j * rng.standard_normal((k, n))
+    if flags & 2:
+        B = np.triu(B)
+    C0 = rng.standard_normal((m, n)) + 1j * rng.standard_normal((m, n))
+    alpha, beta = 0.7 - 0.2j, -0.3 + 0.5j
+    (Ah, Ad), (Bh, Bd), (Ch, Cd) = padded(A), padded(B), padded(C0)
+    check(lib.dftk_mi_zgemm_ex(bs.h, trans.encode(), m, n, k, cplx(alpha), Ad.data_ptr(), Ah.shape[1], Bd.data_ptr(), Bh.shape[1],
+                               cplx(beta), Cd.data_ptr(), Ch.shape[1], flags))
+    bs.sync()
+    got = Cd.cpu().numpy()[:n, :m].T
+    ref = alpha * ((A if trans == "N" else A.conj().T) @ B) + beta * C0
+    sel = np.triu_indices(m, 0, n) if flags & 1 else np.nonzero(np.ones((m, n)))
+    assert relerr(got[sel], ref[sel]) < 1e-13
+    assert padding_untouched(Ch, Cd, m, n) and padding_untouched(Ah, Ad, *A.shape) and padding_untouched(Bh, Bd, k, n)
+
+
 @pytest.mark.parametrize("m,k", [(259, 3000), (777, 2500), (141, 4100), (64, 300), (5, 2100), (1006, 9000), (1300, 300)])
 def test_zgemm_upper_only(lib, m, k):
     """DFTK_MI_GEMM_UPPER: tiles that intersect the upper triangle hold A^H B, the others are untouched;
@@ -222,8 +261,8 @@ def test_zgemm_asymmetric_layout(lib):
 def test_potrf_trtri(lib, n):
     """32 < n <= 512 takes the cooperative one-launch factorisation (16-column blocks, dataflow over flags: exact block
     multiples, one column over, one short, the 503 of the headline cell, the last size before the blocked path); the
-    other sizes the three-launches-per-panel path.  ``lda`` > n and NaNs in the strict lower triangle check that only
-    the upper triangle is read and written."""
+    other sizes the three-launches-per-panel path.  NaNs in the strict lower triangle (n = 100, 503) check that only the
+    upper triangle is read and written; ``lda`` > n with poisoned padding is test_potrf_trtri_padded_ld."""
     rng = np.random.default_rng(n)
     bs = Basis(lib, 8, 8, 8)
     X = rng.standard_normal((3 * n + 5, n)) + (1j if n % 2 else 0) * rng.standard_normal((3 * n + 5, n))
@@ -250,6 +289,27 @@ def test_potrf_trtri(lib, n):
     Bd = dev(Bad.T.copy())
     st = lib.dftk_mi_potrf_trtri(bs.h, n, Bd.data_ptr(), n, Id.data_ptr(), n)
     assert st == 2
+
+
+@pytest.mark.parametrize("n", [24, 259])
+def test_potrf_trtri_padded_ld(lib, n):
+    """``lda``, ``ldi`` > n as in the drivers (Gram matrices are sub-blocks of wider buffers), NaN in the padding rows, in
+    a column beyond the last and in the strict lower triangle of A: none of it is read or written."""
+    rng = np.random.default_rng(n)
+    bs = Basis(lib, 8, 8, 8)
+    X = rng.standard_normal((3 * n + 5, n)) + 1j * rng.standard_normal((3 * n + 5, n))
+    O = X.conj().T @ X
+    Oh, Od = padded(np.triu(O) + np.tril(np.full((n, n), np.nan), -1))
+    Ih, Id = padded(np.full((n, n), complex(np.nan, np.nan)))
+    check(lib.dftk_mi_potrf_trtri(bs.h, n, Od.data_ptr(), Oh.shape[1], Id.data_ptr(), Ih.shape[1]))
+    bs.sync()
+    got, invR = Od.cpu().numpy()[:n, :n].T, Id.cpu().numpy()[:n, :n].T
+    R = np.triu(got)
+    assert relerr(R.conj().T @ R, O) < 1e-13
+    assert np.linalg.norm(invR @ R - np.eye(n)) < 1e-10 * np.linalg.cond(R)
+    assert np.allclose(np.tril(invR, -1), 0)
+    assert np.all(np.isnan(got[np.tril_indices(n, -1)]))
+    assert padding_untouched(Oh, Od, n, n) and padding_untouched(Ih, Id, n, n)
 
 
 @pytest.mark.parametrize("n", [5, 33, 48, 100, 259, 503, 512, 600])
@@ -303,6 +363,27 @@ def test_heev(lib, n):
     assert np.abs(W - wref).max() < 1e-12 * scale
     assert np.linalg.norm(V.conj().T @ V - np.eye(n)) < max(1e-12, 5e-14 * n)
     assert np.linalg.norm(A @ V - V * W[None, :]) < 1e-11 * scale * np.sqrt(n)
+
+
+@pytest.mark.parametrize("n", [24, 300])
+def test_heev_padded_ld(lib, n):
+    """``lda``, ``ldv`` > n as in the drivers (the Rayleigh-Ritz matrix is a sub-block of a wider buffer), NaN in the
+    padding rows and in a column beyond the last: test_heev's assertions, and the padding is bitwise what it was."""
+    rng = np.random.default_rng(n)
+    bs = Basis(lib, 8, 8, 8)
+    X = rng.standard_normal((n, n)) + 1j * rng.standard_normal((n, n))
+    A = (X + X.conj().T) / 2
+    (Ah, Ad), (Vh, Vd) = padded(A), padded(np.full((n, n), complex(np.nan, np.nan)))
+    W = np.zeros(n)
+    check(lib.dftk_mi_heev(bs.h, n, Ad.data_ptr(), Ah.shape[1], W.ctypes.data, Vd.data_ptr(), Vh.shape[1]))
+    bs.sync()
+    V = Vd.cpu().numpy()[:n, :n].T
+    wref = np.linalg.eigvalsh(A)
+    scale = max(np.abs(wref).max(), 1.0)
+    assert np.abs(W - wref).max() < 1e-12 * scale
+    assert np.linalg.norm(V.conj().T @ V - np.eye(n)) < max(1e-12, 5e-14 * n)
+    assert np.linalg.norm(A @ V - V * W[None, :]) < 1e-11 * scale * np.sqrt(n)
+    assert padding_untouched(Ah, Ad, n, n) and padding_untouched(Vh, Vd, n, n)
 
 
 # ----------------------------------------------------------------------------------- FFT pipeline
