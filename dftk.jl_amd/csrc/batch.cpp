@@ -154,13 +154,8 @@ int exec_one(BOp& o) {
             return zgemm(o.b, o.trans, o.gm, o.gn, o.gk, o.alpha, (const cd*)o.A, o.lda, (const cd*)o.B, o.ldb, o.beta, Cc,
                          o.ldc, o.flags);
         case BOP_COLRED:
-            switch (o.mode) {
-                case 0: return ew_colnorms(o.b, o.n, o.m, (const cd*)o.A, o.lda, (double*)o.C);
-                case 1: return ew_coldots(o.b, o.n, o.m, (const cd*)o.A, o.lda, (const cd*)o.B, o.ldb, (double*)o.C);
-                case 2: return ew_weighted_colsums(o.b, o.n, o.m, (const cd*)o.A, o.lda, (const double*)o.W, (double*)o.C);
-                case 3: return ew_frob2(o.b, o.n, o.m, (const cd*)o.A, o.lda, (double*)o.C);
-                default: return ew_coldots_im(o.b, o.n, o.m, (const cd*)o.A, o.lda, (const cd*)o.B, o.ldb, (double*)o.C);
-            }
+            return ew_colreduce(o.b, o.mode, o.n, o.m, (const cd*)o.A, o.lda, (const cd*)o.B, o.ldb, (const double*)o.W,
+                                (double*)o.C);
         case BOP_RESIDUAL:
             return ew_residual(o.b, o.n, o.m, (const cd*)o.A, o.lda, (const cd*)o.B, o.ldb, (const double*)o.W, Cc, o.ldc,
                                (double*)o.D, (const double*)o.W2, (double*)o.E, (double*)o.F);

@@ -3,7 +3,7 @@
 // of per-item arguments (staged through the round's pinned ring) and a grid whose z dimension is the item index; x / y
 // are sized for the largest item, smaller items let their surplus workgroups exit at once.
 //
-//   element-wise / column kernels   the arithmetic of dense_kernels.hip's k_col_reduce, k_residual, k_tpa, ... per item
+//   element-wise / column kernels   the device bodies of ew_device.h (shared with dense_kernels.hip), one item per z
 //   small products                  C = alpha A^H B + beta C  (m, n <= 96; the long dimension is reduced inside ONE
 //                                   workgroup per 16 x 16 tile: deterministic) and C = alpha A B + beta C (inner
 //                                   dimension <= 128), honouring zgemm()'s UPPER / B_UPPER flags
@@ -14,29 +14,12 @@
 // These are latency problems (n_G ~ 1e3, 6-8 bands, matrices of order <= 3 M): no roofline applies; what counts is
 // launches and host synchronisations per LOBPCG iteration.
 #include "batch.h"
+#include "ew_device.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 namespace dftk_batch {   // (a NAMED namespace: kernels of an anonymous one show up without names in rocprofv3 traces)
-
-__device__ __forceinline__ double b_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-// block-wide sum for 256 threads; result valid in thread 0
-__device__ __forceinline__ double b_block_sum(double v, double* sh) {
-    v = b_wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-    __syncthreads();
-    return r;
-}
 
 struct EwItem {
     int64_t n, lda, ldb, ldc;
@@ -47,117 +30,59 @@ struct EwItem {
     size_t bytes;
 };
 
-// ---- column reductions / residual / TPA: one workgroup per (column, item), same trees as the per-block kernels ----
+// ---- column reductions / residual / TPA: one workgroup per (column, item); the bodies of ew_device.h with NT = 256 ----
 __global__ __launch_bounds__(256) void k_b_colred(const EwItem* __restrict__ items) {
     const EwItem it = items[blockIdx.z];
     const int c = blockIdx.x;
     if (c >= it.m) return;
-    __shared__ double sh[4];
-    const cd* x = reinterpret_cast<const cd*>(it.A) + (int64_t)c * it.lda;
-    const cd* y = it.B ? reinterpret_cast<const cd*>(it.B) + (int64_t)c * it.ldb : nullptr;
-    const double* w = reinterpret_cast<const double*>(it.W);
-    double acc = 0.0;
-    for (int64_t i = threadIdx.x; i < it.n; i += 256) {
-        const cd a = x[i];
-        if (it.mode == 1) {
-            const cd bb = y[i];
-            acc += a.x * bb.x + a.y * bb.y;
-        } else if (it.mode == 4) {
-            const cd bb = y[i];
-            acc += a.x * bb.y - a.y * bb.x;
-        } else if (it.mode == 2) {
-            acc += w[i] * (a.x * a.x + a.y * a.y);
-        } else {
-            acc += a.x * a.x + a.y * a.y;
-        }
-    }
-    const double r = b_block_sum(acc, sh);
-    if (threadIdx.x == 0) reinterpret_cast<double*>(it.C)[c] = (it.mode == 0) ? sqrt(r) : r;
+    ew_col_reduce<256>(it.mode, it.n, reinterpret_cast<const cd*>(it.A) + (int64_t)c * it.lda,
+                       it.B ? reinterpret_cast<const cd*>(it.B) + (int64_t)c * it.ldb : nullptr,
+                       reinterpret_cast<const double*>(it.W), reinterpret_cast<double*>(it.C) + c);
 }
 
 __global__ __launch_bounds__(256) void k_b_residual(const EwItem* __restrict__ items) {
     const EwItem it = items[blockIdx.z];
     const int c = blockIdx.x;
     if (c >= it.m) return;
-    __shared__ double sh[4];
-    const cd* AX = reinterpret_cast<const cd*>(it.A);
-    const cd* X = reinterpret_cast<const cd*>(it.B);
-    cd* R = reinterpret_cast<cd*>(it.C);
-    const double* kin = reinterpret_cast<const double*>(it.W2);
     // (W3: the Rayleigh quotients of the start block, lam = <x, Ax> / <x, x>, formed here instead of on the host)
     const double l = it.W3 ? reinterpret_cast<const double*>(it.W)[c] / reinterpret_cast<const double*>(it.W3)[c]
                            : reinterpret_cast<const double*>(it.W)[c];
-    double acc = 0.0, acck = 0.0, accx = 0.0;
-    for (int64_t i = threadIdx.x; i < it.n; i += 256) {
-        const cd a = AX[(int64_t)c * it.lda + i];
-        const cd x = X[(int64_t)c * it.ldb + i];
-        const cd r = make_double2(a.x - l * x.x, a.y - l * x.y);
-        R[(int64_t)c * it.ldc + i] = r;
-        acc += r.x * r.x + r.y * r.y;
-        const double x2 = x.x * x.x + x.y * x.y;
-        accx += x2;
-        if (kin) acck += kin[i] * x2;
-    }
-    const double s = b_block_sum(acc, sh);
-    const double sk = b_block_sum(acck, sh);
-    const double sx = b_block_sum(accx, sh);
-    if (threadIdx.x == 0) {
-        reinterpret_cast<double*>(it.D)[c] = sqrt(s);
-        if (kin) reinterpret_cast<double*>(it.E)[c] = sk;
-        if (it.F) reinterpret_cast<double*>(it.F)[c] = sx;
-    }
+    ew_residual_col<256>(it.n, reinterpret_cast<const cd*>(it.A) + (int64_t)c * it.lda,
+                         reinterpret_cast<const cd*>(it.B) + (int64_t)c * it.ldb, l,
+                         reinterpret_cast<cd*>(it.C) + (int64_t)c * it.ldc, reinterpret_cast<double*>(it.D) + c,
+                         reinterpret_cast<const double*>(it.W2), it.W2 ? reinterpret_cast<double*>(it.E) + c : nullptr,
+                         it.F ? reinterpret_cast<double*>(it.F) + c : nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_b_tpa(const EwItem* __restrict__ items) {
     const EwItem it = items[blockIdx.z];
     const int c = blockIdx.x;
     if (c >= it.m) return;
-    __shared__ double sh[4];
-    const cd* src = reinterpret_cast<const cd*>(it.A);
-    cd* dst = reinterpret_cast<cd*>(it.C);
-    const double* kin = reinterpret_cast<const double*>(it.W);
-    const double* mean_kin = reinterpret_cast<const double*>(it.W2);
-    const double mk = (kin && mean_kin) ? mean_kin[c] : 0.0;
-    double acc = 0.0;
-    for (int64_t i = threadIdx.x; i < it.n; i += 256) {
-        cd r = src[(int64_t)c * it.lda + i];
-        if (kin) {
-            const double f = mean_kin ? mk / (mk + kin[i]) : 1.0 / (kin[i] + it.s0);
-            r.x *= f;
-            r.y *= f;
-        }
-        dst[(int64_t)c * it.ldc + i] = r;
-        acc += r.x * r.x + r.y * r.y;
-    }
-    const double s = b_block_sum(acc, sh);
-    if (threadIdx.x == 0) reinterpret_cast<double*>(it.D)[c] = sqrt(s);
+    ew_tpa_col<256>(it.n, reinterpret_cast<const cd*>(it.A) + (int64_t)c * it.lda,
+                    reinterpret_cast<cd*>(it.C) + (int64_t)c * it.ldc, reinterpret_cast<const double*>(it.W),
+                    it.W2 ? reinterpret_cast<const double*>(it.W2) + c : nullptr, reinterpret_cast<double*>(it.D) + c, it.s0);
 }
 
-// ---- element-wise: grid (row blocks of the largest item, columns of the widest item, items) ----
-// kind 0: scale columns (s or 1/s), 1: copy, 2: gather columns through perm, 3: zero fill of `bytes`
+// ---- element-wise: grid (EW_ROWS-row blocks of the largest item, columns of the widest item, items) ----
+// kind 0: scale columns (s or 1/s), 1: copy, 2: gather columns through perm (ew_rows of ew_device.h);
+// 3: zero fill of `bytes` (grid x: 256-entry blocks, grid-stride)
 __global__ __launch_bounds__(256) void k_b_rows(const EwItem* __restrict__ items, int kind) {
     const EwItem it = items[blockIdx.z];
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c = blockIdx.y;
     if (kind == 3) {
         double* p = reinterpret_cast<double*>(it.C);
         const int64_t nd = (int64_t)(it.bytes / sizeof(double));
-        for (int64_t t = i; t < nd; t += (int64_t)gridDim.x * 256) p[t] = 0.0;
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < nd; t += (int64_t)gridDim.x * 256) p[t] = 0.0;
         return;
     }
-    if (c >= it.m || i >= it.n) return;
-    cd* C = reinterpret_cast<cd*>(it.C);
+    const int c = blockIdx.y;
+    if (c >= it.m || (int64_t)blockIdx.x * EW_ROWS >= it.n) return;
+    cd* y = reinterpret_cast<cd*>(it.C) + (int64_t)c * it.ldc;
     if (kind == 0) {
         const double s = reinterpret_cast<const double*>(it.W)[c];
-        const double f = it.flags ? 1.0 / s : s;
-        cd v = C[(int64_t)c * it.ldc + i];
-        v.x *= f;
-        v.y *= f;
-        C[(int64_t)c * it.ldc + i] = v;
+        ew_rows<true>(it.n, blockIdx.x, y, y, it.flags ? 1.0 / s : s);
     } else {
-        const cd* A = reinterpret_cast<const cd*>(it.A);
         const int sc = kind == 2 ? reinterpret_cast<const int*>(it.W)[c] : c;
-        C[(int64_t)c * it.ldc + i] = A[(int64_t)sc * it.lda + i];
+        ew_rows<false>(it.n, blockIdx.x, reinterpret_cast<const cd*>(it.A) + (int64_t)sc * it.lda, y, 1.0);
     }
 }
 
@@ -167,25 +92,14 @@ __global__ __launch_bounds__(256) void k_b_small(const EwItem* __restrict__ item
     const EwItem it = items[blockIdx.z];
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     cd* C = reinterpret_cast<cd*>(it.C);
-    if (kind == 0) {
-        if (idx < it.m && it.i0 + idx < it.n) C[(it.i0 + idx) + idx * it.ldc].x -= 1.0;
-    } else if (kind == 1) {
-        if (idx < it.m) C[idx + idx * it.ldc].x += it.s0;
-    } else {
-        const int n = it.m;
-        if (idx >= (int64_t)n * n) return;
-        const int j = (int)(idx / n), i = (int)(idx - (int64_t)j * n);
-        if (kind == 2) {
-            if (i == j) C[i + (int64_t)j * it.ldc].y = 0.0;
-            if (i < j) {
-                const cd v = C[i + (int64_t)j * it.ldc];
-                C[j + (int64_t)i * it.ldc] = make_double2(v.x, -v.y);
-            }
-        } else {
-            const cd v = reinterpret_cast<const cd*>(it.A)[j + (int64_t)i * it.lda];
-            C[i + (int64_t)j * it.ldc] = make_double2(v.x, -v.y);
-        }
-    }
+    if (kind == 0)
+        ew_sub_identity_at(idx, it.n, it.m, C, it.ldc, it.i0);
+    else if (kind == 1)
+        ew_add_diag_at(idx, it.m, C, it.ldc, it.s0);
+    else if (kind == 2)
+        ew_hermitize_at(idx, it.m, C, it.ldc);
+    else
+        ew_conj_transpose_at(idx, it.m, reinterpret_cast<const cd*>(it.A), it.lda, C, it.ldc);
 }
 
 // ---- host <-> device traffic of a round: many tiny copies as ONE copy + a scatter / gather kernel ----
@@ -357,6 +271,19 @@ struct DenseItem {
     double* ev;       // HEEV : optional DEVICE copy of the eigenvalues (read by later kernels of the same round)
 };
 extern __shared__ __attribute__((aligned(16))) char b_smem[];
+// k_b_potrf / k_b_heev run with 256 threads or, for n <= 32, ONE wave: their workgroup size is a launch argument, so the
+// number of wave partials is read from blockDim (block_sum<NT> of common.h needs it at compile time)
+__device__ __forceinline__ double b_block_sum(double v, double* sh) {   // result valid in thread 0
+    v = wave_sum(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) sh[w] = v;
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
+    __syncthreads();
+    return r;
+}
 
 __global__ __launch_bounds__(256) void k_b_potrf(const DenseItem* __restrict__ items, int pitch) {
     const DenseItem it = items[blockIdx.x];
@@ -644,7 +571,7 @@ __global__ __launch_bounds__(256) void k_b_heev(const DenseItem* __restrict__ it
     }
 }
 
-// Y = D X per item: banded real D (n_p x n_p, half bandwidth bw), X and Y n_p x nb complex (k_apply_D of dense_kernels.hip)
+// Y = D X per item: banded real D (n_p x n_p, half bandwidth bw), X and Y n_p x nb complex (ew_apply_D_at of ew_device.h)
 struct ApplyDItem {
     int n_p, nb, bw;
     const double* D;
@@ -653,18 +580,7 @@ struct ApplyDItem {
 };
 __global__ __launch_bounds__(256) void k_b_apply_D(const ApplyDItem* __restrict__ items) {
     const ApplyDItem it = items[blockIdx.y];
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (int64_t)it.n_p * it.nb) return;
-    const int c = (int)(idx / it.n_p), i = (int)(idx - (int64_t)c * it.n_p);
-    const int j0 = max(0, i - it.bw), j1 = min(it.n_p - 1, i + it.bw);
-    double sr = 0.0, si = 0.0;
-    for (int j = j0; j <= j1; ++j) {
-        const double d = it.D[i + (int64_t)j * it.n_p];
-        const cd x = it.X[j + (int64_t)c * it.n_p];
-        sr += d * x.x;
-        si += d * x.y;
-    }
-    it.Y[idx] = make_double2(sr, si);
+    ew_apply_D_at((int64_t)blockIdx.x * 256 + threadIdx.x, it.n_p, it.nb, it.bw, it.D, it.X, it.Y);
 }
 
 
@@ -727,7 +643,7 @@ __device__ __forceinline__ void o_block_sum8(const double (&v)[OR_M], double* s_
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int j = 0; j < OR_M; ++j) {
-        const double s = b_wave_sum(v[j]);
+        const double s = wave_sum(v[j]);
         if (lane == 0) s_red[w * OR_M + j] = s;
     }
     __syncthreads();
@@ -1525,7 +1441,7 @@ int batch_exec_group(BatchCtx* ctx, hipStream_t stream, int type, std::vector<BO
         }
         const EwItem* d = reinterpret_cast<const EwItem*>(batch_stage(ctx, items.data(), items.size() * sizeof(EwItem)));
         if (!d) return DFTK_MI_EHIP;
-        const unsigned rows = (unsigned)((maxn + 255) / 256);
+        const unsigned rows = (unsigned)((maxn + EW_ROWS - 1) / EW_ROWS);
         switch (type) {
             case BOP_COLRED: hipLaunchKernelGGL(k_b_colred, dim3(maxm, 1, n_items), dim3(256), 0, stream, d); break;
             case BOP_RESIDUAL: hipLaunchKernelGGL(k_b_residual, dim3(maxm, 1, n_items), dim3(256), 0, stream, d); break;

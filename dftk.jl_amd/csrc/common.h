@@ -83,6 +83,29 @@ __device__ inline void block_reduce(double* v) {
         for (int k = 0; k < K; ++k) v[k] = sh[k][0];
 }
 
+// sum over the 64 lanes of a wave (shuffle-down tree); result valid in lane 0
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+// sum over a workgroup of NT threads: wave_sum, then thread 0 adds the NT / 64 wave partials sh[0 .. NT / 64) in wave
+// order; result valid in thread 0.  Ends with a barrier: sh may be reused at once.
+template <int NT>
+__device__ __forceinline__ double block_sum(double v, double* sh) {
+    v = wave_sum(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) sh[w] = v;
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NT / 64; ++i) r += sh[i];
+    }
+    __syncthreads();
+    return r;
+}
+
 // ------------------------------------------------------------------------------------ 1-D plans
 #define DFTK_MAX_RADICES 32
 struct FftAxis {            // passed to kernels by value
@@ -330,6 +353,9 @@ struct ProfMute {    // RAII: nothing inside is booked (the enclosing scope book
 int jacobi_schedule_host(int n, int round, int* nb_out, int* pairs, int* where);
 int apply_D(dftk_mi_kblock* kb, int n_bands, const cd* X /*n_p x nb*/, cd* Y);
 // elementwise / reductions used by LOBPCG (all on b->stream)
+// out[c] of column c, by mode: 0 ||X||, 1 Re <X, Y>, 2 sum w |X|^2, 3 ||X||^2, 4 Im <X, Y>; the five names below are its modes
+int ew_colreduce(dftk_mi_basis* b, int mode, int64_t n, int m, const cd* X, int64_t ldx, const cd* Y, int64_t ldy,
+                 const double* w, double* out_d);
 int ew_colnorms(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, double* out_d);
 int ew_coldots(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, const cd* Y, int64_t ldy,
                double* out_re_d);

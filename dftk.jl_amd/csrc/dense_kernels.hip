@@ -9,6 +9,7 @@
 //   D * (P' psi)                              src/terms/operators.jl:127               (K8)
 #include "common.h"
 #include "batch.h"
+#include "ew_device.h"
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -17,173 +18,33 @@
 #include <cstring>
 #include <vector>
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// block-wide sum for 256 threads; result valid in thread 0
-__device__ __forceinline__ double block_sum256(double v, double* sh) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-    }
-    __syncthreads();
-    return r;
-}
-
-// ---------------------------------------------------------------------------- column reductions
-// The n_G-sized streaming kernels of one LOBPCG iteration.  They are HBM-bound, and what bounds them is the number of
-// bytes in flight: one 16-byte load per thread and 2 x 256 threads per CU (the round 1-3 form) keeps 8 KB per CU in the
-// air and reaches 1.2-1.5 TB/s (tools/ew_bench.py).  Here every thread issues EW_UNR independent loads per operand before
-// it touches any of them, and a long column gets a workgroup of 1024 threads: 64 KB per operand and workgroup in flight.
-// One workgroup per column; deterministic (fixed strides, fixed tree; the tree depends on the workgroup size, which is a
-// function of n alone).
-#define EW_UNR 4
-#define EW_LONG 8192      // rows from which a column gets 1024 threads
-template <int NT>
-__device__ __forceinline__ double block_sum(double v, double* sh) {   // sh[NT / 64]; result valid in thread 0
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < NT / 64; ++i) r += sh[i];
-    }
-    __syncthreads();
-    return r;
-}
-// mode 0: out[c] = sqrt(sum |X|^2) ; 1: out[c] = Re sum conj(X) Y ; 2: out[c] = sum w |X|^2 ; 3: sum |X|^2 ; 4: Im sum conj(X) Y
+// ---------------------------------------------------------------------------- column kernels (bodies: ew_device.h)
+// one workgroup of NT threads per column (blockIdx.x)
 template <int NT>
 __global__ __launch_bounds__(NT) void k_col_reduce(int mode, int64_t n, const cd* __restrict__ X, int64_t ldx,
                                                    const cd* __restrict__ Y, int64_t ldy,
                                                    const double* __restrict__ w, double* __restrict__ out) {
-    __shared__ double sh[NT / 64];
     const int c = blockIdx.x;
-    const cd* x = X + (int64_t)c * ldx;
-    const cd* y = Y ? Y + (int64_t)c * ldy : nullptr;
-    const bool two = mode == 1 || mode == 4;
-    double acc = 0.0;
-    for (int64_t i0 = threadIdx.x; i0 < n; i0 += (int64_t)NT * EW_UNR) {
-        cd a[EW_UNR], bb[EW_UNR];
-        double ww[EW_UNR];
-#pragma unroll
-        for (int u = 0; u < EW_UNR; ++u) {
-            const int64_t i = i0 + (int64_t)u * NT;
-            const bool in = i < n;
-            a[u] = in ? x[i] : make_double2(0.0, 0.0);
-            bb[u] = (in && two) ? y[i] : make_double2(0.0, 0.0);
-            ww[u] = (in && mode == 2) ? w[i] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < EW_UNR; ++u) {
-            if (mode == 1)
-                acc += a[u].x * bb[u].x + a[u].y * bb[u].y;
-            else if (mode == 4)      // Im conj(a) b
-                acc += a[u].x * bb[u].y - a[u].y * bb[u].x;
-            else if (mode == 2)
-                acc += ww[u] * (a[u].x * a[u].x + a[u].y * a[u].y);
-            else
-                acc += a[u].x * a[u].x + a[u].y * a[u].y;
-        }
-    }
-    const double r = block_sum<NT>(acc, sh);
-    if (threadIdx.x == 0) out[c] = (mode == 0) ? sqrt(r) : r;
+    ew_col_reduce<NT>(mode, n, X + (int64_t)c * ldx, Y ? Y + (int64_t)c * ldy : nullptr, w, out + c);
 }
-
-// R = AX - X * lam ; norms[c] = ||R[:,c]|| ; in the same pass over X (optional, kin != null / xx != null):
-// mk[c] = sum kin |X|^2 (precondprep! of the TPA preconditioner) and xx[c] = sum |X|^2 (normalisation check)
 template <int NT>
 __global__ __launch_bounds__(NT) void k_residual(int64_t n, const cd* __restrict__ AX, int64_t lda,
                                                  const cd* __restrict__ X, int64_t ldx,
                                                  const double* __restrict__ lam, cd* __restrict__ R, int64_t ldr,
                                                  double* __restrict__ norms, const double* __restrict__ kin,
                                                  double* __restrict__ mk, double* __restrict__ xx) {
-    __shared__ double sh[NT / 64];
     const int c = blockIdx.x;
-    const double l = lam[c];
-    const cd* ax = AX + (int64_t)c * lda;
-    const cd* xc = X + (int64_t)c * ldx;
-    cd* rc = R + (int64_t)c * ldr;
-    double acc = 0.0, acck = 0.0, accx = 0.0;
-    for (int64_t i0 = threadIdx.x; i0 < n; i0 += (int64_t)NT * EW_UNR) {
-        cd a[EW_UNR], x[EW_UNR];
-        double kk[EW_UNR];
-#pragma unroll
-        for (int u = 0; u < EW_UNR; ++u) {
-            const int64_t i = i0 + (int64_t)u * NT;
-            const bool in = i < n;
-            a[u] = in ? ax[i] : make_double2(0.0, 0.0);
-            x[u] = in ? xc[i] : make_double2(0.0, 0.0);
-            kk[u] = (in && kin) ? kin[i] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < EW_UNR; ++u) {
-            const int64_t i = i0 + (int64_t)u * NT;
-            const cd r = make_double2(a[u].x - l * x[u].x, a[u].y - l * x[u].y);
-            if (i < n) rc[i] = r;
-            acc += r.x * r.x + r.y * r.y;
-            const double x2 = x[u].x * x[u].x + x[u].y * x[u].y;
-            accx += x2;
-            acck += kk[u] * x2;
-        }
-    }
-    const double s = block_sum<NT>(acc, sh);
-    const double sk = block_sum<NT>(acck, sh);
-    const double sx = block_sum<NT>(accx, sh);
-    if (threadIdx.x == 0) {
-        norms[c] = sqrt(s);
-        if (kin) mk[c] = sk;
-        if (xx) xx[c] = sx;
-    }
+    ew_residual_col<NT>(n, AX + (int64_t)c * lda, X + (int64_t)c * ldx, lam[c], R + (int64_t)c * ldr, norms + c, kin,
+                        kin ? mk + c : nullptr, xx ? xx + c : nullptr);
 }
-
-// ldiv!(precon, R) of the TPA preconditioner, out of place and with the column norms of the result:
-//   dst[:,c] = src[:,c] * mean_kin[c] / (mean_kin[c] + kin) ; norms[c] = ||dst[:,c]||     (kin == null: plain copy)
-// One workgroup per column (same reduction tree as k_col_reduce).
 template <int NT>
 __global__ __launch_bounds__(NT) void k_tpa(int64_t n, const cd* __restrict__ src, int64_t lds, cd* __restrict__ dst,
                                             int64_t ldd, const double* __restrict__ kin,
                                             const double* __restrict__ mean_kin, double* __restrict__ norms,
                                             double default_shift) {
-    __shared__ double sh[NT / 64];
     const int c = blockIdx.x;
-    const double mk = (kin && mean_kin) ? mean_kin[c] : 0.0;
-    const cd* sc = src + (int64_t)c * lds;
-    cd* dc = dst + (int64_t)c * ldd;
-    double acc = 0.0;
-    for (int64_t i0 = threadIdx.x; i0 < n; i0 += (int64_t)NT * EW_UNR) {
-        cd r[EW_UNR];
-        double kk[EW_UNR];
-#pragma unroll
-        for (int u = 0; u < EW_UNR; ++u) {
-            const int64_t i = i0 + (int64_t)u * NT;
-            const bool in = i < n;
-            r[u] = in ? sc[i] : make_double2(0.0, 0.0);
-            kk[u] = (in && kin) ? kin[i] : 1.0;
-        }
-#pragma unroll
-        for (int u = 0; u < EW_UNR; ++u) {
-            const int64_t i = i0 + (int64_t)u * NT;
-            if (kin) {
-                // mean_kin == null: precondprep! has not run yet -> ldiv!(Y, Diagonal(kin .+ default_shift), R)
-                const double f = mean_kin ? mk / (mk + kk[u]) : 1.0 / (kk[u] + default_shift);
-                r[u].x *= f;
-                r[u].y *= f;
-            }
-            if (i < n) dc[i] = r[u];
-            acc += r[u].x * r[u].x + r[u].y * r[u].y;
-        }
-    }
-    const double s = block_sum<NT>(acc, sh);
-    if (threadIdx.x == 0) norms[c] = sqrt(s);
+    ew_tpa_col<NT>(n, src + (int64_t)c * lds, dst + (int64_t)c * ldd, kin, mean_kin ? mean_kin + c : nullptr, norms + c,
+                   default_shift);
 }
 // launch one workgroup per column with the workgroup size the column length asks for
 #define EW_LAUNCH_COLS(kernel, n, m, stream, ...)                                                            \
@@ -195,114 +56,43 @@ __global__ __launch_bounds__(NT) void k_tpa(int64_t n, const cd* __restrict__ sr
     } while (0)
 
 __global__ void k_conj_transpose(int n, const cd* __restrict__ A, int64_t lda, cd* __restrict__ B, int64_t ldb) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)n * n) return;
-    const int j = (int)(idx / n), i = (int)(idx - (int64_t)j * n);
-    const cd v = A[j + (int64_t)i * lda];
-    B[i + (int64_t)j * ldb] = make_double2(v.x, -v.y);
+    ew_conj_transpose_at((int64_t)blockIdx.x * blockDim.x + threadIdx.x, n, A, lda, B, ldb);
 }
 __global__ void k_unary(int mode, double* __restrict__ d, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) d[i] = mode == 0 ? d[i] * d[i] : sqrt(d[i]);
 }
 
-// the row-parallel forms: a workgroup of 256 threads takes EW_UNR * 256 consecutive rows of one column (blockIdx.y)
-#define EW_ROWS (256 * EW_UNR)
+// the row-parallel forms: block (blockIdx.x, blockIdx.y) takes EW_ROWS consecutive rows of column blockIdx.y
 __global__ __launch_bounds__(256) void k_scale_cols(int64_t n, int m, cd* __restrict__ X, int64_t ldx,
                                                     const double* __restrict__ s, int invert) {
     const int c = blockIdx.y;
-    const double f = invert ? 1.0 / s[c] : s[c];
     cd* x = X + (int64_t)c * ldx;
-    const int64_t i0 = (int64_t)blockIdx.x * EW_ROWS + threadIdx.x;
-    cd v[EW_UNR];
-#pragma unroll
-    for (int u = 0; u < EW_UNR; ++u) {
-        const int64_t i = i0 + u * 256;
-        v[u] = i < n ? x[i] : make_double2(0.0, 0.0);
-    }
-#pragma unroll
-    for (int u = 0; u < EW_UNR; ++u) {
-        const int64_t i = i0 + u * 256;
-        if (i < n) x[i] = make_double2(v[u].x * f, v[u].y * f);
-    }
+    ew_rows<true>(n, blockIdx.x, x, x, invert ? 1.0 / s[c] : s[c]);
 }
-
 __global__ __launch_bounds__(256) void k_copy(int64_t n, int m, const cd* __restrict__ X, int64_t ldx, cd* __restrict__ Y,
                                               int64_t ldy) {
     const int c = blockIdx.y;
-    const cd* x = X + (int64_t)c * ldx;
-    cd* y = Y + (int64_t)c * ldy;
-    const int64_t i0 = (int64_t)blockIdx.x * EW_ROWS + threadIdx.x;
-    cd v[EW_UNR];
-#pragma unroll
-    for (int u = 0; u < EW_UNR; ++u) {
-        const int64_t i = i0 + u * 256;
-        v[u] = i < n ? x[i] : make_double2(0.0, 0.0);
-    }
-#pragma unroll
-    for (int u = 0; u < EW_UNR; ++u) {
-        const int64_t i = i0 + u * 256;
-        if (i < n) y[i] = v[u];
-    }
+    ew_rows<false>(n, blockIdx.x, X + (int64_t)c * ldx, Y + (int64_t)c * ldy, 1.0);
 }
-
 __global__ __launch_bounds__(256) void k_gather_cols(int64_t n, const cd* __restrict__ X, int64_t ldx,
                                                      const int* __restrict__ perm, cd* __restrict__ Y, int64_t ldy) {
     const int c = blockIdx.y;
-    const cd* x = X + (int64_t)perm[c] * ldx;
-    cd* y = Y + (int64_t)c * ldy;
-    const int64_t i0 = (int64_t)blockIdx.x * EW_ROWS + threadIdx.x;
-    cd v[EW_UNR];
-#pragma unroll
-    for (int u = 0; u < EW_UNR; ++u) {
-        const int64_t i = i0 + u * 256;
-        v[u] = i < n ? x[i] : make_double2(0.0, 0.0);
-    }
-#pragma unroll
-    for (int u = 0; u < EW_UNR; ++u) {
-        const int64_t i = i0 + u * 256;
-        if (i < n) y[i] = v[u];
-    }
+    ew_rows<false>(n, blockIdx.x, X + (int64_t)perm[c] * ldx, Y + (int64_t)c * ldy, 1.0);
 }
 
-// C[row0 + a, a] -= 1 for a in [0, cols)   (the "e" matrix of lobpcg_hyper_impl.jl:493-499)
 __global__ void k_sub_identity_shifted(int rows, int cols, cd* __restrict__ C, int64_t ldc, int row0) {
-    const int a = blockIdx.x * blockDim.x + threadIdx.x;
-    if (a < cols && row0 + a < rows) C[(row0 + a) + (int64_t)a * ldc].x -= 1.0;
+    ew_sub_identity_at((int64_t)blockIdx.x * blockDim.x + threadIdx.x, rows, cols, C, ldc, row0);
 }
-
 __global__ void k_add_diag(int n, cd* __restrict__ A, int64_t lda, double shift) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) A[i + (int64_t)i * lda].x += shift;
+    ew_add_diag_at((int64_t)blockIdx.x * blockDim.x + threadIdx.x, n, A, lda, shift);
 }
-
-// make A exactly Hermitian from its upper triangle: A[j,i] = conj(A[i,j]) (i<j), Im A[i,i] = 0
 __global__ void k_hermitize_upper(int n, cd* __restrict__ A, int64_t lda) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)n * n) return;
-    const int j = (int)(idx / n), i = (int)(idx - (int64_t)j * n);
-    if (i == j) A[i + (int64_t)j * lda].y = 0.0;
-    if (i < j) {
-        const cd v = A[i + (int64_t)j * lda];
-        A[j + (int64_t)i * lda] = make_double2(v.x, -v.y);
-    }
+    ew_hermitize_at((int64_t)blockIdx.x * blockDim.x + threadIdx.x, n, A, lda);
 }
-
-// Y = D * X for the banded real D (n_p x n_p, half bandwidth bw), X is n_p x nb complex
 __global__ void k_apply_D(int n_p, int nb, int bw, const double* __restrict__ D, const cd* __restrict__ X,
                           cd* __restrict__ Y) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)n_p * nb) return;
-    const int c = (int)(idx / n_p), i = (int)(idx - (int64_t)c * n_p);
-    const int j0 = max(0, i - bw), j1 = min(n_p - 1, i + bw);
-    double sr = 0.0, si = 0.0;
-    for (int j = j0; j <= j1; ++j) {
-        const double d = D[i + (int64_t)j * n_p];
-        const cd x = X[j + (int64_t)c * n_p];
-        sr += d * x.x;
-        si += d * x.y;
-    }
-    Y[idx] = make_double2(sr, si);
+    ew_apply_D_at((int64_t)blockIdx.x * blockDim.x + threadIdx.x, n_p, nb, bw, D, X, Y);
 }
 
 // ---------------------------------------------------------------------------- Cholesky + inverse
@@ -772,8 +562,8 @@ __global__ __launch_bounds__(256) void k_normest_upper(int n, const cd* __restri
     }
     smax[threadIdx.x] = mx;
     __syncthreads();
-    const double o = block_sum256(off, sh);
-    const double bsum = block_sum256(bad, sh);
+    const double o = block_sum<256>(off, sh);
+    const double bsum = block_sum<256>(bad, sh);
     if (threadIdx.x == 0) {
         double m2 = 0.0;
         for (int i = 0; i < 256; ++i) m2 = fmax(m2, smax[i]);
@@ -1291,9 +1081,9 @@ __global__ __launch_bounds__(256) void k_offdiag_norm(int n, const ET* __restric
         else
             off += a2;
     }
-    const double o = block_sum256(off, sh);
-    const double d = block_sum256(dg, sh);
-    const double i2 = block_sum256(im2, sh);
+    const double o = block_sum<256>(off, sh);
+    const double d = block_sum<256>(dg, sh);
+    const double i2 = block_sum<256>(im2, sh);
     if (threadIdx.x == 0) {
         out[2 * blockIdx.x] = o;
         out[2 * blockIdx.x + 1] = d;
@@ -1786,60 +1576,38 @@ int apply_D(dftk_mi_kblock* kb, int n_bands, const cd* X, cd* Y) {
 }
 
 // ---- thin launch wrappers -------------------------------------------------------------------
-int ew_colnorms(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, double* out_d) {
+// the five column reductions are one record-or-launch; mode as in ew_col_reduce (Y for modes 1 / 4, w for mode 2)
+int ew_colreduce(dftk_mi_basis* b, int mode, int64_t n, int m, const cd* X, int64_t ldx, const cd* Y, int64_t ldy,
+                 const double* w, double* out_d) {
     if (m <= 0) return 0;
     if (batching()) {
         BOp o;
         o.b = b;
-        o.type = BOP_COLRED; o.mode = 0; o.n = n; o.m = m; o.A = X; o.lda = ldx; o.C = out_d;
+        o.type = BOP_COLRED; o.mode = mode; o.n = n; o.m = m; o.A = X; o.lda = ldx; o.B = Y; o.ldb = ldy; o.W = w; o.C = out_d;
         return batch_record(std::move(o));
     }
-    ProfScope prof_scope(b, PROF_EW, n >= 4096 ? 16.0 * (double)n * m : 0.0);
-    EW_LAUNCH_COLS(k_col_reduce, n, m, b->stream, 0, n, X, ldx, (const cd*)nullptr, (int64_t)0, (const double*)nullptr, out_d);
+    ProfScope prof_scope(b, PROF_EW, n >= 4096 ? (Y ? 32.0 : 16.0) * (double)n * m : 0.0);
+    EW_LAUNCH_COLS(k_col_reduce, n, m, b->stream, mode, n, X, ldx, Y, ldy, w, out_d);
     HIPCHK(hipGetLastError());
     return 0;
+}
+int ew_colnorms(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, double* out_d) {
+    return ew_colreduce(b, 0, n, m, X, ldx, nullptr, 0, nullptr, out_d);
 }
 int ew_coldots(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, const cd* Y, int64_t ldy,
                double* out_re_d) {
-    if (m <= 0) return 0;
-    if (batching()) {
-        BOp o;
-        o.b = b;
-        o.type = BOP_COLRED; o.mode = 1; o.n = n; o.m = m; o.A = X; o.lda = ldx; o.B = Y; o.ldb = ldy; o.C = out_re_d;
-        return batch_record(std::move(o));
-    }
-    ProfScope prof_scope(b, PROF_EW, n >= 4096 ? 32.0 * (double)n * m : 0.0);
-    EW_LAUNCH_COLS(k_col_reduce, n, m, b->stream, 1, n, X, ldx, Y, ldy, (const double*)nullptr, out_re_d);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return ew_colreduce(b, 1, n, m, X, ldx, Y, ldy, nullptr, out_re_d);
 }
 int ew_coldots_im(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, const cd* Y, int64_t ldy,
                   double* out_im_d) {
-    if (m <= 0) return 0;
-    if (batching()) {
-        BOp o;
-        o.b = b;
-        o.type = BOP_COLRED; o.mode = 4; o.n = n; o.m = m; o.A = X; o.lda = ldx; o.B = Y; o.ldb = ldy; o.C = out_im_d;
-        return batch_record(std::move(o));
-    }
-    ProfScope prof_scope(b, PROF_EW, n >= 4096 ? 32.0 * (double)n * m : 0.0);
-    EW_LAUNCH_COLS(k_col_reduce, n, m, b->stream, 4, n, X, ldx, Y, ldy, (const double*)nullptr, out_im_d);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return ew_colreduce(b, 4, n, m, X, ldx, Y, ldy, nullptr, out_im_d);
 }
 int ew_weighted_colsums(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, const double* w_d,
                         double* out_d) {
-    if (m <= 0) return 0;
-    if (batching()) {
-        BOp o;
-        o.b = b;
-        o.type = BOP_COLRED; o.mode = 2; o.n = n; o.m = m; o.A = X; o.lda = ldx; o.W = w_d; o.C = out_d;
-        return batch_record(std::move(o));
-    }
-    ProfScope prof_scope(b, PROF_EW, n >= 4096 ? 16.0 * (double)n * m : 0.0);
-    EW_LAUNCH_COLS(k_col_reduce, n, m, b->stream, 2, n, X, ldx, (const cd*)nullptr, (int64_t)0, w_d, out_d);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return ew_colreduce(b, 2, n, m, X, ldx, nullptr, 0, w_d, out_d);
+}
+int ew_frob2(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, double* out_d) {
+    return ew_colreduce(b, 3, n, m, X, ldx, nullptr, 0, nullptr, out_d);
 }
 int ew_conj_transpose(dftk_mi_basis* b, int n, const cd* A, int64_t lda, cd* B, int64_t ldb) {
     if (n <= 0) return 0;
@@ -1863,19 +1631,6 @@ int ew_square(dftk_mi_basis* b, double* d, size_t n) {
 int ew_sqrt(dftk_mi_basis* b, double* d, size_t n) {
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_unary, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, 1, d, n);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int ew_frob2(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, double* out_d) {
-    if (m <= 0) return 0;
-    if (batching()) {
-        BOp o;
-        o.b = b;
-        o.type = BOP_COLRED; o.mode = 3; o.n = n; o.m = m; o.A = X; o.lda = ldx; o.C = out_d;
-        return batch_record(std::move(o));
-    }
-    ProfScope prof_scope(b, PROF_EW, n >= 4096 ? 16.0 * (double)n * m : 0.0);
-    EW_LAUNCH_COLS(k_col_reduce, n, m, b->stream, 3, n, X, ldx, (const cd*)nullptr, (int64_t)0, (const double*)nullptr, out_d);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -40,22 +40,6 @@ static const double EIG_L_HAT = 1e-2;
 
 namespace {
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double bsum256(double v, double* sh) {   // result valid in thread 0
-    v = wsum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) r = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return r;
-}
-
 // column j: diag[j] = Re A_jj, rowabs[j] = sum_i |A_ij|  (Hermitian: column sums = row sums)
 __global__ __launch_bounds__(256) void k_eig_colstats(int n, const cd* __restrict__ A, int64_t lda,
                                                       double* __restrict__ diag, double* __restrict__ rowabs) {
@@ -66,7 +50,7 @@ __global__ __launch_bounds__(256) void k_eig_colstats(int n, const cd* __restric
         const cd v = A[i + (int64_t)j * lda];
         s += sqrt(v.x * v.x + v.y * v.y);
     }
-    const double t = bsum256(s, sh);
+    const double t = block_sum<256>(s, sh);
     if (threadIdx.x == 0) {
         rowabs[j] = t;
         diag[j] = A[j + (int64_t)j * lda].x;
@@ -138,8 +122,8 @@ __global__ __launch_bounds__(256) void k_eig_poly(int n, cd* __restrict__ Y, int
             Y[j + (int64_t)i * ldy] = make_double2(v.x, -v.y);
         }
     }
-    const double a = bsum256(tr, sh);
-    const double f = bsum256(fro, sh);
+    const double a = block_sum<256>(tr, sh);
+    const double f = block_sum<256>(fro, sh);
     if (threadIdx.x == 0) {
         part[2 * blockIdx.x] = a;
         part[2 * blockIdx.x + 1] = f;

@@ -28,7 +28,8 @@
 #define FL_KZ 2         // consecutive z planes per thread
 #define FL_WAVES 4      // waves per workgroup, stacked along y
 
-__device__ inline double wave_sum(double v) {
+// xor butterfly: the sum arrives in every lane (common.h's wave_sum is the shuffle-down tree, lane 0 only)
+__device__ inline double wave_sum_all(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(64 * FL_WAVES, 4) void k_forces_local(int nx, int n
         const double fx = gx * (S0r * t.y + S0i * t.x);      // Im(t S)
         const double fy = Syr * t.y + Syi * t.x;
         const double fz = Szr * t.y + Szi * t.x;
-        const double sx = wave_sum(fx), sy = wave_sum(fy), sz = wave_sum(fz);
+        const double sx = wave_sum_all(fx), sy = wave_sum_all(fy), sz = wave_sum_all(fz);
         if (lane == 0) {
             partial[(int64_t)(3 * a + 0) * n_waves + wid] = sx;
             partial[(int64_t)(3 * a + 1) * n_waves + wid] = sy;

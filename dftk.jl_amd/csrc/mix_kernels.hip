@@ -30,14 +30,9 @@ struct PtrTable {
     double c[MAXK];
 };
 
-__device__ __forceinline__ double m_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 // block-wide sum (MT = 256 threads); result valid in every thread
 __device__ __forceinline__ double m_block_sum(double v, double* sh /* [8] */) {
-    v = m_wave_sum(v);
+    v = wave_sum(v);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     __syncthreads();
     if (lane == 0) sh[w] = v;

@@ -14,22 +14,6 @@
 namespace dftk_xc {   // (named: kernels of an anonymous namespace lose their names in rocprofv3 traces)
 const int XC_BLOCKS = 1024;
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    v = wave_sum_d(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(256) void k_real_to_complex(int64_t n, const double* __restrict__ x, cd* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
         out[i] = make_double2(x[i], 0.0);
@@ -46,7 +30,7 @@ __global__ __launch_bounds__(256) void k_poisson(int64_t n, cd* __restrict__ c, 
         acc += g * (v.x * v.x + v.y * v.y);
         c[i] = make_double2(g * v.x, g * v.y);
     }
-    const double s = block_sum(acc, sh);
+    const double s = block_sum<256>(acc, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -344,8 +328,8 @@ __global__ __launch_bounds__(256) void k_xc_sum(int64_t n, const double* __restr
         if (vh_cube) tot += vh_scale * vh_cube[i].x;
         if (V) V[i] = tot;
     }
-    const double s0 = block_sum(acc_xc, sh);
-    const double s1 = block_sum(acc_loc, sh);
+    const double s0 = block_sum<256>(acc_xc, sh);
+    const double s1 = block_sum<256>(acc_loc, sh);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = s0;
         partial[XC_BLOCKS + blockIdx.x] = s1;
@@ -387,8 +371,8 @@ __global__ __launch_bounds__(256) void k_xc_sum_spin(int64_t n, const double* __
             V_dn[i] = common + e.d[1];
         }
     }
-    const double s0 = block_sum(acc_xc, sh);
-    const double s1 = block_sum(acc_loc, sh);
+    const double s0 = block_sum<256>(acc_xc, sh);
+    const double s1 = block_sum<256>(acc_loc, sh);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = s0;
         partial[XC_BLOCKS + blockIdx.x] = s1;
@@ -493,7 +477,7 @@ __global__ __launch_bounds__(256) void k_poisson_sum(int64_t n, const cd* __rest
         acc += g * (x * x + y * y);
         out[i] = make_double2(g * x, g * y);
     }
-    const double s = block_sum(acc, sh);
+    const double s = block_sum<256>(acc, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 // g: d_a rho_up (a = 0, 1, 2), then d_a rho_down; sigma: uu, ud, dd

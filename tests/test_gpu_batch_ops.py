@@ -308,7 +308,10 @@ def test_products_outside_the_batched_kernels(lib, bs, mode, kind):
 
 
 # ------------------------------------------------------------------------------------------------- column kernels
-COL_SHAPES = [(1, 1), (255, 7), (256, 24), (257, 1), (1350, 7), (4653, 24)]
+# 1024 | 1025: the last full and the first partial pass of a 256-thread workgroup with four rows per thread; 8191 | 8192 |
+# 8193: the one-by-one form switches to 1024 threads from 8192 rows on, 8193 is its one-row tail
+COL_SHAPES = [(1, 1), (255, 7), (256, 24), (257, 1), (1350, 7), (4653, 24), (1024, 3), (1025, 3), (8191, 2), (8192, 2),
+              (8193, 3)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -344,13 +347,12 @@ def reduction_ok(got, ref, terms, n, squared=False):
     return float(np.max(err / bound))
 
 
-def test_column_kernels(lib, bs, mode):
-    """k_b_colred (modes 0-4, a different one per fiber at every position), k_b_residual with and without the kinetic
-    sums, k_b_tpa in its three forms: n = 1 .. 4653 rows and m = 1, 7, 24 columns in every launch, whose grid is sized by
-    the widest item."""
-    tab = Table(len(COL_SHAPES))
+def column_table(shapes):
+    """One fiber per shape: COLRED in its five modes (a different one per fiber at every position), RESIDUAL with and
+    without the kinetic sums, TPA in its three forms.  Returns the table and, per fiber, its data and output buffers."""
+    tab = Table(len(shapes))
     per = []
-    for f, (n, m) in enumerate(COL_SHAPES):
+    for f, (n, m) in enumerate(shapes):
         d = col_data(n, m)
         X, Y, w, kin = Mat(d["X"]), Mat(d["Y"]), Mat(d["w"]), Mat(d["kin"])
         lam, mk = Mat(d["lam"]), Mat(d["mk"])
@@ -372,6 +374,14 @@ def test_column_kernels(lib, bs, mode):
             tab.add(TPA, f, n=n, m=m, A=Y, lda=Y.ld, C=dst, ldc=dst.ld, W=k_, W2=mk_, D=nr, s0=s0)
             o[key] = (dst, nr)
         per.append(o)
+    return tab, per
+
+
+def test_column_kernels(lib, bs, mode):
+    """k_b_colred (modes 0-4, a different one per fiber at every position), k_b_residual with and without the kinetic
+    sums, k_b_tpa in its three forms: n = 1 .. 8193 rows and m = 1 .. 24 columns in every launch, whose grid is sized by
+    the widest item.  One by one, the rows of 8192 and 8193 run the 1024-thread forms of the same bodies."""
+    tab, per = column_table(COL_SHAPES)
     tab.run(lib, bs, mode)
     worst = {}
 
@@ -419,6 +429,41 @@ def test_column_kernels(lib, bs, mode):
             note(key + " norms", reduction_ok(nr.fetch()[:, 0], sumsq(got), sumsq(got), n, squared=True))
             assert dst.rest_untouched() and nr.rest_untouched()
     print(f"column kernels ({mode}): worst error / bound", {k: round(v, 3) for k, v in worst.items()})
+
+
+def test_column_kernels_merged_equals_one_by_one(lib, bs, monkeypatch):
+    """One device body per operation (csrc/ew_device.h): below 8192 rows the merged launch and the original entry point
+    both run it with 256 threads per column, so every output of COLRED / RESIDUAL / TPA -- reductions, R, dst, norms, E,
+    F -- is the same bits either way.  (From 8192 rows on the entry point takes 1024 threads: another, equally fixed,
+    summation tree; those items are held to the bounds of test_column_kernels only.)"""
+    shapes = [(1024, 3), (1025, 3), (8191, 2), (8192, 2), (8193, 3), (257, 1), (1350, 7), (4653, 24)]
+
+    def outputs(mode):
+        tab, per = column_table(shapes)
+        tab.run(lib, bs, mode)
+        res = []
+        for o in per:
+            mats = [out for _, out in o["red"]] + list(o["res_kin"]) + list(o["res"][:2]) + list(o["tpa_mk"])
+            mats += list(o["tpa_shift"]) + list(o["tpa_copy"])
+            res.append([mt.fetch() for mt in mats])
+        return res
+
+    monkeypatch.delenv("DFTK_MI_KBATCH_SEQUENTIAL", raising=False)
+    merged_out = outputs("merged")
+    monkeypatch.setenv("DFTK_MI_KBATCH_SEQUENTIAL", "1")
+    single_out = outputs("one-by-one")
+    names = [f"colred@{p}" for p in range(5)] + ["res_kin R", "res_kin norms", "res_kin E", "res_kin F", "res R", "res norms",
+                                                 "tpa_mk dst", "tpa_mk norms", "tpa_shift dst", "tpa_shift norms",
+                                                 "tpa_copy dst", "tpa_copy norms"]
+    compared = 0
+    for (n, m), a, b in zip(shapes, merged_out, single_out):
+        if n >= 8192:
+            continue
+        assert len(a) == len(b) == len(names)
+        for name, x, y in zip(names, a, b):
+            assert same_bits(x, y), (name, n, m)
+            compared += 1
+    assert compared == 6 * len(names)
 
 
 def test_residual_with_device_rayleigh_quotients(lib, bs, merged):
