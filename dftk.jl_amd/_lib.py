@@ -169,6 +169,7 @@ _SIGNATURES = {
                                    C.c_double, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int),
                                    C.POINTER(C.c_int)]),
     "dftk_mi_launch_count": (C.c_int, [C.POINTER(_i64), C.POINTER(_i64)]),
+    "dftk_mi_device_buffers_live": (C.c_int, [C.POINTER(_i64), C.POINTER(_i64)]),
     "dftk_mi_kblock_reuse_AX": (C.c_int, [C.c_void_p, C.c_int]),
     "dftk_mi_ax_reuse_count": (C.c_int, [C.POINTER(_i64)]),
     "dftk_mi_planes_reuse_count": (C.c_int, [C.POINTER(_i64)]),

@@ -27,14 +27,9 @@ hipError_t dftk_scratch_malloc(void** p, size_t bytes) {
     if (e == hipSuccess && poison) e = hipMemset(*p, 0xFF, bytes);
     return e;
 }
-int scratch_grow(dftk_mi_basis* b, void** buf, size_t* have, size_t need) {
-    if (need <= *have) return 0;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (*buf) HIPCHK(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    HIPCHK(dftk_scratch_malloc(buf, need));
-    *have = need;
+extern "C" int dftk_mi_device_buffers_live(int64_t* count, int64_t* bytes) {
+    if (count) *count = g_devbuf_live_count.load(std::memory_order_relaxed);
+    if (bytes) *bytes = g_devbuf_live_bytes.load(std::memory_order_relaxed);
     return 0;
 }
 #ifndef DFTK_MI_SRC_HASH
@@ -47,7 +42,7 @@ extern "C" const char* dftk_mi_version(void) {
 
 // ------------------------------------------------------------------------------------ profiling
 int prof_begin(dftk_mi_basis* b, int fam, double work, uint64_t tag) {
-    Prof* p = b->prof;
+    Prof* p = b->prof.get();
     if (!p || !p->on || p->mute > 0) return -1;
     // slots index `pending`, and scopes nest (apply_H / heev hold one across inner zgemm / FFT scopes): never
     // flush while a scope is open
@@ -71,18 +66,18 @@ int prof_begin(dftk_mi_basis* b, int fam, double work, uint64_t tag) {
 }
 void prof_end(dftk_mi_basis* b, int slot) {
     if (slot < 0) return;
-    Prof* p = b->prof;
+    Prof* p = b->prof.get();
     if (p->open > 0) p->open -= 1;
     if ((size_t)slot < p->pending.size()) hipEventRecord(p->pending[slot].b, b->stream);
 }
 void prof_count(dftk_mi_basis* b, int fam, double work) {
-    Prof* p = b->prof;
+    Prof* p = b->prof.get();
     if (!p || !p->on) return;
     p->work[fam] += work;
     p->launches[fam] += 1;
 }
 int host_wait(dftk_mi_basis* b) {
-    Prof* p = b->prof;
+    Prof* p = b->prof.get();
     if (!p || !p->on) {
         HIPCHK(hipStreamSynchronize(b->stream));
         return 0;
@@ -94,7 +89,7 @@ int host_wait(dftk_mi_basis* b) {
     return 0;
 }
 int prof_resolve(dftk_mi_basis* b) {
-    Prof* p = b->prof;
+    Prof* p = b->prof.get();
     if (!p) return 0;
     HIPCHK(hipStreamSynchronize(b->stream));
     for (auto& pr : p->pending) {
@@ -309,12 +304,11 @@ extern "C" int dftk_mi_sphere_tables_host(int nx, int ny, int nz, int64_t n_G, c
 }
 
 // ------------------------------------------------------------------------------------ basis
-template <typename T>
-static int upload(const std::vector<T>& v, T** d) {
-    *d = nullptr;
+template <typename T, typename U>
+static int upload(const std::vector<T>& v, DevTable<U>& d) {
+    HIPCHK(d.alloc(v.size() * sizeof(T)));
     if (v.empty()) return 0;
-    HIPCHK(hipMalloc((void**)d, v.size() * sizeof(T)));
-    HIPCHK(hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -338,8 +332,7 @@ extern "C" int dftk_mi_basis_create(int nx, int ny, int nz, double unit_cell_vol
     if (!out || nx < 1 || ny < 1 || nz < 1 || !(unit_cell_volume > 0)) return DFTK_MI_EINVAL;
     CHK(check_device(device));
     HIPCHK(hipSetDevice(device));
-    dftk_mi_basis* b = new dftk_mi_basis();
-    memset(b, 0, sizeof(*b));
+    std::unique_ptr<dftk_mi_basis> b(new dftk_mi_basis());   // every early return below releases what was built so far
     b->nx = nx;
     b->ny = ny;
     b->nz = nz;
@@ -350,17 +343,16 @@ extern "C" int dftk_mi_basis_create(int nx, int ny, int nz, double unit_cell_vol
     // every stage loses bandwidth to its fill / drain (tools/fft_bench.py 5 256 <group>: pipeline + density of 256 bands
     // 149.1 ms at 8, 143.3 at 16, 134.5 at 32, 135.6 at 64); scratch = group x (T1 + T2) = 2.8 GB at the 1000-electron cell
     b->fft_batch = 32;
-    b->prof = new Prof();
+    b->prof.reset(new Prof());
     const char* g = getenv("DFTK_MI_GEMM");
     b->use_mfma = (g && strcmp(g, "naive") == 0) ? 0 : 1;
-    HIPCHK(hipStreamCreate(&b->stream));
+    HIPCHK(hipStreamCreate(&b->stream.s));
     const int dims[3] = {nx, ny, nz};
     for (int a = 0; a < 3; ++a) {
         const int n = dims[a];
         FftAxis& ax = b->ax[a];
         ax.n = n;
         if (plan_radices(n, &ax.nrad, ax.rad) != 0) {
-            dftk_mi_basis_destroy(b);   // this path only: the Prof, the stream and the tables of the earlier axes
             dftk_set_error("cannot plan FFT axis of length %d", n);
             return DFTK_MI_EINVAL;
         }
@@ -373,19 +365,15 @@ extern "C" int dftk_mi_basis_create(int nx, int ny, int nz, double unit_cell_vol
             tw[2 * t] = (double)cosl(ang);
             tw[2 * t + 1] = (double)sinl(ang);
         }
-        double* dtw;
-        int* dpos;
-        CHK(upload(tw, &dtw));
-        CHK(upload(pos, &dpos));
-        ax.tw = reinterpret_cast<const cd*>(dtw);
-        ax.pos = dpos;
-        b->d_tables[2 * a] = dtw;
-        b->d_tables[2 * a + 1] = dpos;
+        CHK(upload(tw, b->d_tables[2 * a]));
+        CHK(upload(pos, b->d_tables[2 * a + 1]));
+        ax.tw = static_cast<const cd*>(b->d_tables[2 * a].get());
+        ax.pos = static_cast<const int*>(b->d_tables[2 * a + 1].get());
     }
-    HIPCHK(hipMalloc((void**)&b->d_scalars, 256 * sizeof(double)));
-    HIPCHK(hipHostMalloc((void**)&b->h_scalars, 256 * sizeof(double)));
-    HIPCHK(hipHostMalloc((void**)&b->h_fetch, HOST_FETCH_BYTES, hipHostMallocMapped));
-    *out = b;
+    HIPCHK(b->d_scalars.alloc(256 * sizeof(double)));
+    HIPCHK(b->h_scalars.alloc(256 * sizeof(double)));
+    HIPCHK(b->h_fetch.alloc(HOST_FETCH_BYTES));
+    *out = b.release();
     return 0;
 }
 
@@ -393,27 +381,7 @@ extern "C" int dftk_mi_basis_destroy(dftk_mi_basis* b) {
     if (!b) return 0;
     hipSetDevice(b->device);
     hipStreamSynchronize(b->stream);
-    for (void* p : b->d_tables)
-        if (p) hipFree(p);
-    if (b->T1) hipFree(b->T1);
-    if (b->T2) hipFree(b->T2);
-    if (b->ws) hipFree(b->ws);
-    if (b->dense_ws) hipFree(b->dense_ws);
-    if (b->eig_ws) hipFree(b->eig_ws);
-    if (b->symm_tab) hipFree(b->symm_tab);
-    if (b->resp_ws) hipFree(b->resp_ws);
-    if (b->d_scalars) hipFree(b->d_scalars);
-    if (b->h_scalars) hipHostFree(b->h_scalars);
-    if (b->h_fetch) hipHostFree(b->h_fetch);
-    if (b->prof) {
-        prof_resolve(b);
-        for (auto& pr : b->prof->pool) {
-            hipEventDestroy(pr.a);
-            hipEventDestroy(pr.b);
-        }
-        delete b->prof;
-    }
-    hipStreamDestroy(b->stream);
+    prof_resolve(b);   // (the events leave `pending` while the stream still exists)
     delete b;
     return 0;
 }
@@ -464,8 +432,7 @@ extern "C" int dftk_mi_kblock_create(dftk_mi_basis* b, int64_t n_G, const int64_
     std::vector<int> zpos(t.zval.size());
     for (size_t i = 0; i < t.zval.size(); ++i) zpos[i] = pos[2][t.zval[i]];
 
-    dftk_mi_kblock* kb = new dftk_mi_kblock();
-    memset(kb, 0, sizeof(*kb));
+    std::unique_ptr<dftk_mi_kblock> kb(new dftk_mi_kblock());
     kb->basis = b;
     kb->device = b->device;
     kb->n_G = n_G;
@@ -478,39 +445,28 @@ extern "C" int dftk_mi_kblock_create(dftk_mi_basis* b, int64_t n_G, const int64_
         for (int i = lo; i < kb->nzx; ++i) ok = ok && t.zval[i] == b->nz - (kb->nzx - i);
         kb->z_lo = ok ? lo : -1;
     }
-    CHK(upload(cpos, &kb->d_cpos));
-    CHK(upload(cx, &kb->d_cx));
-    CHK(upload(line_start, &kb->d_line_start));
-    CHK(upload(line_ypos, &kb->d_line_ypos));
-    CHK(upload(line_yval, &kb->d_line_yval));
-    CHK(upload(t.zls, &kb->d_zls));
-    CHK(upload(zpos, &kb->d_zpos));
-    CHK(upload(t.zval, &kb->d_zval));
+    CHK(upload(cpos, kb->d_cpos));
+    CHK(upload(cx, kb->d_cx));
+    CHK(upload(line_start, kb->d_line_start));
+    CHK(upload(line_ypos, kb->d_line_ypos));
+    CHK(upload(line_yval, kb->d_line_yval));
+    CHK(upload(t.zls, kb->d_zls));
+    CHK(upload(zpos, kb->d_zpos));
+    CHK(upload(t.zval, kb->d_zval));
     std::vector<double> kin(n_G, 0.0);
     if (kinetic_h) std::copy(kinetic_h, kinetic_h + n_G, kin.begin());
-    CHK(upload(kin, &kb->d_kin));
-    kb->h_mapping = new std::vector<int64_t>(mapping0_h, mapping0_h + n_G);
-    kb->h_kin = new std::vector<double>(kin);
-    *out = kb;
+    CHK(upload(kin, kb->d_kin));
+    kb->h_mapping.assign(mapping0_h, mapping0_h + n_G);
+    kb->h_kin = std::move(kin);
+    *out = kb.release();
     return 0;
 }
 
-// one padded potential shared by the k-blocks of a dftk_mi_kblocks_set_potential call (they all apply the SAME V)
-struct SharedVs {
-    double* p = nullptr;
-    int refs = 0;
-};
-// the block lets go of its padded potential (the caller has made sure no kernel reading it is in flight)
+// the block lets go of its padded potential, its own or a shared one: the last holder frees the buffer (the caller has
+// made sure no kernel reading it is in flight)
 static void release_Vs(dftk_mi_kblock* kb) {
-    if (kb->Vs_share) {
-        if (--kb->Vs_share->refs == 0) {
-            if (kb->Vs_share->p) hipFree(kb->Vs_share->p);
-            delete kb->Vs_share;
-        }
-        kb->Vs_share = nullptr;
-    } else if (kb->d_Vs) {
-        hipFree(kb->d_Vs);
-    }
+    kb->Vs_buf.reset();
+    kb->Vs_shared = false;
     kb->d_Vs = nullptr;
 }
 
@@ -518,22 +474,6 @@ extern "C" int dftk_mi_kblock_destroy(dftk_mi_kblock* kb) {
     if (!kb) return 0;
     hipSetDevice(kb->device);
     hipDeviceSynchronize();   // the basis may already be gone: never dereference it here
-    release_Vs(kb);
-    if (kb->d_Vs_ax) hipFree(kb->d_Vs_ax);
-    if (kb->d_dVs) hipFree(kb->d_dVs);
-    if (kb->planes) hipFree(kb->planes);
-    delete kb->planes_valid;
-    void* ptrs[] = {kb->d_cpos, kb->d_cx, kb->d_line_start, kb->d_line_ypos, kb->d_line_yval, kb->d_zls,
-                    kb->d_zpos, kb->d_zval, kb->d_kin, kb->d_D, kb->lob_buf};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    if (kb->sh_buf) hipFree(kb->sh_buf);
-    if (kb->d_G3) hipFree(kb->d_G3);
-    delete kb->sh_rows;
-    delete kb->lob_hist;
-    delete kb->h_mapping;
-    delete kb->h_kin;
-    gamma_destroy(kb->gr);
     delete kb;
     return 0;
 }
@@ -542,7 +482,7 @@ extern "C" int dftk_mi_kblock_destroy(dftk_mi_kblock* kb) {
 static int64_t local_rows(const dftk_mi_kblock* kb) {
     if (!kb->sh_comm) return kb->n_G;
     const int r = comm_rank(kb->sh_comm);
-    return (*kb->sh_rows)[r + 1] - (*kb->sh_rows)[r];
+    return kb->sh_rows[r + 1] - kb->sh_rows[r];
 }
 
 extern "C" int dftk_mi_kblock_set_shard(dftk_mi_kblock* kb, dftk_mi_comm* comm, const int64_t* row_starts_h) {
@@ -572,8 +512,7 @@ extern "C" int dftk_mi_kblock_set_shard(dftk_mi_kblock* kb, dftk_mi_comm* comm, 
         dftk_set_error("set_shard: call before dftk_mi_kblock_set_projectors (P becomes the row slab of this rank)");
         return DFTK_MI_EINVAL;
     }
-    if (!kb->sh_rows) kb->sh_rows = new std::vector<int64_t>();
-    kb->sh_rows->assign(row_starts_h, row_starts_h + p + 1);
+    kb->sh_rows.assign(row_starts_h, row_starts_h + p + 1);
     kb->sh_comm = comm;
     return 0;
 }
@@ -590,7 +529,7 @@ static int shard_buffers(dftk_mi_kblock* kb, int nb, cd** R1, cd** F, cd** G) {
     const size_t maxc = (size_t)(nb + p - 1) / p;
     const size_t each = (size_t)kb->n_G * (maxc ? maxc : 1);
     const size_t need = 3 * each * sizeof(cd);
-    CHK(scratch_grow(kb->basis, (void**)&kb->sh_buf, &kb->sh_bytes, need));
+    CHK(scratch_grow(kb->basis, kb->sh_buf, need));
     *R1 = kb->sh_buf;
     *F = kb->sh_buf + each;
     *G = kb->sh_buf + 2 * each;
@@ -645,7 +584,7 @@ struct Transposer {
     std::vector<int> c0;
     std::vector<size_t> slab_off, slab_cnt, band_off, band_cnt;
     Transposer(dftk_mi_kblock* k, int nbands, const std::vector<int64_t>* row_offsets = nullptr)
-        : kb(k), nb(nbands), rows(row_offsets ? row_offsets : k->sh_rows) {
+        : kb(k), nb(nbands), rows(row_offsets ? row_offsets : &k->sh_rows) {
         p = comm_size(kb->sh_comm);
         me = comm_rank(kb->sh_comm);
         nloc = (*rows)[me + 1] - (*rows)[me];
@@ -679,7 +618,7 @@ struct Transposer {
 // Half-format blocks are sharded by half-format rows; whole bands exist only between two all-to-alls, where the
 // pair packing / FFT pipeline / compress / expand kernels run on this rank's share of the bands.
 int gamma_apply_H_sharded(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t ldpsi, cd* Hpsi, int64_t ldH) {
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     dftk_mi_basis* b = kb->basis;
     const int64_t hl = gamma_local_rows(kb);
     if (ldpsi != hl || ldH != hl) {
@@ -716,15 +655,12 @@ int gamma_apply_H_sharded(dftk_mi_kblock* kb, int which, int nb, const cd* psi, 
 
 // this rank's slab of the half-format projectors from its slab of the full-sphere ones (two all-to-alls, once)
 int gamma_projectors_sharded(dftk_mi_kblock* kb) {
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     if (gr->P_src == kb->P && gr->P_n_p == kb->n_p && gr->P_half) return 0;
     dftk_mi_basis* b = kb->basis;
     const int64_t hl = gamma_local_rows(kb), fl = local_rows(kb);
     const int n_p = kb->n_p;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (gr->P_half) HIPCHK(hipFree(gr->P_half));
-    gr->P_half = nullptr;
-    HIPCHK(hipMalloc((void**)&gr->P_half, (size_t)hl * n_p * sizeof(cd)));
+    CHK(gamma_projectors_renew(kb, (size_t)hl * n_p));
     cd *R1, *F, *Gf;
     CHK(shard_buffers(kb, n_p, &R1, &F, &Gf));
     Transposer tf(kb, n_p), th(kb, n_p, &gr->half_rows);
@@ -741,8 +677,7 @@ int gamma_projectors_sharded(dftk_mi_kblock* kb) {
     HIPCHK(hipStreamSynchronize(b->stream));
     if (bad != 0.0) {
         dftk_set_error("gamma_real: the projectors are not real-symmetric (max |P(-G) - conj P(G)| = %.3e on this rank)", h[0]);
-        HIPCHK(hipFree(gr->P_half));
-        gr->P_half = nullptr;
+        gr->P_half.reset();
         return DFTK_MI_EINVAL;
     }
     CHK(th.to_slabs(Gf, R1, gr->P_half));
@@ -768,7 +703,7 @@ int gamma_density_sharded(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldp
 int gamma_lobpcg_load(dftk_mi_kblock* kb, int M, const cd* Xuser, int64_t ldX, cd* Xh, int64_t ldh, bool align) {
     if (!kb->sh_comm)
         return align ? gamma_compress_aligned(kb, M, Xuser, ldX, Xh, ldh) : gamma_compress(kb, M, Xuser, ldX, Xh, ldh);
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     dftk_mi_basis* b = kb->basis;
     const int64_t hl = gamma_local_rows(kb), fl = local_rows(kb);
     if (ldh != hl) return DFTK_MI_EINVAL;
@@ -786,7 +721,7 @@ int gamma_lobpcg_load(dftk_mi_kblock* kb, int M, const cd* Xuser, int64_t ldX, c
 
 int gamma_lobpcg_store(dftk_mi_kblock* kb, int M, const cd* Xh, int64_t ldh, cd* Xuser, int64_t ldX) {
     if (!kb->sh_comm) return gamma_expand(kb, M, Xh, ldh, Xuser, ldX);
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     dftk_mi_basis* b = kb->basis;
     const int64_t hl = gamma_local_rows(kb), fl = local_rows(kb);
     if (ldh != hl) return DFTK_MI_EINVAL;
@@ -805,10 +740,7 @@ extern "C" int dftk_mi_kblock_set_projectors(dftk_mi_kblock* kb, int n_p, const 
     if (!kb || n_p < 0) return DFTK_MI_EINVAL;
     HIPCHK(hipSetDevice(kb->basis->device));
     HIPCHK(hipStreamSynchronize(kb->basis->stream));
-    if (kb->d_D) {
-        HIPCHK(hipFree(kb->d_D));
-        kb->d_D = nullptr;
-    }
+    HIPCHK(kb->d_D.reset());
     kb->n_p = 0;
     kb->P = nullptr;
     kb->ax_keep = nullptr;                  // (an A X kept by the LOBPCG driver belongs to the old nonlocal term)
@@ -822,7 +754,7 @@ extern "C" int dftk_mi_kblock_set_projectors(dftk_mi_kblock* kb, int n_p, const 
         for (int i = 0; i < n_p; ++i)
             if (D_h[i + (size_t)j * n_p] != 0.0) bw = std::max(bw, std::abs(i - j));
     std::vector<double> D(D_h, D_h + (size_t)n_p * n_p);
-    CHK(upload(D, &kb->d_D));
+    CHK(upload(D, kb->d_D));
     kb->D_bw = bw;
     kb->n_p = n_p;
     kb->P = reinterpret_cast<const cd*>(P_d);
@@ -834,12 +766,17 @@ extern "C" int dftk_mi_kblock_set_potential(dftk_mi_kblock* kb, const double* V_
     if (!kb) return DFTK_MI_EINVAL;
     dftk_mi_basis* b = kb->basis;
     HIPCHK(hipSetDevice(b->device));
-    if (!V_d || kb->Vs_share) {   // (a block that shares its buffer gets one of its own again: the others keep theirs)
+    if (!V_d || kb->Vs_shared) {   // (a block that shares its buffer gets one of its own again: the others keep theirs)
         HIPCHK(hipStreamSynchronize(b->stream));
         release_Vs(kb);
         if (!V_d) return 0;
     }
-    if (!kb->d_Vs) HIPCHK(hipMalloc((void**)&kb->d_Vs, (size_t)b->nz * b->ny * b->nxp * sizeof(double)));
+    if (!kb->Vs_buf) {
+        auto own = std::make_shared<DevTable<double>>();
+        HIPCHK(own->alloc((size_t)b->nz * b->ny * b->nxp * sizeof(double)));
+        kb->Vs_buf = std::move(own);
+        kb->d_Vs = kb->Vs_buf->get();
+    }
     return launch_pad_potential(kb, V_d);
 }
 
@@ -860,22 +797,21 @@ extern "C" int dftk_mi_kblocks_set_potential(int n_kblocks, dftk_mi_kblock* cons
     dftk_mi_basis* b = kbs[0]->basis;
     HIPCHK(hipSetDevice(b->device));
     // already one shared buffer held by exactly these blocks (the call of the previous SCF step): refill it
-    SharedVs* sh = kbs[0]->Vs_share;
-    bool reuse = sh != nullptr && sh->refs == n_kblocks;
-    for (int i = 0; i < n_kblocks && reuse; ++i) reuse = kbs[i]->Vs_share == sh;
+    std::shared_ptr<DevTable<double>> sh = kbs[0]->Vs_shared ? kbs[0]->Vs_buf : nullptr;
+    bool reuse = sh != nullptr && sh.use_count() == n_kblocks + 1;   // (+ 1: the local copy)
+    for (int i = 0; i < n_kblocks && reuse; ++i) reuse = kbs[i]->Vs_shared && kbs[i]->Vs_buf == sh;
     if (!reuse) {
         HIPCHK(hipStreamSynchronize(b->stream));
         for (int i = 0; i < n_kblocks; ++i) release_Vs(kbs[i]);
-        sh = new SharedVs();
-        if (hipMalloc((void**)&sh->p, (size_t)b->nz * b->ny * b->nxp * sizeof(double)) != hipSuccess) {
-            delete sh;
+        sh = std::make_shared<DevTable<double>>();
+        if (sh->alloc((size_t)b->nz * b->ny * b->nxp * sizeof(double)) != hipSuccess) {
             dftk_set_error("dftk_mi_kblocks_set_potential: out of device memory");
             return DFTK_MI_EHIP;
         }
         for (int i = 0; i < n_kblocks; ++i) {
-            kbs[i]->Vs_share = sh;
-            kbs[i]->d_Vs = sh->p;
-            sh->refs += 1;
+            kbs[i]->Vs_buf = sh;
+            kbs[i]->Vs_shared = true;
+            kbs[i]->d_Vs = sh->get();
         }
     }
     return launch_pad_potential(kbs[0], V_d);     // asynchronous on the basis' stream
@@ -895,7 +831,7 @@ int apply_nonlocal_rows(dftk_mi_kblock* kb, int nb, const cd* P, int64_t ldP, in
     }
     // scratch for the two n_p x nb panels lives in T1 (free outside the FFT pipeline)
     const size_t need = 2 * (size_t)kb->n_p * nb * sizeof(cd);
-    CHK(scratch_grow(b, (void**)&b->T1, &b->T1_bytes, need));
+    CHK(scratch_grow(b, b->T1, need));
     cd* Ppsi = b->T1;
     cd* DPpsi = b->T1 + (size_t)kb->n_p * nb;
     // (sharded block: P, psi, Hpsi are row slabs; the projections are partial sums -> one small all-reduce)
@@ -1322,7 +1258,7 @@ extern "C" int dftk_mi_band_kinetic_multi(int n_kblocks, dftk_mi_kblock* const* 
     }
     HIPCHK(hipSetDevice(b->device));
     CHK(ensure_ws(b, total * sizeof(double)));
-    double* d = reinterpret_cast<double*>(b->ws);
+    double* d = reinterpret_cast<double*>(b->ws.get());
     std::vector<std::function<int()>> bodies;
     size_t off = 0;
     for (int i = 0; i < n_kblocks; ++i) {
@@ -1498,13 +1434,13 @@ extern "C" int dftk_mi_potrf_trtri_real(dftk_mi_basis* b, int n, dftk_mi_cplx* A
 // ------------------------------------------------------------------------------------ LOBPCG building blocks
 extern "C" int dftk_mi_lobpcg_history(dftk_mi_kblock* kb, int* M_out, int* n_iter_out, double* hist_h, size_t cap,
                                       int* n_svd_out) {
-    if (!kb || !kb->lob_hist) return DFTK_MI_EINVAL;
+    if (!kb || kb->lob_hist.empty()) return DFTK_MI_EINVAL;
     if (M_out) *M_out = kb->lob_hist_M;
     if (n_iter_out) *n_iter_out = kb->lob_hist_iters;
     if (n_svd_out) *n_svd_out = kb->lob_n_svd;
     if (hist_h) {
-        if (cap < kb->lob_hist->size()) return DFTK_MI_EINVAL;
-        std::copy(kb->lob_hist->begin(), kb->lob_hist->end(), hist_h);
+        if (cap < kb->lob_hist.size()) return DFTK_MI_EINVAL;
+        std::copy(kb->lob_hist.begin(), kb->lob_hist.end(), hist_h);
     }
     return 0;
 }
@@ -1521,7 +1457,7 @@ extern "C" int dftk_mi_columnwise_norms(dftk_mi_basis* b, int64_t n, int m, cons
     if (m == 0) return 0;
     HIPCHK(hipSetDevice(b->device));
     CHK(ensure_ws(b, (size_t)m * sizeof(double)));
-    double* d = reinterpret_cast<double*>(b->ws);
+    double* d = reinterpret_cast<double*>(b->ws.get());
     CHK(ew_colnorms(b, n, m, reinterpret_cast<const cd*>(X_d), ldx, d));
     return fetch(b, d, norms_h, m);
 }
@@ -1532,7 +1468,7 @@ extern "C" int dftk_mi_columnwise_dots(dftk_mi_basis* b, int64_t n, int m, const
     if (m == 0) return 0;
     HIPCHK(hipSetDevice(b->device));
     CHK(ensure_ws(b, 2 * (size_t)m * sizeof(double)));
-    double* d = reinterpret_cast<double*>(b->ws);
+    double* d = reinterpret_cast<double*>(b->ws.get());
     CHK(ew_coldots(b, n, m, reinterpret_cast<const cd*>(A_d), lda, reinterpret_cast<const cd*>(B_d), ldb, d));
     CHK(ew_coldots_im(b, n, m, reinterpret_cast<const cd*>(A_d), lda, reinterpret_cast<const cd*>(B_d), ldb, d + m));
     std::vector<double> h(2 * (size_t)m);
@@ -1558,7 +1494,7 @@ extern "C" int dftk_mi_tpa_precondprep(dftk_mi_kblock* kb, int m, const dftk_mi_
     dftk_mi_basis* b = kb->basis;
     HIPCHK(hipSetDevice(b->device));
     CHK(ensure_ws(b, (size_t)m * sizeof(double)));
-    double* d = reinterpret_cast<double*>(b->ws);
+    double* d = reinterpret_cast<double*>(b->ws.get());
     CHK(ew_weighted_colsums(b, kb->n_G, m, reinterpret_cast<const cd*>(X_d), ldx, kb->d_kin, d));
     return fetch(b, d, mean_kin_h, m);
 }
@@ -1570,7 +1506,7 @@ extern "C" int dftk_mi_tpa_ldiv(dftk_mi_kblock* kb, int m, const dftk_mi_cplx* R
     dftk_mi_basis* b = kb->basis;
     HIPCHK(hipSetDevice(b->device));
     CHK(ensure_ws(b, 2 * (size_t)m * sizeof(double)));
-    double* d = reinterpret_cast<double*>(b->ws);
+    double* d = reinterpret_cast<double*>(b->ws.get());
     if (mean_kin_h) {
         HIPCHK(hipMemcpyAsync(d, mean_kin_h, m * sizeof(double), hipMemcpyHostToDevice, b->stream));
         HIPCHK(hipStreamSynchronize(b->stream));
@@ -1589,7 +1525,7 @@ extern "C" int dftk_mi_block_residual(dftk_mi_kblock* kb, int m, const dftk_mi_c
     dftk_mi_basis* b = kb->basis;
     HIPCHK(hipSetDevice(b->device));
     CHK(ensure_ws(b, 4 * (size_t)m * sizeof(double)));
-    double* d = reinterpret_cast<double*>(b->ws);
+    double* d = reinterpret_cast<double*>(b->ws.get());
     HIPCHK(hipMemcpyAsync(d, lambda_h, m * sizeof(double), hipMemcpyHostToDevice, b->stream));
     CHK(ew_residual(b, kb->n_G, m, reinterpret_cast<const cd*>(AX_d), lda, reinterpret_cast<const cd*>(X_d), ldx, d,
                     reinterpret_cast<cd*>(R_d), ldr, d + m, kb->d_kin, d + 2 * m, d + 3 * m));

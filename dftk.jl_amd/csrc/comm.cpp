@@ -85,24 +85,17 @@ const int NCCL_F64 = 8, NCCL_SUM = 0;   // ncclFloat64 / ncclSum (nccl.h enums, 
 }  // namespace
 
 struct dftk_mi_comm {
-    int backend;   // 0 = RCCL, 1 = host callbacks
-    ncclComm_t_ comm;
-    int n_ranks, rank, device;
-    dftk_mi_allreduce_fn allreduce;
-    dftk_mi_alltoallv_fn alltoallv;
-    void* user;
-    double* stage[2];   // pinned host staging buffers (host back end), grown on demand
-    size_t stage_bytes[2];
+    int backend = 0;   // 0 = RCCL, 1 = host callbacks
+    ncclComm_t_ comm = nullptr;
+    int n_ranks = 0, rank = 0, device = 0;
+    dftk_mi_allreduce_fn allreduce = nullptr;
+    dftk_mi_alltoallv_fn alltoallv = nullptr;
+    void* user = nullptr;              // borrowed
+    PinnedBuf<double> stage[2];        // pinned host staging buffers (host back end), grown on demand
 };
 
 static int stage_ensure(dftk_mi_comm* c, int which, size_t bytes) {
-    if (bytes <= c->stage_bytes[which]) return 0;
-    if (c->stage[which]) HIPCHK(hipHostFree(c->stage[which]));
-    c->stage[which] = nullptr;
-    c->stage_bytes[which] = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    HIPCHK(hipHostMalloc((void**)&c->stage[which], want));
-    c->stage_bytes[which] = want;
+    HIPCHK(c->stage[which].reserve(bytes, bytes / 4 + 4096));
     return 0;
 }
 
@@ -123,7 +116,6 @@ extern "C" int dftk_mi_comm_init_rank(const char id[128], int n_ranks, int rank,
     ncclUniqueId_t uid;
     memcpy(uid.internal, id, 128);
     dftk_mi_comm* c = new dftk_mi_comm();
-    memset(c, 0, sizeof(*c));
     c->backend = 0;
     c->n_ranks = n_ranks;
     c->rank = rank;
@@ -141,7 +133,6 @@ extern "C" int dftk_mi_comm_create_host(int n_ranks, int rank, int device, dftk_
                                         dftk_mi_alltoallv_fn alltoallv, void* user, dftk_mi_comm** out) {
     if (!out || n_ranks < 1 || rank < 0 || rank >= n_ranks || !allreduce) return DFTK_MI_EINVAL;
     dftk_mi_comm* c = new dftk_mi_comm();
-    memset(c, 0, sizeof(*c));
     c->backend = 1;
     c->n_ranks = n_ranks;
     c->rank = rank;
@@ -156,8 +147,6 @@ extern "C" int dftk_mi_comm_create_host(int n_ranks, int rank, int device, dftk_
 extern "C" int dftk_mi_comm_destroy(dftk_mi_comm* c) {
     if (!c) return 0;
     if (c->backend == 0 && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-    for (int i = 0; i < 2; ++i)
-        if (c->stage[i]) hipHostFree(c->stage[i]);
     delete c;
     return 0;
 }

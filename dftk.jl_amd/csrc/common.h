@@ -6,6 +6,8 @@
 #include <string>
 #include <map>
 #include <vector>
+#include <memory>
+#include "devbuf.h"
 #include "../../include/dftk_mi355x.h"
 
 typedef double2 cd;   // complex fp64, (x, y) = (re, im); layout-compatible with dftk_mi_cplx
@@ -27,8 +29,8 @@ inline hipError_t dftk_counted_stream_sync(hipStream_t s) {
     } while (0)
 
 void dftk_set_error(const char* fmt, ...);
-// hipMalloc for library-owned scratch; DFTK_MI_POISON=1 fills it with 0xFF bytes (NaN doubles) so that any read
-// of scratch that was not written in the current call shows up as a non-finite result (debugging aid)
+// hipMalloc for library-owned scratch (behind DevBuf, devbuf.h); DFTK_MI_POISON=1 fills it with 0xFF bytes (NaN doubles) so
+// that any read of scratch that was not written in the current call shows up as a non-finite result (debugging aid)
 hipError_t dftk_scratch_malloc(void** p, size_t bytes);
 
 #define HIPCHK(expr)                                                                      \
@@ -120,37 +122,48 @@ int  plan_radices(int n, int* nrad, int* rad);          // host: factorise into 
 void plan_positions(int n, int nrad, const int* rad, int* pos);
 
 // ------------------------------------------------------------------------------------ handles
+// Ownership: every device / pinned allocation of a handle is a Buf member (devbuf.h) and every host container a plain
+// std::vector, so that deleting the handle releases all of it; members commented "borrowed" are raw pointers into memory of
+// the caller or of another handle.
+struct StreamOwner {     // the basis' stream: declared before every buffer of the basis, so destroyed after them
+    hipStream_t s = nullptr;
+    StreamOwner() = default;
+    StreamOwner(const StreamOwner&) = delete;
+    StreamOwner& operator=(const StreamOwner&) = delete;
+    ~StreamOwner() { if (s) hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
 struct dftk_mi_basis {
-    int nx, ny, nz, nxp;          // nxp = nx rounded up to a multiple of FFT_L (padded x pitch)
-    double volume;
-    int device;
-    hipStream_t stream;
-    FftAxis ax[3];                // x, y, z
-    void* d_tables[6];            // device tw/pos buffers (owned)
-    int fft_batch;                // bands per launch group
+    int nx = 0, ny = 0, nz = 0, nxp = 0;   // nxp = nx rounded up to a multiple of FFT_L (padded x pitch)
+    double volume = 0.0;
+    int device = 0;
+    StreamOwner stream;
+    FftAxis ax[3] = {};           // x, y, z (tw / pos point into d_tables)
+    DevTable<void> d_tables[6];   // device tw/pos buffers
+    int fft_batch = 0;            // bands per launch group
     // scratch pool (grown on demand)
-    cd* T1; size_t T1_bytes;
-    cd* T2; size_t T2_bytes;
+    DevBuf<cd> T1;
+    DevBuf<cd> T2;
     // general workspace for dense algebra (split-K slabs, small matrices)
-    void* ws; size_t ws_bytes;
-    double* d_scalars;            // small device buffer for reductions (256 doubles)
-    double* h_scalars;            // pinned host mirror
-    char* h_fetch;                // pinned, device-visible landing zone of host_fetch() (zero-copy device -> host results)
-    int use_mfma;                 // 0 => naive GEMM kernels (env DFTK_MI_GEMM=naive)
-    struct Prof* prof;            // per-family HIP-event timing (dftk_mi_prof_*)
+    DevBuf<void> ws;
+    DevTable<double> d_scalars;   // small device buffer for reductions (256 doubles)
+    PinnedBuf<double> h_scalars;  // pinned host mirror
+    Buf<char, Mem::PinnedMapped> h_fetch;   // device-visible landing zone of host_fetch() (zero-copy device -> host results)
+    int use_mfma = 0;             // 0 => naive GEMM kernels (env DFTK_MI_GEMM=naive)
+    std::unique_ptr<struct Prof> prof;      // per-family HIP-event timing (dftk_mi_prof_*)
     // workspace of the dense factorizations (heev ping-pong copies, rotation buffers); owned by the basis so
-    // that several bases / devices in one process never share it (freed in dftk_mi_basis_destroy)
-    void* dense_ws; size_t dense_ws_bytes;
+    // that several bases / devices in one process never share it
+    DevBuf<void> dense_ws;
     // workspace of the partial-spectrum eigensolver (eig_kernels.hip): its iterates live across calls into the routines
     // that use dense_ws (Cholesky, Jacobi on the projected matrix), so it cannot share that buffer
-    void* eig_ws; size_t eig_ws_bytes;
-    struct dftk_mi_comm* comm;    // plane-wave (row-slab) communicator of a sharded k-block, or null (borrowed)
-    // device copy of the symmetry tables of the last cube_symmetrize call (owned; keyed by a hash of the operations: an SCF
+    DevBuf<void> eig_ws;
+    struct dftk_mi_comm* comm = nullptr;    // plane-wave (row-slab) communicator of a sharded k-block, or null (borrowed)
+    // device copy of the symmetry tables of the last cube_symmetrize call (keyed by a hash of the operations: an SCF
     // symmetrises with the same group every step -- no upload and no host synchronisation after the first call)
-    void* symm_tab; uint64_t symm_key; int symm_n;
+    DevTable<void> symm_tab; uint64_t symm_key = 0; int symm_n = 0;
     // workspace of the Sternheimer solver (sternheimer.cpp): its blocks live across calls into the H apply (T1 / T2), the
     // zgemm (ws) and nothing of a k-block's LOBPCG state, so it shares none of those buffers
-    void* resp_ws; size_t resp_ws_bytes;
+    DevBuf<void> resp_ws;
 };
 
 // ------------------------------------------------------------------------------------ profiling
@@ -196,6 +209,16 @@ struct Prof {
     double ms[PROF_NFAM] = {0};
     double work[PROF_NFAM] = {0};
     int64_t launches[PROF_NFAM] = {0};
+    Prof() = default;
+    Prof(const Prof&) = delete;
+    Prof& operator=(const Prof&) = delete;
+    ~Prof() {                           // (prof_resolve has moved every pair of `pending` into the pool)
+        for (auto* v : {&pending, &pool})
+            for (auto& pr : *v) {
+                hipEventDestroy(pr.a);
+                hipEventDestroy(pr.b);
+            }
+    }
 };
 int prof_begin(dftk_mi_basis* b, int fam, double work, uint64_t tag = 0);   // returns slot index or -1
 void prof_end(dftk_mi_basis* b, int slot);
@@ -221,76 +244,80 @@ int host_fetch(dftk_mi_basis* b, void* dst_h, const void* src_d, size_t bytes);
 struct GammaReal {
     bool on = false;              // dftk_mi_lobpcg iterates in the half-sphere format
     int64_t n_half = 0;           // (n_G + 1) / 2
-    int *d_g = nullptr, *d_mg = nullptr;   // [n_half] sphere rows of G_j and -G_j (j = 0: G = 0)
-    double* d_kin_half = nullptr;
-    cd* P_half = nullptr;         // n_half x n_p, scaled like the vectors (built on first use)
-    const cd* P_src = nullptr;
+    DevTable<int> d_g, d_mg;      // [n_half] sphere rows of G_j and -G_j (j = 0: G = 0)
+    DevTable<double> d_kin_half;
+    DevTable<cd> P_half;          // n_half x n_p, scaled like the vectors (built on first use)
+    const cd* P_src = nullptr;    // borrowed: the kb->P that P_half was built from
     int P_n_p = 0;
-    cd* buf = nullptr;            // pack / unpack scratch
-    size_t buf_bytes = 0;
+    DevBuf<cd> buf;               // pack / unpack scratch
     // plane-wave sharded block: rank r owns the half-format rows [half_rows[r], half_rows[r + 1]) (split evenly);
     // P_half is then this rank's slab of the half-format projectors
     std::vector<int64_t> half_rows;
 };
 
 struct dftk_mi_kblock {
-    dftk_mi_basis* basis;
-    int device;                   // copy of basis->device (destroy must not touch the basis)
-    int64_t n_G;
-    int64_t n_lines;              // non-empty x-lines (iy, iz)
-    int nzx;                      // distinct z planes touched by the sphere
-    int z_lo;                     // the sphere planes are {0 .. z_lo-1} u {nz-(nzx-z_lo) .. nz-1} (always so for a sphere
+    dftk_mi_basis* basis = nullptr;   // borrowed
+    int device = 0;               // copy of basis->device (destroy must not touch the basis)
+    int64_t n_G = 0;
+    int64_t n_lines = 0;          // non-empty x-lines (iy, iz)
+    int nzx = 0;                  // distinct z planes touched by the sphere
+    int z_lo = 0;                 // the sphere planes are {0 .. z_lo-1} u {nz-(nzx-z_lo) .. nz-1} (always so for a sphere
                                   // of G vectors; -1 otherwise: the register-resident z kernels then stay off)
-    // device tables (owned)
-    int*   d_cpos;                // [n_G]   pos_x[ix] of each coefficient
-    int*   d_line_start;          // [n_lines+1] first coefficient of each line
-    int*   d_line_ypos;           // [n_lines] pos_y[iy] of each line
-    int*   d_zls;                 // [nzx+1] first line of each z plane
-    int*   d_zpos;                // [nzx]   pos_z[iz] of each plane
-    int*   d_zval;                // [nzx]   iz of each plane (natural index)
-    int*   d_line_yval;           // [n_lines] iy of each line (natural index)
-    int*   d_cx;                  // [n_G]   ix of each coefficient (natural index)
-    double* d_kin;                // [n_G]
-    double* d_Vs;                 // [nz*ny*nxp] potential / N, padded pitch (owned, or shared: Vs_share) or null
-    struct SharedVs* Vs_share;    // non-null: d_Vs is the buffer of this reference-counted object (dftk_mi_kblocks_set_potential)
+    // device tables
+    DevTable<int> d_cpos;         // [n_G]   pos_x[ix] of each coefficient
+    DevTable<int> d_line_start;   // [n_lines+1] first coefficient of each line
+    DevTable<int> d_line_ypos;    // [n_lines] pos_y[iy] of each line
+    DevTable<int> d_zls;          // [nzx+1] first line of each z plane
+    DevTable<int> d_zpos;         // [nzx]   pos_z[iz] of each plane
+    DevTable<int> d_zval;         // [nzx]   iz of each plane (natural index)
+    DevTable<int> d_line_yval;    // [n_lines] iy of each line (natural index)
+    DevTable<int> d_cx;           // [n_G]   ix of each coefficient (natural index)
+    DevTable<double> d_kin;       // [n_G]
+    // [nz*ny*nxp] potential / N, padded pitch: the block's own buffer, or (Vs_shared) the one buffer held by all blocks of a
+    // dftk_mi_kblocks_set_potential call; the last holder to let go frees it
+    std::shared_ptr<DevTable<double>> Vs_buf;
+    bool Vs_shared = false;       // attached by dftk_mi_kblocks_set_potential (stays set when the other holders have left)
+    double* d_Vs = nullptr;       // the potential the kernels apply (borrowed: Vs_buf, or d_dVs while the LOBPCG start applies
+                                  // V_new - V_old), or null
     // nonlocal
-    int n_p;
-    const cd* P;                  // borrowed device pointer, n_G x n_p
-    int64_t ldP;
-    double* d_D;                  // [n_p*n_p] dense (owned)
-    int D_bw;                     // half bandwidth of D
-    // LOBPCG workspace (owned, grown on demand)
-    cd* lob_buf; size_t lob_bytes;
-    cd* last_AX;
+    int n_p = 0;
+    const cd* P = nullptr;        // borrowed device pointer, n_G x n_p
+    int64_t ldP = 0;
+    DevTable<double> d_D;         // [n_p*n_p] dense
+    int D_bw = 0;                 // half bandwidth of D
+    // LOBPCG workspace (grown on demand)
+    DevBuf<cd> lob_buf;
+    cd* last_AX = nullptr;        // borrowed (points into lob_buf)
     // A X of the last dftk_mi_lobpcg exit in the driver's own format (general driver; points into lob_buf), its shape, and the
     // padded potential that was bound then: the next call may start from A_new X = A_old X + (V_new - V_old) X instead of a
     // full H X (dftk_mi_kblock_reuse_AX: kinetic and nonlocal parts do not change between SCF steps)
-    cd* ax_keep; int ax_M; int64_t ax_rows; int64_t ax_ld;
-    double* d_Vs_ax;              // [nz*ny*nxp] snapshot of d_Vs at that exit (owned)
-    double* d_dVs;                // [nz*ny*nxp] scratch: V_new - V_old (owned)
-    bool ax_reuse_next;           // the caller's one-shot promise: X0 of the next call IS the X returned by the last one
+    cd* ax_keep = nullptr; int ax_M = 0; int64_t ax_rows = 0; int64_t ax_ld = 0;   // ax_keep: borrowed (into lob_buf)
+    DevTable<double> d_Vs_ax;     // [nz*ny*nxp] snapshot of d_Vs at that exit
+    DevTable<double> d_dVs;       // [nz*ny*nxp] scratch: V_new - V_old
+    bool ax_reuse_next = false;   // the caller's one-shot promise: X0 of the next call IS the X returned by the last one
     // y-planes (stage-B output, the layout of T2) of the band pairs of the block the general driver returned last, written
     // by the Gamma-real density pass over that block instead of into the recycled scratch: the kept-A X start of the next
     // call applies (V_new - V_old) from stage C on.  Un-sharded, un-batched Gamma-real blocks only.
-    const cd* ret_X; int64_t ret_ld; int ret_M;   // where the last general-driver call left its X (null: none since, or not eligible)
-    cd* planes; size_t planes_bytes;              // pair p in slot p, nzx * ny * nxp elements each (owned, allocated on first use)
-    bool planes_on;                               // the slots belong to ret_X: planes_valid[p] tells which were written
-    bool planes_declined;                         // the device had no room for the buffer: the feature stays off for this block
-    int planes_batch;                             // basis->fft_batch of the density pass (the launch groups the valid bits follow)
-    std::vector<char>* planes_valid;              // [(ret_M + 1) / 2] (owned)
+    const cd* ret_X = nullptr; int64_t ret_ld = 0; int ret_M = 0;   // where the last general-driver call left its X (borrowed;
+                                                                    // null: none since, or not eligible)
+    DevTable<cd> planes;                          // pair p in slot p, nzx * ny * nxp elements each (allocated on first use)
+    bool planes_on = false;                       // the slots belong to ret_X: planes_valid[p] tells which were written
+    bool planes_declined = false;                 // the device had no room for the buffer: the feature stays off for this block
+    int planes_batch = 0;                         // basis->fft_batch of the density pass (the launch groups the valid bits follow)
+    std::vector<char> planes_valid;               // [(ret_M + 1) / 2]
     // plane-wave (row-slab) sharding of this block over a communicator (dftk_mi_kblock_set_shard): orbital blocks
     // handed to apply_H / lobpcg / density_accumulate and the projector matrix are the rows
     // [sh_rows[rank], sh_rows[rank + 1]) of the sphere; the sphere tables / potential above stay complete
-    dftk_mi_comm* sh_comm;           // borrowed; null = not sharded
-    std::vector<int64_t>* sh_rows;   // [n_ranks + 1] row offsets (owned)
-    cd* sh_buf; size_t sh_bytes;     // transpose buffers (owned, grown on demand)
-    // residual history of the last dftk_mi_lobpcg call: hist[i + M * it], it = 0 .. n_iter (host, owned)
-    std::vector<double>* lob_hist; int lob_hist_M, lob_hist_iters, lob_n_svd;
+    dftk_mi_comm* sh_comm = nullptr; // borrowed; null = not sharded
+    std::vector<int64_t> sh_rows;    // [n_ranks + 1] row offsets
+    DevBuf<cd> sh_buf;               // transpose buffers (grown on demand)
+    // residual history of the last dftk_mi_lobpcg call: hist[i + M * it], it = 0 .. n_iter (host; empty: no call yet)
+    std::vector<double> lob_hist; int lob_hist_M = 0, lob_hist_iters = 0, lob_n_svd = 0;
     // host copies of the sphere (pair tables of the Gamma-real format are built from them on demand)
-    std::vector<int64_t>* h_mapping;
-    std::vector<double>* h_kin;
-    GammaReal* gr;                   // owned; null until dftk_mi_kblock_set_gamma_real / density_accumulate_real
-    int32_t* d_G3;                   // [3 n_G] integer G of every sphere row (owned; built by the first forces call)
+    std::vector<int64_t> h_mapping;
+    std::vector<double> h_kin;
+    std::unique_ptr<GammaReal> gr;   // null until dftk_mi_kblock_set_gamma_real / density_accumulate_real
+    DevTable<int32_t> d_G3;          // [3 n_G] integer G of every sphere row (built by the first forces call)
 };
 
 // ------------------------------------------------------------------------------------ internal API
@@ -326,9 +353,15 @@ int launch_kinetic_only(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi
 int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alpha, const cd* A,
           int64_t lda, const cd* B, int64_t ldb, cd beta, cd* C, int64_t ldc, int upper = 0);
 int ensure_ws(dftk_mi_basis* b, size_t bytes);
-// api.cpp: if *have < need: synchronise the stream, free *buf, dftk_scratch_malloc exactly `need` bytes, record them
-// (the contents are not kept)
-int scratch_grow(dftk_mi_basis* b, void** buf, size_t* have, size_t need);
+// grow a buffer that work on the basis' stream may still use: if `need` exceeds what it holds, synchronise the stream, then
+// reserve (exactly `need` bytes unless `slack` adds some; the contents are not kept; a failure leaves the owner empty)
+template <class B>
+int scratch_grow(dftk_mi_basis* b, B& buf, size_t need, size_t slack = 0) {
+    if (need <= buf.bytes()) return 0;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(buf.reserve(need, slack));
+    return 0;
+}
 
 // dense_kernels.hip
 int dense_potrf_trtri(dftk_mi_basis* b, int n, cd* A, int64_t lda, cd* invR, int64_t ldi,
@@ -443,7 +476,6 @@ int list_projector_columns(int n_species, const double* rp_h, const int* nproj_h
 int gamma_tables_host(int nx, int ny, int nz, int64_t n_G, const int64_t* mapping, int64_t* n_half_out, int32_t* g,
                       int32_t* mg);
 int gamma_enable(dftk_mi_kblock* kb, int on);
-void gamma_destroy(GammaReal* gr);
 int gamma_compress(dftk_mi_kblock* kb, int m, const cd* X, int64_t ldx, cd* H, int64_t ldh);
 // ... after rotating every column by the global phase that maximises its real-symmetric part (LOBPCG entry)
 int gamma_compress_aligned(dftk_mi_kblock* kb, int m, const cd* X, int64_t ldx, cd* H, int64_t ldh);
@@ -464,6 +496,7 @@ int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64
 int64_t gamma_local_rows(const dftk_mi_kblock* kb);     // half-format rows held by this rank
 int64_t gamma_row0(const dftk_mi_kblock* kb);
 int gamma_projectors(dftk_mi_kblock* kb);               // half-format projectors of this rank (built on first use)
+int gamma_projectors_renew(dftk_mi_kblock* kb, size_t elems);   // shared start of a rebuild: sync, release, allocate
 // api.cpp: the plane-wave sharded variants (slab <-> band all-to-alls around the local building blocks) and the
 // entry / exit conversions of dftk_mi_lobpcg (caller's full-sphere block <-> half-format block, sharded or not)
 int gamma_apply_H_sharded(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t ldpsi, cd* Hpsi, int64_t ldH);

@@ -254,10 +254,8 @@ int cube_symmetrize(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, cons
     mix(tau_h, 3 * (size_t)n_sym * sizeof(double));
     if (!(b->symm_tab && b->symm_key == key && b->symm_n == n_sym)) {
         HIPCHK(hipStreamSynchronize(b->stream));
-        if (b->symm_tab) HIPCHK(hipFree(b->symm_tab));
-        b->symm_tab = nullptr;
-        HIPCHK(hipMalloc(&b->symm_tab, tab + 64));
-        double* t_tau = reinterpret_cast<double*>(b->symm_tab);
+        HIPCHK(b->symm_tab.alloc(tab + 64));
+        double* t_tau = static_cast<double*>(b->symm_tab.get());
         int* t_invS = reinterpret_cast<int*>(t_tau + 3 * (size_t)n_sym);
         int* t_S = t_invS + 9 * (size_t)n_sym;
         HIPCHK(hipMemcpy(t_tau, tau_h, 3 * (size_t)n_sym * sizeof(double), hipMemcpyHostToDevice));
@@ -266,10 +264,10 @@ int cube_symmetrize(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, cons
         b->symm_key = key;
         b->symm_n = n_sym;
     }
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd)));
-    cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+    CHK(scratch_grow(b, b->dense_ws, 2 * (size_t)N * sizeof(cd)));
+    cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
     cd* c2 = c1 + N;
-    const double* d_tau = reinterpret_cast<const double*>(b->symm_tab);
+    const double* d_tau = reinterpret_cast<const double*>(b->symm_tab.get());
     const int* d_invS = reinterpret_cast<const int*>(d_tau + 3 * (size_t)n_sym);
     const int* d_S = d_invS + 9 * (size_t)n_sym;
     CHK(cube_forward_real(cube_kb, rho_in, nullptr, c1, c2));                       // c2 = F[rho]
@@ -286,8 +284,8 @@ int cube_fourier_filter(dftk_mi_kblock* cube_kb, int kind, const double* recip_h
     int64_t N;
     CHK(check_cube(cube_kb, &N));
     dftk_mi_basis* b = cube_kb->basis;
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd)));
-    cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+    CHK(scratch_grow(b, b->dense_ws, 2 * (size_t)N * sizeof(cd)));
+    cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
     cd* c2 = c1 + N;
     CHK(cube_forward_real(cube_kb, f, nullptr, c1, c2));
     const Lat9 L = make_lat(recip_h);

@@ -1145,7 +1145,7 @@ int host_fetch(dftk_mi_basis* b, void* dst_h, const void* src_d, size_t bytes) {
     const size_t words = bytes / 4;
     const unsigned blocks = (unsigned)std::min<size_t>(32, (words + 255) / 256);
     hipLaunchKernelGGL(k_fetch_words, dim3(blocks), dim3(256), 0, b->stream, reinterpret_cast<const uint32_t*>(src_d),
-                       reinterpret_cast<uint32_t*>(b->h_fetch), words);
+                       reinterpret_cast<uint32_t*>(b->h_fetch.get()), words);
     HIPCHK(hipGetLastError());
     CHK(host_wait(b));
     std::memcpy(dst_h, b->h_fetch, bytes);
@@ -1226,8 +1226,8 @@ int dense_potrf_trtri(dftk_mi_basis* b, int n, cd* A, int64_t lda, cd* invR, int
     if (coop) {
         const int nb = (n + CCB - 1) / CCB, np = nb * CCB;
         const size_t need = ((size_t)nb * np * CCB + (size_t)nb * CCB * CCB) * sizeof(cd) + 64 * sizeof(int);
-        CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, need));
-        cd* Lbuf = reinterpret_cast<cd*>(b->dense_ws);
+        CHK(scratch_grow(b, b->dense_ws, need));
+        cd* Lbuf = reinterpret_cast<cd*>(b->dense_ws.get());
         cd* Wbuf = Lbuf + (size_t)nb * np * CCB;
         int* flags = reinterpret_cast<int*>(Wbuf + (size_t)nb * CCB * CCB);
         HIPCHK(hipMemsetAsync(flags, 0, 64 * sizeof(int), b->stream));
@@ -1349,8 +1349,8 @@ static int heev_impl(dftk_mi_basis* b, int n, cd* A, int64_t lda, double* W_h, c
     const size_t szW = (size_t)np * np * sizeof(cd);
     const size_t szU = (size_t)npairs * J2B * J2B * sizeof(cd);
     const size_t total = 3 * szW + 2 * szU + (size_t)np * (sizeof(double) + sizeof(int)) + 4096 * sizeof(double);
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, total));   // per basis: one stream, one device
-    char* base = reinterpret_cast<char*>(b->dense_ws);
+    CHK(scratch_grow(b, b->dense_ws, total));   // per basis: one stream, one device
+    char* base = reinterpret_cast<char*>(b->dense_ws.get());
     ET* W = reinterpret_cast<ET*>(base);
     ET* Vw = reinterpret_cast<ET*>(base + szW);
     ET* Wb[2] = {W, reinterpret_cast<ET*>(base + 2 * szW)};
@@ -1524,8 +1524,8 @@ static int heev_impl(dftk_mi_basis* b, int n, cd* A, int64_t lda, double* W_h, c
 
 int dense_input_norms(dftk_mi_basis* b, int n, const cd* A, int64_t lda, double* off2_out, double* dg2_out, double* im2_out) {
     const int redblocks = 64;
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 4096 * sizeof(double)));
-    double* d_red = reinterpret_cast<double*>(b->dense_ws);
+    CHK(scratch_grow(b, b->dense_ws, 4096 * sizeof(double)));
+    double* d_red = reinterpret_cast<double*>(b->dense_ws.get());
     hipLaunchKernelGGL(k_offdiag_norm<cd>, dim3(redblocks), dim3(256), 0, b->stream, n, A, lda, d_red);
     std::vector<double> hred(3 * redblocks);
     CHK(host_fetch(b, hred.data(), d_red, hred.size() * sizeof(double)));

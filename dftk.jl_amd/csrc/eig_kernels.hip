@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void k_eig_tall_to_cd(int n, const cd* __restr
 }
 
 int ws_ensure(dftk_mi_basis* b, size_t bytes) {
-    return scratch_grow(b, &b->eig_ws, &b->eig_ws_bytes, bytes);
+    return scratch_grow(b, b->eig_ws, bytes);
 }
 
 double a_of(double l) { return std::sqrt(3.0 / (1.0 + l + l * l)); }
@@ -227,7 +227,7 @@ static int heev_lowest_impl(dftk_mi_basis* b, int n, int nev, cd* A, int64_t lda
     const size_t n_cd = 3 * szTall + szY + 3 * szB + (REAL ? (size_t)n * kcap : 0) + 4 * szK;
     const size_t n_dbl = 3 * (size_t)n + 2 * (size_t)ntile + 64;
     CHK(ws_ensure(b, n_cd * sizeof(cd) + n_dbl * sizeof(double) + (size_t)n * sizeof(int) + 256));
-    cd* w = reinterpret_cast<cd*>(b->eig_ws);
+    cd* w = reinterpret_cast<cd*>(b->eig_ws.get());
     auto take = [&](size_t c) {
         cd* r = w;
         w += c;

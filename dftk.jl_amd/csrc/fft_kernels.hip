@@ -1124,18 +1124,8 @@ static size_t lds_bytes(int n, int ls = FFT_LS_YZ) { return (size_t)n * (ls + 1)
 int fft_ensure_scratch(dftk_mi_basis* b, dftk_mi_kblock* kb, int nb) {
     const size_t t1 = (size_t)nb * kb->n_lines * b->nxp * sizeof(cd);
     const size_t t2 = (size_t)nb * kb->nzx * b->ny * b->nxp * sizeof(cd);
-    if (t1 > b->T1_bytes) {
-        if (b->T1) HIPCHK(hipFree(b->T1));
-        b->T1 = nullptr;
-        HIPCHK(dftk_scratch_malloc((void**)&b->T1, t1));
-        b->T1_bytes = t1;
-    }
-    if (t2 > b->T2_bytes) {
-        if (b->T2) HIPCHK(hipFree(b->T2));
-        b->T2 = nullptr;
-        HIPCHK(dftk_scratch_malloc((void**)&b->T2, t2));
-        b->T2_bytes = t2;
-    }
+    HIPCHK(b->T1.reserve(t1));
+    HIPCHK(b->T2.reserve(t2));
     return 0;
 }
 
@@ -1417,7 +1407,7 @@ static int band_groups(dftk_mi_kblock* kb, int nb, int slots, const double* wa_h
     double* d = nullptr;
     if (wa_h) {
         CHK(ensure_ws(b, 2 * (size_t)nb * sizeof(double)));
-        d = reinterpret_cast<double*>(b->ws);
+        d = reinterpret_cast<double*>(b->ws.get());
         HIPCHK(hipMemcpyAsync(d, wa_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
         if (wb_h) HIPCHK(hipMemcpyAsync(d + nb, wb_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
     }
@@ -1536,7 +1526,7 @@ int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, con
         const FftPipe p = kblock_pipe(kb, nbb, 0, keep_planes ? kb->planes + (int64_t)b0 * s2 : nullptr);
         CHK(stage_A(p, psi + (int64_t)b0 * ldpsi, ldpsi));
         CHK(stage_B(p));
-        if (keep_planes) std::fill_n(kb->planes_valid->begin() + b0, nbb, (char)1);
+        if (keep_planes) std::fill_n(kb->planes_valid.begin() + b0, nbb, (char)1);
         return stage_density(p, w_d, wim_d, rho);
     });
 }

@@ -162,8 +162,8 @@ int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, 
     CHK(check_species_grouped("forces_local", n_species, n_atoms, species_of_atom_h));
     if (n_atoms == 0) return 0;
     // R(G): forward cube DFT of the total density (unnormalised), in the dense workspace as atomic_superposition uses it
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd)));
-    cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+    CHK(scratch_grow(b, b->dense_ws, 2 * (size_t)N * sizeof(cd)));
+    cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
     cd* c2 = c1 + N;
     CHK(launch_real_to_cplx(b, N, rho_d, c1));
     CHK(launch_fft_from_cube(cube_kb, c1, c2));          // (c1 is overwritten by the transform)
@@ -275,17 +275,17 @@ __global__ __launch_bounds__(256) void k_nl_contract(int n_p, int nb, const cd* 
 int ensure_G3(dftk_mi_kblock* kb) {
     if (kb->d_G3) return 0;
     dftk_mi_basis* b = kb->basis;
-    if (!kb->h_mapping) return DFTK_MI_EINVAL;
+    if (kb->h_mapping.empty()) return DFTK_MI_EINVAL;
     const int nx = b->nx, ny = b->ny, nz = b->nz;
     std::vector<int> G((size_t)3 * kb->n_G);
     for (int64_t c = 0; c < kb->n_G; ++c) {
-        const int64_t lin = (*kb->h_mapping)[c];
+        const int64_t lin = kb->h_mapping[c];
         const int ix = (int)(lin % nx), iy = (int)((lin / nx) % ny), iz = (int)(lin / ((int64_t)nx * ny));
         G[3 * c + 0] = signed_freq(ix, nx);
         G[3 * c + 1] = signed_freq(iy, ny);
         G[3 * c + 2] = signed_freq(iz, nz);
     }
-    HIPCHK(hipMalloc((void**)&kb->d_G3, G.size() * sizeof(int)));
+    HIPCHK(kb->d_G3.alloc(G.size() * sizeof(int)));
     HIPCHK(hipMemcpy(kb->d_G3, G.data(), G.size() * sizeof(int), hipMemcpyHostToDevice));
     return 0;
 }
@@ -303,9 +303,9 @@ int forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int nb, const cd
     if (nb == 0 || kb->n_p == 0) return 0;
     if (!psi || !weight_h) return DFTK_MI_EINVAL;
     const bool sharded = kb->sh_comm != nullptr;
-    const int64_t full_rows = sharded ? (*kb->sh_rows)[comm_rank(kb->sh_comm) + 1] - (*kb->sh_rows)[comm_rank(kb->sh_comm)]
+    const int64_t full_rows = sharded ? kb->sh_rows[comm_rank(kb->sh_comm) + 1] - kb->sh_rows[comm_rank(kb->sh_comm)]
                                       : kb->n_G;
-    const int64_t full_row0 = sharded ? (*kb->sh_rows)[comm_rank(kb->sh_comm)] : 0;
+    const int64_t full_row0 = sharded ? kb->sh_rows[comm_rank(kb->sh_comm)] : 0;
     if (ld_psi < full_rows) return DFTK_MI_EINVAL;
     const bool gamma = kb->gr && kb->gr->on;
     if (gamma && (kcoord_h[0] != 0.0 || kcoord_h[1] != 0.0 || kcoord_h[2] != 0.0)) return DFTK_MI_EINVAL;
@@ -322,7 +322,7 @@ int forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int nb, const cd
     const int n_p = kb->n_p;
     // band chunk: panel (rows x 4 cb) + products (n_p x 4 cb) in the basis scratch T1 (free outside the FFT pipeline)
     const size_t per_band = 4 * (size_t)(rows + n_p) * sizeof(cd);
-    const size_t budget = std::max(b->T1_bytes, (size_t)512 << 20);
+    const size_t budget = std::max(b->T1.bytes(), (size_t)512 << 20);
     const int cb = (int)std::max<size_t>(1, std::min<size_t>((size_t)nb, budget / per_band));
     cd *Z, *Q;
     double *d_w, *d_acc;
@@ -330,7 +330,7 @@ int forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int nb, const cd
     WsCarver ws;
     ws.take(&Z, (size_t)rows * 4 * cb), ws.take(&Q, (size_t)n_p * 4 * cb), ws.take(&d_w, (size_t)nb);
     ws.take(&d_acc, (size_t)(3 * n_atoms + 1)), ws.take(&d_cs, (size_t)(n_atoms + 1));
-    CHK(scratch_grow(b, (void**)&b->T1, &b->T1_bytes, ws.bytes()));
+    CHK(scratch_grow(b, b->T1, ws.bytes()));
     ws.bind(b->T1);
     HIPCHK(hipMemcpyAsync(d_w, weight_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemcpyAsync(d_cs, col_start_h, (size_t)(n_atoms + 1) * sizeof(int), hipMemcpyHostToDevice, b->stream));

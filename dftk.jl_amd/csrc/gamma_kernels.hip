@@ -353,24 +353,25 @@ int gamma_enable(dftk_mi_kblock* kb, int on) {
         kb->gr->on = true;
         return 0;
     }
-    if (!kb->h_mapping || !kb->h_kin) return DFTK_MI_EINVAL;
+    if (kb->h_mapping.empty() || kb->h_kin.empty()) return DFTK_MI_EINVAL;
     std::vector<int32_t> g((size_t)(kb->n_G + 1) / 2 + 1), mg(g.size());
     int64_t nh = 0;
-    CHK(gamma_tables_host(b->nx, b->ny, b->nz, kb->n_G, kb->h_mapping->data(), &nh, g.data(), mg.data()));
+    CHK(gamma_tables_host(b->nx, b->ny, b->nz, kb->n_G, kb->h_mapping.data(), &nh, g.data(), mg.data()));
     std::vector<double> kin((size_t)nh);
     for (int64_t j = 0; j < nh; ++j) {
-        const double a = (*kb->h_kin)[g[j]], c = (*kb->h_kin)[mg[j]];
+        const double a = kb->h_kin[g[j]], c = kb->h_kin[mg[j]];
         if (std::fabs(a - c) > 1e-12 * (1.0 + std::fabs(a))) {
             dftk_set_error("gamma_real: kinetic energies of G and -G differ (k != 0?)");
             return DFTK_MI_EINVAL;
         }
         kin[j] = a;
     }
-    GammaReal* gr = kb->gr ? kb->gr : new GammaReal();   // (gamma_density may have created the scratch holder)
+    std::unique_ptr<GammaReal> fresh(kb->gr ? nullptr : new GammaReal());   // (gamma_density may have created the scratch holder)
+    GammaReal* gr = kb->gr ? kb->gr.get() : fresh.get();
     gr->n_half = nh;
-    HIPCHK(hipMalloc((void**)&gr->d_g, nh * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&gr->d_mg, nh * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&gr->d_kin_half, nh * sizeof(double)));
+    HIPCHK(gr->d_g.alloc(nh * sizeof(int)));
+    HIPCHK(gr->d_mg.alloc(nh * sizeof(int)));
+    HIPCHK(gr->d_kin_half.alloc(nh * sizeof(double)));
     HIPCHK(hipMemcpy(gr->d_g, g.data(), nh * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(gr->d_mg, mg.data(), nh * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(gr->d_kin_half, kin.data(), nh * sizeof(double), hipMemcpyHostToDevice));
@@ -380,7 +381,6 @@ int gamma_enable(dftk_mi_kblock* kb, int on) {
         const int p = comm_size(kb->sh_comm);
         if (nh < p) {
             dftk_set_error("gamma_real: more ranks than half-sphere rows");
-            if (!kb->gr) delete gr;
             return DFTK_MI_EINVAL;
         }
         gr->half_rows.assign(p + 1, 0);
@@ -388,34 +388,26 @@ int gamma_enable(dftk_mi_kblock* kb, int on) {
         for (int r = 0; r < p; ++r) gr->half_rows[r + 1] = gr->half_rows[r] + base + (r < rem ? 1 : 0);
     }
     gr->on = true;
-    kb->gr = gr;
+    if (fresh) kb->gr = std::move(fresh);
     return 0;
 }
 
 int64_t gamma_local_rows(const dftk_mi_kblock* kb) {
-    const GammaReal* gr = kb->gr;
+    const GammaReal* gr = kb->gr.get();
     if (!kb->sh_comm) return gr->n_half;
     const int r = comm_rank(kb->sh_comm);
     return gr->half_rows[r + 1] - gr->half_rows[r];
 }
 int64_t gamma_row0(const dftk_mi_kblock* kb) { return kb->sh_comm ? kb->gr->half_rows[comm_rank(kb->sh_comm)] : 0; }
 
-void gamma_destroy(GammaReal* gr) {
-    if (!gr) return;
-    void* ptrs[] = {gr->d_g, gr->d_mg, gr->d_kin_half, gr->P_half, gr->buf};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    delete gr;
-}
-
 int gamma_ensure_buf(dftk_mi_kblock* kb, size_t elems) {
-    GammaReal* gr = kb->gr;
-    return scratch_grow(kb->basis, (void**)&gr->buf, &gr->buf_bytes, elems * sizeof(cd));
+    GammaReal* gr = kb->gr.get();
+    return scratch_grow(kb->basis, gr->buf, elems * sizeof(cd));
 }
 
 int gamma_compress(dftk_mi_kblock* kb, int m, const cd* X, int64_t ldx, cd* H, int64_t ldh) {
     if (m <= 0) return 0;
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     ProfScope prof_scope(kb->basis, PROF_EW, 48.0 * (double)gr->n_half * m);
     hipLaunchKernelGGL(k_gr_compress, gr_grid_unr(gr->n_half, m), dim3(256), 0, kb->basis->stream, gr->n_half, gr->d_g,
                        gr->d_mg, X, ldx, H, ldh);
@@ -425,7 +417,7 @@ int gamma_compress(dftk_mi_kblock* kb, int m, const cd* X, int64_t ldx, cd* H, i
 
 int gamma_compress_aligned(dftk_mi_kblock* kb, int m, const cd* X, int64_t ldx, cd* H, int64_t ldh) {
     if (m <= 0) return 0;
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     ProfScope prof_scope(kb->basis, PROF_EW, 64.0 * (double)gr->n_half * m);
     hipLaunchKernelGGL(k_gr_compress_aligned, dim3(m), dim3(GRA_NT), 0, kb->basis->stream, gr->n_half, gr->d_g, gr->d_mg, X, ldx,
                        H, ldh);
@@ -435,7 +427,7 @@ int gamma_compress_aligned(dftk_mi_kblock* kb, int m, const cd* X, int64_t ldx, 
 
 int gamma_expand(dftk_mi_kblock* kb, int m, const cd* H, int64_t ldh, cd* X, int64_t ldx) {
     if (m <= 0) return 0;
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     ProfScope prof_scope(kb->basis, PROF_EW, 48.0 * (double)gr->n_half * m);
     hipLaunchKernelGGL(k_gr_expand, gr_grid_unr(gr->n_half, m), dim3(256), 0, kb->basis->stream, gr->n_half, gr->d_g,
                        gr->d_mg, H, ldh, X, ldx);
@@ -446,9 +438,9 @@ int gamma_expand(dftk_mi_kblock* kb, int m, const cd* H, int64_t ldh, cd* X, int
 // half-format projectors (built on first use after dftk_mi_kblock_set_projectors); refuses projectors that are
 // not Fourier transforms of real functions
 int gamma_gather_P(dftk_mi_kblock* kb, int ncols, const cd* P, int64_t ldP, cd* Ph, int64_t ldh, double* asym_mag_h) {
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     dftk_mi_basis* b = kb->basis;
-    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(b->d_scalars);
+    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(b->d_scalars.get());
     HIPCHK(hipMemsetAsync(d_out, 0, 2 * sizeof(unsigned long long), b->stream));
     if (ncols > 0) {
         hipLaunchKernelGGL(k_gr_gather_P, gr_grid(gr->n_half, ncols), dim3(256), 0, b->stream, gr->n_half, gr->d_g,
@@ -460,22 +452,25 @@ int gamma_gather_P(dftk_mi_kblock* kb, int ncols, const cd* P, int64_t ldP, cd* 
     return 0;
 }
 
+// a rebuild of the half-format projectors (local or sharded) starts here: wait for the work that reads the old copy, let it
+// go, allocate `elems` elements
+int gamma_projectors_renew(dftk_mi_kblock* kb, size_t elems) {
+    HIPCHK(hipStreamSynchronize(kb->basis->stream));
+    HIPCHK(kb->gr->P_half.alloc(elems * sizeof(cd)));
+    return 0;
+}
+
 static int gr_projectors(dftk_mi_kblock* kb) {
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     if (gr->P_src == kb->P && gr->P_n_p == kb->n_p && gr->P_half) return 0;
     if (kb->sh_comm) return gamma_projectors_sharded(kb);
-    dftk_mi_basis* b = kb->basis;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (gr->P_half) HIPCHK(hipFree(gr->P_half));
-    gr->P_half = nullptr;
-    HIPCHK(hipMalloc((void**)&gr->P_half, (size_t)gr->n_half * kb->n_p * sizeof(cd)));
+    CHK(gamma_projectors_renew(kb, (size_t)gr->n_half * kb->n_p));
     double h[2];
     CHK(gamma_gather_P(kb, kb->n_p, kb->P, kb->ldP, gr->P_half, gr->n_half, h));
     if (!(std::isfinite(h[1]) && h[0] <= 1e-10 * (h[1] > 0 ? h[1] : 1.0))) {
         dftk_set_error("gamma_real: the projectors are not real-symmetric (max |P(-G) - conj P(G)| = %.3e, max |P| = %.3e)",
                        h[0], h[1]);
-        HIPCHK(hipFree(gr->P_half));
-        gr->P_half = nullptr;
+        gr->P_half.reset();
         return DFTK_MI_EINVAL;
     }
     gr->P_src = kb->P;
@@ -487,7 +482,7 @@ int gamma_projectors(dftk_mi_kblock* kb) { return gr_projectors(kb); }
 
 int gamma_pack_pairs(dftk_mi_kblock* kb, int nb, const cd* H, int64_t ldh, cd* Z, int64_t ldz) {
     if (nb <= 0) return 0;
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     ProfScope prof_scope(kb->basis, PROF_EW, 32.0 * (double)gr->n_half * nb);
     hipLaunchKernelGGL(k_gr_pack, gr_grid_unr(gr->n_half, (nb + 1) / 2), dim3(256), 0, kb->basis->stream, gr->n_half, nb,
                        gr->d_g, gr->d_mg, H, ldh, Z, ldz);
@@ -496,7 +491,7 @@ int gamma_pack_pairs(dftk_mi_kblock* kb, int nb, const cd* H, int64_t ldh, cd* Z
 }
 int gamma_unpack_pairs(dftk_mi_kblock* kb, int nb, const cd* W, int64_t ldw, cd* H, int64_t ldh) {
     if (nb <= 0) return 0;
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     ProfScope prof_scope(kb->basis, PROF_EW, 32.0 * (double)gr->n_half * nb);
     hipLaunchKernelGGL(k_gr_unpack, gr_grid_unr(gr->n_half, (nb + 1) / 2), dim3(256), 0, kb->basis->stream, gr->n_half, nb,
                        gr->d_g, gr->d_mg, W, ldw, H, ldh);
@@ -516,7 +511,7 @@ int gamma_pack_full(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Z,
 int gamma_apply_H(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t ldpsi, cd* Hpsi, int64_t ldH) {
     if (nb <= 0) return 0;
     if (kb->sh_comm) return gamma_apply_H_sharded(kb, which, nb, psi, ldpsi, Hpsi, ldH);
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     dftk_mi_basis* b = kb->basis;
     const int nb2 = (nb + 1) / 2;
     const bool local = (which & 1) && kb->d_Vs != nullptr;
@@ -550,8 +545,7 @@ int gamma_apply_H(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t 
 int gamma_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho) {
     if (nb <= 0) return 0;
     if (!kb->gr) {                       // only the scratch buffer of the structure is needed here
-        kb->gr = new GammaReal();
-        kb->gr->on = false;
+        kb->gr.reset(new GammaReal());
     }
     if (kb->sh_comm) return gamma_density_sharded(kb, nb, psi, ldpsi, w_h, rho);
     return gamma_density_bands(kb, nb, psi, ldpsi, w_h, rho);
@@ -574,23 +568,18 @@ static int planes_prepare(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldp
         return 0;
     const size_t nb2 = (size_t)(nb + 1) / 2;
     const size_t need = nb2 * (size_t)kb->nzx * b->ny * b->nxp * sizeof(cd);
-    if (need > kb->planes_bytes) {
+    if (need > kb->planes.bytes()) {
         HIPCHK(hipStreamSynchronize(b->stream));
-        if (kb->planes) HIPCHK(hipFree(kb->planes));
-        kb->planes = nullptr;
-        kb->planes_bytes = 0;
+        HIPCHK(kb->planes.reset());
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        if (free_b < 2 * need + ((size_t)1 << 30) || hipMalloc((void**)&kb->planes, need) != hipSuccess) {
+        if (free_b < 2 * need + ((size_t)1 << 30) || kb->planes.reserve(need) != hipSuccess) {
             (void)hipGetLastError();
-            kb->planes = nullptr;
             kb->planes_declined = true;
             return 0;
         }
-        kb->planes_bytes = need;
     }
-    if (!kb->planes_valid) kb->planes_valid = new std::vector<char>();
-    kb->planes_valid->assign(nb2, 0);
+    kb->planes_valid.assign(nb2, 0);
     kb->planes_batch = b->fft_batch;
     *keep = true;
     return 0;
@@ -616,7 +605,7 @@ int gamma_density_bands(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi
 bool gamma_planes_ready(const dftk_mi_kblock* kb, int M) {
     return planes_wanted() && kb->planes_on && kb->planes != nullptr && kb->ret_M == M && kb->gr && kb->gr->on &&
            !kb->sh_comm && !batching() && kb->planes_batch == kb->basis->fft_batch &&
-           kb->planes_valid->size() == (size_t)(M + 1) / 2;
+           kb->planes_valid.size() == (size_t)(M + 1) / 2;
 }
 
 // The local part of H psi (the bound potential) in the half-sphere format for the nb bands whose y-planes the density pass
@@ -624,7 +613,7 @@ bool gamma_planes_ready(const dftk_mi_kblock* kb, int M) {
 // first, from the caller's full-format block X (the block those planes belong to).  The planes are consumed.
 int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Hpsi, int64_t ldH) {
     if (nb <= 0) return 0;
-    GammaReal* gr = kb->gr;
+    GammaReal* gr = kb->gr.get();
     dftk_mi_basis* b = kb->basis;
     const int nb2 = (nb + 1) / 2;
     kb->planes_on = false;
@@ -639,7 +628,7 @@ int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64
     cd* W = gr->buf + (size_t)kb->n_G * nb2;
     prof_count(b, PROF_A2A_MODEL, 16.0 * (double)gr->n_half * nb);   // (as gamma_apply_H: what a sharded run of the call moves)
     prof_count(b, PROF_A2A_MODEL, 16.0 * (double)gr->n_half * nb);
-    const std::vector<char>& valid = *kb->planes_valid;
+    const std::vector<char>& valid = kb->planes_valid;
     const int group = fft_group_size(b);
     for (int b0 = 0; b0 < nb2; b0 += group) {
         const int nbb = std::min(group, nb2 - b0);

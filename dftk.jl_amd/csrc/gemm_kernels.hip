@@ -559,15 +559,7 @@ extern "C" int dftk_mi_diag_mfma_peak(dftk_mi_basis* b, int waves_per_simd, int 
 }
 
 int ensure_ws(dftk_mi_basis* b, size_t bytes) {
-    if (bytes <= b->ws_bytes) return 0;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (b->ws) HIPCHK(hipFree(b->ws));
-    b->ws = nullptr;
-    b->ws_bytes = 0;
-    size_t want = bytes + bytes / 4;
-    HIPCHK(dftk_scratch_malloc(&b->ws, want));
-    b->ws_bytes = want;
-    return 0;
+    return scratch_grow(b, b->ws, bytes, bytes / 4);
 }
 
 // ---------------------------------------------------------------------------------------- planning
@@ -833,8 +825,8 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
     const size_t bytesI = spI.nsplit > 1 ? (size_t)spI.nsplit * plane : 0;
     const size_t bytesB = spB.nsplit > 1 ? (size_t)spB.nsplit * plane : 0;
     if (bytesI + bytesB) CHK(ensure_ws(b, bytesI + bytesB));
-    if (bytesI) spI.slab = (cd*)b->ws;
-    if (bytesB) spB.slab = (cd*)((char*)b->ws + bytesI);
+    if (bytesI) spI.slab = (cd*)b->ws.get();
+    if (bytesB) spB.slab = (cd*)((char*)b->ws.get() + bytesI);
     auto launch = [&](int mode, int gm_s, int gn_s, int rt0, int ct0, int lsplit, const Split& sp) -> int {
         if (gm_s <= 0 || gn_s <= 0) return 0;
         const bool zmajor = sp.zmajor;

@@ -662,14 +662,10 @@ struct Lob {
         // the y-planes of the returned X go the same way: this call uses them at its start or not at all
         kept_planes = kept_AX != nullptr && real_mode && comm == nullptr && gamma_planes_ready(kb, M);
         planes_drop(kb);
-        if (need > kb->lob_bytes) {
+        if (need > kb->lob_buf.bytes()) {
             CHK(host_wait(b));
-            if (kb->lob_buf) HIPCHK(hipFree(kb->lob_buf));
-            kb->lob_buf = nullptr;
-            kb->lob_bytes = 0;
-            kept_AX = nullptr;               // (it lived in the buffer that has just gone)
-            HIPCHK(dftk_scratch_malloc((void**)&kb->lob_buf, need));
-            kb->lob_bytes = need;
+            kept_AX = nullptr;               // (it lives in the buffer that goes now)
+            HIPCHK(kb->lob_buf.reserve(need));
         }
         cd* w = kb->lob_buf;
         auto take = [&](size_t n) {
@@ -926,10 +922,9 @@ struct Lob {
             resid_h[i] = RH(perm[i], final_iter);
         }
         for (int i = 0; i < n_conv_check; ++i) maxres = std::max(maxres, resid_h[i]);
-        if (!kb->lob_hist) kb->lob_hist = new std::vector<double>();
-        kb->lob_hist->assign((size_t)M * (final_iter + 1), 0.0);
+        kb->lob_hist.assign((size_t)M * (final_iter + 1), 0.0);
         for (int it = 0; it <= final_iter; ++it)
-            for (int i = 0; i < M; ++i) (*kb->lob_hist)[(size_t)i + (size_t)M * it] = RH(perm[i], it);
+            for (int i = 0; i < M; ++i) kb->lob_hist[(size_t)i + (size_t)M * it] = RH(perm[i], it);
         kb->lob_hist_M = M;
         kb->lob_hist_iters = final_iter;
         kb->lob_n_svd = c.n_svd;
@@ -944,12 +939,12 @@ struct Lob {
 int lobpcg_ortho(dftk_mi_basis* b, int64_t n, int m, cd* X, int64_t ldx, int force_svd, int* n_chol, int* used_svd) {
     if (m <= 0) return 0;
     const size_t elems = (size_t)n * m + 4 * (size_t)m * m;
-    void* buf = nullptr;
-    HIPCHK(hipMalloc(&buf, elems * sizeof(cd) + 2 * (size_t)(m + 8) * sizeof(double)));
+    DevTable<cd> buf;
+    HIPCHK(buf.alloc(elems * sizeof(cd) + 2 * (size_t)(m + 8) * sizeof(double)));
     Ctx c;
     c.kb = nullptr;
     c.b = b;
-    cd* w = reinterpret_cast<cd*>(buf);
+    cd* w = buf;
     cd* tmp = w;
     c.O = w + (size_t)n * m;
     c.Rw = c.O + (size_t)m * m;
@@ -964,7 +959,6 @@ int lobpcg_ortho(dftk_mi_basis* b, int64_t n, int m, cd* X, int64_t ldx, int for
     double gr = 1.0;
     int st = ortho_X(c, Mat{X, ldx, n, m}, tmp, 2 * EPS, &nch, &gr, true, n, force_svd != 0);
     if (st == 0 && hipStreamSynchronize(b->stream) != hipSuccess) st = DFTK_MI_EHIP;
-    hipFree(buf);
     if (n_chol) *n_chol = nch;
     if (used_svd) *used_svd = c.n_svd;
     return st;
@@ -985,11 +979,11 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
     }
     // a sharded block works on this rank's row slab of every n_G-sized array (see Ctx::reduce_*)
     dftk_mi_comm* comm = (kb->sh_comm && comm_size(kb->sh_comm) > 1) ? kb->sh_comm : nullptr;
-    const int64_t row0 = comm ? (*kb->sh_rows)[comm_rank(comm)] : 0;
+    const int64_t row0 = comm ? kb->sh_rows[comm_rank(comm)] : 0;
     // Gamma-real block: iterate on the half-sphere images of real-symmetric vectors (the caller's X is projected
     // onto that subspace on entry and expanded back to the full sphere on exit)
     const bool real_mode = kb->gr && kb->gr->on;
-    const int64_t N = real_mode ? gamma_local_rows(kb) : comm ? (*kb->sh_rows)[comm_rank(comm) + 1] - row0 : kb->n_G;
+    const int64_t N = real_mode ? gamma_local_rows(kb) : comm ? kb->sh_rows[comm_rank(comm) + 1] - row0 : kb->n_G;
     const double* kin = !use_tpa ? nullptr : real_mode ? kb->gr->d_kin_half + gamma_row0(kb) : kb->d_kin + row0;
     auto apply_H = [&](int nb, const cd* in, int64_t ldin, cd* out, int64_t ldout) -> int {
         if (real_mode) return gamma_apply_H(kb, 7, nb, in, ldin, out, ldout);
@@ -1028,7 +1022,7 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
         // projector products of an H X (P' psi and P (D P' psi): 11.5 of 131 ms per late SCF step of the 1000-electron cell)
         // for one triangular product, one local-only application and two element-wise passes.
         const size_t cube = (size_t)b->nz * b->ny * b->nxp;
-        if (!kb->d_dVs) HIPCHK(hipMalloc((void**)&kb->d_dVs, cube * sizeof(double)));
+        if (!kb->d_dVs) HIPCHK(kb->d_dVs.alloc(cube * sizeof(double)));
         CHK(ew_sub_real(b, (int64_t)cube, kb->d_Vs, kb->d_Vs_ax, kb->d_dVs));
         double* const Vs_bound = kb->d_Vs;
         if (s.kept_planes) {
@@ -1147,7 +1141,7 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
     // keep A X (sorted like the returned X) and the potential it belongs to for a dftk_mi_kblock_reuse_AX start of the next call
     if (kb->d_Vs != nullptr && !batching()) {
         const size_t cube = (size_t)b->nz * b->ny * b->nxp;
-        if (!kb->d_Vs_ax) HIPCHK(hipMalloc((void**)&kb->d_Vs_ax, cube * sizeof(double)));
+        if (!kb->d_Vs_ax) HIPCHK(kb->d_Vs_ax.alloc(cube * sizeof(double)));
         HIPCHK(hipMemcpyAsync(kb->d_Vs_ax, kb->d_Vs, cube * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
         kb->ax_keep = s.AX.p;
         kb->ax_ld = s.AX.ld;

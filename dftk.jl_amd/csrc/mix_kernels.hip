@@ -326,7 +326,7 @@ extern "C" int dftk_mi_step_sums(dftk_mi_basis* b, int64_t n, const double* a_d,
                                  double* out_h) {
     if (!b || n < 1 || !a_d || (!b_d && !c_d) || !out_h) return DFTK_MI_EINVAL;
     HIPCHK(hipSetDevice(b->device));
-    double* hpart = reinterpret_cast<double*>(b->h_fetch);
+    double* hpart = reinterpret_cast<double*>(b->h_fetch.get());
     hipLaunchKernelGGL(k_step_sums, grid(), dim3(MT), 0, b->stream, n, a_d, b_d, c_d, hpart);
     HIPCHK(hipGetLastError());
     CHK(host_wait(b));
@@ -337,11 +337,11 @@ extern "C" int dftk_mi_step_sums(dftk_mi_basis* b, int64_t n, const double* a_d,
 
 // =============================================================================================== Anderson acceleration
 struct dftk_mi_anderson {
-    dftk_mi_basis* b;
-    int64_t n;
-    int m;
-    double maxcond, errorfactor;
-    double* buf;                       // (m + 1) slots of (x, r): 2 (m + 1) n doubles
+    dftk_mi_basis* b = nullptr;        // borrowed
+    int64_t n = 0;
+    int m = 0;
+    double maxcond = 0.0, errorfactor = 0.0;
+    DevBuf<double> buf;                // (m + 1) slots of (x, r): 2 (m + 1) n doubles
     std::vector<int> slots;            // history order -> slot index
     std::vector<int> free_slots;
     std::vector<double> errors;        // ||r_i||
@@ -352,29 +352,26 @@ extern "C" int dftk_mi_anderson_create(dftk_mi_basis* b, int64_t n, int m, doubl
                                        dftk_mi_anderson** out) {
     if (!b || n < 1 || m < 0 || m >= MAXK || !out) return DFTK_MI_EINVAL;
     HIPCHK(hipSetDevice(b->device));
-    dftk_mi_anderson* a = new dftk_mi_anderson();
+    std::unique_ptr<dftk_mi_anderson> a(new dftk_mi_anderson());
     a->b = b;
     a->n = n;
     a->m = m;
     a->maxcond = maxcond;
     a->errorfactor = errorfactor;
-    a->buf = nullptr;
     if (m > 0) {
-        if (dftk_scratch_malloc((void**)&a->buf, 2 * (size_t)(m + 1) * n * sizeof(double)) != hipSuccess) {
-            delete a;
+        if (a->buf.alloc(2 * (size_t)(m + 1) * n * sizeof(double)) != hipSuccess) {
             dftk_set_error("anderson_create: cannot allocate %d history entries of %lld doubles", m + 1, (long long)n);
             return DFTK_MI_EHIP;
         }
         for (int i = m; i >= 0; --i) a->free_slots.push_back(i);
     }
-    *out = a;
+    *out = a.release();
     return 0;
 }
 extern "C" int dftk_mi_anderson_destroy(dftk_mi_anderson* a) {
     if (!a) return 0;
     hipSetDevice(a->b->device);
     hipStreamSynchronize(a->b->stream);
-    if (a->buf) hipFree(a->buf);
     delete a;
     return 0;
 }
@@ -429,7 +426,7 @@ extern "C" int dftk_mi_anderson_step(dftk_mi_anderson* a, const double* x_d, dou
     int nh = (int)a->slots.size();
     // <r_i, pf> for the whole history and <pf, pf>: one kernel, partials into the pinned landing zone, one synchronisation
     for (int k = 0; k < nh; ++k) R.p[k] = slot_r(a->slots[k]);
-    double* hpart = reinterpret_cast<double*>(b->h_fetch);
+    double* hpart = reinterpret_cast<double*>(b->h_fetch.get());
     hipLaunchKernelGGL(k_anderson_dots, grid(), dim3(MT), 0, b->stream, n, pf_d, nh, R, hpart);
     HIPCHK(hipGetLastError());
     CHK(host_wait(b));
@@ -627,16 +624,16 @@ extern "C" int dftk_mi_chi0_mix(dftk_mi_kblock* cube_kb, int n_comp, const doubl
     if (n_applies) *n_applies = 0;
     if (converged) *converged = 1;
     const dim3 g = grid(), t(MT);
-    double* hpart = reinterpret_cast<double*>(b->h_fetch);
+    double* hpart = reinterpret_cast<double*>(b->h_fetch.get());
     // workspace: three complex cubes, dV, partials, then the vectors of the solver: b, x, r / w, and the Krylov basis
     // (krylovdim + 1 vectors; the buffer grows geometrically -- a solve that ends in 2-3 steps must not reserve 31 cubes)
     const size_t fixed = 3 * (size_t)N * sizeof(cd) + (size_t)N * sizeof(double) + 4 * MB * sizeof(double) + 256;
     int vcap = std::min(krylovdim + 1, 8);
     auto total_bytes = [&](int cap) { return fixed + (size_t)(3 + cap) * Nt * sizeof(double); };
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, total_bytes(vcap)));
+    CHK(scratch_grow(b, b->dense_ws, total_bytes(vcap)));
     MixWork w;
     auto bind = [&]() {
-        char* p = reinterpret_cast<char*>(b->dense_ws);
+        char* p = reinterpret_cast<char*>(b->dense_ws.get());
         w.c1 = reinterpret_cast<cd*>(p);
         w.c2 = w.c1 + N;
         w.c3 = w.c2 + N;
@@ -709,15 +706,12 @@ extern "C" int dftk_mi_chi0_mix(dftk_mi_kblock* cube_kb, int n_comp, const doubl
                 // grow the Krylov basis: new buffer, everything allocated so far moves with one device copy
                 const int ncap = std::min(krylovdim + 1, 2 * vcap);
                 const size_t old_bytes = total_bytes(vcap);
-                void* old = b->dense_ws;
                 CHK(host_wait(b));
-                void* nw = nullptr;
-                HIPCHK(dftk_scratch_malloc(&nw, total_bytes(ncap)));
-                HIPCHK(hipMemcpyAsync(nw, old, old_bytes, hipMemcpyDeviceToDevice, b->stream));
+                DevBuf<void> nw;
+                HIPCHK(nw.alloc(total_bytes(ncap)));
+                HIPCHK(hipMemcpyAsync(nw, b->dense_ws, old_bytes, hipMemcpyDeviceToDevice, b->stream));
                 CHK(host_wait(b));
-                HIPCHK(hipFree(old));
-                b->dense_ws = nw;
-                b->dense_ws_bytes = total_bytes(ncap);
+                b->dense_ws = std::move(nw);     // (frees the old buffer)
                 vcap = ncap;
                 bind();
             }

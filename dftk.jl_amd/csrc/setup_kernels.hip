@@ -122,7 +122,7 @@ int build_projectors_hgh(dftk_mi_basis* b, int64_t n_rows, const int32_t* G_d, c
     const unsigned gy = (unsigned)std::min<size_t>(cols.size(), 64);
     hipLaunchKernelGGL(k_build_projectors, dim3((unsigned)((n_rows + 255) / 256), gy), dim3(256), 0, b->stream, n_rows,
                        (int)cols.size(), G_d, make_mat3(recip_h), k_h[0], k_h[1], k_h[2], 1.0 / sqrt(volume),
-                       reinterpret_cast<const ProjCol*>(b->ws), P_d, ldP);
+                       reinterpret_cast<const ProjCol*>(b->ws.get()), P_d, ldP);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(b->stream));   // cols (host vector) and b->ws are reused by the next call
     return 0;
@@ -220,12 +220,12 @@ int atomic_superposition(dftk_mi_kblock* cube_kb, int kind, const double* recip_
     std::vector<AtomPar> atoms(n_atoms);
     for (int a = 0; a < n_atoms; ++a)
         atoms[a] = AtomPar{positions_h[3 * a], positions_h[3 * a + 1], positions_h[3 * a + 2], species_of_atom_h[a]};
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd)));
-    cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+    CHK(scratch_grow(b, b->dense_ws, 2 * (size_t)N * sizeof(cd)));
+    cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
     cd* c2 = c1 + N;
     const size_t tab = (size_t)n_atoms * sizeof(AtomPar) + (size_t)n_species * 8 * sizeof(double);
     CHK(ensure_ws(b, tab));
-    AtomPar* d_atoms = reinterpret_cast<AtomPar*>(b->ws);
+    AtomPar* d_atoms = reinterpret_cast<AtomPar*>(b->ws.get());
     double* d_par = reinterpret_cast<double*>(d_atoms + n_atoms);
     HIPCHK(hipMemcpyAsync(d_atoms, atoms.data(), (size_t)n_atoms * sizeof(AtomPar), hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemcpyAsync(d_par, par_h, (size_t)n_species * 8 * sizeof(double), hipMemcpyHostToDevice, b->stream));

@@ -128,7 +128,7 @@ int sternheimer_run(dftk_mi_kblock* kb, int n_occ, const cd* psi_occ, int64_t ld
     ws.take(&s.S, 2 * (size_t)s.nc * n_occ);
     ws.take(&s.U, (size_t)n_extra * n_occ);
     ws.take(&s.dbl, 7 * (size_t)n_occ + (size_t)n_extra + 1);
-    CHK(scratch_grow(b, &b->resp_ws, &b->resp_ws_bytes, ws.bytes()));
+    CHK(scratch_grow(b, b->resp_ws, ws.bytes()));
     ws.bind(b->resp_ws);
     s.eps_d = s.dbl;
     s.gam[0] = s.eps_d + n_occ;

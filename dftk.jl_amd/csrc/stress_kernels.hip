@@ -205,7 +205,7 @@ int stress_kinetic_nonlocal(dftk_mi_kblock* kb, const double* recip_h, const dou
     ws.take(&T, (size_t)6 * cc_max * cb), ws.take(&d_w, (size_t)nb), ws.take(&d_part, (size_t)(6 * n_atoms + 1));
     ws.take(&d_cs, (size_t)(n_atoms + 1)), ws.take(&d_cols, cols.size()), ws.take(&d_kin, (size_t)6 * kin_blocks);
     ws.take(&d_out, 6);
-    CHK(scratch_grow(b, (void**)&b->T1, &b->T1_bytes, ws.bytes()));
+    CHK(scratch_grow(b, b->T1, ws.bytes()));
     ws.bind(b->T1);
     HIPCHK(hipMemcpyAsync(d_w, weight_h, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, b->stream));
     const Mat3 B = make_mat3(recip_h);
@@ -336,8 +336,8 @@ int stress_cube(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, c
     }
     if (n_atoms < 0 || n_species < 0 || (n_atoms > 0 && (!species_of_atom_h || !positions_h || !par_h))) return DFTK_MI_EINVAL;
     CHK(check_species_grouped("stress_cube", n_species, n_atoms, species_of_atom_h));
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd)));
-    cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+    CHK(scratch_grow(b, b->dense_ws, 2 * (size_t)N * sizeof(cd)));
+    cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
     cd* c2 = c1 + N;
     CHK(launch_real_to_cplx(b, N, rho_d, c1));
     CHK(launch_fft_from_cube(cube_kb, c1, c2));

@@ -568,8 +568,8 @@ int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const 
                        "(mask %d)", fun_mask);
         return DFTK_MI_EINVAL;
     }
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd) + 3 * XC_BLOCKS * sizeof(double)));
-    cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+    CHK(scratch_grow(b, b->dense_ws, 2 * (size_t)N * sizeof(cd) + 3 * XC_BLOCKS * sizeof(double)));
+    cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
     cd* c2 = c1 + N;
     double* partial = reinterpret_cast<double*>(c2 + N);
     const double *up = rho, *dn = rho + N;
@@ -611,9 +611,9 @@ int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h
     if (!gga_mask) return local_potential_collinear(cube_kb, rho, vloc, green, fun_mask, V_out, energies_h);
     // complex cubes: c1 | F[rho_up], F[rho_down] | six gradient / flux cubes; real cubes: 6 gradients, 3 sigma, e, 2 v_rho,
     // 3 v_sigma; then the reduction partials
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes,
+    CHK(scratch_grow(b, b->dense_ws,
                      9 * (size_t)N * sizeof(cd) + 15 * (size_t)N * sizeof(double) + 3 * XC_BLOCKS * sizeof(double)));
-    cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+    cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
     cd* f2 = c1 + N;                                   // F[rho_up], F[rho_down]; later the two divergences
     cd* g6 = f2 + 2 * N;
     double* grad = reinterpret_cast<double*>(g6 + 6 * N);   // d_a rho_up (a = 0, 1, 2), d_a rho_down
@@ -677,8 +677,8 @@ int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const do
     // complex cubes c1, c2 (+ three more and 7 real cubes for GGA) + reduction partials in the basis' dense workspace
     const size_t need = (gga_mask ? 5 : 2) * (size_t)N * sizeof(cd) + (gga_mask ? 7 : 0) * (size_t)N * sizeof(double) +
                         3 * XC_BLOCKS * sizeof(double);
-    CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, need));
-    cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+    CHK(scratch_grow(b, b->dense_ws, need));
+    cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
     cd* c2 = c1 + N;
     cd* g3 = gga_mask ? c2 + N : nullptr;          // three cubes behind one another (one FFT pipeline for the three)
     double* rbase = reinterpret_cast<double*>(c2 + N + (gga_mask ? 3 * N : 0));
@@ -754,8 +754,8 @@ int apply_kernel_lda(dftk_mi_kblock* cube_kb, const double* rho, const double* d
     }
     const cd* vh = nullptr;
     if (green) {
-        CHK(scratch_grow(b, &b->dense_ws, &b->dense_ws_bytes, 2 * (size_t)N * sizeof(cd) + XC_BLOCKS * sizeof(double)));
-        cd* c1 = reinterpret_cast<cd*>(b->dense_ws);
+        CHK(scratch_grow(b, b->dense_ws, 2 * (size_t)N * sizeof(cd) + XC_BLOCKS * sizeof(double)));
+        cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
         cd* c2 = c1 + N;
         double* partial = reinterpret_cast<double*>(c2 + N);
         hipLaunchKernelGGL(k_real_to_complex, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, drho, c1);

@@ -671,6 +671,12 @@ int dftk_mi_chi0_mix(dftk_mi_kblock* cube_kblock, int n_comp, const double* reci
  * many-small-k workloads these two ARE the cost model; either pointer may be NULL. */
 int dftk_mi_launch_count(int64_t* launches, int64_t* host_syncs);
 
+/* Process-wide: the device allocations the library's handles hold right now and their bytes (every handle owns its
+ * buffers by member, so both return to their earlier values when a handle is destroyed; the staging pool of the batched
+ * k-point driver is kept for the life of the process and not counted).  Lets a test check releases exactly where the
+ * device-wide free memory of a shared machine cannot; either pointer may be NULL. */
+int dftk_mi_device_buffers_live(int64_t* count, int64_t* bytes);
+
 /* The two density-sized scalars an SCF step reads on the host besides the term energies, in one kernel and one
  * synchronisation: out_h[0] = sum_i a[i] b[i] (b_d may be NULL: 0), out_h[1] = sum_i (a[i] - c[i])^2 (c_d may be NULL: 0);
  * n doubles each, on the device.  The host mirror passes a = rho_out, b = V_in (the nonlocal energy from the Ritz values:

@@ -1395,6 +1395,21 @@ def test_host_side_orthogonalisation_of_small_ritz_coefficient_blocks():
     assert res.stdout.count("done=1") == 9 and res.stdout.count("done=0") == 2
 
 
+def test_allocation_owners_release_exactly_once_on_every_path():
+    """``Buf`` of csrc/devbuf.h -- the owner of every device and pinned allocation of the library -- through
+    tools/host_devbuf_check.cpp, which points the header's allocate / free macros at counting fakes and runs without a
+    GPU, its host code under AddressSanitizer and UBSan: alloc / reserve / reset / move keep the live counters exact, a
+    reserve that fits allocates nothing, a failed grow leaves an empty owner (null AND 0 bytes), a struct of five owners
+    whose k-th allocation fails frees exactly the k - 1 earlier ones for every k, nothing is freed twice, nothing stays."""
+    import subprocess
+    from dftk_jl_amd import _build
+    exe = _build.build_host_devbuf_check()
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, (res.returncode, res.stdout[-3000:], res.stderr[-3000:])
+    assert "host_devbuf_check OK" in res.stdout and "FAILED" not in res.stdout
+    assert "Sanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-3000:]
+
+
 def test_memory_statistics_and_plan_for_the_literal_4096_electron_cell():
     """``estimate_memory_usage`` (src/memory_usage.jl:35-87: psi_k, P_k, rho bytes and the 1 P + 2 psi + 6 psi_k + 12 rho
     peak) and the per-GPU plan of the plane-wave-sharded Gamma block: the headline 1000-electron cell fits one
