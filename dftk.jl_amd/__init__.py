@@ -13,7 +13,10 @@ from ._lib import load as load_library, DftkMiError, EXPORTED_SYMBOLS  # noqa: F
 from ._build import build as build_library  # noqa: F401
 from .psp import PspHgh, load_psp, parse_psp_hgh  # noqa: F401,E402
 from .model import (Model, ElementPsp, model_DFT, model_atomic, create_supercell, silicon_cell,  # noqa: F401,E402
-                    MonkhorstPack, ExplicitKpoints)
+                    MonkhorstPack, ExplicitKpoints, ExactExchange, PBE0, model_HF)
+from .exchange import (Coulomb, ShortRangeCoulomb, LongRangeCoulomb, SphericallyTruncatedCoulomb,  # noqa: F401,E402
+                       WignerSeitzTruncatedCoulomb, ProbeCharge, ReplaceSingularity, VoxelAveraged, VanillaExx, AceExx,
+                       compute_kernel_fourier, apply_exchange)
 from .comm import KptComm, split_evenly, distribute_kpoints  # noqa: F401,E402
 from .basis import PlaneWaveBasis, Kpoint, compute_fft_size  # noqa: F401,E402
 from .hamiltonian import DftHamiltonianBlock, mul_  # noqa: F401,E402

@@ -85,6 +85,8 @@ _SIGNATURES = {
     "dftk_mi_density_response_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, _i64, C.c_void_p,
                                                       C.c_void_p, C.c_void_p]),
     "dftk_mi_apply_kernel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dftk_mi_exx_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64,
+                                    C.c_void_p, _i64, C.c_int]),
     "dftk_mi_lobpcg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_double, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                  C.POINTER(C.c_int), C.POINTER(_i64)]),

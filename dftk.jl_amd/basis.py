@@ -167,6 +167,12 @@ class PlaneWaveBasis:
         # gamma_real: None = automatic at k = 0 (env DFTK_MI_GAMMA_REAL=0 switches it off), True = required, False = off
         if gamma_real is None and os.environ.get("DFTK_MI_GAMMA_REAL", "1") == "0":
             gamma_real = False
+        # exact exchange: the pair densities conj(phi_n) psi_m of real-symmetric orbitals are not real-symmetric blocks of
+        # the half-sphere format, and dftk_mi_exx_apply refuses Gamma-real blocks
+        if getattr(model, "exact_exchange", None) is not None:
+            if gamma_real is True:
+                raise NotImplementedError("gamma_real=True is not available for models with exact exchange")
+            gamma_real = False
         self.gamma_real = gamma_real
         self.model = model
         self.Ecut = float(Ecut)
@@ -229,6 +235,9 @@ class PlaneWaveBasis:
         (kc, kw, self.kcoords_global, self.kweights_global,
          self.krange_allprocs) = distribute_kpoints(kgrid.kcoords, kgrid.kweights, self.comm_kpts)
         self.krange_thisproc = self.krange_allprocs[self.comm_kpts.rank]
+        if getattr(model, "exact_exchange", None) is not None:     # (before any k-block is created on the device)
+            from .exchange import check_gamma_only
+            check_gamma_only(self.kcoords_global, self.comm_kpts.size, self.comm_pw.size)
         self.kweights = kw
         # Lanes: k-blocks are tiny on k-point workloads (n_G ~ 1e3, 6-8 bands: launch-latency bound), and the
         # reference loops over them sequentially (diag.jl:24).  Here the local k-points are dealt round-robin onto

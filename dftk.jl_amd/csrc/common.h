@@ -164,6 +164,9 @@ struct dftk_mi_basis {
     // workspace of the Sternheimer solver (sternheimer.cpp): its blocks live across calls into the H apply (T1 / T2), the
     // zgemm (ws) and nothing of a k-block's LOBPCG state, so it shares none of those buffers
     DevBuf<void> resp_ws;
+    // workspace of the exact-exchange apply (exx_kernels.hip): the cubes of the occupied orbitals, of a group of columns
+    // and of a group of pair densities live across calls into the sphere <-> cube pipelines (T1 / T2)
+    DevBuf<void> exx_ws;
 };
 
 // ------------------------------------------------------------------------------------ profiling
@@ -549,6 +552,8 @@ int sternheimer_run(dftk_mi_kblock* kb, int n_occ, const cd* psi_occ, int64_t ld
                     const cd* psi_extra, int64_t ld_extra, const cd* rhs, int64_t ld_rhs, const double* tol_h, int miniter,
                     int maxiter, const cd* dpsi0, int64_t ld_dpsi0, cd* dpsi, int64_t ld_dpsi, int* n_iter, double* resid_h,
                     int* converged);
+
+// exx_kernels.hip: dftk_mi_exx_apply (the entry point is the whole interface: see include/dftk_mi355x.h)
 
 // lobpcg.cpp
 // ortho!(X) (Cholesky-QR with the reference's shift-and-retry and SVD fallback) on a stand-alone block;

@@ -104,6 +104,9 @@ def lobpcg_hyper(A: DftHamiltonianBlock, X0: torch.Tensor, maxiter: int = 100, p
         raise ValueError(f"Mismatch in dimension between guess ({n_loc}) and Hamiltonian ({A.n_loc})")
     if tol is None:
         tol = 20 * A.n_G * EPS                  # diag_lobpcg_hyper.jl:6
+    if getattr(A, "exchange", None) is not None and A.exchange.psi_occ is not None:
+        raise NotImplementedError("lobpcg_hyper: the uncompressed exchange operator (VanillaExx) is applied by mul_ only; "
+                                  "build the Hamiltonian with exxalg=AceExx() to diagonalise it")
     A.bind()
     X = X0.clone().contiguous()
     lam = np.zeros(M)

@@ -16,7 +16,8 @@ from . import _lib
 from .symmetry import symmetrize_forces
 from .terms import energy_forces_ewald, local_species_tables, occupied_block, total_density
 
-_NO_FORCES = ("Kinetic", "Hartree", "PspCorrection", "Entropy")
+# (ExactExchange: a functional of the orbitals alone, no explicit dependence on the positions)
+_NO_FORCES = ("Kinetic", "Hartree", "PspCorrection", "Entropy", "ExactExchange")
 
 
 def _group_order(model):
@@ -67,6 +68,12 @@ def _forces_nonlocal(basis, psi, occupation):
             return out
         ps, w = block
         kh = np.ascontiguousarray(kpt.coordinate, dtype=np.float64)
+        if getattr(T, "exx_kernel", None) is not None:
+            # the projector slot may hold a compressed exchange operator behind P: the nonlocal term alone goes back in
+            # (the Hamiltonian block that owns the slot re-binds on its next use)
+            from .exchange import bind_projectors
+            bind_projectors(basis, ik, None)
+            kpt._exx_owner = None
         basis.pre_call()
         _lib.check(basis.lib.dftk_mi_forces_nonlocal(kpt.handle, kh.ctypes.data, len(w), ps.data_ptr(), ps.stride(0),
                                                      w.ctypes.data, n_atoms, col_start.ctypes.data, out.ctypes.data))

@@ -18,18 +18,30 @@ class DftHamiltonianBlock:
         basis._require_gpu()
         self.basis, self.kpoint = basis, kpoint
         self.potential = potential.to(torch.float64).contiguous() if potential is not None else None
+        # the exchange term of this block (exchange.ExchangeOperator; models with ExactExchange only): like the potential,
+        # the device handle holds one at a time -- in its projector slot -- and bind() puts this block's back
+        self.exchange = None
         if bind:
             self.bind(force=True)
 
     @staticmethod
-    def for_all_kpoints(basis, potential):
+    def for_all_kpoints(basis, potential, exchange=None):
         """The blocks of every local k-point for ONE summed potential (Hamiltonian.jl:36-57), bound with a single library
-        call (``dftk_mi_kblocks_set_potential``) instead of one host round trip per k-point."""
+        call (``dftk_mi_kblocks_set_potential``) instead of one host round trip per k-point.  ``exchange`` (models with
+        ExactExchange): {k-block index: ExchangeOperator}, attached BEFORE the blocks are bound, so that the projector slot is
+        set once per Hamiltonian."""
         import ctypes as C
+
+        def attach(blocks):
+            if exchange is not None:
+                for ik, b_ in enumerate(blocks):
+                    b_.exchange = exchange.get(ik)
+                    b_.kpoint._exx_owner = None
+            return blocks
         if potential is not None and potential.dim() == 4:
             # collinear spin: potential[s] belongs to the k-blocks of spin s + 1 (xc.jl:163-175: Vxc[:, :, :, kpt.spin])
             pots = [potential[s_].to(torch.float64).contiguous() for s_ in range(potential.shape[0])]
-            blocks = [DftHamiltonianBlock(basis, kpt, pots[kpt.spin - 1], bind=False) for kpt in basis.kpoints]
+            blocks = attach([DftHamiltonianBlock(basis, kpt, pots[kpt.spin - 1], bind=False) for kpt in basis.kpoints])
             basis.pre_call()
             for s_, pot_s in enumerate(pots):
                 mine = [b_ for b_ in blocks if b_.kpoint.spin == s_ + 1]
@@ -37,9 +49,10 @@ class DftHamiltonianBlock:
                 _lib.check(basis.lib.dftk_mi_kblocks_set_potential(len(mine), kbs, pot_s.data_ptr()))
             for b_ in blocks:
                 b_.kpoint._pot_owner = b_
+                b_.bind()                      # (the potential is in place: the exchange operator, if any)
             return blocks
         pot = potential.to(torch.float64).contiguous() if potential is not None else None
-        blocks = [DftHamiltonianBlock(basis, kpt, pot, bind=False) for kpt in basis.kpoints]
+        blocks = attach([DftHamiltonianBlock(basis, kpt, pot, bind=False) for kpt in basis.kpoints])
         if pot is None or len(blocks) < 2:
             for b_ in blocks:
                 b_.bind(force=True)
@@ -50,19 +63,34 @@ class DftHamiltonianBlock:
         _lib.check(basis.lib.dftk_mi_kblocks_set_potential(n, kbs, pot.data_ptr()))
         for b_ in blocks:
             b_.kpoint._pot_owner = b_
+            b_.bind()
         return blocks
 
     def bind(self, force: bool = False):
         """Make the device handle of the k-point apply THIS block's potential."""
         kpt = self.kpoint
-        if not force and kpt._pot_owner is self:
-            return
-        if self.potential is not None:
-            self.basis.pre_call()
-            _lib.check(self.basis.lib.dftk_mi_kblock_set_potential(kpt.handle, self.potential.data_ptr()))
-        else:
-            _lib.check(self.basis.lib.dftk_mi_kblock_set_potential(kpt.handle, None))
-        kpt._pot_owner = self
+        if force or kpt._pot_owner is not self:
+            if self.potential is not None:
+                self.basis.pre_call()
+                _lib.check(self.basis.lib.dftk_mi_kblock_set_potential(kpt.handle, self.potential.data_ptr()))
+            else:
+                _lib.check(self.basis.lib.dftk_mi_kblock_set_potential(kpt.handle, None))
+            kpt._pot_owner = self
+        if self._has_exchange_term() and (force or getattr(kpt, "_exx_owner", None) is not self):
+            from .exchange import bind_projectors
+            xi = self.exchange.xi if self.exchange is not None else None
+            bind_projectors(self.basis, self.basis.kpoints.index(kpt), xi)
+            kpt._exx_owner = self
+
+    def _has_exchange_term(self):
+        return getattr(self.basis.terms, "exx_kernel", None) is not None
+
+    def set_exchange(self, op):
+        """Attach the exchange operator this Hamiltonian was built with (None: no orbitals yet, the term is absent) and
+        bind it."""
+        self.exchange = op
+        self.kpoint._exx_owner = None
+        self.bind()
 
     @property
     def n_G(self):
@@ -90,6 +118,11 @@ class DftHamiltonianBlock:
         self.basis.pre_call()
         _lib.check(self.basis.lib.dftk_mi_apply_H_parts(self.kpoint.handle, which, nb, psi.data_ptr(), psi.stride(0),
                                                         Hpsi.data_ptr(), Hpsi.stride(0)))
+        if which & 4 and self.exchange is not None and self.exchange.psi_occ is not None:
+            # the uncompressed exchange operator (VanillaExx) is no projector term: its own pass, added to H psi
+            from .exchange import apply_exchange
+            apply_exchange(self.basis, self.basis.kpoints.index(self.kpoint), self.exchange.psi_occ, self.exchange.occ, psi,
+                           out=Hpsi, accumulate=True)
         self.basis.post_call(self.kpoint.lane)
         return Hpsi
 

@@ -54,7 +54,23 @@ def model_to_dict(model) -> dict:
         "n_electrons": model.n_electrons, "pseudofamily": "hgh",
         **_symmetries_to_dict(model.symmetries),
         "terms": list(model.term_types), "functionals": list(model.functionals),
+        **_hybrid_to_dict(model),
     }
+
+
+def _hybrid_to_dict(model) -> dict:
+    """What the term and functional names do not say (models with exact exchange only): the multipliers of the functionals,
+    the scaling factor and the interaction kernel of the ExactExchange term."""
+    exx = getattr(model, "exact_exchange", None)
+    if exx is None:
+        return {}
+    from dataclasses import asdict
+    kernel = exx.kernel
+    return {"functional_scales": list(model.functional_scales),
+            "exact_exchange": {"scaling_factor": float(exx.scaling_factor), "kernel": type(kernel).__name__,
+                               "kernel_parameters": {k: (v if isinstance(v, (int, float, type(None))) else
+                                                         {"type": type(getattr(kernel, k)).__name__, **v})
+                                                     for k, v in asdict(kernel).items()}}}
 
 
 def basis_to_dict(basis) -> dict:

@@ -102,6 +102,8 @@ def plan_planewave_sharded(model, Ecut, n_ranks, fft_size=None, gamma_real=True,
       kept_planes       ceil(M / 2) x T2: the y-planes the density pass keeps for the next LOBPCG start (un-sharded
                         Gamma-real block only; gamma_kernels.hip planes_prepare)
     Also returned: the per-step communication volumes of one H psi sweep and one Rayleigh-Ritz Gram all-reduce."""
+    from .exchange import refuse
+    refuse(model, "plane-wave sharding (plan_planewave_sharded)")
     from .scf import AdaptiveBands
     p = int(n_ranks)
     fft = _fft_size(model, Ecut, fft_size)

@@ -8,10 +8,11 @@ is ``symmetries=False`` (explicit lists / unreduced Monkhorst-Pack meshes).
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
+from .exchange import Coulomb
 from .psp import ATOMIC_NUMBER, PspHgh, load_psp
 
 
@@ -35,6 +36,22 @@ class ElementPsp:
         return self.charge_nuclear - self.psp.Zion
 
 
+@dataclass(frozen=True)
+class ExactExchange:
+    """``ExactExchange(; scaling_factor, kernel)`` (terms/exact_exchange.jl:19-22): the only term that carries parameters.
+    In a term list it stands for the name "ExactExchange"; the model keeps the object as ``model.exact_exchange``."""
+    scaling_factor: float = 1.0
+    kernel: object = field(default_factory=Coulomb)
+
+
+@dataclass(frozen=True)
+class PBE0:
+    """``PBE0(; exx_fraction, exx_kernel)`` (standard_models.jl): ``functionals=PBE0()`` of ``model_DFT`` expands to
+    (1 - a) gga_x_pbe + gga_c_pbe + ExactExchange(a, kernel) with a = 0.25 and the Coulomb kernel unless given."""
+    exx_fraction: float | None = None
+    exx_kernel: object = None
+
+
 def compute_recip_lattice(lattice):
     """structure.jl:24-26 (lattice vectors are columns)."""
     return 2 * math.pi * np.linalg.inv(np.asarray(lattice, dtype=float).T)
@@ -47,16 +64,26 @@ class Model:
 
     def __init__(self, lattice, atoms, positions, terms, functionals=("lda_x", "lda_c_pw"),
                  temperature=0.0, smearing=None, n_electrons=None, symmetries=False, magnetic_moments=(),
-                 spin_polarization=None):
+                 spin_polarization=None, functional_scales=None):
         self.lattice = np.asarray(lattice, dtype=float)
         self.atoms = list(atoms)
         self.positions = [np.asarray(p, dtype=float) for p in positions]
         if len(self.atoms) != len(self.positions):
             raise ValueError("Length of atoms and positions vectors need to agree.")
-        self.term_types = tuple(terms)
+        # terms are names; ExactExchange alone has parameters: the object (or the bare name: the defaults) is kept apart
+        exx = [t for t in terms if isinstance(t, ExactExchange) or t == "ExactExchange"]
+        if len(exx) > 1:
+            raise ValueError("Model with more than one ExactExchange term not supported.")
+        self.exact_exchange = (ExactExchange() if exx[0] == "ExactExchange" else exx[0]) if exx else None
+        self.term_types = tuple("ExactExchange" if isinstance(t, ExactExchange) else t for t in terms)
         if not self.term_types:
             raise ValueError("Model without terms not supported.")
         self.functionals = tuple(functionals)
+        # multiplier of every functional in the Xc term (1 unless a hybrid scales its exchange part)
+        self.functional_scales = (tuple(float(s) for s in functional_scales) if functional_scales is not None
+                                  else (1.0,) * len(self.functionals))
+        if len(self.functional_scales) != len(self.functionals):
+            raise ValueError("one scale per functional")
         self.temperature = float(temperature)
         self.smearing = smearing if smearing is not None else ("fermi_dirac" if temperature > 0 else "none")
         self.recip_lattice = compute_recip_lattice(self.lattice)
@@ -120,9 +147,20 @@ def model_atomic(lattice, atoms, positions, extra_terms=(), **kw):
 
 
 def model_DFT(lattice, atoms, positions, functionals=("lda_x", "lda_c_pw"), **kw):
-    """standard_models.jl:116-131; default functionals = ``LDA()`` (:220)."""
+    """standard_models.jl:116-131; default functionals = ``LDA()`` (:220).  ``functionals=PBE0(...)``: the hybrid."""
+    if isinstance(functionals, PBE0):
+        a = 0.25 if functionals.exx_fraction is None else float(functionals.exx_fraction)
+        kernel = Coulomb() if functionals.exx_kernel is None else functionals.exx_kernel
+        return model_atomic(lattice, atoms, positions, extra_terms=("Hartree", "Xc", ExactExchange(a, kernel)),
+                            functionals=("gga_x_pbe", "gga_c_pbe"), functional_scales=(1.0 - a, 1.0), **kw)
     return model_atomic(lattice, atoms, positions, extra_terms=("Hartree", "Xc"),
                         functionals=tuple(functionals), **kw)
+
+
+def model_HF(lattice, atoms, positions, exx_kernel=None, **kw):
+    """``model_HF`` (standard_models.jl): the atomic model + Hartree + ExactExchange(1, exx_kernel)."""
+    kernel = Coulomb() if exx_kernel is None else exx_kernel
+    return model_atomic(lattice, atoms, positions, extra_terms=("Hartree", ExactExchange(1.0, kernel)), **kw)
 
 
 def create_supercell(lattice, atoms, positions, supercell_size):

@@ -173,6 +173,8 @@ def determine_band_tolerances(alg, density_tol):
 
 # ------------------------------------------------------------------------------------------ checks
 def _check_supported(basis, q=None):
+    from .exchange import refuse
+    refuse(basis.model, "the density response (no exchange kernel term, no Sternheimer solve with the Fock operator)")
     if q is not None and np.any(np.asarray(q, dtype=float) != 0):
         raise NotImplementedError("response at q != 0 (phonons) is not implemented: q = 0 only")
     if basis.model.n_spin_components != 1:
@@ -250,6 +252,8 @@ def sternheimer_solver(Hk, psik, eps, rhs, psik_extra=None, tol=1e-9, miniter=1,
 def compute_delta_occ(basis, psi, eF, eps, dHpsi, dtemperature=0.0):
     """``compute_docc!`` (chi0.jl:314-350): the derivatives of the occupations of the given (occupied) bands and of the Fermi
     level, ``(doccupation, deF)``.  A model with a fixed Fermi level (``model.eF``) keeps it; sums run over ``comm_kpts``."""
+    from .exchange import refuse
+    refuse(basis.model, "the density response")
     from .eigen import columnwise_dots
     model = basis.model
     T, kind, filled = model.temperature, model.smearing, model.filled_occupation
@@ -409,6 +413,8 @@ def compute_delta_rho(basis, psi, dpsi, occupation, doccupation=None, occupation
 def multiply_psi_by_potential(basis, psi, dV):
     """``dV psi`` for every k-point: the local part of the H apply (``which = 1``) of a temporary block that owns ``dV``.
     The ground-state blocks re-upload their potential on their next ``bind()``."""
+    from .exchange import refuse
+    refuse(basis.model, "the density response")
     dV = dV.to(torch.float64).contiguous()
 
     def one(ik, psik):

@@ -389,10 +389,13 @@ class ScfStepper:
     scf_solvers.jl:85-98).  ``step()`` performs exactly one SCF iteration."""
 
     def __init__(self, basis, rho=None, psi=None, tol=1e-6, damping=0.8, nbandsalg=None, is_converged=None,
-                 eigensolver=lobpcg_hyper, anderson_m=10, seed=0, determine_tol=determine_diagtol, mixing=None,
-                 phase_timers=None, coarse_start=True):
+                 eigensolver=lobpcg_hyper, anderson_m=None, seed=0, determine_tol=determine_diagtol, mixing=None,
+                 phase_timers=None, coarse_start=True, exxalg=None):
         basis._require_gpu()
         self.basis = basis
+        # exact exchange: the Hamiltonian of a step is built from the previous step's orbitals (self_consistent_field.jl:207)
+        self.has_exx = getattr(basis.model, "exact_exchange", None) is not None
+        self.exxalg = exxalg
         # two-level start of the first diagonalisation when the basis carries a companion basis (basis.py; an extension)
         self.coarse_start = bool(coarse_start)
         self.phase_timers = (os.environ.get("DFTK_MI_PHASE_TIMERS") is not None) if phase_timers is None else bool(phase_timers)
@@ -400,7 +403,8 @@ class ScfStepper:
         self.mixing = mixing if mixing is not None else LdosMixing()
         # per-step nonlocal energy from the Ritz values (terms.energy_hamiltonian); the energies returned by
         # finalize() / self_consistent_field always come from the projections themselves
-        self.ritz_energies = os.environ.get("DFTK_MI_EXACT_STEP_ENERGIES") is None
+        # (off with exact exchange: the Ritz values contain the exchange operator)
+        self.ritz_energies = os.environ.get("DFTK_MI_EXACT_STEP_ENERGIES") is None and not self.has_exx
         self.gen = torch.Generator(device=basis.device)
         self.gen.manual_seed(seed + 7919 * basis.comm_kpts.rank)
         self.seed = seed
@@ -410,6 +414,12 @@ class ScfStepper:
         if determine_tol is None or determine_tol is determine_diagtol:
             determine_tol = default_diagtolalg(basis, tol)      # self_consistent_field.jl:179
         self.eigensolver, self.damping, self.determine_tol = eigensolver, damping, determine_tol
+        # anderson_m None: a history of 10 as the reference; 0 (plain damping) for models with exact exchange, where the
+        # orbitals that build the operator lag one step behind the density the accelerator extrapolates and the accelerated
+        # iteration stalls near a residual of 1e-7.  An explicit value is taken as given.
+        if anderson_m is None:
+            anderson_m = 0 if self.has_exx else 10
+        self.anderson_m = anderson_m
         from .mixing import _torch_mix
         self.accel = AndersonAcceleration(m=anderson_m) if _torch_mix() else AndersonNative(basis, m=anderson_m)
         self.sqrt_dvol = math.sqrt(basis.dvol)
@@ -440,7 +450,9 @@ class ScfStepper:
         t = time.time()
         # only the Hamiltonian of rho_in is needed here; the psi-dependent energy terms of this call
         # would be thrown away (the energies reported for the step are those of (psi_out, rho_out) below)
-        _, ham = energy_hamiltonian(basis, None, None, rho=self.rho_in, only_hamiltonian=True)
+        exx = (dict(exxalg=self.exxalg, occupation_threshold=self.nbandsalg.occupation_threshold) if self.has_exx else {})
+        _, ham = energy_hamiltonian(basis, info["psi"] if self.has_exx else None, info["occupation"] if self.has_exx else None,
+                                    rho=self.rho_in, only_hamiltonian=True, **exx)
         t = lap("energy_hamiltonian", t)
         diagtol = self.determine_tol(info["n_iter"], info["history_drho"])
         nxt = next_density(ham, self.nbandsalg, self.eigensolver, psi=info["psi"], eigenvalues=info["eigenvalues"],
@@ -454,7 +466,7 @@ class ScfStepper:
         energies, _ = energy_hamiltonian(basis, nxt["psi"], nxt["occupation"], rho=nxt["rho"], only_energies=True,
                                          eigenvalues=nxt["eigenvalues"], eF=nxt["eF"], ritz_potential=ritz_pot,
                                          ritz_occupation_threshold=self.nbandsalg.occupation_threshold,
-                                         ritz_potential_dot=None if sums is None or ritz_pot is None else sums[0])
+                                         ritz_potential_dot=None if sums is None or ritz_pot is None else sums[0], **exx)
         t = lap("energies", t)
         drho = nxt["rho"] - self.rho_in
         n_matvec_total = info["n_matvec"] + nxt["n_matvec"]
@@ -513,22 +525,26 @@ class ScfStepper:
     def finalize(self):
         info = self.info
         with self.basis.on_library_stream():
+            exx = (dict(exxalg=self.exxalg, occupation_threshold=self.nbandsalg.occupation_threshold) if self.has_exx
+                   else {})
             energies, ham = energy_hamiltonian(self.basis, info["psi"], info["occupation"], rho=info["rho"],
-                                               eigenvalues=info["eigenvalues"], eF=info["eF"])
+                                               eigenvalues=info["eigenvalues"], eF=info["eF"], **exx)
             self.basis.sync()
         info.update(energies=energies, ham=ham)
         return info
 
 
 def self_consistent_field(basis, rho=None, psi=None, tol=1e-6, maxiter=100, damping=0.8, nbandsalg=None,
-                          is_converged=None, callback=None, eigensolver=lobpcg_hyper, anderson_m=10, seed=0,
-                          determine_tol=determine_diagtol, mixing=None, coarse_start=True):
+                          is_converged=None, callback=None, eigensolver=lobpcg_hyper, anderson_m=None, seed=0,
+                          determine_tol=determine_diagtol, mixing=None, coarse_start=True, exxalg=None):
     """``self_consistent_field(basis; rho, psi, tol, maxiter, damping, nbandsalg, is_converged, callback,
-    eigensolver)`` (self_consistent_field.jl:164-289)."""
+    eigensolver, exxalg)`` (self_consistent_field.jl:164-289).  ``exxalg``: ``AceExx()`` unless given (models with exact
+    exchange; the final Hamiltonian carries the compressed operator of all computed bands).  ``anderson_m``:
+    10 unless given, 0 (plain damping) for models with exact exchange."""
     t0 = time.time()
     stepper = ScfStepper(basis, rho=rho, psi=psi, tol=tol, damping=damping, nbandsalg=nbandsalg,
                          is_converged=is_converged, eigensolver=eigensolver, anderson_m=anderson_m, seed=seed,
-                         determine_tol=determine_tol, mixing=mixing, coarse_start=coarse_start)
+                         determine_tol=determine_tol, mixing=mixing, coarse_start=coarse_start, exxalg=exxalg)
     for _ in range(maxiter):
         info = stepper.step()
         if callback is not None:

@@ -49,6 +49,8 @@ _projector_tables = projector_species_tables      # (the name this module had fo
 
 
 def _check_unsharded(basis):
+    from .exchange import refuse
+    refuse(basis.model, "the stress tensor (no exact-exchange stress term)")
     if basis.comm_pw.size > 1:
         raise NotImplementedError("stresses of a basis whose plane waves are sharded over comm_pw are not implemented")
 

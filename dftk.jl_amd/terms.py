@@ -482,6 +482,8 @@ def xc_energy_potential(basis, rho):
     """xc_potential_real (xc.jl:84-160): E = sum e dvol, V = V_rho - 2 div(V_sigma grad rho); LDA terms
     have V_sigma = 0, for GGAs grad rho and the divergence are taken in Fourier space on the cube with
     the device FFT pipeline (LibxcDensities xc.jl:356-409, divergence_real :576-584)."""
+    if any(s != 1.0 for s in getattr(basis.model, "functional_scales", ())):
+        raise NotImplementedError("scaled functionals (hybrids) need the library's local-potential pipeline")
     rc = torch.clamp(rho, min=1e-300)
     e = torch.zeros_like(rho)
     v = torch.zeros_like(rho)
@@ -636,6 +638,13 @@ def instantiate_terms(basis):
     T.E_ewald = (energy_ewald(model.lattice, [a.charge_ionic for a in model.atoms], model.positions)
                  if "Ewald" in T.names else None)
     T.E_pspcorr = energy_psp_correction(model) if "PspCorrection" in T.names else None
+    # ExactExchange (exact_exchange.jl:29-34): scaling_factor * compute_kernel_fourier on the Gamma sphere (shared by the
+    # spin blocks); the refusals of compute_kernel_fourier are raised here
+    T.exx_kernel = None
+    if "ExactExchange" in T.names:
+        from .exchange import compute_kernel_fourier
+        exx = model.exact_exchange
+        T.exx_kernel = (float(exx.scaling_factor) * compute_kernel_fourier(exx.kernel, basis)).contiguous()
     # terms that need cube FFTs can only be instantiated with the device library
     T.V_loc = T.poisson = None
     if basis.handle is not None:
@@ -690,6 +699,26 @@ _SPIN_GGA = ("gga_x_pbe", "gga_c_pbe")                   # ... through dftk_mi_l
 
 
 def local_potential_fused(basis, rho, want_potential=True, want_energies=True):
+    """``_local_potential_call`` for the model's functionals; a functional scaled by s != 1 (the exchange part of a hybrid)
+    is taken out again by a second pass over the Xc part alone, V -= (1 - s) v_f, E_xc -= (1 - s) E_f: the pipeline is
+    linear in the functionals and takes a set of them, not multipliers."""
+    model = basis.model
+    out = _local_potential_call(basis, rho, model.functionals, True, want_potential, want_energies)
+    if out is None or "Xc" not in basis.terms.names:
+        return out
+    for name, s in zip(model.functionals, getattr(model, "functional_scales", ())):
+        if s == 1.0:
+            continue
+        part = _local_potential_call(basis, rho, (name,), False, want_potential, want_energies)
+        if part is None:
+            return None
+        out["Xc"] = out["Xc"] - (1.0 - s) * part["Xc"]
+        if out["V"] is not None:
+            out["V"].sub_(part["V"], alpha=1.0 - s)
+    return out
+
+
+def _local_potential_call(basis, rho, functionals, with_local_terms, want_potential=True, want_energies=True):
     """Hartree + XC (LDA point-wise; PBE with its gradient / divergence Fourier passes) + V_loc summed into one
     potential and their three energies by ONE library call (``dftk_mi_local_potential`` / ``_gga``; a collinear density
     (rho.dim() == 4) goes to ``_collinear`` / ``_collinear_gga``: hartree.jl:50-59, xc.jl:84-160,356-409,576-584,
@@ -699,7 +728,7 @@ def local_potential_fused(basis, rho, want_potential=True, want_energies=True):
     T = basis.terms
     mask = 0
     if "Xc" in T.names:
-        for name in basis.model.functionals:
+        for name in functionals:
             if name in _LDA_BITS:
                 mask |= _LDA_BITS[name]
             elif name in _GGA_BITS:
@@ -708,16 +737,16 @@ def local_potential_fused(basis, rho, want_potential=True, want_energies=True):
                 return None
     rho = rho.to(torch.float64).contiguous()
     V = torch.empty_like(rho) if want_potential else None
-    vloc = T.V_loc if "AtomicLocal" in T.names else None
-    green = T.poisson if "Hartree" in T.names else None
+    vloc = T.V_loc if "AtomicLocal" in T.names and with_local_terms else None
+    green = T.poisson if "Hartree" in T.names and with_local_terms else None
     E3 = (C.c_double * 3)() if want_energies or not want_potential else None
     basis.pre_call()
     args = (vloc.data_ptr() if vloc is not None else None, green.data_ptr() if green is not None else None)
     if rho.dim() == 4:
         # collinear spin: (rho_up, rho_down) -> (V_up, V_down); Hartree and the local term see the total density
-        if "Xc" in T.names and any(f not in _SPIN_LDA + _SPIN_GGA for f in basis.model.functionals):
+        if "Xc" in T.names and any(f not in _SPIN_LDA + _SPIN_GGA for f in functionals):
             raise NotImplementedError(f"collinear spin: spin-polarised forms exist for {_SPIN_LDA + _SPIN_GGA} only, got "
-                                      f"{basis.model.functionals}")
+                                      f"{functionals}")
         if mask & 24:
             Bh = np.asfortranarray(basis.model.recip_lattice, dtype=np.float64)
             _lib.check(basis.lib.dftk_mi_local_potential_collinear_gga(
@@ -762,12 +791,16 @@ def smearing_entropy(kind, x):
 
 
 def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, eigenvalues=None, eF=None,
-                       ritz_potential=None, ritz_occupation_threshold=0.0, only_hamiltonian=False, ritz_potential_dot=None):
+                       ritz_potential=None, ritz_occupation_threshold=0.0, only_hamiltonian=False, ritz_potential_dot=None,
+                       exxalg=None, occupation_threshold=0.0):
     """``energy_hamiltonian(basis, psi, occupation; rho, eigenvalues, eF)`` (Hamiltonian.jl:200-227); with
     ``only_energies`` it is ``energy(...)`` (:232-236).  Returns (Energies, [DftHamiltonianBlock]).  The entropy
     term -TS (terms/entropy.jl:11-42) needs this rank's eigenvalues and the Fermi level, else it is Inf.
     ``only_hamiltonian`` (the SCF stepper's first call of a step, whose energies nobody reads): the local-potential pipeline
-    returns no energies and does not synchronise; Hartree / Xc / AtomicLocal are NaN in the returned Energies."""
+    returns no energies and does not synchronise; Hartree / Xc / AtomicLocal are NaN in the returned Energies.
+    ``exxalg`` (``AceExx()`` unless given; ``VanillaExx()``) and ``occupation_threshold``: how the exchange operator of a
+    model with ExactExchange is built from ``psi`` (exact_exchange.jl:36-58); without orbitals the term contributes E = 0 and
+    no operator, like the reference's NoopOperator."""
     basis._require_gpu()
     T = basis.terms
     E = Energies()
@@ -775,6 +808,7 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
     have_psi = psi is not None and occupation is not None
     reduce_kpts = []       # terms that are sums over this rank's k-points: ONE fused reduction at the end
     ritz_fix = None
+    exx_ops = {}            # per k-block: the exchange operator built from psi (absent: the term has no operator)
     kin_bands = []          # per k-point: kinetic energy of every band (library reduction), or None
     # local-potential pipeline behind the C ABI (LDA and PBE); DFTK_MI_TORCH_LOCAL=1 keeps the torch formulation
     # (the parity twin of tests/test_gpu_scf.py)
@@ -882,6 +916,20 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
                 reduce_kpts.append(name)
             else:
                 E[name] = math.inf
+        elif name == "ExactExchange":
+            # (no k-weight on a channel's energy, as the reference: exact_exchange.jl:55)
+            from . import exchange as _exx
+            e = 0.0
+            if have_psi and basis.model.exact_exchange.scaling_factor != 0:
+                for ik, psik in enumerate(psi):
+                    if only_energies:
+                        e += _exx.exchange_energy(basis, ik, psik, occupation[ik], occupation_threshold)
+                    else:
+                        e_k, op = _exx.exx_operator(_exx.AceExx() if exxalg is None else exxalg, basis, ik, psik,
+                                                    occupation[ik], occupation_threshold)
+                        e += e_k
+                        exx_ops[ik] = op
+            E[name] = e
         elif name == "Ewald":
             E[name] = T.E_ewald
         elif name == "PspCorrection":
@@ -922,5 +970,5 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
         E["AtomicNonlocal"] = E["AtomicNonlocal"] - (0.0 if ritz_fix[1] else E["Kinetic"]) - ritz_fix[0]
     if only_energies:
         return E, None
-    ham = DftHamiltonianBlock.for_all_kpoints(basis, pot)
+    ham = DftHamiltonianBlock.for_all_kpoints(basis, pot, exchange=exx_ops if T.exx_kernel is not None else None)
     return E, ham

@@ -329,6 +329,24 @@ int dftk_mi_density_response_accumulate(dftk_mi_kblock* kb, int n_bands, const d
 int dftk_mi_apply_kernel(dftk_mi_kblock* cube_kb, const double* rho_d, const double* drho_d, const double* poisson_green_d,
                          int xc_functionals, double* dV_d);
 
+/* ---- exact exchange at the Gamma point (src/terms/exact_exchange.jl, ExchangeOperator of src/terms/operators.jl:184-210) --
+ * The Fock operator built from n_occ orbitals phi (n_G x n_occ) applied to n_bands columns psi:
+ *     W_m (+)= - sum_n weight_h[n] FFT[ phi_n(r) IFFT[ K(G) FFT[ conj(phi_n(r)) psi_m(r) ] ] ]
+ * in the reference's normalisations (phi_n(r) = ifft(basis, kpt, phi_n), fft / ifft of the k-point: the pair density is
+ * taken on the k-block's own sphere).  weight_h[n] = occupation_n / filled_occupation; orbitals with weight 0 are skipped.
+ * kernel_d: n_G reals on the block's sphere = scaling_factor * compute_kernel_fourier (src/coulomb.jl).  accumulate = 0
+ * overwrites W, otherwise W += ...; rows beyond n_G of a column (ld > n_G) are neither read nor written.  n_bands = 0 does
+ * nothing; n_occ = 0 (or all weights 0) zero-fills W when accumulate = 0.  Asynchronous on the basis' stream.
+ * Cost: 2 pruned transforms per (orbital, column) pair.  Workspace (the basis' exchange workspace, released with the basis),
+ * in complex numbers with N = nx ny nz, g = the FFT launch group, g_phi = min(g, n_occ), g_psi = min(g, n_bands):
+ *     (c + 2 g_psi + g_phi) N + (2 g_phi + g_psi) n_G,   c = n_occ while n_occ N 16 B <= 8 GiB (the orbitals' cubes are then
+ * transformed once per call), else g_phi (they are transformed again for every group of columns).
+ * Refused with DFTK_MI_EINVAL: Gamma-real blocks, plane-wave sharded blocks, null pointers, leading dimensions below n_G.
+ * (The library's own batched multi-k drivers never call it: a guard inside refuses that too, unreachable through this ABI.) */
+int dftk_mi_exx_apply(dftk_mi_kblock* kb, int n_occ, const dftk_mi_cplx* phi_d, int64_t ld_phi, const double* weight_h,
+                      const double* kernel_d, int n_bands, const dftk_mi_cplx* psi_d, int64_t ld_psi, dftk_mi_cplx* W_d,
+                      int64_t ld_W, int accumulate);
+
 /* ---- lobpcg_hyper(A, X0; prec=PreconditionerTPA, tol, miniter, maxiter, n_conv_check)
  *      (src/eigen/diag_lobpcg_hyper.jl:5-18 -> LOBPCG, src/eigen/lobpcg_hyper_impl.jl:354-582;
  *       PreconditionerTPA src/eigen/preconditioners.jl:27-78) ----------------------------------
