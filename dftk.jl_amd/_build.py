@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libdftk_mi355x.so")
 SOURCES = ["api.cpp", "comm.cpp", "lobpcg.cpp", "batch.cpp", "batch_kernels.hip", "fft_kernels.hip", "gemm_kernels.hip", "dense_kernels.hip", "eig_kernels.hip", "xc_kernels.hip", "setup_kernels.hip", "gamma_kernels.hip", "cube_kernels.hip", "mix_kernels.hip", "force_kernels.hip", "stress_kernels.hip", "sternheimer.cpp", "response_kernels.hip", "exx_kernels.hip"]
-HEADERS = ["common.h", "devbuf.h", "batch.h", "ew_device.h", "hgh_forms.h"]     # every header under csrc/: part of both hashes below
+HEADERS = ["common.h", "devbuf.h", "handover.h", "batch.h", "ew_device.h", "hgh_forms.h"]     # every header under csrc/: part of both hashes below
 
 HASHPATH = LIBPATH + ".srchash"
 
@@ -183,9 +183,33 @@ def build_host_devbuf_check(force: bool = False) -> str:
     return DEVBUF_CHECK_BIN
 
 
+HANDOVER_CHECK_SRC = os.path.join(os.path.dirname(HERE), "tools", "host_handover_check.cpp")
+HANDOVER_CHECK_BIN = os.path.join(os.path.dirname(HERE), "tools", "bin", "host_handover_check")
+
+
+def build_host_handover_check(force: bool = False) -> str:
+    """tools/host_handover_check.cpp -> tools/bin/host_handover_check: the host-only walk through the transition table of
+    ``LobHandover`` (csrc/handover.h: what a k-block keeps between two LOBPCG calls) with fake allocate / free functions.
+    Compiled like the devbuf check (host part under AddressSanitizer and UBSan); it calls no HIP runtime function and runs
+    without a GPU."""
+    src_time = max(os.path.getmtime(p) for p in (HANDOVER_CHECK_SRC, os.path.join(CSRC, "handover.h"),
+                                                  os.path.join(CSRC, "devbuf.h")))
+    if not force and os.path.exists(HANDOVER_CHECK_BIN) and os.path.getmtime(HANDOVER_CHECK_BIN) >= src_time:
+        return HANDOVER_CHECK_BIN
+    os.makedirs(os.path.dirname(HANDOVER_CHECK_BIN), exist_ok=True)
+    cmd = [shutil.which("hipcc") or "/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "hip", "--offload-arch=gfx950",
+           "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+           "-I", CSRC, HANDOVER_CHECK_SRC, "-o", HANDOVER_CHECK_BIN, "-fsanitize=address,undefined"]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    if res.returncode != 0:
+        raise RuntimeError("hipcc failed on tools/host_handover_check.cpp:\n" + res.stdout + res.stderr)
+    return HANDOVER_CHECK_BIN
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     print(build_abi_check(force=True))
     print(build_host_ortho_check(force=True))
     print(build_host_stress_check(force=True))
     print(build_host_devbuf_check(force=True))
+    print(build_host_handover_check(force=True))

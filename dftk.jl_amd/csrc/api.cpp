@@ -489,7 +489,7 @@ extern "C" int dftk_mi_kblock_set_shard(dftk_mi_kblock* kb, dftk_mi_comm* comm, 
     if (!kb) return DFTK_MI_EINVAL;
     HIPCHK(hipSetDevice(kb->basis->device));
     HIPCHK(hipStreamSynchronize(kb->basis->stream));
-    planes_drop(kb);
+    kb->ho.forget_planes();
     if (!comm || comm_size(comm) == 1) {      // a one-rank communicator owns the whole sphere: nothing to shard
         kb->sh_comm = nullptr;
         return 0;
@@ -743,9 +743,7 @@ extern "C" int dftk_mi_kblock_set_projectors(dftk_mi_kblock* kb, int n_p, const 
     HIPCHK(kb->d_D.reset());
     kb->n_p = 0;
     kb->P = nullptr;
-    kb->ax_keep = nullptr;                  // (an A X kept by the LOBPCG driver belongs to the old nonlocal term)
-    kb->ax_reuse_next = false;
-    planes_drop(kb);
+    kb->ho.forget();                        // (an A X kept by the LOBPCG driver belongs to the old nonlocal term)
     if (kb->gr) kb->gr->P_src = nullptr;   // the half-format copy is rebuilt on its next use
     if (n_p == 0) return 0;
     if (!P_d || !D_h || ldP < local_rows(kb)) return DFTK_MI_EINVAL;
@@ -1360,12 +1358,12 @@ extern "C" int dftk_mi_fermi_bisection(int n_k, const int* n_bands, const double
 
 extern "C" int dftk_mi_kblock_reuse_AX(dftk_mi_kblock* kb, int on) {
     if (!kb) return DFTK_MI_EINVAL;
-    kb->ax_reuse_next = on != 0 && kb->ax_keep != nullptr;
+    kb->ho.promise(on != 0);
     return 0;
 }
 
 extern "C" const dftk_mi_cplx* dftk_mi_lobpcg_last_AX(dftk_mi_kblock* kb) {
-    return kb ? reinterpret_cast<const dftk_mi_cplx*>(kb->last_AX) : nullptr;
+    return kb ? reinterpret_cast<const dftk_mi_cplx*>(kb->ho.last_AX()) : nullptr;
 }
 
 // ------------------------------------------------------------------------------------ dense helpers

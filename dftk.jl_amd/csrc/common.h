@@ -8,6 +8,7 @@
 #include <vector>
 #include <memory>
 #include "devbuf.h"
+#include "handover.h"
 #include "../../include/dftk_mi355x.h"
 
 typedef double2 cd;   // complex fp64, (x, y) = (re, im); layout-compatible with dftk_mi_cplx
@@ -280,7 +281,7 @@ struct dftk_mi_kblock {
     // dftk_mi_kblocks_set_potential call; the last holder to let go frees it
     std::shared_ptr<DevTable<double>> Vs_buf;
     bool Vs_shared = false;       // attached by dftk_mi_kblocks_set_potential (stays set when the other holders have left)
-    double* d_Vs = nullptr;       // the potential the kernels apply (borrowed: Vs_buf, or d_dVs while the LOBPCG start applies
+    double* d_Vs = nullptr;       // the potential the kernels apply (borrowed: Vs_buf, or ho.dV while the LOBPCG start applies
                                   // V_new - V_old), or null
     // nonlocal
     int n_p = 0;
@@ -290,24 +291,9 @@ struct dftk_mi_kblock {
     int D_bw = 0;                 // half bandwidth of D
     // LOBPCG workspace (grown on demand)
     DevBuf<cd> lob_buf;
-    cd* last_AX = nullptr;        // borrowed (points into lob_buf)
-    // A X of the last dftk_mi_lobpcg exit in the driver's own format (general driver; points into lob_buf), its shape, and the
-    // padded potential that was bound then: the next call may start from A_new X = A_old X + (V_new - V_old) X instead of a
-    // full H X (dftk_mi_kblock_reuse_AX: kinetic and nonlocal parts do not change between SCF steps)
-    cd* ax_keep = nullptr; int ax_M = 0; int64_t ax_rows = 0; int64_t ax_ld = 0;   // ax_keep: borrowed (into lob_buf)
-    DevTable<double> d_Vs_ax;     // [nz*ny*nxp] snapshot of d_Vs at that exit
-    DevTable<double> d_dVs;       // [nz*ny*nxp] scratch: V_new - V_old
-    bool ax_reuse_next = false;   // the caller's one-shot promise: X0 of the next call IS the X returned by the last one
-    // y-planes (stage-B output, the layout of T2) of the band pairs of the block the general driver returned last, written
-    // by the Gamma-real density pass over that block instead of into the recycled scratch: the kept-A X start of the next
-    // call applies (V_new - V_old) from stage C on.  Un-sharded, un-batched Gamma-real blocks only.
-    const cd* ret_X = nullptr; int64_t ret_ld = 0; int ret_M = 0;   // where the last general-driver call left its X (borrowed;
-                                                                    // null: none since, or not eligible)
-    DevTable<cd> planes;                          // pair p in slot p, nzx * ny * nxp elements each (allocated on first use)
-    bool planes_on = false;                       // the slots belong to ret_X: planes_valid[p] tells which were written
-    bool planes_declined = false;                 // the device had no room for the buffer: the feature stays off for this block
-    int planes_batch = 0;                         // basis->fft_batch of the density pass (the launch groups the valid bits follow)
-    std::vector<char> planes_valid;               // [(ret_M + 1) / 2]
+    // what the block keeps between two dftk_mi_lobpcg calls: the A X of the last exit and the y-planes of the density pass
+    // over the block it returned (handover.h)
+    LobHandover ho;
     // plane-wave (row-slab) sharding of this block over a communicator (dftk_mi_kblock_set_shard): orbital blocks
     // handed to apply_H / lobpcg / density_accumulate and the projector matrix are the rows
     // [sh_rows[rank], sh_rows[rank + 1]) of the sphere; the sphere tables / potential above stay complete
@@ -332,8 +318,8 @@ int launch_local_apply(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi,
 int launch_ifft_to_cube(dftk_mi_kblock* kb, const cd* c, cd* cube, int nb = 1);
 int launch_fft_from_cube(dftk_mi_kblock* kb, const cd* cube, cd* c, int nb = 1);
 // w_im_h (optional): separate weights for the squared IMAGINARY parts (two real bands packed into one transform)
-// keep_planes: stage B of band i writes slot i of kb->planes instead of the scratch, and kb->planes_valid[i] is set for the
-// bands of every launch group that ran (the caller has sized both; never inside a batched call)
+// keep_planes: stage B of band i writes slot i of kb->ho.planes instead of the scratch, and every launch group that ran is
+// marked there (the caller has begun the pass and sized the buffer; never inside a batched call)
 int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho,
                    const double* w_im_h = nullptr, const double* w2_h = nullptr, double* rho2 = nullptr,
                    bool keep_planes = false);
@@ -492,9 +478,9 @@ int gamma_unpack_pairs(dftk_mi_kblock* kb, int nb, const cd* W, int64_t ldw, cd*
 int gamma_pack_full(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Z, int64_t ldz);
 int gamma_gather_P(dftk_mi_kblock* kb, int ncols, const cd* P, int64_t ldP, cd* Ph, int64_t ldh, double* asym_mag_h);
 int gamma_density_bands(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho);
-// y-planes kept by the density pass over the block the general LOBPCG driver returned (kb->planes)
-inline void planes_drop(dftk_mi_kblock* kb) { kb->planes_on = false; kb->ret_X = nullptr; }
-bool gamma_planes_ready(const dftk_mi_kblock* kb, int M);     // kept, for M bands, under today's launch-group size
+// y-planes kept by the density pass over the block the general LOBPCG driver returned (kb->ho): may this
+// block keep and use them now (DFTK_MI_PLANES_REUSE, Gamma-real format on, un-sharded, outside a batched call)?
+bool planes_eligible(const dftk_mi_kblock* kb);
 int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Hpsi, int64_t ldH);
 int64_t gamma_local_rows(const dftk_mi_kblock* kb);     // half-format rows held by this rank
 int64_t gamma_row0(const dftk_mi_kblock* kb);

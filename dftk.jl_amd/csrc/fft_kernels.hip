@@ -1200,7 +1200,7 @@ struct FftPipe {
     int64_t n_G;          // booked bytes of stages A / E
 };
 // t_off: the first of the nb scratch slots (bands) of T1 / T2 the launch group uses (after fft_ensure_scratch)
-// planes (nullable): the group's y-planes live there, band i in slot i, instead of in T2 (kb->planes: slot = band of the call)
+// planes (nullable): the group's y-planes live there, band i in slot i, instead of in T2 (kb->ho.planes: slot = band of the call)
 static FftPipe kblock_pipe(dftk_mi_kblock* kb, int nb, int t_off = 0, cd* planes = nullptr) {
     dftk_mi_basis* b = kb->basis;
     const int64_t s1 = (int64_t)kb->n_lines * b->nxp, s2 = (int64_t)kb->nzx * b->ny * b->nxp;
@@ -1497,7 +1497,7 @@ static int check_density_nz(const dftk_mi_basis* b) {
 int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho,
                    const double* w_im_h, const double* w2_h, double* rho2, bool keep_planes) {
     dftk_mi_basis* b = kb->basis;
-    if (!keep_planes) kb->planes_on = false;   // planes kept by an earlier pass belong to another block or shape
+    if (!keep_planes) kb->ho.planes_off();     // planes kept by an earlier pass belong to another block or shape
     if (batching() && nb > 0) {   // part of a batched multi-k call: the bands of all k-blocks share one pipeline later
         // payload: [w | wim (flags & 1) | w2 (flags & 2)]; D = the second cube of a two-weight pass
         BOp o;
@@ -1523,10 +1523,10 @@ int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, con
     CHK(check_density_nz(b));
     const int64_t s2 = (int64_t)kb->nzx * b->ny * b->nxp;
     return band_groups(kb, nb, 1, w_h, w_im_h, [&](int b0, int nbb, const double* w_d, const double* wim_d) -> int {
-        const FftPipe p = kblock_pipe(kb, nbb, 0, keep_planes ? kb->planes + (int64_t)b0 * s2 : nullptr);
+        const FftPipe p = kblock_pipe(kb, nbb, 0, keep_planes ? kb->ho.planes + (int64_t)b0 * s2 : nullptr);
         CHK(stage_A(p, psi + (int64_t)b0 * ldpsi, ldpsi));
         CHK(stage_B(p));
-        if (keep_planes) std::fill_n(kb->planes_valid.begin() + b0, nbb, (char)1);
+        if (keep_planes) kb->ho.planes_mark(b0, nbb);
         return stage_density(p, w_d, wim_d, rho);
     });
 }

@@ -344,7 +344,7 @@ static dim3 gr_grid_unr(int64_t rows, int cols) { return dim3((unsigned)((rows +
 
 int gamma_enable(dftk_mi_kblock* kb, int on) {
     dftk_mi_basis* b = kb->basis;
-    planes_drop(kb);                      // (kept y-planes belong to the format that was on when the block was returned)
+    kb->ho.forget_planes();               // (kept y-planes belong to the format that was on when the block was returned)
     if (!on) {
         if (kb->gr) kb->gr->on = false;
         return 0;
@@ -557,30 +557,31 @@ static bool planes_wanted() {
     return !(e && atoi(e) == 0);
 }
 
+bool planes_eligible(const dftk_mi_kblock* kb) {
+    return planes_wanted() && kb->gr && kb->gr->on && !kb->sh_comm && !batching();
+}
+
 // Does this density pass run over the very block the general LOBPCG driver returned last (un-sharded, un-batched
 // Gamma-real block)?  Then its y-planes are kept for the next call's start: the buffer is allocated on
 // first use, and only where the device has room for it twice over -- otherwise the block declines for good.
 static int planes_prepare(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, bool* keep) {
     *keep = false;
     dftk_mi_basis* b = kb->basis;
-    if (!planes_wanted() || !kb->gr->on || kb->sh_comm || batching() || kb->planes_declined || kb->ret_X == nullptr ||
-        kb->ret_X != psi || kb->ret_ld != ldpsi || kb->ret_M != nb)
-        return 0;
+    LobHandover& ho = kb->ho;
+    if (!planes_eligible(kb) || !ho.pass_keeps_planes(psi, ldpsi, nb)) return 0;
     const size_t nb2 = (size_t)(nb + 1) / 2;
     const size_t need = nb2 * (size_t)kb->nzx * b->ny * b->nxp * sizeof(cd);
-    if (need > kb->planes.bytes()) {
+    if (need > ho.planes.bytes()) {
         HIPCHK(hipStreamSynchronize(b->stream));
-        HIPCHK(kb->planes.reset());
+        HIPCHK(ho.planes.reset());
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        if (free_b < 2 * need + ((size_t)1 << 30) || kb->planes.reserve(need) != hipSuccess) {
+        if (free_b < 2 * need + ((size_t)1 << 30) || ho.planes.reserve(need) != hipSuccess) {
             (void)hipGetLastError();
-            kb->planes_declined = true;
+            ho.planes_decline();
             return 0;
         }
     }
-    kb->planes_valid.assign(nb2, 0);
-    kb->planes_batch = b->fft_batch;
     *keep = true;
     return 0;
 }
@@ -598,14 +599,8 @@ int gamma_density_bands(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi
         wre[p] = w_h[2 * p];
         wim[p] = (2 * p + 1 < nb) ? w_h[2 * p + 1] : 0.0;
     }
-    kb->planes_on = keep;
+    if (keep) kb->ho.planes_begin(nb, kb->basis->fft_batch);   // (a pass that keeps nothing: launch_density switches them off)
     return launch_density(kb, nb2, kb->gr->buf, kb->n_G, wre.data(), rho, wim.data(), nullptr, nullptr, keep);
-}
-
-bool gamma_planes_ready(const dftk_mi_kblock* kb, int M) {
-    return planes_wanted() && kb->planes_on && kb->planes != nullptr && kb->ret_M == M && kb->gr && kb->gr->on &&
-           !kb->sh_comm && !batching() && kb->planes_batch == kb->basis->fft_batch &&
-           kb->planes_valid.size() == (size_t)(M + 1) / 2;
 }
 
 // The local part of H psi (the bound potential) in the half-sphere format for the nb bands whose y-planes the density pass
@@ -616,7 +611,7 @@ int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64
     GammaReal* gr = kb->gr.get();
     dftk_mi_basis* b = kb->basis;
     const int nb2 = (nb + 1) / 2;
-    kb->planes_on = false;
+    const std::vector<char>& valid = kb->ho.planes_consume();
     const int slot = prof_begin(b, PROF_APPLY_H, (double)nb);
     struct G {
         dftk_mi_basis* b;
@@ -628,14 +623,13 @@ int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64
     cd* W = gr->buf + (size_t)kb->n_G * nb2;
     prof_count(b, PROF_A2A_MODEL, 16.0 * (double)gr->n_half * nb);   // (as gamma_apply_H: what a sharded run of the call moves)
     prof_count(b, PROF_A2A_MODEL, 16.0 * (double)gr->n_half * nb);
-    const std::vector<char>& valid = kb->planes_valid;
     const int group = fft_group_size(b);
     for (int b0 = 0; b0 < nb2; b0 += group) {
         const int nbb = std::min(group, nb2 - b0);
         if (std::all_of(valid.begin() + b0, valid.begin() + b0 + nbb, [](char v) { return v != 0; })) continue;
         CHK(gamma_pack_full(kb, std::min(2 * nbb, nb - 2 * b0), X + (int64_t)(2 * b0) * ldx, ldx, Z, kb->n_G));
-        CHK(launch_planes_fill(kb, b0, nbb, Z, kb->n_G, kb->planes));
+        CHK(launch_planes_fill(kb, b0, nbb, Z, kb->n_G, kb->ho.planes));
     }
-    CHK(launch_local_apply_from_planes(kb, nb2, kb->planes, W, kb->n_G));
+    CHK(launch_local_apply_from_planes(kb, nb2, kb->ho.planes, W, kb->n_G));
     return gamma_unpack_pairs(kb, nb, W, kb->n_G, Hpsi, ldH);
 }

@@ -24,6 +24,9 @@
 #include <utility>
 #include <vector>
 
+std::atomic<int64_t> g_ax_reuse_count{0};     // calls that started from the kept A X (dftk_mi_ax_reuse_count)
+std::atomic<int64_t> g_planes_reuse_count{0}; // ... and applied V_new - V_old from the kept y-planes (dftk_mi_planes_reuse_count)
+
 namespace {
 
 const double EPS = 2.220446049250313e-16;
@@ -588,7 +591,7 @@ struct NoComm {
 // One LOBPCG call on one k-block: the workspace, the state of the iteration and every step that does not depend on HOW the
 // orthogonalisations, the Rayleigh-Ritz eigenproblem and the residual pass are issued.  The two drivers below
 // (lobpcg_run_general, lobpcg_run_small) issue those in their own way and call the steps in the reference's order:
-//   bind; [entry: ortho!(X), A X, Rayleigh quotients]; rayleigh_quotients;
+//   bind; [entry: ortho!(X), A X (general driver: start_AX), Rayleigh quotients]; rayleigh_quotients;
 //   per iteration: views; [A R, Rayleigh-Ritz]; ritz_update; [residuals, fetch into hf]; lock; update_P; advance;
 //                  [ortho!(R, [X P])]; check_ortho
 //   sort_pairs; [copy-out]; report
@@ -610,7 +613,7 @@ struct Lob {
     // A X kept at the last exit of the general driver on this block, if the caller promised the same X and the shape fits
     cd* kept_AX = nullptr;
     int64_t kept_ld = 0;
-    bool kept_planes = false;       // ... and the density pass over that X has left its y-planes (gamma_planes_ready)
+    bool kept_planes = false;       // ... and the density pass over that X has left its y-planes
     // ---- state of the call ----
     std::vector<double> resid_history, full_lam;
     double& RH(int i, int it) { return resid_history[(size_t)i + (size_t)M * it]; }
@@ -653,18 +656,15 @@ struct Lob {
         const size_t dbl = 9 * (size_t)DS;
         const size_t need = (nbig * blk + small_elems) * sizeof(cd) + dbl * sizeof(double) + m3 * sizeof(int) + 1024;
         // The kept A X (dftk_mi_kblock_reuse_AX) lives in this buffer and every call overwrites it: whichever driver binds the
-        // workspace consumes the promise and drops what is kept
-        const bool reuse_asked = kb->ax_reuse_next;
-        kb->ax_reuse_next = false;
-        kept_AX = reuse_asked && kb->ax_M == M && kb->ax_rows == N ? kb->ax_keep : nullptr;
-        kept_ld = kb->ax_ld;
-        kb->ax_keep = nullptr;
-        // the y-planes of the returned X go the same way: this call uses them at its start or not at all
-        kept_planes = kept_AX != nullptr && real_mode && comm == nullptr && gamma_planes_ready(kb, M);
-        planes_drop(kb);
-        if (need > kb->lob_buf.bytes()) {
+        // workspace consumes the promise and drops what is kept.  The y-planes of the returned X go the same way: this call
+        // uses them at its start or not at all.
+        const bool grows = need > kb->lob_buf.bytes();   // (a kept A X lives in the buffer that goes then)
+        const LobHandover::Taken kept = kb->ho.take(M, N, grows, planes_eligible(kb), b->fft_batch);
+        kept_AX = kept.AX;
+        kept_ld = kept.ld;
+        kept_planes = kept.planes;
+        if (grows) {
             CHK(host_wait(b));
-            kept_AX = nullptr;               // (it lives in the buffer that goes now)
             HIPCHK(kb->lob_buf.reserve(need));
         }
         cd* w = kb->lob_buf;
@@ -718,11 +718,100 @@ struct Lob {
         c.rng_rep.seed((seed ? seed : 0x9E3779B97F4A7C15ull) ^ 0xD1B54A32D192ED03ull);
         X = Yb[0].cols_from(0, M);
         AX = AYb[0].cols_from(0, M);
-        kb->last_AX = real_mode ? nullptr : AX.p;   // (half-format blocks are not handed out)
+        kb->ho.set_last_AX(real_mode ? nullptr : AX.p);   // (half-format blocks are not handed out)
         resid_history.assign((size_t)M * (maxiter + 1), 0.0);
         full_lam.assign(M, 0.0);
         final_iter = maxiter;
         n_matvec = M;
+        return 0;
+    }
+
+    // H on a block in the general driver's own format (half sphere of a Gamma-real block, this rank's slab, or n_G rows)
+    int apply_H(int nb, const cd* in, int64_t ldin, cd* out, int64_t ldout) {
+        if (c.real_mode) return gamma_apply_H(kb, 7, nb, in, ldin, out, ldout);
+        return dftk_mi_apply_H(kb, nb, reinterpret_cast<const dftk_mi_cplx*>(in), ldin,
+                               reinterpret_cast<dftk_mi_cplx*>(out), ldout);
+    }
+
+    // (A_old X) inv(R) -> AX: straight into place unless the kept block IS AX's storage (through newR then)
+    int kept_times_invR() {
+        if (kept_AX != AX.p) return c.mm('N', N, M, M, ONE, kept_AX, kept_ld, c.invR, M, ZERO, AX.p, AX.ld, /*B upper triangular=*/2);
+        CHK(c.mm('N', N, M, M, ONE, kept_AX, kept_ld, c.invR, M, ZERO, newR.p, newR.ld, /*B upper triangular=*/2));
+        return ew_copy(b, N, M, newR.p, newR.ld, AX.p, AX.ld);
+    }
+
+    // Entry of the general driver: X = ortho!(copy(X0)); AX = A X -- from the A X kept at the last exit where bind has taken
+    // one (LobHandover::take), by a full application otherwise.  Xp, ldX: the caller's start block.
+    int start_AX(const cd* Xp, int64_t ldX) {
+        LobHandover& ho = kb->ho;
+        bool reuse_ax = kept_AX != nullptr && kb->d_Vs != nullptr && ho.V_kept != nullptr;
+        if (c.real_mode)
+            CHK(gamma_lobpcg_load(kb, M, Xp, ldX, X.p, X.ld, /*align=*/true));
+        else
+            CHK(ew_copy(b, N, M, Xp, ldX, X.p, X.ld));
+        {
+            int nch;
+            double gr;
+            CHK(ortho_X(c, X, tmp, ORTHO_TOL, &nch, &gr));
+            // the kept A X follows X through ONE plain Cholesky-QR pass (X <- X inv(R), the common case: X comes back orthonormal
+            // to round-off from the previous step); anything else (several passes, shifts, the SVD fallback) takes the full H X
+            if (reuse_ax && !(nch == 1)) reuse_ax = false;
+        }
+        if (!reuse_ax) return apply_H(M, X.p, X.ld, AX.p, AX.ld);
+        g_ax_reuse_count.fetch_add(1);
+        // A_new X = (A_old X) inv(R) + (V_new - V_old) X: kinetic and nonlocal parts are those of the last call.  Saves the two
+        // projector products of an H X (P' psi and P (D P' psi): 11.5 of 131 ms per late SCF step of the 1000-electron cell)
+        // for one triangular product, one local-only application and two element-wise passes.
+        const size_t cube = (size_t)b->nz * b->ny * b->nxp;
+        if (!ho.dV) HIPCHK(ho.dV.alloc(cube * sizeof(double)));
+        CHK(ew_sub_real(b, (int64_t)cube, kb->d_Vs, ho.V_kept, ho.dV));
+        double* const Vs_bound = kb->d_Vs;
+        if (kept_planes) {
+            // The density pass over the returned X left that block's y-planes (gamma_density_bands): (V_new - V_old) is applied
+            // to the RETURNED X from stage C on -- no pack, no stages A and B -- and follows the kept block through inv(R):
+            // A_new X = (A_old X_ret + (V_new - V_old) X_ret) inv(R), the same operator before the triangular factor.
+            g_planes_reuse_count.fetch_add(1);
+            kb->d_Vs = ho.dV;
+            const int st_dv = gamma_apply_local_from_planes(kb, M, Xp, ldX, newR.p, newR.ld);
+            kb->d_Vs = Vs_bound;
+            CHK(st_dv);
+            CHK(ew_add(b, N, M, newR.p, newR.ld, kept_AX, kept_ld));
+            CHK(kept_times_invR());
+        } else {
+            CHK(kept_times_invR());
+            kb->d_Vs = ho.dV;                                     // (the kernels take the pointer at launch)
+            const int st_dv = c.real_mode ? gamma_apply_H(kb, 1, M, X.p, X.ld, newR.p, newR.ld)
+                                          : dftk_mi_apply_H_parts(kb, 1, M, reinterpret_cast<const dftk_mi_cplx*>(X.p), X.ld,
+                                                                  reinterpret_cast<dftk_mi_cplx*>(newR.p), newR.ld);
+            kb->d_Vs = Vs_bound;
+            CHK(st_dv);
+            CHK(ew_add(b, N, M, newR.p, newR.ld, AX.p, AX.ld));
+        }
+        static const bool ax_check = getenv("DFTK_MI_AX_REUSE_CHECK") != nullptr;
+        if (ax_check) {     // diagnostic: the full application beside it (costs what the path saves, and a synchronisation)
+            CHK(apply_H(M, X.p, X.ld, newR.p, newR.ld));
+            std::vector<cd> h1((size_t)N * M), h2((size_t)N * M);
+            CHK(stream_sync(b));
+            HIPCHK(hipMemcpy(h1.data(), AX.p, h1.size() * sizeof(cd), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(h2.data(), newR.p, h2.size() * sizeof(cd), hipMemcpyDeviceToHost));
+            double worst = 0.0, nrm = 0.0;
+            int wc = -1;
+            for (int j = 0; j < M; ++j) {
+                double d = 0.0, r = 0.0;
+                for (int64_t i = 0; i < N; ++i) {
+                    const cd a = h1[(size_t)i + (size_t)j * N], f = h2[(size_t)i + (size_t)j * N];
+                    d += (a.x - f.x) * (a.x - f.x) + (a.y - f.y) * (a.y - f.y);
+                    r += f.x * f.x + f.y * f.y;
+                }
+                nrm = std::max(nrm, std::sqrt(r));
+                if (std::sqrt(d) > worst) {
+                    worst = std::sqrt(d);
+                    wc = j;
+                }
+            }
+            fprintf(stderr, "[ax reuse check] M=%d N=%lld: max column error %.3e (column %d), max ||H x|| %.3e\n", M, (long long)N, worst,
+                    wc, nrm);
+        }
         return 0;
     }
 
@@ -898,7 +987,7 @@ struct Lob {
     int sort_pairs(bool* permuted) {
         X = Yb[cur].cols_from(0, M);
         AX = AYb[cur].cols_from(0, M);
-        kb->last_AX = c.real_mode ? nullptr : AX.p;
+        kb->ho.set_last_AX(c.real_mode ? nullptr : AX.p);
         perm.resize(M);
         std::iota(perm.begin(), perm.end(), 0);
         *permuted = !std::is_sorted(full_lam.begin(), full_lam.end());
@@ -964,9 +1053,6 @@ int lobpcg_ortho(dftk_mi_basis* b, int64_t n, int m, cd* X, int64_t ldx, int for
     return st;
 }
 
-std::atomic<int64_t> g_ax_reuse_count{0};     // calls that started from the kept A X (dftk_mi_ax_reuse_count)
-std::atomic<int64_t> g_planes_reuse_count{0}; // ... and applied V_new - V_old from the kept y-planes (dftk_mi_planes_reuse_count)
-
 // The host-driven driver: every block shape, plane-wave sharded and Gamma-real blocks.  Each orthogonalisation, the
 // eigensolver and the residual pass come back to the host by themselves (4-6 synchronisations per iteration).
 static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, double tol, int miniter, int maxiter,
@@ -985,11 +1071,6 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
     const bool real_mode = kb->gr && kb->gr->on;
     const int64_t N = real_mode ? gamma_local_rows(kb) : comm ? kb->sh_rows[comm_rank(comm) + 1] - row0 : kb->n_G;
     const double* kin = !use_tpa ? nullptr : real_mode ? kb->gr->d_kin_half + gamma_row0(kb) : kb->d_kin + row0;
-    auto apply_H = [&](int nb, const cd* in, int64_t ldin, cd* out, int64_t ldout) -> int {
-        if (real_mode) return gamma_apply_H(kb, 7, nb, in, ldin, out, ldout);
-        return dftk_mi_apply_H(kb, nb, reinterpret_cast<const dftk_mi_cplx*>(in), ldin,
-                               reinterpret_cast<dftk_mi_cplx*>(out), ldout);
-    };
     if (N < 1) {
         dftk_set_error("sharded k-block: empty row slab on rank %d", comm_rank(comm));
         return DFTK_MI_EINVAL;
@@ -1000,91 +1081,7 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
     const int DS = M + 8;
     CHK(s.bind(kb, M, N, DS, comm, real_mode, kin, seed, maxiter));
     Ctx& c = s.c;
-    bool reuse_ax = s.kept_AX != nullptr && kb->d_Vs != nullptr && kb->d_Vs_ax != nullptr;
-    if (real_mode)
-        CHK(gamma_lobpcg_load(kb, M, Xp, ldX, s.X.p, s.X.ld, /*align=*/true));
-    else
-        CHK(ew_copy(b, N, M, Xp, ldX, s.X.p, s.X.ld));
-
-    // ---- X = ortho!(copy(X)); AX = A X --------------------------------------------------------
-    {
-        int nch;
-        double gr;
-        CHK(ortho_X(c, s.X, s.tmp, ORTHO_TOL, &nch, &gr));
-        // the kept A X follows X through ONE plain Cholesky-QR pass (X <- X inv(R), the common case: X comes back orthonormal
-        // to round-off from the previous step); anything else (several passes, shifts, the SVD fallback) takes the full H X
-        if (reuse_ax && !(nch == 1)) reuse_ax = false;
-    }
-    if (reuse_ax) {
-        const Mat &X = s.X, &AX = s.AX, &newR = s.newR;
-        g_ax_reuse_count.fetch_add(1);
-        // A_new X = (A_old X) inv(R) + (V_new - V_old) X: kinetic and nonlocal parts are those of the last call.  Saves the two
-        // projector products of an H X (P' psi and P (D P' psi): 11.5 of 131 ms per late SCF step of the 1000-electron cell)
-        // for one triangular product, one local-only application and two element-wise passes.
-        const size_t cube = (size_t)b->nz * b->ny * b->nxp;
-        if (!kb->d_dVs) HIPCHK(kb->d_dVs.alloc(cube * sizeof(double)));
-        CHK(ew_sub_real(b, (int64_t)cube, kb->d_Vs, kb->d_Vs_ax, kb->d_dVs));
-        double* const Vs_bound = kb->d_Vs;
-        if (s.kept_planes) {
-            // The density pass over the returned X left that block's y-planes (gamma_density_bands): (V_new - V_old) is applied
-            // to the RETURNED X from stage C on -- no pack, no stages A and B -- and follows the kept block through inv(R):
-            // A_new X = (A_old X_ret + (V_new - V_old) X_ret) inv(R), the same operator before the triangular factor.
-            g_planes_reuse_count.fetch_add(1);
-            kb->d_Vs = kb->d_dVs;
-            const int st_dv = gamma_apply_local_from_planes(kb, M, Xp, ldX, newR.p, newR.ld);
-            kb->d_Vs = Vs_bound;
-            CHK(st_dv);
-            CHK(ew_add(b, N, M, newR.p, newR.ld, s.kept_AX, s.kept_ld));
-            if (s.kept_AX != AX.p) {
-                CHK(c.mm('N', N, M, M, ONE, s.kept_AX, s.kept_ld, c.invR, M, ZERO, AX.p, AX.ld, /*B upper triangular=*/2));
-            } else {
-                CHK(c.mm('N', N, M, M, ONE, s.kept_AX, s.kept_ld, c.invR, M, ZERO, newR.p, newR.ld, /*B upper triangular=*/2));
-                CHK(ew_copy(b, N, M, newR.p, newR.ld, AX.p, AX.ld));
-            }
-        } else {
-        // (A_old X) inv(R) -> AX (straight into place unless the kept block IS AX's storage: through newR then)
-        if (s.kept_AX != AX.p) {
-            CHK(c.mm('N', N, M, M, ONE, s.kept_AX, s.kept_ld, c.invR, M, ZERO, AX.p, AX.ld, /*B upper triangular=*/2));
-        } else {
-            CHK(c.mm('N', N, M, M, ONE, s.kept_AX, s.kept_ld, c.invR, M, ZERO, newR.p, newR.ld, /*B upper triangular=*/2));
-            CHK(ew_copy(b, N, M, newR.p, newR.ld, AX.p, AX.ld));
-        }
-        kb->d_Vs = kb->d_dVs;                                  // (the kernels take the pointer at launch)
-        const int st_dv = real_mode ? gamma_apply_H(kb, 1, M, X.p, X.ld, newR.p, newR.ld)
-                                    : dftk_mi_apply_H_parts(kb, 1, M, reinterpret_cast<const dftk_mi_cplx*>(X.p), X.ld,
-                                                            reinterpret_cast<dftk_mi_cplx*>(newR.p), newR.ld);
-        kb->d_Vs = Vs_bound;
-        CHK(st_dv);
-        CHK(ew_add(b, N, M, newR.p, newR.ld, AX.p, AX.ld));
-        }
-        static const bool ax_check = getenv("DFTK_MI_AX_REUSE_CHECK") != nullptr;
-        if (ax_check) {     // diagnostic: the full application beside it (costs what the path saves, and a synchronisation)
-            CHK(apply_H(M, X.p, X.ld, newR.p, newR.ld));
-            std::vector<cd> h1((size_t)N * M), h2((size_t)N * M);
-            CHK(stream_sync(b));
-            HIPCHK(hipMemcpy(h1.data(), AX.p, h1.size() * sizeof(cd), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(h2.data(), newR.p, h2.size() * sizeof(cd), hipMemcpyDeviceToHost));
-            double worst = 0.0, nrm = 0.0;
-            int wc = -1;
-            for (int j = 0; j < M; ++j) {
-                double d = 0.0, r = 0.0;
-                for (int64_t i = 0; i < N; ++i) {
-                    const cd a = h1[(size_t)i + (size_t)j * N], f = h2[(size_t)i + (size_t)j * N];
-                    d += (a.x - f.x) * (a.x - f.x) + (a.y - f.y) * (a.y - f.y);
-                    r += f.x * f.x + f.y * f.y;
-                }
-                nrm = std::max(nrm, std::sqrt(r));
-                if (std::sqrt(d) > worst) {
-                    worst = std::sqrt(d);
-                    wc = j;
-                }
-            }
-            fprintf(stderr, "[ax reuse check] M=%d N=%lld: max column error %.3e (column %d), max ||H x|| %.3e\n", M, (long long)N, worst,
-                    wc, nrm);
-        }
-    } else {
-        CHK(apply_H(M, s.X.p, s.X.ld, s.AX.p, s.AX.ld));
-    }
+    CHK(s.start_AX(Xp, ldX));
     // (R is written at the end of iteration 0 and P at the end of iteration 1, before their first use)
     CHK(ew_coldots(b, N, M, s.X.p, s.X.ld, s.AX.p, s.AX.ld, c.d_a));
     CHK(ew_coldots(b, N, M, s.X.p, s.X.ld, s.X.p, s.X.ld, c.d_b));
@@ -1096,7 +1093,7 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
         s.views();
         const int nact = s.nact, nY = s.nY;
         if (s.niter > 0) {
-            CHK(apply_H(nact, s.Ra.p, s.Ra.ld, s.ARa.p, s.ARa.ld));
+            CHK(s.apply_H(nact, s.Ra.p, s.Ra.ld, s.ARa.p, s.ARa.ld));
             s.n_matvec += nact;
             // rayleigh_ritz: G = Y' AY (upper triangle), eigen, take the lowest nact
             CHK(c.mm('C', nY, nY, N, ONE, s.Y.p, s.Y.ld, s.AY.p, s.AY.ld, ZERO, s.G, nY, /*upper=*/1));
@@ -1141,18 +1138,12 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
     // keep A X (sorted like the returned X) and the potential it belongs to for a dftk_mi_kblock_reuse_AX start of the next call
     if (kb->d_Vs != nullptr && !batching()) {
         const size_t cube = (size_t)b->nz * b->ny * b->nxp;
-        if (!kb->d_Vs_ax) HIPCHK(kb->d_Vs_ax.alloc(cube * sizeof(double)));
-        HIPCHK(hipMemcpyAsync(kb->d_Vs_ax, kb->d_Vs, cube * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
-        kb->ax_keep = s.AX.p;
-        kb->ax_ld = s.AX.ld;
-        kb->ax_M = M;
-        kb->ax_rows = N;
+        LobHandover& ho = kb->ho;
+        if (!ho.V_kept) HIPCHK(ho.V_kept.alloc(cube * sizeof(double)));
+        HIPCHK(hipMemcpyAsync(ho.V_kept, kb->d_Vs, cube * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
+        ho.keep(s.AX.p, s.AX.ld, M, N);
         // where the returned X lives: a Gamma-real density pass over exactly this block keeps its y-planes (un-sharded only)
-        if (real_mode && !kb->sh_comm) {
-            kb->ret_X = Xp;
-            kb->ret_ld = ldX;
-            kb->ret_M = M;
-        }
+        if (real_mode && !kb->sh_comm) ho.returned(Xp, ldX, M);
     }
     return stream_sync(b);
 }

@@ -33,12 +33,13 @@ def _ax(lib):
     return n.value
 
 
-def _setup(edge=None):
+def _setup(edge=None, supercell=(2, 2, 2)):
     """basis (Si (2,2,2), Ecut 10, Gamma, coarse_start=False), the two densities of test_gpu_ax_reuse and a 40-band start
-    block; built once per cube edge"""
-    if edge not in _cache:
+    block; built once per cube edge (and cell)"""
+    key = edge if supercell == (2, 2, 2) else (edge, supercell)
+    if key not in _cache:
         assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-        lat, atoms, pos = dftk.silicon_cell((2, 2, 2))
+        lat, atoms, pos = dftk.silicon_cell(supercell)
         model = dftk.model_DFT(lat, atoms, pos, functionals=("lda_x", "lda_c_pw"))
         if edge is not None:
             assert edge >= max(dftk.compute_fft_size(model, 10))
@@ -50,8 +51,8 @@ def _setup(edge=None):
         rho2 = rho1 * (1.0 + 0.2 * torch.cos(2 * np.pi * z / basis.fft_size[2]))[:, None, None]
         gen = torch.Generator(device="cuda").manual_seed(3)
         X0 = dftk.random_orbitals(basis, basis.kpoints[0], 40, gen)
-        _cache[edge] = (basis, rho1, rho2, X0)
-    return _cache[edge]
+        _cache[key] = (basis, rho1, rho2, X0)
+    return _cache[key]
 
 
 def _solve(basis, rho, X, reuse=False, n_conv_check=32):
@@ -134,15 +135,15 @@ def test_groups_the_density_pass_skipped_are_filled(monkeypatch, M):
     assert np.abs(true - rep)[~reported].max() < 1.05e-7
 
 
-def _stale(monkeypatch, between, second_X=lambda r1: r1.X):
-    basis, rho1, rho2, X0 = _setup(None)
+def _stale(monkeypatch, between, second_X=lambda r1: r1.X, setup=(None,), M=40, n_occ=N_OCC, n_conv_check=32):
+    basis, rho1, rho2, X0 = _setup(*setup)
     lib = basis.lib
     monkeypatch.delenv("DFTK_MI_PLANES_REUSE", raising=False)
-    r1 = _solve(basis, rho1, X0)
-    _density(basis, r1.X)
+    r1 = _solve(basis, rho1, X0[:M], n_conv_check=n_conv_check)
+    _density(basis, r1.X, n_occ)
     between(basis, r1)
     p0 = _planes(lib)
-    r2 = _solve(basis, rho2, second_X(r1), reuse=True)
+    r2 = _solve(basis, rho2, second_X(r1), reuse=True, n_conv_check=n_conv_check)
     assert _planes(lib) == p0 and r2.converged
     return r2
 
@@ -190,6 +191,46 @@ def test_stale_small_driver_call_in_between(monkeypatch):
     a0 = _ax(basis.lib)
     _stale(monkeypatch, small_call)
     assert _ax(basis.lib) == a0
+
+
+def _stale_small(monkeypatch, between):
+    """The two drop events below on the smallest shape that still has every edge: Si primitive cell, cube 24^3 (a few hundred
+    plane waves), 7 bands (the last pair holds one band), fft_batch 3 (two launch groups, the second ragged), 4 occupied.
+    Returns the rise of the A X counter over the promised call."""
+    basis = _setup(24, (1, 1, 1))[0]
+    lib = basis.lib
+    counts = {}
+
+    def counted(basis, r1):
+        between(basis, r1)
+        counts["ax"] = _ax(lib)
+    try:
+        assert lib.dftk_mi_basis_set_fft_batch(basis.handle, 3) == 0
+        _stale(monkeypatch, counted, setup=(24, (1, 1, 1)), M=7, n_occ=4, n_conv_check=4)
+    finally:
+        assert lib.dftk_mi_basis_set_fft_batch(basis.handle, 32) == 0
+    return _ax(lib) - counts["ax"]
+
+
+def test_stale_density_through_the_complex_entry_point(monkeypatch):
+    """A density pass over the very tensor the call returned, but not as real-symmetric orbitals: it keeps no planes, and the
+    ones the real-symmetric pass before it kept are switched off.  The kept A X is untouched."""
+    def complex_pass(basis, r1):
+        occ = np.zeros(r1.X.shape[0])
+        occ[:4] = 2.0
+        dftk.compute_density(basis, [r1.X], [occ], real_symmetric=[False])
+    assert _stale_small(monkeypatch, complex_pass) == 1
+
+
+def test_stale_projectors_rebound(monkeypatch):
+    """New projectors (here: the same ones, bound again) between the density pass and the promised call drop the kept A X, the
+    promise and the planes: a full application."""
+    def rebind(basis, r1):
+        T = basis.terms
+        D = np.asfortranarray(T.D.cpu().numpy() if torch.is_tensor(T.D) else T.D, dtype=np.float64)
+        assert basis.lib.dftk_mi_kblock_set_projectors(basis.kpoints[0].handle, T.P[0].shape[0], T.P[0].data_ptr(),
+                                                       T.P[0].stride(0), D.ctypes.data) == 0
+    assert _stale_small(monkeypatch, rebind) == 0
 
 
 def test_scf_with_and_without_the_kept_planes(monkeypatch):

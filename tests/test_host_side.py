@@ -1410,6 +1410,23 @@ def test_allocation_owners_release_exactly_once_on_every_path():
     assert "Sanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-3000:]
 
 
+def test_lobpcg_handover_transition_table_on_the_host():
+    """``LobHandover`` of csrc/handover.h -- the A X and the y-planes a k-block keeps between two LOBPCG calls -- through
+    tools/host_handover_check.cpp (no GPU; host code under AddressSanitizer and UBSan; fake allocate / free): the kept A X is
+    handed out once, only when promised, for the same shape and an unmoved workspace; every take leaves nothing kept (a call
+    without a promise drops the block: the small-driver case); the planes go only with the A X, and only if eligible, on,
+    written for M bands under the same launch-group size; a pass that keeps nothing switches them off but the returned block
+    is remembered; new projectors drop everything, a new shard or format only the planes; declining is for good; the three
+    buffers are freed once each with the object."""
+    import subprocess
+    from dftk_jl_amd import _build
+    exe = _build.build_host_handover_check()
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, (res.returncode, res.stdout[-3000:], res.stderr[-3000:])
+    assert "host_handover_check OK" in res.stdout and "FAILED" not in res.stdout
+    assert "Sanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-3000:]
+
+
 def test_memory_statistics_and_plan_for_the_literal_4096_electron_cell():
     """``estimate_memory_usage`` (src/memory_usage.jl:35-87: psi_k, P_k, rho bytes and the 1 P + 2 psi + 6 psi_k + 12 rho
     peak) and the per-GPU plan of the plane-wave-sharded Gamma block: the headline 1000-electron cell fits one
