@@ -44,3 +44,6 @@ from .response import (occupation_divided_difference, compute_alpha_mn, is_effec
                        compute_delta_occ, sternheimer_solver, apply_chi0_4P, apply_chi0, compute_delta_rho,
                        apply_kernel, solve_OmegaPlusK_split, solve_OmegaPlusK, compute_chi0,
                        multiply_psi_by_potential)
+from .terms import dynmat_ewald  # noqa: F401,E402
+from .phonon import (compute_dynmat, compute_dynmat_term, compute_delta_H_psi_alpha_s, phonon_modes,  # noqa: F401,E402
+                     dynmat_red_to_cart, mass_matrix)

@@ -67,6 +67,14 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     "dftk_mi_forces_nonlocal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_void_p]),
+    "dftk_mi_local_potential_displacement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                       C.c_void_p]),
+    "dftk_mi_dynmat_local": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "dftk_mi_nonlocal_displacement_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                      C.c_void_p, _i64, C.c_void_p, _i64]),
+    "dftk_mi_dynmat_nonlocal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, _i64, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dftk_mi_stress_kinetic_nonlocal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p,
                                                   C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]),

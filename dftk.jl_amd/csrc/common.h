@@ -504,6 +504,9 @@ int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, 
 int forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int nb, const cd* psi, int64_t ld_psi,
                     const double* weight_h, int n_atoms, const int* col_start_h, double* forces_h);
 int ensure_G3(dftk_mi_kblock* kb);       // kb->d_G3 (integer G of every sphere row), built on first use
+// Z[:, n] = psi[:, n], Z[:, (1 + alpha) nb + n] = i g_alpha psi[:, n] for nb columns, g = G + k (reduced) of sphere row row0 + i
+int launch_nl_operands_full(dftk_mi_basis* b, int64_t rows, int nb, int64_t row0, const int* G3, const double* kcoord_h,
+                            const cd* psi, int64_t ldpsi, cd* Z, int64_t ldz);
 // out[r] = scale * sum_i in[r * n + i], one workgroup per row, fixed reduction order
 int launch_rowsum(dftk_mi_basis* b, int rows, int64_t n, const double* in, double scale, double* out);
 int launch_real_to_cplx(dftk_mi_basis* b, int64_t n, const double* x, cd* y);      // y = x + 0 i
@@ -538,6 +541,9 @@ int sternheimer_run(dftk_mi_kblock* kb, int n_occ, const cd* psi_occ, int64_t ld
                     const cd* psi_extra, int64_t ld_extra, const cd* rhs, int64_t ld_rhs, const double* tol_h, int miniter,
                     int maxiter, const cd* dpsi0, int64_t ld_dpsi0, cd* dpsi, int64_t ld_dpsi, int* n_iter, double* resid_h,
                     int* converged);
+
+// phonon_kernels.hip: dftk_mi_local_potential_displacement / dftk_mi_dynmat_local / dftk_mi_nonlocal_displacement_apply /
+// dftk_mi_dynmat_nonlocal (the entry points are the whole interface: see include/dftk_mi355x.h)
 
 // exx_kernels.hip: dftk_mi_exx_apply (the entry point is the whole interface: see include/dftk_mi355x.h)
 

@@ -218,6 +218,14 @@ __global__ __launch_bounds__(256) void k_nl_operands_full(int64_t rows, int nb, 
         Z[i + (int64_t)((1 + al) * nb + n) * ldz] = make_double2(-gv[al] * x.y, gv[al] * x.x);
 }
 
+int launch_nl_operands_full(dftk_mi_basis* b, int64_t rows, int nb, int64_t row0, const int* G3, const double* kcoord_h,
+                            const cd* psi, int64_t ldpsi, cd* Z, int64_t ldz) {
+    hipLaunchKernelGGL(k_nl_operands_full, dim3((unsigned)((rows + 255) / 256), (unsigned)nb), dim3(256), 0, b->stream, rows,
+                       nb, row0, G3, kcoord_h[0], kcoord_h[1], kcoord_h[2], psi, ldpsi, Z, ldz);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // half-format operands from the half-format block in Z[:, 0 .. nb): row j holds i G_alpha(G_j) psi_h(j), G_j = the
 // representative of global pair row0 + j (row 0 is G = 0: zero)
 __global__ __launch_bounds__(256) void k_nl_operands_half(int64_t rows, int nb, int64_t row0, const int* __restrict__ G3,
@@ -345,9 +353,7 @@ int forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int nb, const cd
             hipLaunchKernelGGL(k_nl_operands_half, dim3((unsigned)((rows + 255) / 256), (unsigned)m), dim3(256), 0,
                                b->stream, rows, m, row0, (const int*)kb->d_G3, (const int*)kb->gr->d_g, Z, rows);
         } else {
-            hipLaunchKernelGGL(k_nl_operands_full, dim3((unsigned)((rows + 255) / 256), (unsigned)m), dim3(256), 0,
-                               b->stream, rows, m, row0, (const int*)kb->d_G3, kcoord_h[0], kcoord_h[1], kcoord_h[2],
-                               ps, ld_psi, Z, rows);
+            CHK(launch_nl_operands_full(b, rows, m, row0, kb->d_G3, kcoord_h, ps, ld_psi, Z, rows));
         }
         HIPCHK(hipGetLastError());
         CHK(zgemm(b, 'C', n_p, 4 * (int64_t)m, rows, one, P, ldP, Z, rows, zero, Q, n_p, gamma ? DFTK_MI_GEMM_REAL : 0));

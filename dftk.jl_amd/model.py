@@ -13,13 +13,18 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .exchange import Coulomb
-from .psp import ATOMIC_NUMBER, PspHgh, load_psp
+from .psp import AMU_IN_ELECTRON_MASSES, ATOMIC_NUMBER, ATOMIC_WEIGHT, PspHgh, load_psp
 
 
 @dataclass(eq=False)
 class ElementPsp:
     symbol: str
     psp: PspHgh
+    mass: float | None = None      # atomic units (electron masses); default: the standard atomic weight of ``symbol``
+
+    def __post_init__(self):
+        if self.mass is None and self.symbol in ATOMIC_WEIGHT:
+            self.mass = ATOMIC_WEIGHT[self.symbol] * AMU_IN_ELECTRON_MASSES
 
     @property
     def charge_nuclear(self):

@@ -73,6 +73,10 @@ _TABLE = {
                      [[1.49964199, -0.13812935], [0.32687369]], [[-9.14535371]]], "Fe GTH-PADE-q8"),
 }
 ATOMIC_NUMBER = {"H": 1, "C": 6, "Al": 13, "Si": 14, "Fe": 26}
+# standard atomic weights (IUPAC 2021 abridged values, unified atomic mass units) of the elements of the HGH table, and
+# the unified atomic mass unit in electron masses (CODATA 2018)
+ATOMIC_WEIGHT = {"H": 1.0080, "C": 12.011, "Al": 26.982, "Si": 28.085, "Fe": 55.845}
+AMU_IN_ELECTRON_MASSES = 1822.888486209
 
 
 def load_psp(symbol: str, functional: str = "lda") -> PspHgh:

@@ -344,6 +344,78 @@ def energy_forces_ewald(lattice, charges, positions, eta=None):
     return (s_recip + s_real) / 2, forces
 
 
+def dynmat_ewald(lattice, charges, positions, eta=None):
+    """The Hessian of ``energy_ewald`` with respect to the REDUCED positions (``compute_dynmat(::TermEwald)`` at q = 0,
+    ewald.jl:181-251): ``D[beta, t, alpha, s] = d^2 E / dr_{t,beta} dr_{s,alpha}``, a (3, n, 3, n) array (host, numpy).
+    Same eta, same sums and same cut-offs as ``energy_forces_ewald``.  Reciprocal sum: with S(G) = sum_j q_j e^{i ph_j},
+    ph_j = 2 pi G.r_j, the pair (s, t) gets 2 q_s q_t cos(ph_s - ph_t) (2 pi)^2 G G' and the diagonal loses
+    2 q_s Re(conj(S) e^{i ph_s}) (2 pi)^2 G G'.  Real-space sum: for f(d) = erfc(eta d) / d at d = |L Delta| the Hessian
+    with respect to Delta is K = (f'' - f'/d) / d^2 (L'L Delta)(L'L Delta)' + (f'/d) L'L; the pair (s, t) gets
+    -q_s q_t sum_R K and the diagonal the negative sum of its row (translation invariance)."""
+    from .basis import estimate_integer_lattice_bounds
+    lattice = np.asarray(lattice, dtype=float)
+    q = np.asarray(charges, dtype=float)
+    pos = np.asarray(positions, dtype=float).reshape(-1, 3)
+    n = len(q)
+    H = np.zeros((n, 3, n, 3))           # [s, alpha, t, beta]
+    if n == 0:
+        return np.zeros((3, 0, 3, 0))
+    recip = TWO_PI * np.linalg.inv(lattice.T)
+    if eta is None:   # default_eta, ewald.jl:40-44
+        eta = math.sqrt(math.sqrt(1.69 * np.linalg.norm(recip / TWO_PI) / np.linalg.norm(lattice))) / 2
+    max_exp = -math.log(np.finfo(float).eps) + 5
+    max_erfc = math.sqrt(max_exp)
+    Glims = estimate_integer_lattice_bounds(recip, math.sqrt(max_exp) * 2 * eta)
+    poslims = [float(np.max(pos[:, i][:, None] - pos[:, i][None, :])) for i in range(3)]
+    Rlims = estimate_integer_lattice_bounds(lattice, max_erfc / eta, poslims)
+    vol = abs(np.linalg.det(lattice))
+    rng = [np.arange(-g, g + 1) for g in Glims]
+    G = np.stack(np.meshgrid(*rng, indexing="ij"), axis=-1).reshape(-1, 3)
+    G = G[np.any(G != 0, axis=1)]
+    Gsq = np.sum((G @ recip.T) ** 2, axis=1)
+    sel = Gsq / (4 * eta ** 2) < max_exp + 40
+    G, Gsq = G[sel].astype(float), Gsq[sel]
+    pref = (4 * math.pi / vol) * TWO_PI ** 2          # 1/2 (energy) * 2 (pairs) * 4 pi / vol * (2 pi)^2
+    for c0 in range(0, len(G), 32768):
+        g = G[c0:c0 + 32768]
+        ph = TWO_PI * (g @ pos.T)
+        cs, sn = np.cos(ph), np.sin(ph)
+        Sc, Ss = cs @ q, sn @ q
+        fac = np.exp(-Gsq[c0:c0 + 32768] / (4 * eta ** 2)) / Gsq[c0:c0 + 32768]
+        gg = fac[:, None, None] * g[:, :, None] * g[:, None, :]                       # (n_G, 3, 3)
+        cc = cs[:, :, None] * cs[:, None, :] + sn[:, :, None] * sn[:, None, :]        # cos(ph_s - ph_t)
+        H += pref * np.einsum("gst,gab->satb", cc * (q[:, None] * q[None, :])[None], gg)
+        re = (Sc[:, None] * cs + Ss[:, None] * sn) * q[None, :]                        # q_s Re(conj(S) e^{i ph_s})
+        diag = pref * np.einsum("gs,gab->sab", re, gg)
+        for s in range(n):
+            H[s, :, s, :] -= diag[s]
+    rr = [np.arange(-g, g + 1) for g in Rlims]
+    R = np.stack(np.meshgrid(*rr, indexing="ij"), axis=-1).reshape(-1, 3).astype(float)
+    qq = q[:, None] * q[None, :]
+    off = ~np.eye(n, dtype=bool)
+    LtL = lattice.T @ lattice
+    M = np.zeros((n, n, 3, 3))
+    for Rv in R:
+        delta = pos[:, None, :] - pos[None, :, :] - Rv[None, None, :]
+        dist = np.linalg.norm(delta @ lattice.T, axis=-1)
+        m = off & (dist * eta < max_erfc + 8)
+        if m.any():
+            dm = dist[m]
+            ex = 2 * eta / math.sqrt(math.pi) * np.exp(-(eta * dm) ** 2)
+            er = erfc(eta * dm)
+            f1 = -ex / dm - er / (dm * dm)
+            f2 = ex * (2 * eta ** 2 + 2 / (dm * dm)) + 2 * er / dm ** 3
+            v = delta[m] @ LtL
+            M[m] += qq[m][:, None, None] * (((f2 - f1 / dm) / (dm * dm))[:, None, None] * v[:, :, None] * v[:, None, :]
+                                            + (f1 / dm)[:, None, None] * LtL[None])
+    for s in range(n):
+        for t in range(n):
+            if s != t:
+                H[s, :, t, :] -= M[s, t]
+                H[s, :, s, :] += M[s, t]
+    return np.ascontiguousarray(H.transpose(3, 2, 1, 0))
+
+
 def stress_ewald(lattice, charges, positions, eta=None):
     """Strain derivative of ``energy_ewald`` (same sums, same cut-offs), sigma = (1 / Omega) dE / d eps at eps = 0 for the
     lattice (I + eps) L at fixed reduced positions: a symmetric (3, 3) array in Cartesian coordinates (host, numpy).

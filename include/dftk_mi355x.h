@@ -142,6 +142,46 @@ int dftk_mi_forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int n_ba
                             int64_t ld_psi, const double* weight_h, int n_atoms, const int* col_start_h,
                             double* forces_h);
 
+/* ---- dynamical matrix at q = 0 (src/postprocess/phonon.jl), the explicit pieces (phonon_kernels.hip) ----
+ * Reduced coordinates; fp64, fixed reduction order, no atomics: two calls give bitwise identical results.
+ *
+ * The local part of the perturbation of a displaced atom (compute_dynmat_dH(::TermAtomicLocal), src/terms/local.jl:183-213):
+ *   out[alpha](r) = irfft( enforce_real( -2 pi i G_alpha ff_s(|G|) e^{-2 pi i G.R} / sqrt(Omega) ) ),  alpha = 0, 1, 2
+ * i.e. the derivative of the cube of dftk_mi_atomic_superposition kind 0 with respect to the position of ONE atom of
+ * species `species` at position_h[3] (same G set, same unpaired-Nyquist handling, params_h as there).  out_d: three real
+ * cubes, one after the other; all three go through one transform pipeline.  Asynchronous on the basis' stream. */
+int dftk_mi_local_potential_displacement(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species,
+                                         const double* params_h, int species, const double* position_h, double* out_d);
+/* compute_dynmat(::TermAtomicLocal), the explicit term (src/terms/local.jl:183-213): out_h[9 a + 3 beta + alpha] is
+ * OVERWRITTEN with d^2 E_loc / dR_{a,beta} dR_{a,alpha}, the exact second derivative of the local energy this library
+ * evaluates (of which dftk_mi_forces_local is minus the first).  Arguments as dftk_mi_forces_local.  One forward FFT of
+ * the density, then one reduction per atom with the factors G_alpha G_beta. */
+int dftk_mi_dynmat_local(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species, const double* params_h,
+                         int n_atoms, const int* species_of_atom_h, const double* positions_h, const double* rho_d,
+                         double* out_h);
+/* compute_dHpsi_alpha_s, the nonlocal part (src/terms/nonlocal.jl:307-383) for ONE k-block and ONE atom: with P_s / D_s the
+ * columns col_start_h[atom] .. col_start_h[atom + 1] of the block's bound P / D and g = G + k (reduced),
+ *   out[alpha] = -2 pi i [ g_alpha o (P_s D_s P_s' psi) - P_s D_s P_s' (g_alpha o psi) ],  alpha = 0, 1, 2
+ * out_d: three blocks of n_bands columns (leading dimension ld_out), one after the other.  One product
+ * P_s' [psi | i g_x psi | i g_y psi | i g_z psi] per band chunk (the operands of dftk_mi_forces_nonlocal), the small
+ * product with D_s, one back-product, and the row scaling fused into the store.  A Gamma-real block is accepted (the
+ * products run in the complex full-sphere layout).  DFTK_MI_EINVAL, with out_d untouched: a plane-wave sharded block, a
+ * D that couples this atom to another, a leading dimension below n_G, a call inside a batched multi-k call. */
+int dftk_mi_nonlocal_displacement_apply(dftk_mi_kblock* kb, const double* kcoord_h, int atom, int n_atoms,
+                                        const int* col_start_h, int n_bands, const dftk_mi_cplx* psi_d, int64_t ld_psi,
+                                        dftk_mi_cplx* out_d, int64_t ld_out);
+/* compute_dynmat(::TermAtomicNonlocal) (src/terms/nonlocal.jl:307-383) for ONE k-block; both outputs are ACCUMULATED.
+ * dpsi_d non-NULL: dforces_h[3 a + alpha] += the derivative of what dftk_mi_forces_nonlocal returns along (dpsi, wd):
+ *   -4 pi sum_n { wd_n Re[p_n' D_a q_alpha,n] + w_n Re[dp_n' D_a q_alpha,n + p_n' D_a dq_alpha,n] }
+ * hess_h non-NULL: hess_h[9 a + 3 beta + alpha] += sum_n w_n <psi_n| d_alpha d_beta (P_a D_a P_a') |psi_n>
+ *   = (2 pi)^2 sum_n w_n 2 Re[ c_alpha' D_a c_beta - c_alphabeta' D_a c ]
+ * from the ten projected blocks P' [psi | g_alpha psi | g_alpha g_beta psi].  w_h[n] = kweight * occupation[n],
+ * wd_h[n] = kweight * d occupation[n]; psi_d / col_start_h as dftk_mi_forces_nonlocal.  Refusals as
+ * dftk_mi_nonlocal_displacement_apply (a coupling D of ANY atom), outputs untouched. */
+int dftk_mi_dynmat_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int n_bands, const dftk_mi_cplx* psi_d,
+                            int64_t ld_psi, const dftk_mi_cplx* dpsi_d, int64_t ld_dpsi, const double* w_h,
+                            const double* wd_h, int n_atoms, const int* col_start_h, double* dforces_h, double* hess_h);
+
 /* ---- stress tensor (src/postprocess/stresses.jl), term by term at fixed orbital coefficients (stress_kernels.hip) ----
  * All results are Omega * sigma contributions in Cartesian coordinates, six numbers in the order xx, yy, zz, zy, zx, yx
  * (the reference's Voigt order).  fp64, fixed reduction order, no atomics: two calls give bitwise identical results.
