@@ -11,7 +11,7 @@ Layout: ``csrc/`` hand-written HIP kernels + the C ABI (include/dftk_mi355x.h),
 """
 from ._lib import load as load_library, DftkMiError, EXPORTED_SYMBOLS  # noqa: F401
 from ._build import build as build_library  # noqa: F401
-from .psp import PspHgh, load_psp, parse_psp_hgh  # noqa: F401,E402
+from .psp import PspHgh, PspUpf, load_psp, parse_psp_hgh, parse_psp_upf  # noqa: F401,E402
 from .model import (Model, ElementPsp, model_DFT, model_atomic, create_supercell, silicon_cell,  # noqa: F401,E402
                     MonkhorstPack, ExplicitKpoints, ExactExchange, PBE0, model_HF)
 from .exchange import (Coulomb, ShortRangeCoulomb, LongRangeCoulomb, SphericallyTruncatedCoulomb,  # noqa: F401,E402

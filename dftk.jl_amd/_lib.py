@@ -65,6 +65,16 @@ _SIGNATURES = {
                                                C.c_void_p, C.c_void_p]),
     "dftk_mi_forces_local": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "dftk_mi_radial_transform": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, _i64,
+                                           C.c_void_p, C.c_void_p]),
+    "dftk_mi_radial_tile": (C.c_int, []),
+    "dftk_mi_build_projectors_radial": (C.c_int, [C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                                  C.c_int, C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, _i64, C.POINTER(C.c_int)]),
+    "dftk_mi_atomic_superposition_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dftk_mi_forces_local_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     "dftk_mi_forces_nonlocal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_void_p]),
     "dftk_mi_local_potential_displacement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,

@@ -1035,6 +1035,51 @@ extern "C" int dftk_mi_forces_local(dftk_mi_kblock* cube_kb, const double* recip
                         forces_h);
 }
 
+extern "C" int dftk_mi_radial_transform(dftk_mi_basis* b, int kind, int l, int n_r, const double* r_h,
+                                        const double* wf_h, double Zion, int64_t n_q, const double* q_d, double* out_d) {
+    if (!b || (kind != 0 && kind != 1) || (kind == 0 && (l < 0 || l > 3)) || n_r < 1 || !r_h || !wf_h || n_q < 0 ||
+        (n_q > 0 && (!q_d || !out_d)))
+        return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(b->device));
+    return radial_transform(b, kind, l, n_r, r_h, wf_h, Zion, n_q, q_d, out_d);
+}
+
+extern "C" int dftk_mi_build_projectors_radial(dftk_mi_basis* b, int64_t n_rows, const int32_t* G_d,
+                                               const double* recip_lattice_h, const double* kcoord_h,
+                                               double unit_cell_volume, int n_species, const double* R_d, int64_t ldR,
+                                               const int* first_chan_h, const int* n_chan_h, int n_atoms,
+                                               const int* species_of_atom_h, const double* positions_h,
+                                               dftk_mi_cplx* P_d, int64_t ldP, int* n_p) {
+    if (!b || n_rows < 0 || !recip_lattice_h || !kcoord_h || !(unit_cell_volume > 0) || n_species < 1 || !first_chan_h ||
+        !n_chan_h || n_atoms < 0 || (n_atoms > 0 && (!species_of_atom_h || !positions_h)) || !n_p || (P_d && !G_d))
+        return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(b->device));
+    return build_projectors_radial(b, n_rows, G_d, recip_lattice_h, kcoord_h, unit_cell_volume, n_species, R_d, ldR,
+                                   first_chan_h, n_chan_h, n_atoms, species_of_atom_h, positions_h,
+                                   reinterpret_cast<cd*>(P_d), ldP, n_p);
+}
+
+extern "C" int dftk_mi_atomic_superposition_table(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species,
+                                                  const double* ff_d, int n_atoms, const int* species_of_atom_h,
+                                                  const double* positions_h, const double* coeff_h, double* out_d) {
+    if (!cube_kb || !recip_lattice_h || n_species < 1 || !ff_d || n_atoms < 1 || !species_of_atom_h || !positions_h ||
+        !out_d || cube_kb->sh_comm)
+        return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(cube_kb->basis->device));
+    return atomic_superposition_table(cube_kb, recip_lattice_h, n_species, ff_d, n_atoms, species_of_atom_h, positions_h,
+                                      coeff_h, out_d);
+}
+
+extern "C" int dftk_mi_forces_local_table(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species,
+                                          const double* ff_d, int n_atoms, const int* species_of_atom_h,
+                                          const double* positions_h, const double* rho_d, double* forces_h) {
+    if (!cube_kb || !recip_lattice_h || (n_atoms > 0 && !ff_d)) return DFTK_MI_EINVAL;
+    if (n_atoms == 0) return 0;
+    HIPCHK(hipSetDevice(cube_kb->basis->device));
+    return forces_local_table(cube_kb, recip_lattice_h, n_species, ff_d, n_atoms, species_of_atom_h, positions_h, rho_d,
+                              forces_h);
+}
+
 extern "C" int dftk_mi_forces_nonlocal(dftk_mi_kblock* kb, const double* kcoord_h, int n_bands, const dftk_mi_cplx* psi_d,
                                        int64_t ld_psi, const double* weight_h, int n_atoms, const int* col_start_h,
                                        double* forces_h) {

@@ -450,6 +450,19 @@ int build_projectors_hgh(dftk_mi_basis* b, int64_t n_rows, const int32_t* G_d, c
 
 int atomic_superposition(dftk_mi_kblock* cube_kb, int kind, const double* recip_h, int n_species, const double* par_h,
                          int n_atoms, const int* species_of_atom_h, const double* positions_h, double* out_d);
+// the table variants (numeric pseudopotentials): tabulated radial parts R_d[channel][row] / form factors ff_d[species][N]
+int build_projectors_radial(dftk_mi_basis* b, int64_t n_rows, const int32_t* G_d, const double* recip_h,
+                            const double* k_h, double volume, int n_species, const double* R_d, int64_t ldR,
+                            const int* first_chan_h, const int* n_chan_h, int n_atoms, const int* species_of_atom_h,
+                            const double* positions_h, cd* P_d, int64_t ldP, int* n_p_out);
+int atomic_superposition_table(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, const double* ff_d,
+                               int n_atoms, const int* species_of_atom_h, const double* positions_h,
+                               const double* coef_h, double* out_d);
+int forces_local_table(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, const double* ff_d, int n_atoms,
+                       const int* species_of_atom_h, const double* positions_h, const double* rho_d, double* forces_h);
+// radial_kernels.hip: dftk_mi_radial_transform (asynchronous on the basis' stream)
+int radial_transform(dftk_mi_basis* b, int kind, int l, int n_r, const double* r_h, const double* wf_h, double Zion,
+                     int64_t n_q, const double* q_d, double* out_d);
 // species indices in range and non-decreasing; `who` names the caller in the error text
 int check_species_grouped(const char* who, int n_species, int n_atoms, const int* species_of_atom_h);
 // per atom [t_x(nx) | t_y(ny) | t_z(nz)], t(i) = exp(-2 pi i g(i) r) with g the signed frequency of index i

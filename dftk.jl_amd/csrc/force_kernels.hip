@@ -35,7 +35,9 @@ __device__ inline double wave_sum_all(double v) {
     return v;
 }
 
-// W_s(G) = ff_s(|G|) conj(R(G)) / N on the whole cube (one species), unpaired Nyquist entries zero
+// W_s(G) = ff_s(|G|) conj(R(G)) / N on the whole cube (one species), unpaired Nyquist entries zero.  TABLE = true: q is
+// the species' row of a device table of form factors per cube point (dftk_mi_forces_local_table), not its 8 parameters
+template <bool TABLE>
 __global__ __launch_bounds__(256) void k_forces_local_w(int nx, int ny, int nz, Mat3 B, const double* __restrict__ q,
                                                         const cd* __restrict__ R, double inv_N, cd* __restrict__ W) {
     const int64_t N = (int64_t)nx * ny * nz;
@@ -49,7 +51,7 @@ __global__ __launch_bounds__(256) void k_forces_local_w(int nx, int ny, int nz, 
     double qx, qy, qz;
     recip_times(B, (double)signed_freq(ix, nx), (double)signed_freq(iy, ny), (double)signed_freq(iz, nz), &qx, &qy, &qz);
     const double p = sqrt(qx * qx + qy * qy + qz * qz);
-    const double ff = hgh_local_ff(q, (p * q[0]) * (p * q[0])) * inv_N;
+    const double ff = (TABLE ? q[idx] : hgh_local_ff(q, (p * q[0]) * (p * q[0]))) * inv_N;
     const cd r = R[idx];
     W[idx] = make_double2(ff * r.x, -ff * r.y);
 }
@@ -147,8 +149,10 @@ int launch_real_to_cplx(dftk_mi_basis* b, int64_t n, const double* x, cd* y) {
     return 0;
 }
 
-int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, const double* par_h, int n_atoms,
-                 const int* species_of_atom_h, const double* positions_h, const double* rho_d, double* forces_h) {
+// par_h: 8 HGH parameters per species (host), or, with ff_d given, unused: form factors from the device table ff_d[s][N]
+static int forces_local_impl(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, const double* par_h,
+                             const double* ff_d, int n_atoms, const int* species_of_atom_h, const double* positions_h,
+                             const double* rho_d, double* forces_h) {
     dftk_mi_basis* b = cube_kb->basis;
     const int nx = b->nx, ny = b->ny, nz = b->nz;
     const int64_t N = (int64_t)nx * ny * nz;
@@ -156,7 +160,7 @@ int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, 
         dftk_set_error("forces_local: the k-block must span the whole cube");
         return DFTK_MI_EINVAL;
     }
-    if (n_atoms < 0 || n_species < 0 || (n_atoms > 0 && (!species_of_atom_h || !positions_h || !par_h)) || !rho_d ||
+    if (n_atoms < 0 || n_species < 0 || (n_atoms > 0 && (!species_of_atom_h || !positions_h || (!par_h && !ff_d))) || !rho_d ||
         (n_atoms > 0 && !forces_h))
         return DFTK_MI_EINVAL;
     CHK(check_species_grouped("forces_local", n_species, n_atoms, species_of_atom_h));
@@ -181,13 +185,19 @@ int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, 
     CHK(ensure_ws(b, ws.bytes()));
     ws.bind(b->ws);
     HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(cd), hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(d_par, par_h, b_par, hipMemcpyHostToDevice, b->stream));
+    if (!ff_d) HIPCHK(hipMemcpyAsync(d_par, par_h, b_par, hipMemcpyHostToDevice, b->stream));
     const Mat3 B = make_mat3(recip_h);
     for (int a0 = 0; a0 < n_atoms;) {
         int a1 = a0 + 1;
         while (a1 < n_atoms && species_of_atom_h[a1] == species_of_atom_h[a0]) ++a1;
-        hipLaunchKernelGGL(k_forces_local_w, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, nx, ny, nz, B,
-                           (const double*)(d_par + 8 * species_of_atom_h[a0]), (const cd*)c2, 1.0 / (double)N, c1);
+        if (ff_d) {
+            hipLaunchKernelGGL(k_forces_local_w<true>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, nx, ny,
+                               nz, B, ff_d + (int64_t)species_of_atom_h[a0] * N, (const cd*)c2, 1.0 / (double)N, c1);
+        } else {
+            hipLaunchKernelGGL(k_forces_local_w<false>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, nx,
+                               ny, nz, B, (const double*)(d_par + 8 * species_of_atom_h[a0]), (const cd*)c2,
+                               1.0 / (double)N, c1);
+        }
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_forces_local, grid, dim3(64 * FL_WAVES), 0, b->stream, nx, ny, nz, a0, a1, (const cd*)c1,
                            (const cd*)d_tab, d_part, n_waves);
@@ -198,6 +208,17 @@ int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, 
     HIPCHK(hipMemcpyAsync(forces_h, d_out, b_out, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));     // (host tables and b->ws are free again)
     return 0;
+}
+
+int forces_local(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, const double* par_h, int n_atoms,
+                 const int* species_of_atom_h, const double* positions_h, const double* rho_d, double* forces_h) {
+    return forces_local_impl(cube_kb, recip_h, n_species, par_h, nullptr, n_atoms, species_of_atom_h, positions_h, rho_d,
+                             forces_h);
+}
+int forces_local_table(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, const double* ff_d, int n_atoms,
+                       const int* species_of_atom_h, const double* positions_h, const double* rho_d, double* forces_h) {
+    return forces_local_impl(cube_kb, recip_h, n_species, nullptr, ff_d, n_atoms, species_of_atom_h, positions_h, rho_d,
+                             forces_h);
 }
 
 // ------------------------------------------------------------------------------------------------ nonlocal term

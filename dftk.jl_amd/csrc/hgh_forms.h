@@ -34,7 +34,8 @@ __host__ __device__ inline void recip_times(const Mat3& B, double px, double py,
 struct ProjCol {         // one column of P
     double rx, ry, rz;   // atom position (reduced)
     double rp;           // r_l of the species
-    int l, m, i, pad;    // angular momentum, magnetic index, radial index (1-based)
+    int l, m, i, chan;   // angular momentum, magnetic index, radial index (1-based); chan: the channel's row of a table
+                         // of radial values (dftk_mi_build_projectors_radial), 0 for the closed forms
 };
 
 // (re + i im) <- (-i)^l (re + i im):  1, -i, -1, i

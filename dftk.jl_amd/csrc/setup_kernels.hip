@@ -61,10 +61,14 @@ int sphere_enumerate_host(int nx, int ny, int nz, const double* B /* recip_latti
 
 // ------------------------------------------------------------------------------------------------ projectors (device)
 // P[g, c] = radial_{l,i}(|q|) * Y_lm(q) * (-i)^l / sqrt(Omega) * exp(-2 pi i (G + k).r),  q = B (G + k)
+// TABLE = false: the HGH closed form of the column's channel; TABLE = true: Rtab[ProjCol::chan][row], the radial
+// transform of a numeric channel at |q| of this row (dftk_mi_radial_transform kind 0), everything else the same body
+template <bool TABLE>
 __global__ __launch_bounds__(256) void k_build_projectors(int64_t n_rows, int n_cols, const int32_t* __restrict__ G,
                                                           Mat3 B, double kx, double ky, double kz, double inv_sqrt_vol,
-                                                          const ProjCol* __restrict__ cols, cd* __restrict__ P,
-                                                          int64_t ldP) {
+                                                          const ProjCol* __restrict__ cols,
+                                                          const double* __restrict__ Rtab, int64_t ldR,
+                                                          cd* __restrict__ P, int64_t ldP) {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= n_rows) return;
     const double px = (double)G[3 * g + 0] + kx, py = (double)G[3 * g + 1] + ky, pz = (double)G[3 * g + 2] + kz;
@@ -74,7 +78,11 @@ __global__ __launch_bounds__(256) void k_build_projectors(int64_t n_rows, int n_
     for (int c = blockIdx.y; c < n_cols; c += gridDim.y) {
         const ProjCol pc = cols[c];
         double R, dR, gY[3];
-        hgh_radial(pc.l, pc.i, pc.rp, (qn * pc.rp) * (qn * pc.rp), &R, &dR);
+        if (TABLE) {
+            R = Rtab[(int64_t)pc.chan * ldR + g];
+        } else {
+            hgh_radial(pc.l, pc.i, pc.rp, (qn * pc.rp) * (qn * pc.rp), &R, &dR);
+        }
         double fr = R * solid_harmonic(pc.l, pc.m, qx, qy, qz, gY) * inv_sqrt_vol, fi = 0.0;
         rotate_minus_i_pow(pc.l, &fr, &fi);
         const double ph = -2.0 * M_PI * (px * pc.rx + py * pc.ry + pz * pc.rz);
@@ -120,9 +128,43 @@ int build_projectors_hgh(dftk_mi_basis* b, int64_t n_rows, const int32_t* G_d, c
     CHK(ensure_ws(b, cols.size() * sizeof(ProjCol)));
     HIPCHK(hipMemcpyAsync(b->ws, cols.data(), cols.size() * sizeof(ProjCol), hipMemcpyHostToDevice, b->stream));
     const unsigned gy = (unsigned)std::min<size_t>(cols.size(), 64);
-    hipLaunchKernelGGL(k_build_projectors, dim3((unsigned)((n_rows + 255) / 256), gy), dim3(256), 0, b->stream, n_rows,
-                       (int)cols.size(), G_d, make_mat3(recip_h), k_h[0], k_h[1], k_h[2], 1.0 / sqrt(volume),
-                       reinterpret_cast<const ProjCol*>(b->ws.get()), P_d, ldP);
+    hipLaunchKernelGGL(k_build_projectors<false>, dim3((unsigned)((n_rows + 255) / 256), gy), dim3(256), 0, b->stream,
+                       n_rows, (int)cols.size(), G_d, make_mat3(recip_h), k_h[0], k_h[1], k_h[2], 1.0 / sqrt(volume),
+                       reinterpret_cast<const ProjCol*>(b->ws.get()), (const double*)nullptr, (int64_t)0, P_d, ldP);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(b->stream));   // cols (host vector) and b->ws are reused by the next call
+    return 0;
+}
+
+// the same columns with tabulated radial parts: species s owns n_chan_h[4 s + l] channels of angular momentum l, rows
+// first_chan_h[4 s + l] ... of R_d (leading dimension ldR >= n_rows); any number of channels per l
+int build_projectors_radial(dftk_mi_basis* b, int64_t n_rows, const int32_t* G_d, const double* recip_h,
+                            const double* k_h, double volume, int n_species, const double* R_d, int64_t ldR,
+                            const int* first_chan_h, const int* n_chan_h, int n_atoms, const int* species_of_atom_h,
+                            const double* positions_h, cd* P_d, int64_t ldP, int* n_p_out) {
+    std::vector<ProjCol> cols;
+    for (int a = 0; a < n_atoms; ++a) {
+        const int s = species_of_atom_h[a];
+        if (s < 0 || s >= n_species) return DFTK_MI_EINVAL;
+        for (int l = 0; l < 4; ++l) {
+            const int nl = n_chan_h[4 * s + l], c0 = first_chan_h[4 * s + l];
+            if (nl < 0 || (nl > 0 && c0 < 0)) return DFTK_MI_EINVAL;
+            for (int m = -l; m <= l; ++m)
+                for (int i = 1; i <= nl; ++i)
+                    cols.push_back(ProjCol{positions_h[3 * a], positions_h[3 * a + 1], positions_h[3 * a + 2], 0.0, l, m,
+                                           i, c0 + i - 1});
+        }
+    }
+    *n_p_out = (int)cols.size();
+    if (cols.empty() || !P_d) return 0;
+    if (ldP < n_rows || ldR < n_rows || !R_d) return DFTK_MI_EINVAL;
+    if (n_rows == 0) return 0;
+    CHK(ensure_ws(b, cols.size() * sizeof(ProjCol)));
+    HIPCHK(hipMemcpyAsync(b->ws, cols.data(), cols.size() * sizeof(ProjCol), hipMemcpyHostToDevice, b->stream));
+    const unsigned gy = (unsigned)std::min<size_t>(cols.size(), 64);
+    hipLaunchKernelGGL(k_build_projectors<true>, dim3((unsigned)((n_rows + 255) / 256), gy), dim3(256), 0, b->stream,
+                       n_rows, (int)cols.size(), G_d, make_mat3(recip_h), k_h[0], k_h[1], k_h[2], 1.0 / sqrt(volume),
+                       reinterpret_cast<const ProjCol*>(b->ws.get()), R_d, ldR, P_d, ldP);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(b->stream));   // cols (host vector) and b->ws are reused by the next call
     return 0;
@@ -139,9 +181,13 @@ struct AtomPar {
     double rx, ry, rz;
     int species;
 };
+// TABLE = true: ff_s(|G|) is read from par[species * N + cube index] (dftk_mi_atomic_superposition_table) instead of
+// being evaluated from the 8 parameters of the species, and atom a enters with the amplitude coef[a] (coef may be null: 1)
+template <bool TABLE>
 __global__ __launch_bounds__(256) void k_atomic_sum(int nx, int ny, int nz, Mat3 B, int kind, int n_atoms,
                                                     const AtomPar* __restrict__ atoms, const double* __restrict__ par,
-                                                    double inv_sqrt_vol, cd* __restrict__ out) {
+                                                    const double* __restrict__ coef, double inv_sqrt_vol,
+                                                    cd* __restrict__ out) {
     const int64_t N = (int64_t)nx * ny * nz;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= N) return;
@@ -162,7 +208,9 @@ __global__ __launch_bounds__(256) void k_atomic_sum(int nx, int ny, int nz, Mat3
         if (at.species != cur) {      // atoms arrive grouped by species: one form-factor evaluation per species
             cur = at.species;
             const double* q = par + 8 * cur;
-            if (kind == 0) {
+            if (TABLE) {
+                ff = par[(int64_t)cur * N + idx];
+            } else if (kind == 0) {
                 ff = hgh_local_ff(q, (p * q[0]) * (p * q[0]));
             } else {
                 const double x = p * q[0];
@@ -172,8 +220,14 @@ __global__ __launch_bounds__(256) void k_atomic_sum(int nx, int ny, int nz, Mat3
         }
         double sn, cs;
         sincos(-2.0 * M_PI * (gx * at.rx + gy * at.ry + gz * at.rz), &sn, &cs);
-        re += ff * cs;
-        im += ff * sn;
+        if (TABLE && coef) {
+            const double f = ff * coef[a];
+            re += f * cs;
+            im += f * sn;
+        } else {
+            re += ff * cs;
+            im += ff * sn;
+        }
     }
     out[idx] = make_double2(re, im);
 }
@@ -208,8 +262,11 @@ std::vector<cd> phase_tables_host(int nx, int ny, int nz, int n_atoms, const dou
     return tab;
 }
 
-int atomic_superposition(dftk_mi_kblock* cube_kb, int kind, const double* recip_h, int n_species, const double* par_h,
-                         int n_atoms, const int* species_of_atom_h, const double* positions_h, double* out_d) {
+// par_h: 8 parameters per species on the host (kind 0 / 1), or, with ff_d given, nothing: the form factors come from
+// the device table ff_d[species][N] and coef_h (nullable) holds one amplitude per atom
+static int atomic_superposition_impl(dftk_mi_kblock* cube_kb, int kind, const double* recip_h, int n_species,
+                                     const double* par_h, const double* ff_d, const double* coef_h, int n_atoms,
+                                     const int* species_of_atom_h, const double* positions_h, double* out_d) {
     dftk_mi_basis* b = cube_kb->basis;
     const int64_t N = (int64_t)b->nx * b->ny * b->nz;
     if (cube_kb->n_G != N) {
@@ -223,14 +280,24 @@ int atomic_superposition(dftk_mi_kblock* cube_kb, int kind, const double* recip_
     CHK(scratch_grow(b, b->dense_ws, 2 * (size_t)N * sizeof(cd)));
     cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
     cd* c2 = c1 + N;
-    const size_t tab = (size_t)n_atoms * sizeof(AtomPar) + (size_t)n_species * 8 * sizeof(double);
+    const size_t tab = (size_t)n_atoms * sizeof(AtomPar) +
+                       std::max((size_t)n_species * 8, (size_t)n_atoms) * sizeof(double);   // parameters or amplitudes
     CHK(ensure_ws(b, tab));
     AtomPar* d_atoms = reinterpret_cast<AtomPar*>(b->ws.get());
     double* d_par = reinterpret_cast<double*>(d_atoms + n_atoms);
     HIPCHK(hipMemcpyAsync(d_atoms, atoms.data(), (size_t)n_atoms * sizeof(AtomPar), hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(d_par, par_h, (size_t)n_species * 8 * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    hipLaunchKernelGGL(k_atomic_sum, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, b->nx, b->ny, b->nz,
-                       make_mat3(recip_h), kind, n_atoms, d_atoms, d_par, 1.0 / sqrt(b->volume), c1);
+    if (ff_d) {
+        if (coef_h)
+            HIPCHK(hipMemcpyAsync(d_par, coef_h, (size_t)n_atoms * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        hipLaunchKernelGGL(k_atomic_sum<true>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, b->nx, b->ny,
+                           b->nz, make_mat3(recip_h), kind, n_atoms, d_atoms, ff_d,
+                           coef_h ? (const double*)d_par : (const double*)nullptr, 1.0 / sqrt(b->volume), c1);
+    } else {
+        HIPCHK(hipMemcpyAsync(d_par, par_h, (size_t)n_species * 8 * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        hipLaunchKernelGGL(k_atomic_sum<false>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, b->nx, b->ny,
+                           b->nz, make_mat3(recip_h), kind, n_atoms, d_atoms, d_par, (const double*)nullptr,
+                           1.0 / sqrt(b->volume), c1);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(b->stream));      // host tables and b->ws are free again (the FFT below reuses ws-free paths)
     CHK(launch_ifft_to_cube(cube_kb, c1, c2));
@@ -239,4 +306,17 @@ int atomic_superposition(dftk_mi_kblock* cube_kb, int kind, const double* recip_
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
+}
+
+int atomic_superposition(dftk_mi_kblock* cube_kb, int kind, const double* recip_h, int n_species, const double* par_h,
+                         int n_atoms, const int* species_of_atom_h, const double* positions_h, double* out_d) {
+    return atomic_superposition_impl(cube_kb, kind, recip_h, n_species, par_h, nullptr, nullptr, n_atoms,
+                                     species_of_atom_h, positions_h, out_d);
+}
+
+int atomic_superposition_table(dftk_mi_kblock* cube_kb, const double* recip_h, int n_species, const double* ff_d,
+                               int n_atoms, const int* species_of_atom_h, const double* positions_h,
+                               const double* coef_h, double* out_d) {
+    return atomic_superposition_impl(cube_kb, 0, recip_h, n_species, nullptr, ff_d, coef_h, n_atoms, species_of_atom_h,
+                                     positions_h, out_d);
 }

@@ -14,7 +14,9 @@ import torch
 
 from . import _lib
 from .symmetry import symmetrize_forces
-from .terms import energy_forces_ewald, local_species_tables, occupied_block, total_density
+from .psp_upf import model_has_upf
+from .terms import (energy_forces_ewald, local_form_factor_table, local_species_tables, occupied_block,
+                    total_density)
 
 # (ExactExchange: a functional of the orbitals alone, no explicit dependence on the positions)
 _NO_FORCES = ("Kinetic", "Hartree", "PspCorrection", "Entropy", "ExactExchange")
@@ -28,10 +30,21 @@ def _group_order(model):
 def _forces_local(basis, rho):
     model = basis.model
     order = _group_order(model)
-    par, species, positions = local_species_tables(model)
     Bh = np.asfortranarray(model.recip_lattice, dtype=np.float64)
     rho_tot = total_density(rho).to(torch.float64).contiguous()
     out = np.zeros((len(order), 3))
+    if model_has_upf(model):
+        # a numeric local part: the form factors of every species as a device table (the one V_loc was built from)
+        ff = local_form_factor_table(basis)
+        _, species, positions = local_species_tables(model, lambda el: [])
+        basis.pre_call()
+        _lib.check(basis.lib.dftk_mi_forces_local_table(basis._cube_handle, Bh.ctypes.data, ff.shape[0], ff.data_ptr(),
+                                                        len(order), species.ctypes.data, positions.ctypes.data,
+                                                        rho_tot.data_ptr(), out.ctypes.data))
+        F = np.zeros((len(model.atoms), 3))
+        F[order] = out
+        return F
+    par, species, positions = local_species_tables(model)
     basis.pre_call()
     _lib.check(basis.lib.dftk_mi_forces_local(basis._cube_handle, Bh.ctypes.data, par.shape[0], par.ctypes.data,
                                               len(order), species.ctypes.data, positions.ctypes.data,

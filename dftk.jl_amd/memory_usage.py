@@ -59,6 +59,15 @@ def _n_projectors(model) -> int:
     return n
 
 
+def form_factor_table_bytes(model, fft_size) -> int:
+    """Bytes of the local form-factor table a basis keeps when its model has a UPF species (one row of N doubles per species
+    group: V_loc is built from it and the forces read it; terms.local_form_factor_table); 0 for HGH-only models."""
+    from .psp_upf import model_has_upf
+    if not model_has_upf(model):
+        return 0
+    return F64 * int(np.prod(fft_size)) * len(model.atom_groups)
+
+
 def _fft_size(model, Ecut, fft_size):
     from .basis import compute_fft_size
     return tuple(int(x) for x in (fft_size if fft_size is not None else compute_fft_size(model, Ecut)))
@@ -97,6 +106,7 @@ def plan_planewave_sharded(model, Ecut, n_ranks, fft_size=None, gamma_real=True,
       fft_scratch       fft_batch x (T1 + T2)                 (fft_kernels.hip fft_ensure_scratch)
       gemm_split_k      <= 1 GiB of split-K slabs             (gemm_kernels.hip)
       cubes             rho, V and its parts, Anderson history of 10 (x, r) pairs: 26 real cubes
+      upf_form_factors  one real cube per species group, only when the model has a UPF species (terms.py)
     Optional (``optional_bytes_per_rank``, not in the total: the library allocates it only where the device has room for it
     twice over, and runs the same without it):
       kept_planes       ceil(M / 2) x T2: the y-planes the density pass keeps for the next LOBPCG start (un-sharded
@@ -133,6 +143,7 @@ def plan_planewave_sharded(model, Ecut, n_ranks, fft_size=None, gamma_real=True,
         "fft_scratch": fft_batch * (n_lines * nxp + nzx * fft[1] * nxp) * CPLX,
         "gemm_split_k": 1 << 30,
         "cubes": 26 * N * F64,
+        "upf_form_factors": form_factor_table_bytes(model, fft),
     }
     total = int(sum(items.values()))
     optional = {"kept_planes": (-(-M // 2) * nzx * fft[1] * nxp * CPLX) if (gamma_real and p == 1) else 0}

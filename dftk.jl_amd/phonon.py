@@ -34,6 +34,8 @@ def _check_supported(basis, q=None):
     from .exchange import refuse
     model = basis.model
     refuse(model, "the dynamical matrix (no response with the Fock operator)")
+    from .psp_upf import refuse_upf
+    refuse_upf(model, "the dynamical matrix and the displacement perturbation")
     if q is not None and np.any(np.asarray(q, dtype=float) != 0):
         raise NotImplementedError("phonons at q != 0 are not implemented: q = 0 only")
     if model.n_spin_components != 1:

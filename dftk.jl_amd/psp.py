@@ -1,7 +1,9 @@
 """HGH/GTH pseudopotentials for the host mirror (src/pseudo/PspHgh.jl, NormConservingPsp.jl:187-234).
 
 Evaluation functions are written with torch so that the O(n_G) / O(N) set-up arrays
-(form factors, local potential) are produced directly in HBM.
+(form factors, local potential) are produced directly in HBM.  The ``eval_psp_*`` functions dispatch on the kind of
+pseudopotential: for a numeric one (``PspUpf``, psp_upf.py) they return the host quadrature's values (the device values come
+from ``dftk_mi_radial_transform``, terms.py).
 """
 from __future__ import annotations
 
@@ -11,6 +13,9 @@ from dataclasses import dataclass
 
 import numpy as np
 import torch
+
+from . import psp_upf
+from .psp_upf import PspUpf, parse_psp_upf  # noqa: F401
 
 
 @dataclass
@@ -37,6 +42,10 @@ class PspHgh:
 
     def has_core_density(self):
         """PspHgh.jl:16: HGH pseudopotentials carry no non-linear core correction."""
+        return False
+
+    def has_valence_density(self):
+        """HGH tables carry no pseudo-atomic density: the guess is the Gaussian of ``atom_decay_length``."""
         return False
 
 
@@ -79,8 +88,12 @@ ATOMIC_WEIGHT = {"H": 1.0080, "C": 12.011, "Al": 26.982, "Si": 28.085, "Fe": 55.
 AMU_IN_ELECTRON_MASSES = 1822.888486209
 
 
-def load_psp(symbol: str, functional: str = "lda") -> PspHgh:
-    """``load_psp`` for the vendored HGH family (data/psp/hgh/<functional>/<symbol>-q<Z>.hgh)."""
+def load_psp(symbol: str, functional: str = "lda"):
+    """``load_psp`` for the vendored HGH family (data/psp/hgh/<functional>/<symbol>-q<Z>.hgh), or, given the path of a
+    ``.upf`` file, the numeric pseudopotential it holds (``PspUpf``)."""
+    low = str(symbol).lower()
+    if low.endswith(".upf") or low.endswith(".psp8"):
+        return PspUpf(str(symbol))
     Z, rloc, cloc, rp, h, desc = _TABLE[(symbol, functional)]
     return _psp(Z, rloc, cloc, rp, h, f"hgh/{functional}/{symbol.lower()}-q{Z}.hgh", desc)
 
@@ -119,8 +132,16 @@ def parse_psp_hgh(text: str, identifier: str = "") -> PspHgh:
     return _psp(Zion, rloc, cloc, rp, hup, identifier, lines[0])
 
 
-def eval_psp_local_fourier(psp: PspHgh, p: torch.Tensor) -> torch.Tensor:
-    """PspHgh.jl:110-124; zero at p == 0 (compensating background)."""
+def _on_host(fn, p: torch.Tensor) -> torch.Tensor:
+    """A NumPy function of |q| applied to a tensor of any shape, result on the tensor's device."""
+    out = fn(p.detach().to("cpu", torch.float64).reshape(-1).numpy())
+    return torch.from_numpy(np.ascontiguousarray(out)).reshape(p.shape).to(p.device)
+
+
+def eval_psp_local_fourier(psp, p: torch.Tensor) -> torch.Tensor:
+    """PspHgh.jl:110-124 / PspUpf.jl:229-263 (host quadrature); zero at p == 0 (compensating background)."""
+    if isinstance(psp, PspUpf):
+        return _on_host(lambda q: psp_upf.eval_psp_local_fourier_upf(psp, q), p)
     t2 = (p * psp.rloc) ** 2
     c = psp.cloc
     P = (c[0] + c[1] * (3 - t2) + c[2] * (15 - 10 * t2 + t2 * t2)
@@ -132,7 +153,7 @@ def eval_psp_local_fourier(psp: PspHgh, p: torch.Tensor) -> torch.Tensor:
 
 
 def eval_psp_local_fourier_derivative(psp: PspHgh, p: torch.Tensor) -> torch.Tensor:
-    """d/dp of ``eval_psp_local_fourier`` (the local term of the stress tensor; the device kernel restates it).  With
+    """(HGH only) d/dp of ``eval_psp_local_fourier`` (the local term of the stress tensor; the device kernel restates it).  With
     t2 = (p rloc)^2 and ff = A e^{-t2/2} (-Z / t2 + B P(t2)):  dff/dt2 = A e^{-t2/2} (Z / t2^2 + B P' - ff-bracket / 2)
     and dff/dp = 2 p rloc^2 dff/dt2; zero at p == 0 like the form factor itself."""
     t2 = (p * psp.rloc) ** 2
@@ -148,8 +169,10 @@ def eval_psp_local_fourier_derivative(psp: PspHgh, p: torch.Tensor) -> torch.Ten
     return torch.where(t2 > 0, val, torch.zeros_like(val))
 
 
-def eval_psp_projector_fourier(psp: PspHgh, i: int, l: int, p: torch.Tensor) -> torch.Tensor:
-    """PspHgh.jl:140-164 (i is 1-based; includes the division by p^l)."""
+def eval_psp_projector_fourier(psp, i: int, l: int, p: torch.Tensor) -> torch.Tensor:
+    """PspHgh.jl:140-164 / PspUpf.jl:186-208 (i is 1-based; includes the division by p^l)."""
+    if isinstance(psp, PspUpf):
+        return _on_host(lambda q: psp_upf.eval_psp_projector_fourier_upf(psp, i, l, q), p)
     rp = psp.rp[l]
     t2 = (p * rp) ** 2
     common = 4 * math.pi ** 1.25 * math.sqrt(2 ** (l + 1) * rp ** 3) * torch.exp(-t2 / 2)
@@ -169,8 +192,17 @@ def eval_psp_projector_fourier(psp: PspHgh, i: int, l: int, p: torch.Tensor) -> 
     return table[(l, i)]()
 
 
-def eval_psp_energy_correction(psp: PspHgh) -> float:
-    """PspHgh.jl:173-184."""
+def eval_psp_valence_density_fourier(psp, p: torch.Tensor) -> torch.Tensor:
+    """PspUpf.jl:269-273: the Hankel transform (l = 0) of the pseudo-atomic valence density of the file."""
+    if not isinstance(psp, PspUpf) or not psp.has_valence_density():
+        raise ValueError("the pseudopotential carries no valence density")
+    return _on_host(lambda q: psp_upf.eval_psp_valence_density_fourier_upf(psp, q), p)
+
+
+def eval_psp_energy_correction(psp) -> float:
+    """PspHgh.jl:173-184 / PspUpf.jl:308-315."""
+    if isinstance(psp, PspUpf):
+        return psp_upf.eval_psp_energy_correction_upf(psp)
     coeffs = (1.0, 3.0, 15.0, 105.0)
     diff = (psp.Zion * psp.rloc ** 2 / 2
             + math.sqrt(math.pi / 2) * psp.rloc ** 3 * sum(a * b for a, b in zip(coeffs, psp.cloc)))

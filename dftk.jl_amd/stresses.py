@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .forces import _check_nlcc
+from .psp_upf import refuse_upf
 from .symmetry import symmetrize_stresses
 from .terms import (_DENSITY_THRESHOLD, _GGA_BITS, _LDA_BITS, _SPIN_LDA, local_species_tables, occupied_block,
                     projector_species_tables, stress_ewald, total_density)
@@ -208,6 +209,7 @@ def compute_stresses_term(name, basis, psi, occupation, rho=None):
     ``occupation`` (the definition recomputes it from the orbitals)."""
     if name not in basis.model.term_types:
         raise ValueError(f"term {name} is not part of the model")
+    refuse_upf(basis.model, "the stress tensor")
     if name == "Entropy":
         return None
     _check_unsharded(basis)
@@ -224,6 +226,7 @@ def compute_stresses_cart(basis_or_scfres, psi=None, occupation=None, rho=None):
         basis, psi, occupation, rho = res["basis"], res["psi"], res["occupation"], res["rho"]
     else:
         basis = basis_or_scfres
+    refuse_upf(basis.model, "the stress tensor")
     _check_unsharded(basis)
     names = [n for n in basis.model.term_types if n != "Entropy"]
     dev = _device_terms(basis, psi, occupation, rho, [n for n in names if n in _DEVICE_TERMS])

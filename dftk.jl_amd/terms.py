@@ -20,7 +20,8 @@ from scipy.special import erfc
 from . import _lib
 from .hamiltonian import DftHamiltonianBlock
 from .psp import (eval_psp_energy_correction, eval_psp_local_fourier, eval_psp_projector_fourier,
-                  solid_harmonic_real)
+                  eval_psp_valence_density_fourier, solid_harmonic_real)
+from .psp_upf import is_upf, model_has_upf
 
 TWO_PI = 2 * math.pi
 
@@ -121,10 +122,88 @@ def _use_setup_abi(basis):
     return basis.handle is not None and os.environ.get("DFTK_MI_TORCH_SETUP") is None
 
 
+# ---------------------------------------------------------------------------------- numeric (UPF) pseudopotentials
+# A model with a UPF species takes the table entries of the library: radial parts / form factors are arrays on the
+# device, written by dftk_mi_radial_transform for UPF species and by the torch closed forms of psp.py for HGH species of
+# the same cell.  A model with only HGH species never comes here.
+def radial_transform_abi(basis, kind, l, r, wf, Zion, q):
+    """``dftk_mi_radial_transform`` of one channel at the device values ``q`` (float64, any shape)."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    wf = np.ascontiguousarray(wf, dtype=np.float64)
+    q = q.contiguous()
+    out = torch.empty_like(q)
+    basis.pre_call()
+    _lib.check(basis.lib.dftk_mi_radial_transform(basis.handle, kind, l, len(r), r.ctypes.data, wf.ctypes.data,
+                                                  float(Zion), q.numel(), q.data_ptr(), out.data_ptr()))
+    basis.post_call()
+    return out
+
+
+def _cube_norms(basis):
+    """|B G| of every cube point, x fastest (the cube index of the kernels)."""
+    return torch.linalg.norm(basis.G_vectors_cart_cube(), dim=-1).reshape(-1).contiguous()
+
+
+def local_form_factor_table(basis):
+    """ff_s(|G|) of the local potential per species group and cube point, (n_groups, N) on the device; kept on the basis
+    (the forces read the same table)."""
+    tab = getattr(basis, "_ff_local_table", None)
+    if tab is None:
+        q = _cube_norms(basis)
+        rows = []
+        for g in basis.model.atom_groups:
+            psp = basis.model.atoms[g[0]].psp
+            if is_upf(psp):
+                r, wf = psp.local_channel()
+                rows.append(radial_transform_abi(basis, 1, 0, r, wf, psp.Zion, q))
+            else:
+                rows.append(eval_psp_local_fourier(psp, q))
+        tab = basis._ff_local_table = torch.stack(rows).contiguous()
+    return tab
+
+
+def _valence_form_factor(basis, el, q):
+    """ValenceDensityAuto (density_methods.jl:245-264): the file's pseudo-atomic density where it has one, else the
+    Gaussian of ``atom_decay_length``."""
+    has = getattr(el.psp, "has_valence_density", None)
+    if has is not None and has():
+        if _use_setup_abi(basis):
+            r, wf = el.psp.valence_channel()
+            return radial_transform_abi(basis, 0, 0, r, wf, 0.0, q)
+        return eval_psp_valence_density_fourier(el.psp, q)
+    return el.charge_ionic * torch.exp(-(q * atom_decay_length(el.n_elec_core, el.charge_ionic)) ** 2)
+
+
+def _model_has_valence_density(model):
+    return any(getattr(a.psp, "has_valence_density", lambda: False)() for a in model.atoms)
+
+
+def _atomic_superposition_table_abi(basis, ff, coefficients=None):
+    """``dftk_mi_atomic_superposition_table``: ``ff`` holds one row of N form factors per species group; ``coefficients``
+    (optional): one amplitude per atom in ``model.atoms`` order, handed to the kernel in species-group order."""
+    model = basis.model
+    _, species, positions = local_species_tables(model, lambda el: [])
+    coef = None
+    if coefficients is not None:
+        coef = np.ascontiguousarray([float(coefficients[ia]) for g in model.atom_groups for ia in g], dtype=np.float64)
+    ff = ff.contiguous()
+    Bh = np.asfortranarray(model.recip_lattice, dtype=np.float64)
+    nx, ny, nz = basis.fft_size
+    out = torch.empty((nz, ny, nx), dtype=torch.float64, device=basis.device)
+    basis.pre_call()
+    _lib.check(basis.lib.dftk_mi_atomic_superposition_table(basis._cube_handle, Bh.ctypes.data, ff.shape[0],
+                                                            ff.data_ptr(), len(species), species.ctypes.data,
+                                                            positions.ctypes.data,
+                                                            None if coef is None else coef.ctypes.data, out.data_ptr()))
+    return out
+
+
 def compute_local_potential(basis):
     """local.jl:108-138."""
     model = basis.model
     if _use_setup_abi(basis):
+        if model_has_upf(model):
+            return _atomic_superposition_table_abi(basis, local_form_factor_table(basis))
         return _atomic_superposition_abi(basis, 0, _hgh_local_params)
     Gnorm = torch.linalg.norm(basis.G_vectors_cart_cube(), dim=-1)
     pot = torch.zeros(Gnorm.shape, dtype=torch.complex128, device=basis.device)
@@ -159,6 +238,8 @@ def build_projection_vectors_abi(basis, kpt):
     into P; same column order as the torch construction below (species groups, atoms, (l, m, i))."""
     import ctypes as C
     model = basis.model
+    if model_has_upf(model):
+        return _build_projection_vectors_radial_abi(basis, kpt)
     n_species, rp, nproj, species, positions, _ = projector_species_tables(model)
     if n_species == 0:
         return None
@@ -172,6 +253,48 @@ def build_projection_vectors_abi(basis, kpt):
     P = torch.empty((n_p.value, kpt.n_loc), dtype=torch.complex128, device=basis.device)
     basis.pre_call()
     _lib.check(basis.lib.dftk_mi_build_projectors_hgh(*args, P.data_ptr(), kpt.n_loc, C.byref(n_p)))
+    return P
+
+
+def _build_projection_vectors_radial_abi(basis, kpt):
+    """The same P through ``dftk_mi_build_projectors_radial``: one row of radial values per channel at |B (G + k)| of this
+    rank's rows (UPF channels by the device transform, HGH channels of a mixed cell by their closed forms)."""
+    import ctypes as C
+    model = basis.model
+    groups = [g for g in model.atom_groups if model.atoms[g[0]].psp.count_n_proj() > 0]
+    if not groups:
+        return None
+    q = torch.linalg.norm(kpt.Gplusk_cart[kpt.row0:kpt.row1], dim=1).contiguous()
+    first = np.zeros((len(groups), 4), dtype=np.int32)
+    count = np.zeros((len(groups), 4), dtype=np.int32)
+    chans, species, positions = [], [], []
+    for s_idx, g in enumerate(groups):
+        psp = model.atoms[g[0]].psp
+        for l in range(psp.lmax + 1):
+            first[s_idx, l], count[s_idx, l] = len(chans), psp.count_n_proj_radial(l)
+            for i in range(psp.count_n_proj_radial(l)):
+                if is_upf(psp):
+                    r, wf = psp.projector_channel(l, i)
+                    chans.append(radial_transform_abi(basis, 0, l, r, wf, 0.0, q))
+                else:
+                    chans.append(eval_psp_projector_fourier(psp, i + 1, l, q))
+        for ia in g:
+            species.append(s_idx)
+            positions.append(np.asarray(model.positions[ia], dtype=float))
+    R = torch.stack(chans).contiguous()
+    species = np.asarray(species, dtype=np.int32)
+    positions = np.ascontiguousarray(np.asarray(positions, dtype=np.float64).reshape(-1, 3))
+    G32 = kpt.G_vectors[kpt.row0:kpt.row1].to(torch.int32).contiguous()
+    Bh = np.asfortranarray(model.recip_lattice, dtype=np.float64)
+    kh = np.ascontiguousarray(kpt.coordinate, dtype=np.float64)
+    n_p = C.c_int()
+    args = (basis.handle, kpt.n_loc, G32.data_ptr(), Bh.ctypes.data, kh.ctypes.data, model.unit_cell_volume,
+            len(groups), R.data_ptr(), max(kpt.n_loc, 1), first.ctypes.data, count.ctypes.data, len(species),
+            species.ctypes.data, positions.ctypes.data)
+    _lib.check(basis.lib.dftk_mi_build_projectors_radial(*args, None, kpt.n_loc, C.byref(n_p)))
+    P = torch.empty((n_p.value, kpt.n_loc), dtype=torch.complex128, device=basis.device)
+    basis.pre_call()
+    _lib.check(basis.lib.dftk_mi_build_projectors_radial(*args, P.data_ptr(), kpt.n_loc, C.byref(n_p)))
     return P
 
 
@@ -630,6 +753,10 @@ def _gaussian_superposition(basis, coefficients=None):
     """atomic_density_superposition with the Gaussian valence densities (density_methods.jl:158-181, :236-244);
     ``coefficients``: one amplitude per atom (default 1)."""
     model = basis.model
+    if _model_has_valence_density(model) and _use_setup_abi(basis):
+        q = _cube_norms(basis)
+        ff = torch.stack([_valence_form_factor(basis, model.atoms[g[0]], q) for g in model.atom_groups])
+        return _atomic_superposition_table_abi(basis, ff, coefficients)
     if _use_setup_abi(basis):
         if coefficients is None:
             return _atomic_superposition_abi(basis, 1, lambda el: [atom_decay_length(el.n_elec_core, el.charge_ionic),
@@ -641,7 +768,7 @@ def _gaussian_superposition(basis, coefficients=None):
     rho_G = torch.zeros(Gnorm.shape, dtype=torch.complex128, device=basis.device)
     for group in model.atom_groups:
         el = model.atoms[group[0]]
-        ff = el.charge_ionic * torch.exp(-(Gnorm * atom_decay_length(el.n_elec_core, el.charge_ionic)) ** 2)
+        ff = _valence_form_factor(basis, el, Gnorm)
         sf = torch.zeros_like(rho_G)
         for ia in group:
             sf += _structure_factor_cube(basis, model.positions[ia]) * (1.0 if coefficients is None else float(coefficients[ia]))

@@ -130,6 +130,38 @@ int dftk_mi_atomic_superposition(dftk_mi_kblock* cube_kb, int kind, const double
 int dftk_mi_forces_local(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species, const double* params_h,
                          int n_atoms, const int* species_of_atom_h, const double* positions_h, const double* rho_d,
                          double* forces_h);
+/* ---- numeric (UPF) norm-conserving pseudopotentials (src/pseudo/PspUpf.jl) -----------------------------------------
+ * Radial transform of one channel on the device.  The quadrature rule of the reference (src/common/quadrature.jl) is
+ * linear in the integrand: the caller folds it into weights w_i once per mesh and passes wf_h[i] = w_i * r2_f[i], cut at
+ * the channel's own length n_r >= 1 (host arrays, read before the call returns), q_d / out_d: n_q device doubles.
+ *   kind 0: out[j] = 4 pi sum_i wf_i r_i^l g_l(q_j r_i), g_l(x) = j_l(x) / x^l, l = 0..3: the modified Hankel transform
+ *           (src/common/hankel.jl), finite at q = 0 (g_l(0) = 1 / (2l+1)!!).
+ *   kind 1: the local potential (PspUpf.jl:229-242) with wf_i = w_i (r_i vloc_i + Zion erf(r_i)):
+ *           out[j] = 4 pi (sum_i wf_i sin(q_j r_i) / q_j - Zion / q_j^2 exp(-q_j^2 / 4)); exactly 0 at q_j = 0; l ignored.
+ * One lane per q, the sum over i in ascending order in that lane: deterministic.  Asynchronous on the basis' stream.
+ * dftk_mi_radial_tile(): the number of mesh points the kernel stages through LDS at a time (host routine). */
+int dftk_mi_radial_transform(dftk_mi_basis* basis, int kind, int l, int n_r, const double* r_h, const double* wf_h,
+                             double Zion, int64_t n_q, const double* q_d, double* out_d);
+int dftk_mi_radial_tile(void);
+/* dftk_mi_build_projectors_hgh with tabulated radial parts: R_d[channel * ldR + row] = the kind-0 transform of the
+ * channel at |B (G + k)| of the row (ldR >= n_rows); species s owns n_chan_h[4 s + l] channels of angular momentum l
+ * (any number), channels first_chan_h[4 s + l] ... of R_d.  Same column order and P layout as the HGH entry. */
+int dftk_mi_build_projectors_radial(dftk_mi_basis* basis, int64_t n_rows, const int32_t* G_d,
+                                    const double* recip_lattice_h, const double* kcoord_h, double unit_cell_volume,
+                                    int n_species, const double* R_d, int64_t ldR, const int* first_chan_h,
+                                    const int* n_chan_h, int n_atoms, const int* species_of_atom_h,
+                                    const double* positions_h, dftk_mi_cplx* P_d, int64_t ldP, int* n_p);
+/* dftk_mi_atomic_superposition / dftk_mi_forces_local with the form factors read from a device table
+ * ff_d[species * N + cube index] (N = nx ny nz, x fastest; the value at G = 0 included) instead of closed forms; the
+ * unpaired-Nyquist rule, the species grouping and everything else as in those entries.  coeff_h (superposition only; NULL
+ * = all 1): one amplitude per atom, as the per-atom coefficients of the spin-density guess
+ * (src/density_methods.jl:126-152). */
+int dftk_mi_atomic_superposition_table(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species,
+                                       const double* ff_d, int n_atoms, const int* species_of_atom_h,
+                                       const double* positions_h, const double* coeff_h, double* out_d);
+int dftk_mi_forces_local_table(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_species, const double* ff_d,
+                               int n_atoms, const int* species_of_atom_h, const double* positions_h,
+                               const double* rho_d, double* forces_h);
 /* compute_forces(::TermAtomicNonlocal) (src/terms/nonlocal.jl:49-98) for ONE k-block, unsymmetrised: the block's P / D
  * (dftk_mi_kblock_set_projectors); kcoord_h = the k-point (reduced); psi_d = n_bands orbitals in the caller's
  * full-sphere layout (leading dimension ld_psi); weight_h[n] = kweight * occupation[n]; atom a owns projector columns
