@@ -112,6 +112,9 @@ _SIGNATURES = {
                                               C.c_double, C.c_void_p, C.c_void_p]),
     "dftk_mi_local_potential_collinear_gga": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                         C.c_double, C.c_void_p, C.c_void_p]),
+    "dftk_mi_local_potential_core": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    "dftk_mi_cube_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dftk_mi_xc_gga_spin": (C.c_int, [C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     "dftk_mi_symmetrize_rho": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

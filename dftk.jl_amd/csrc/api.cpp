@@ -906,8 +906,8 @@ extern "C" int dftk_mi_local_potential(dftk_mi_kblock* cube_kb, const double* rh
                                        double* energies_h) {
     if (!cube_kb || !rho_d || (!energies_h && !V_out_d) || (xc_functionals & ~(7 | 32)) || cube_kb->sh_comm) return DFTK_MI_EINVAL;
     HIPCHK(hipSetDevice(cube_kb->basis->device));
-    return local_potential_lda(cube_kb, nullptr, rho_d, V_loc_d, poisson_green_d, xc_functionals, 0.0, V_out_d,
-                               energies_h);
+    return local_potential_lda(cube_kb, nullptr, rho_d, nullptr, nullptr, V_loc_d, poisson_green_d, xc_functionals, 0.0,
+                               V_out_d, energies_h);
 }
 
 extern "C" int dftk_mi_local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho_d, const double* V_loc_d,
@@ -915,7 +915,7 @@ extern "C" int dftk_mi_local_potential_collinear(dftk_mi_kblock* cube_kb, const 
                                                  double* energies_h) {
     if (!cube_kb || !rho_d || (!energies_h && !V_out_d) || cube_kb->sh_comm) return DFTK_MI_EINVAL;
     HIPCHK(hipSetDevice(cube_kb->basis->device));
-    return local_potential_collinear(cube_kb, rho_d, V_loc_d, poisson_green_d, xc_functionals, V_out_d, energies_h);
+    return local_potential_collinear(cube_kb, rho_d, nullptr, V_loc_d, poisson_green_d, xc_functionals, V_out_d, energies_h);
 }
 
 // Julia's column-major 3x3 (entry (i, j) at i + 3 j) -> the kernels' row-major copy
@@ -932,8 +932,8 @@ extern "C" int dftk_mi_local_potential_gga(dftk_mi_kblock* cube_kb, const double
     HIPCHK(hipSetDevice(cube_kb->basis->device));
     double B[9] = {0};
     if (recip_lattice_h) rowmajor3(recip_lattice_h, B);
-    return local_potential_lda(cube_kb, B, rho_d, V_loc_d, poisson_green_d, xc_functionals, density_threshold, V_out_d,
-                               energies_h);
+    return local_potential_lda(cube_kb, B, rho_d, nullptr, nullptr, V_loc_d, poisson_green_d, xc_functionals,
+                               density_threshold, V_out_d, energies_h);
 }
 
 extern "C" int dftk_mi_local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_lattice_h,
@@ -946,8 +946,50 @@ extern "C" int dftk_mi_local_potential_collinear_gga(dftk_mi_kblock* cube_kb, co
     HIPCHK(hipSetDevice(cube_kb->basis->device));
     double B[9] = {0};
     if (recip_lattice_h) rowmajor3(recip_lattice_h, B);
-    return local_potential_collinear_gga(cube_kb, B, rho_d, V_loc_d, poisson_green_d, xc_functionals, density_threshold,
-                                         V_out_d, energies_h);
+    return local_potential_collinear_gga(cube_kb, B, rho_d, nullptr, nullptr, V_loc_d, poisson_green_d, xc_functionals,
+                                         density_threshold, V_out_d, energies_h);
+}
+
+// The four entries above with the core density of a non-linear core correction as one more operand of their passes.
+extern "C" int dftk_mi_local_potential_core(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_spin,
+                                            const double* rho_d, const double* rho_core_d, const double* grad_core_d,
+                                            const double* V_loc_d, const double* poisson_green_d, int xc_functionals,
+                                            double density_threshold, double* V_out_d, double* energies_h) {
+    if (!cube_kb || !rho_d || (!energies_h && !V_out_d) || cube_kb->sh_comm) return DFTK_MI_EINVAL;
+    if (n_spin != 1 && n_spin != 2) {
+        dftk_set_error("local_potential_core: n_spin = %d (1 or 2)", n_spin);
+        return DFTK_MI_EINVAL;
+    }
+    const int gga = xc_functionals & 24;
+    // the masks of the entry of the same kind: unpolarised LDA 7 | 32, unpolarised GGA 31, collinear 1 | 4 | 32 | 24
+    const int allowed = n_spin == 2 ? (1 | 4 | 32 | 24) : (gga ? 31 : (7 | 32));
+    if (xc_functionals & ~allowed) {
+        dftk_set_error("local_potential_core: functional mask %d outside %d (n_spin = %d)", xc_functionals, allowed, n_spin);
+        return DFTK_MI_EINVAL;
+    }
+    if (gga && !recip_lattice_h) return DFTK_MI_EINVAL;
+    if (gga && rho_core_d && !grad_core_d) {
+        dftk_set_error("local_potential_core: a GGA functional needs the gradient of the core density (grad_core_d)");
+        return DFTK_MI_EINVAL;
+    }
+    HIPCHK(hipSetDevice(cube_kb->basis->device));
+    double B[9] = {0};
+    if (recip_lattice_h) rowmajor3(recip_lattice_h, B);
+    const double* gc = rho_core_d ? grad_core_d : nullptr;
+    if (n_spin == 2)
+        return local_potential_collinear_gga(cube_kb, B, rho_d, rho_core_d, gc, V_loc_d, poisson_green_d, xc_functionals,
+                                             density_threshold, V_out_d, energies_h);
+    return local_potential_lda(cube_kb, gga ? B : nullptr, rho_d, rho_core_d, gc, V_loc_d, poisson_green_d, xc_functionals,
+                               gga ? density_threshold : 0.0, V_out_d, energies_h);
+}
+
+extern "C" int dftk_mi_cube_gradient(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, const double* f_d,
+                                     double* grad_d) {
+    if (!cube_kb || !recip_lattice_h || !f_d || !grad_d || cube_kb->sh_comm) return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(cube_kb->basis->device));
+    double B[9];
+    rowmajor3(recip_lattice_h, B);
+    return cube_gradient(cube_kb, B, f_d, grad_d);
 }
 
 extern "C" int dftk_mi_symmetrize_rho(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, const double* tau_h,

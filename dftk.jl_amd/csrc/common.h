@@ -420,12 +420,16 @@ int comm_alltoallv(dftk_mi_comm* c, dftk_mi_basis* b, const cd* send, const size
                    cd* recv, const size_t* roff, const size_t* rcnt);
 
 // xc_kernels.hip
-int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const double* vloc, const double* green,
-                              int fun_mask, double* V_out, double* energies_h);
-int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* vloc,
-                        const double* green, int fun_mask, double threshold, double* V_out, double* energies_h);
-int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* vloc,
-                                  const double* green, int fun_mask, double threshold, double* V_out, double* energies_h);
+// (core: the total core density of a non-linear core correction, ONE cube, and grad_core its three gradient cubes; both NULL
+// without one.  The XC forms see rho_s + core / n_spin and grad rho_s + grad core / n_spin, every other term rho alone.)
+int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const double* core, const double* vloc,
+                              const double* green, int fun_mask, double* V_out, double* energies_h);
+int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* core,
+                        const double* grad_core, const double* vloc, const double* green, int fun_mask, double threshold,
+                        double* V_out, double* energies_h);
+int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* core,
+                                  const double* grad_core, const double* vloc, const double* green, int fun_mask,
+                                  double threshold, double* V_out, double* energies_h);
 int xc_gga_spin_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, int fun_mask,
                           double threshold, double* e, double* vrho, double* vsigma);
 
@@ -438,6 +442,8 @@ int cube_symmetrize(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, cons
                     const double* rho_in, double* rho_out);
 int cube_fourier_filter(dftk_mi_kblock* cube_kb, int kind, const double* recip_h, double p0, double p1,
                         const double* mult_d, const double* f, double* out);
+// grad (three real cubes) = Re irfft(i G_a fft(f)): the operator chain of the GGA pipelines of xc_kernels.hip
+int cube_gradient(dftk_mi_kblock* cube_kb, const double* recip_h, const double* f, double* grad);
 int xc_gga_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, int fun_mask,
                      double threshold, double* e, double* vrho, double* vsigma);
 

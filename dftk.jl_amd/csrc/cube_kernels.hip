@@ -205,6 +205,25 @@ int cube_axpy_real(dftk_mi_basis* b, int64_t N, const double* a, double scale, c
     return 0;
 }
 
+// grad[a] = Re irfft(i G_a fft(f)), a = 0, 1, 2: the chain the GGA pipelines apply to the density (cube_forward_real, the
+// three gradient multipliers, ONE three-cube backward pipeline, real part / N), so that the gradient of a sum of two cubes
+// and the sum of their gradients differ by rounding only.  Set-up of the core density of a non-linear core correction.
+int cube_gradient(dftk_mi_kblock* cube_kb, const double* recip_h, const double* f, double* grad) {
+    int64_t N;
+    CHK(check_cube(cube_kb, &N));
+    dftk_mi_basis* b = cube_kb->basis;
+    CHK(scratch_grow(b, b->dense_ws, 5 * (size_t)N * sizeof(cd)));
+    cd* c1 = reinterpret_cast<cd*>(b->dense_ws.get());
+    cd* c2 = c1 + N;
+    cd* g3 = c2 + N;                                 // three cubes behind one another
+    CHK(cube_forward_real(cube_kb, f, nullptr, c1, c2));                            // c2 = F[f]
+    for (int a = 0; a < 3; ++a) CHK(cube_gradient_multiply(cube_kb, recip_h, a, c2, g3 + a * N, false));
+    CHK(launch_ifft_to_cube(cube_kb, g3, g3, 3));                                   // in place: N grad f
+    hipLaunchKernelGGL(k_c2r, dim3(CUBE_BLOCKS), dim3(256), 0, b->stream, 3 * N, (const cd*)g3, 1.0 / (double)N, grad);
+    HIPCHK(hipGetLastError());
+    return 0;            // asynchronous on the basis' stream (header conventions)
+}
+
 // symmetrize_rho(basis, rho; symmetries, do_lowpass) for one spin component (symmetry.jl:346-357)
 int cube_symmetrize(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, const double* tau_h, int do_lowpass,
                     const double* rho_in, double* rho_out) {

@@ -148,12 +148,13 @@ __device__ __forceinline__ D3 gga_c_pbe(D3 rho, D3 sigma) {
 }
 
 // e, de/drho, de/dsigma per grid point; points with rho <= threshold contribute nothing (libxc-style threshold)
-__global__ __launch_bounds__(256) void k_gga(int64_t n, const double* __restrict__ rho, const double* __restrict__ sigma,
-                                             int fun_mask, double threshold, double* __restrict__ e,
-                                             double* __restrict__ vrho, double* __restrict__ vsigma) {
+// core (optional): the core density of a non-linear core correction, the forms are evaluated at rho + core
+__global__ __launch_bounds__(256) void k_gga(int64_t n, const double* __restrict__ rho, const double* __restrict__ core,
+                                             const double* __restrict__ sigma, int fun_mask, double threshold,
+                                             double* __restrict__ e, double* __restrict__ vrho, double* __restrict__ vsigma) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         D3 acc = dc<D3>(0.0);
-        const double r = rho[i];
+        const double r = core ? rho[i] + core[i] : rho[i];
         if (r > threshold) {
             const D3 dr = D3{r, {1.0, 0.0}}, dsg = D3{sigma[i], {0.0, 1.0}};
             if (fun_mask & DFTK_MI_XC_GGA_X_PBE) acc = acc + gga_x_pbe(dr, dsg);
@@ -246,7 +247,9 @@ __device__ __forceinline__ D4 gga_c_pbe_spin(D4 ra, D4 rb, D4 sigma) {
 }
 // Floors as lda_spin_sum: a channel enters as max(rho_s, 1e-20) and the derivatives are those of the clamped variables;
 // rho_up + rho_down <= max(threshold, 2e-20) gives zeros; sigma_uu, sigma_dd and sigma_tot enter as max(., 0).
+// core (optional): the TOTAL core density of a non-linear core correction, half of it joins each channel
 __global__ __launch_bounds__(256) void k_gga_spin(int64_t n, const double* __restrict__ up, const double* __restrict__ dn,
+                                                  const double* __restrict__ core,
                                                   const double* __restrict__ suu, const double* __restrict__ sud,
                                                   const double* __restrict__ sdd, int fun_mask, double threshold,
                                                   double* __restrict__ e, double* __restrict__ vup, double* __restrict__ vdn,
@@ -255,7 +258,12 @@ __global__ __launch_bounds__(256) void k_gga_spin(int64_t n, const double* __res
     const double floor_ = 1e-20;
     const double cut = threshold > 2.0 * floor_ ? threshold : 2.0 * floor_;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double a = up[i], b = dn[i];
+        double a = up[i], b = dn[i];
+        if (core) {
+            const double hc = 0.5 * core[i];
+            a += hc;
+            b += hc;
+        }
         double ev = 0.0, va = 0.0, vb = 0.0, wuu = 0.0, wud = 0.0, wdd = 0.0;
         if (a + b > cut) {
             const double ra = a > floor_ ? a : floor_, rb = b > floor_ ? b : floor_;
@@ -294,7 +302,9 @@ __global__ __launch_bounds__(256) void k_gga_spin(int64_t n, const double* __res
 #pragma clang fp contract(fast)
 
 // V = V_loc + V_H + v_xc ; partials: [0] sum e_xc, [1] sum rho V_loc
-__global__ __launch_bounds__(256) void k_xc_sum(int64_t n, const double* __restrict__ rho, const cd* __restrict__ vh_cube,
+// core (optional): e_xc and v_xc are those of rho + core, the local energy (and V_H, computed elsewhere) those of rho
+__global__ __launch_bounds__(256) void k_xc_sum(int64_t n, const double* __restrict__ rho, const double* __restrict__ core,
+                                                const cd* __restrict__ vh_cube,
                                                 double vh_scale, const double* __restrict__ vloc, int fun_mask,
                                                 const double* __restrict__ e_extra, const double* __restrict__ v_extra,
                                                 double* __restrict__ V, double* __restrict__ partial) {
@@ -302,14 +312,15 @@ __global__ __launch_bounds__(256) void k_xc_sum(int64_t n, const double* __restr
     double acc_xc = 0.0, acc_loc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double r = rho[i];
+        const double rx = core ? r + core[i] : r;         // the argument of the XC forms
         double e = 0.0, v = 0.0;
-        if (fun_mask != 0 && r > 1e-300) {
+        if (fun_mask != 0 && rx > 1e-300) {
             double ei, vi;
-            if (fun_mask & DFTK_MI_XC_LDA_X) { lda_x(r, ei, vi); e += ei; v += vi; }
-            if (fun_mask & DFTK_MI_XC_LDA_C_VWN) { lda_c_vwn(r, ei, vi); e += ei; v += vi; }
-            if (fun_mask & DFTK_MI_XC_LDA_C_PW) { lda_c_pw(r, ei, vi); e += ei; v += vi; }
+            if (fun_mask & DFTK_MI_XC_LDA_X) { lda_x(rx, ei, vi); e += ei; v += vi; }
+            if (fun_mask & DFTK_MI_XC_LDA_C_VWN) { lda_c_vwn(rx, ei, vi); e += ei; v += vi; }
+            if (fun_mask & DFTK_MI_XC_LDA_C_PW) { lda_c_pw(rx, ei, vi); e += ei; v += vi; }
             if (fun_mask & DFTK_MI_XC_LDA_XC_TETER93) {   // the polarised form at rho_up = rho_down = rho / 2
-                const D3 t = lda_spin_sum(0.5 * r, 0.5 * r, DFTK_MI_XC_LDA_XC_TETER93);
+                const D3 t = lda_spin_sum(0.5 * rx, 0.5 * rx, DFTK_MI_XC_LDA_XC_TETER93);
                 e += t.v;
                 v += t.d[0];
             }
@@ -342,7 +353,9 @@ __global__ __launch_bounds__(256) void k_total_to_complex(int64_t n, const doubl
         out[i] = make_double2(up[i] + dn[i], 0.0);
 }
 // V_s = V_loc + V_H[rho_tot] + v_xc,s(rho_up, rho_down), s = up, down ; partials: [0] sum e_xc, [1] sum rho_tot V_loc
+// core (optional): the TOTAL core density; the XC forms see rho_s + core / 2, the local energy rho_tot alone
 __global__ __launch_bounds__(256) void k_xc_sum_spin(int64_t n, const double* __restrict__ up, const double* __restrict__ dn,
+                                                     const double* __restrict__ core,
                                                      const cd* __restrict__ vh_cube, double vh_scale,
                                                      const double* __restrict__ vloc, int fun_mask,
                                                      const double* __restrict__ e_extra, const double* __restrict__ v_extra,
@@ -352,7 +365,8 @@ __global__ __launch_bounds__(256) void k_xc_sum_spin(int64_t n, const double* __
     double acc_xc = 0.0, acc_loc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double ra = up[i], rb = dn[i];
-        D3 e = lda_spin_sum(ra, rb, fun_mask);
+        const double hc = core ? 0.5 * core[i] : 0.0;
+        D3 e = core ? lda_spin_sum(ra + hc, rb + hc, fun_mask) : lda_spin_sum(ra, rb, fun_mask);
         if (e_extra) {                       // GGA part: e and v_rho,s - 2 div(...) of the two channels (v_extra: 2 cubes)
             e.v += e_extra[i];
             e.d[0] += v_extra[i];
@@ -450,9 +464,15 @@ __global__ __launch_bounds__(256) void k_fxc_sum(int64_t n, const double* __rest
 }  // namespace dftk_xc
 using namespace dftk_xc;
 
-// out[i] = scale * Re(c[i])
-__global__ __launch_bounds__(256) void k_xc_real_part_scaled(int64_t n, const cd* __restrict__ c, double scale, double* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = scale * c[i].x;
+// out[i] = scale * Re(c[i]) (+ add_scale * add[i mod n_add]: the gradient cubes of the core density, n_add = 3 N, joined
+// to the three gradient cubes of the density or, halved, to the six of two spin channels; n <= 2 n_add)
+__global__ __launch_bounds__(256) void k_xc_real_part_scaled(int64_t n, const cd* __restrict__ c, double scale,
+                                                             const double* __restrict__ add, double add_scale, int64_t n_add,
+                                                             double* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double v = scale * c[i].x;
+        out[i] = add ? v + add_scale * add[i < n_add ? i : i - n_add] : v;
+    }
 }
 // out[a n + i] = v[i] * g[a n + i], a = 0, 1, 2 (as complex numbers)
 __global__ __launch_bounds__(256) void k_product3_to_complex(int64_t n, const double* __restrict__ v, const double* __restrict__ g,
@@ -529,7 +549,8 @@ static int collinear_energies(dftk_mi_basis* b, int64_t N, const double* partial
 // rho: (up, down), sigma: (uu, ud, dd), vrho: (up, down), vsigma: (uu, ud, dd), n values each
 int xc_gga_spin_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, int fun_mask,
                           double threshold, double* e, double* vrho, double* vsigma) {
-    hipLaunchKernelGGL(k_gga_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, n, rho, rho + n, sigma, sigma + n, sigma + 2 * n,
+    hipLaunchKernelGGL(k_gga_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, n, rho, rho + n, (const double*)nullptr, sigma,
+                       sigma + n, sigma + 2 * n,
                        fun_mask, threshold, e, vrho, vrho + n, vsigma, vsigma + n, vsigma + 2 * n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(b->stream));
@@ -538,8 +559,8 @@ int xc_gga_spin_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const 
 
 int xc_gga_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, int fun_mask,
                      double threshold, double* e, double* vrho, double* vsigma) {
-    hipLaunchKernelGGL(k_gga, dim3(XC_BLOCKS), dim3(256), 0, b->stream, n, rho, sigma, fun_mask, threshold, e, vrho,
-                       vsigma);
+    hipLaunchKernelGGL(k_gga, dim3(XC_BLOCKS), dim3(256), 0, b->stream, n, rho, (const double*)nullptr, sigma, fun_mask,
+                       threshold, e, vrho, vsigma);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
@@ -554,8 +575,9 @@ int cube_axpy_real(dftk_mi_basis* b, int64_t N, const double* a, double scale, c
 
 // Collinear-spin LDA pipeline: rho = (rho_up, rho_down), two cubes; Hartree of the TOTAL density, V_loc, and the spin-resolved
 // XC potential summed into (V_up, V_down); energies = Hartree, Xc, AtomicLocal (rho_tot V_loc).
-int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const double* vloc, const double* green,
-                              int fun_mask, double* V_out, double* energies_h) {
+// core (optional, ONE cube): the XC forms see rho_s + core / 2 (non-linear core correction), everything else rho.
+int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const double* core, const double* vloc,
+                              const double* green, int fun_mask, double* V_out, double* energies_h) {
     dftk_mi_basis* b = cube_kb->basis;
     const int64_t N = (int64_t)b->nx * b->ny * b->nz;
     if (cube_kb->n_G != N) {
@@ -581,8 +603,9 @@ int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const 
         CHK(launch_ifft_to_cube(cube_kb, c2, c1));
         vh = c1;
     }
-    hipLaunchKernelGGL(k_xc_sum_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, up, dn, vh, 1.0 / (double)N, vloc, fun_mask,
-                       (const double*)nullptr, (const double*)nullptr, V_out, V_out ? V_out + N : (double*)nullptr, partial);
+    hipLaunchKernelGGL(k_xc_sum_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, up, dn, core, vh, 1.0 / (double)N, vloc,
+                       fun_mask, (const double*)nullptr, (const double*)nullptr, V_out, V_out ? V_out + N : (double*)nullptr,
+                       partial);
     HIPCHK(hipGetLastError());
     if (!energies_h) return 0;      // potential only: asynchronous, like every call that returns no host data
     return collinear_energies(b, N, partial, green != nullptr, energies_h);
@@ -593,8 +616,11 @@ int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const 
 //   V_s += v_rho,s - 2 div(v_sigma,ss grad rho_s + 1/2 v_sigma,ud grad rho_s')
 // F[rho_up], F[rho_down] are computed once (the Poisson pass works on their sum); the six gradient cubes and the six flux
 // cubes go through one transform pipeline each.  17 cube FFTs in 5 pipelines, 35 launches with Hartree.
-int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* vloc,
-                                  const double* green, int fun_mask, double threshold, double* V_out, double* energies_h) {
+// core / grad_core (optional: one cube and its three gradient cubes): half of each joins rho_s and grad rho_s in the XC
+// forms, sigma and the flux; no transform and no launch more.
+int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* core,
+                                  const double* grad_core, const double* vloc, const double* green, int fun_mask,
+                                  double threshold, double* V_out, double* energies_h) {
     dftk_mi_basis* b = cube_kb->basis;
     const int64_t N = (int64_t)b->nx * b->ny * b->nz;
     if (cube_kb->n_G != N) {
@@ -608,7 +634,7 @@ int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h
         return DFTK_MI_EINVAL;
     }
     const int gga_mask = fun_mask & 24;
-    if (!gga_mask) return local_potential_collinear(cube_kb, rho, vloc, green, fun_mask, V_out, energies_h);
+    if (!gga_mask) return local_potential_collinear(cube_kb, rho, core, vloc, green, fun_mask, V_out, energies_h);
     // complex cubes: c1 | F[rho_up], F[rho_down] | six gradient / flux cubes; real cubes: 6 gradients, 3 sigma, e, 2 v_rho,
     // 3 v_sigma; then the reduction partials
     CHK(scratch_grow(b, b->dense_ws,
@@ -636,9 +662,9 @@ int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h
     }
     CHK(launch_ifft_to_cube(cube_kb, g6, g6, 6));                                      // in place: N grad rho_s
     hipLaunchKernelGGL(k_xc_real_part_scaled, dim3(XC_BLOCKS), dim3(256), 0, b->stream, 6 * N, (const cd*)g6, 1.0 / (double)N,
-                       grad);
+                       core ? grad_core : (const double*)nullptr, 0.5, 3 * N, grad);
     hipLaunchKernelGGL(k_sigma_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, (const double*)grad, sigma);
-    hipLaunchKernelGGL(k_gga_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, up, dn, (const double*)sigma,
+    hipLaunchKernelGGL(k_gga_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, up, dn, core, (const double*)sigma,
                        (const double*)(sigma + N), (const double*)(sigma + 2 * N), gga_mask, threshold, e_g, vrho, vrho + N, vsig,
                        vsig + N, vsig + 2 * N);
     HIPCHK(hipGetLastError());
@@ -650,7 +676,7 @@ int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h
     CHK(launch_ifft_to_cube(cube_kb, f2, g6, 2));                                      // g6[s] = N div(flux_s)
     double* v_g = sigma;                                                               // (sigma is dead by now): two cubes
     CHK(cube_axpy_real(b, 2 * N, vrho, -2.0 / (double)N, g6, v_g));
-    hipLaunchKernelGGL(k_xc_sum_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, up, dn, vh, 1.0 / (double)N, vloc,
+    hipLaunchKernelGGL(k_xc_sum_spin, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, up, dn, core, vh, 1.0 / (double)N, vloc,
                        fun_mask & (1 | 4 | 32), (const double*)e_g, (const double*)v_g, V_out,
                        V_out ? V_out + N : (double*)nullptr, partial);
     HIPCHK(hipGetLastError());
@@ -664,8 +690,12 @@ int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h
 //   sigma = |grad rho|^2, (e, v_rho, v_sigma) = point-wise PBE forms (k_gga)
 //   v_xc = v_rho - 2 div(v_sigma grad rho),  div f = irfft(sum_a i G_a fft(f_a))   (xc.jl:140-150, :576-584)
 // with G in cartesian coordinates from recip_h (row-major recip_lattice).  8 cube FFTs in total.
-int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* vloc,
-                        const double* green, int fun_mask, double threshold, double* V_out, double* energies_h) {
+// core / grad_core (optional: one cube and its three gradient cubes, non-linear core correction): the XC forms are evaluated
+// at rho + core with grad rho + grad core in sigma and the flux; Hartree and the local energy see rho alone.  The core is
+// one more operand of passes that run anyway: no transform and no launch more.
+int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* core,
+                        const double* grad_core, const double* vloc, const double* green, int fun_mask, double threshold,
+                        double* V_out, double* energies_h) {
     dftk_mi_basis* b = cube_kb->basis;
     const int64_t N = (int64_t)b->nx * b->ny * b->nz;
     if (cube_kb->n_G != N) {
@@ -705,10 +735,11 @@ int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const do
         }
         CHK(launch_ifft_to_cube(cube_kb, g3, g3, 3));                                  // in place: N grad rho (complex cubes)
         hipLaunchKernelGGL(k_xc_real_part_scaled, dim3(XC_BLOCKS), dim3(256), 0, b->stream, 3 * N, (const cd*)g3, 1.0 / (double)N,
+                           core ? grad_core : (const double*)nullptr, 1.0, 3 * N,
                            grad[0]);                                                   // the three gradients are adjacent
         CHK(cube_sigma(b, N, grad[0], grad[1], grad[2], sigma));
-        hipLaunchKernelGGL(k_gga, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, rho, sigma, gga_mask, threshold, e_g, vrho,
-                           vsig);
+        hipLaunchKernelGGL(k_gga, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, rho, core, (const double*)sigma, gga_mask,
+                           threshold, e_g, vrho, vsig);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_product3_to_complex, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, (const double*)vsig,
                            (const double*)grad[0], g3);                                // v_sigma d_a rho, a = 0, 1, 2
@@ -724,7 +755,7 @@ int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const do
         CHK(launch_ifft_to_cube(cube_kb, c2, c1));                        // c1 = N * V_H(r)
         vh = c1;
     }
-    hipLaunchKernelGGL(k_xc_sum, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, rho, vh, 1.0 / (double)N, vloc,
+    hipLaunchKernelGGL(k_xc_sum, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, rho, core, vh, 1.0 / (double)N, vloc,
                        fun_mask & (7 | 32), (const double*)e_g, (const double*)v_g, V_out, partial);
     HIPCHK(hipGetLastError());
     if (!energies_h) return 0;      // potential only: asynchronous (no fetch, no synchronisation)

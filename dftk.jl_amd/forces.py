@@ -5,8 +5,9 @@ converts them with covector_red_to_cart, F_cart = inv(lattice') F_red (forces.jl
 Device terms (the library's force kernels, force_kernels.hip): AtomicLocal (local.jl:142-177, the exact derivative of the
 local energy on the cube) and AtomicNonlocal (nonlocal.jl:49-98, one projector product per k-block, symmetrised as the
 reference does).  Ewald (ewald.jl:24-31) is analytic on the host.  Kinetic, Hartree, PspCorrection and Entropy have no
-explicit position dependence (terms.jl:85); Xc forces vanish without a non-linear core correction, which HGH
-pseudopotentials do not carry.  There is no torch fall-back: a basis without the library raises."""
+explicit position dependence (terms.jl:85).  Xc (xc.jl:200-270) has one through the core densities of a non-linear core
+correction alone: the AtomicLocal sum with (rho, ff_loc) replaced by (v_xc, ff_core), through the same kernel; without a
+core density (HGH) the term has no forces.  There is no torch fall-back: a basis without the library raises."""
 from __future__ import annotations
 
 import numpy as np
@@ -14,9 +15,9 @@ import torch
 
 from . import _lib
 from .symmetry import symmetrize_forces
-from .psp_upf import model_has_upf
-from .terms import (energy_forces_ewald, local_form_factor_table, local_species_tables, occupied_block,
-                    total_density)
+from .psp_upf import is_upf, model_has_upf
+from .terms import (_local_potential_call, core_form_factor_table, energy_forces_ewald, local_form_factor_table,
+                    local_species_tables, model_uses_nlcc, occupied_block, total_density)
 
 # (ExactExchange: a functional of the orbitals alone, no explicit dependence on the positions)
 _NO_FORCES = ("Kinetic", "Hartree", "PspCorrection", "Entropy", "ExactExchange")
@@ -104,12 +105,43 @@ def _forces_nonlocal(basis, psi, occupation):
 
 
 def _check_nlcc(model):
-    """Xc forces are zero only without a non-linear core correction (xc.jl:200-); a pseudopotential that has one, or
-    that cannot say (no ``has_core_density``), is refused."""
+    """Xc forces come from the core densities of UPF core channels (xc.jl:200-); a pseudopotential that claims a core
+    density the library cannot evaluate, or that cannot say (no ``has_core_density``), is refused."""
     for el in model.atoms:
         has = getattr(el.psp, "has_core_density", None)
-        if has is None or has():
-            raise NotImplementedError(f"XC forces with a non-linear core correction ({el.symbol}) are not implemented")
+        if has is None or (has() and not is_upf(el.psp)):
+            raise NotImplementedError(f"XC forces with a non-linear core correction ({el.symbol}) are not implemented "
+                                      "for this pseudopotential (UPF core channels only)")
+
+
+def _forces_xc(basis, rho):
+    """xc.jl:200-270: F_a = -Re sum_G (-2 pi i G) conj(v_xc(G)) ff_core,s(|G|) e^{-2 pi i G.r_a} / sqrt(Omega), v_xc the
+    XC potential alone (averaged over the channels of a collinear model) at rho + rho_core."""
+    model = basis.model
+    T = basis.terms
+    out = _local_potential_call(basis, rho, model.functionals, False, want_potential=True, want_energies=False)
+    if out is None:
+        raise NotImplementedError(f"XC forces: the functionals {model.functionals} are not evaluated by the library")
+    vxc = out["V"]
+    for name, s in zip(model.functionals, getattr(model, "functional_scales", ())):
+        if s != 1.0:                   # (a hybrid's scaled exchange part, as local_potential_fused takes it out)
+            part = _local_potential_call(basis, rho, (name,), False, want_potential=True, want_energies=False)
+            vxc.sub_(part["V"], alpha=1.0 - s)
+    if vxc.dim() == 4:
+        vxc = 0.5 * (vxc[0] + vxc[1])
+    vxc = vxc.contiguous()
+    ff = T.core_ff if getattr(T, "core_ff", None) is not None else core_form_factor_table(basis)
+    order = _group_order(model)
+    _, species, positions = local_species_tables(model, lambda el: [])
+    Bh = np.asfortranarray(model.recip_lattice, dtype=np.float64)
+    res = np.zeros((len(order), 3))
+    basis.pre_call()
+    _lib.check(basis.lib.dftk_mi_forces_local_table(basis._cube_handle, Bh.ctypes.data, ff.shape[0], ff.data_ptr(),
+                                                    len(order), species.ctypes.data, positions.ctypes.data,
+                                                    vxc.data_ptr(), res.ctypes.data))
+    F = np.zeros((len(model.atoms), 3))
+    F[order] = res
+    return symmetrize_forces(basis, F)
 
 
 def compute_forces_term(name, basis, psi, occupation, rho=None):
@@ -122,7 +154,13 @@ def compute_forces_term(name, basis, psi, occupation, rho=None):
         return None
     if name == "Xc":
         _check_nlcc(model)
-        return None
+        if not model_uses_nlcc(model):
+            return None
+        if rho is None:
+            raise ValueError("Xc forces need the density")
+        basis._require_gpu()
+        with basis.on_library_stream():
+            return _forces_xc(basis, rho)
     if name == "Ewald":
         # computed on the first forces call (not at set-up: instantiate_terms and the SCF are unchanged), then kept
         T = basis.terms

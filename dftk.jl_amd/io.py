@@ -54,6 +54,7 @@ def model_to_dict(model) -> dict:
         "n_electrons": model.n_electrons, "pseudofamily": "hgh",
         **_symmetries_to_dict(model.symmetries),
         "terms": list(model.term_types), "functionals": list(model.functionals),
+        "use_nlcc": bool(getattr(model, "use_nlcc", True)),
         **_hybrid_to_dict(model),
     }
 

@@ -61,11 +61,17 @@ def _n_projectors(model) -> int:
 
 def form_factor_table_bytes(model, fft_size) -> int:
     """Bytes of the local form-factor table a basis keeps when its model has a UPF species (one row of N doubles per species
-    group: V_loc is built from it and the forces read it; terms.local_form_factor_table); 0 for HGH-only models."""
+    group: V_loc is built from it and the forces read it; terms.local_form_factor_table), plus what a non-linear core correction
+    adds (terms._instantiate_core_density); 0 for HGH-only models."""
     from .psp_upf import model_has_upf
     if not model_has_upf(model):
         return 0
-    return F64 * int(np.prod(fft_size)) * len(model.atom_groups)
+    rows = len(model.atom_groups)
+    from .terms import _GGA_BITS, model_uses_nlcc
+    if model_uses_nlcc(model):
+        # non-linear core correction: the core table, the core cube and, for GGA functionals, its three gradient cubes
+        rows += len(model.atom_groups) + 1 + (3 if any(f in _GGA_BITS for f in model.functionals) else 0)
+    return F64 * int(np.prod(fft_size)) * rows
 
 
 def _fft_size(model, Ecut, fft_size):

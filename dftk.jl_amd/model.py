@@ -69,7 +69,7 @@ class Model:
 
     def __init__(self, lattice, atoms, positions, terms, functionals=("lda_x", "lda_c_pw"),
                  temperature=0.0, smearing=None, n_electrons=None, symmetries=False, magnetic_moments=(),
-                 spin_polarization=None, functional_scales=None):
+                 spin_polarization=None, functional_scales=None, use_nlcc=True):
         self.lattice = np.asarray(lattice, dtype=float)
         self.atoms = list(atoms)
         self.positions = [np.asarray(p, dtype=float) for p in positions]
@@ -89,6 +89,8 @@ class Model:
                                   else (1.0,) * len(self.functionals))
         if len(self.functional_scales) != len(self.functionals):
             raise ValueError("one scale per functional")
+        # Xc(...; use_nlcc) (xc.jl:9-17): whether the core densities of the pseudopotentials join rho in the Xc term
+        self.use_nlcc = bool(use_nlcc)
         self.temperature = float(temperature)
         self.smearing = smearing if smearing is not None else ("fermi_dirac" if temperature > 0 else "none")
         self.recip_lattice = compute_recip_lattice(self.lattice)
@@ -152,7 +154,9 @@ def model_atomic(lattice, atoms, positions, extra_terms=(), **kw):
 
 
 def model_DFT(lattice, atoms, positions, functionals=("lda_x", "lda_c_pw"), **kw):
-    """standard_models.jl:116-131; default functionals = ``LDA()`` (:220).  ``functionals=PBE0(...)``: the hybrid."""
+    """standard_models.jl:116-131; default functionals = ``LDA()`` (:220).  ``functionals=PBE0(...)``: the hybrid.
+    ``use_nlcc=False`` (the switch of the reference's ``Xc``) leaves the non-linear core correction of the pseudopotentials
+    out of the Xc term."""
     if isinstance(functionals, PBE0):
         a = 0.25 if functionals.exx_fraction is None else float(functionals.exx_fraction)
         kernel = Coulomb() if functionals.exx_kernel is None else functionals.exx_kernel

@@ -199,6 +199,13 @@ def eval_psp_valence_density_fourier(psp, p: torch.Tensor) -> torch.Tensor:
     return _on_host(lambda q: psp_upf.eval_psp_valence_density_fourier_upf(psp, q), p)
 
 
+def eval_psp_core_density_fourier(psp, p: torch.Tensor) -> torch.Tensor:
+    """PspUpf.jl:279-283: the Hankel transform (l = 0) of the core density of the non-linear core correction."""
+    if not isinstance(psp, PspUpf) or not psp.has_core_density():
+        raise ValueError("the pseudopotential carries no core density")
+    return _on_host(lambda q: psp_upf.eval_psp_core_density_fourier_upf(psp, q), p)
+
+
 def eval_psp_energy_correction(psp) -> float:
     """PspHgh.jl:173-184 / PspUpf.jl:308-315."""
     if isinstance(psp, PspUpf):

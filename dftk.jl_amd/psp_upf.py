@@ -127,6 +127,7 @@ class PspUpf:
             order[l].append(ib)
         self.h = tuple(f["dij"][np.ix_(idx, idx)] * 2 if idx else np.zeros((0, 0)) for idx in order)
         self.r2_rhoion = f["rhoatom"] / (4 * math.pi)
+        self.r2_rhocore = self.rgrid ** 2 * f["nlcc"]               # PP_NLCC is rho_core(r) itself (PspUpf.jl:147-151)
         self.identifier = "" if identifier is None else identifier
         self.description = f["comment"]
         self._weights = {}
@@ -143,7 +144,7 @@ class PspUpf:
         return self.count_n_proj_radial(l) * (2 * l + 1)
 
     def has_core_density(self):
-        return False                 # files with a non-linear core correction are refused by the reader
+        return bool(np.any(self.r2_rhocore != 0))
 
     def has_valence_density(self):
         return bool(np.any(self.r2_rhoion != 0))
@@ -169,6 +170,11 @@ class PspUpf:
     def valence_channel(self):
         n = self.ircut
         return self.rgrid[:n], self.weights(n) * self.r2_rhoion[:n]
+
+    def core_channel(self):
+        """``(r, wf)`` of the core density of the non-linear core correction, cut at ircut (PspUpf.jl:279-283)."""
+        n = self.ircut
+        return self.rgrid[:n], self.weights(n) * self.r2_rhocore[:n]
 
 
 def parse_psp_upf(text, identifier=""):
@@ -234,8 +240,12 @@ def _read_upf(text):
     if _truthy(a.get("is_ultrasoft")):
         unsupported.append("ultrasoft (US)")
     nlcc = _numbers(root.find("PP_NLCC"))
-    if _truthy(a.get("core_correction")) or np.any(nlcc != 0):
-        unsupported.append("non-linear core correction (NLCC)")
+    # a core correction is taken when header and data agree; the two inconsistent forms are refused
+    if _truthy(a.get("core_correction")):
+        if not np.any(nlcc != 0):
+            unsupported.append("non-linear core correction flagged in the header (core_correction) without PP_NLCC data")
+    elif np.any(nlcc != 0):
+        unsupported.append('non-zero PP_NLCC data although the header says core_correction="F" (non-linear core correction)')
     if unsupported:
         raise NotImplementedError("UPF pseudopotential with unsupported features: " + ", ".join(unsupported))
     mesh = root.find("PP_MESH")
@@ -266,11 +276,16 @@ def _read_upf(text):
             raise ValueError("malformed UPF file: PP_DIJ")
         dij = d.reshape(len(betas), len(betas))
     lmax = max([int(a.get("l_max", -1))] + [b[0] for b in betas])
+    if np.any(nlcc != 0) and len(nlcc) != len(r):
+        raise NotImplementedError("UPF pseudopotential with unsupported features: non-linear core correction whose "
+                                  "PP_NLCC block is not as long as the mesh")
+    if len(nlcc) != len(r):
+        nlcc = np.zeros(len(r))
     rho = _numbers(root.find("PP_RHOATOM"))
     if len(rho) < len(r):                    # absent, or shorter than the mesh: zero beyond what the file gives
         rho = np.concatenate([rho, np.zeros(len(r) - len(rho))])
     return {"Zion": int(round(float(re.sub(r"[dD]", "E", a["z_valence"])))), "lmax": lmax, "r": r, "rab": rab,
-            "vloc": vloc, "betas": betas, "dij": dij, "rhoatom": rho[:len(r)], "comment": a.get("comment", "") or ""}
+            "vloc": vloc, "betas": betas, "dij": dij, "rhoatom": rho[:len(r)], "nlcc": nlcc, "comment": a.get("comment", "") or ""}
 
 
 # ------------------------------------------------------------------------------------------ host values
@@ -332,6 +347,12 @@ def eval_psp_projector_fourier_upf(psp, i, l, q):
 
 def eval_psp_valence_density_fourier_upf(psp, q):
     r, wf = psp.valence_channel()
+    return hankel_host(r, wf, 0, q)
+
+
+def eval_psp_core_density_fourier_upf(psp, q):
+    """PspUpf.jl:279-283: hankel(rgrid[1:ircut], r2_rhocore, 0, q); no normalisation."""
+    r, wf = psp.core_channel()
     return hankel_host(r, wf, 0, q)
 
 

@@ -489,6 +489,10 @@ def apply_kernel(basis, drho, rho=None, RPA=False, q=None):
         raise TypeError("apply_kernel: drho must be a real (nz, ny, nx) CUDA cube")
     drho = drho.to(torch.float64).contiguous()
     rho_t = total_density(rho).to(torch.float64).contiguous() if (mask and rho is not None) else None
+    if rho_t is not None and getattr(T, "rho_core", None) is not None:
+        # non-linear core correction: f_xc is that of rho + rho_core (xc.jl:245-250); rho_d feeds f_xc alone, the Hartree
+        # part acts on drho
+        rho_t = rho_t + T.rho_core
     green = T.poisson if "Hartree" in T.names else None
     dV = torch.empty_like(drho)
     basis.pre_call()

@@ -198,6 +198,76 @@ def _atomic_superposition_table_abi(basis, ff, coefficients=None):
     return out
 
 
+# ---------------------------------------------------------------------------------- non-linear core correction
+def model_uses_nlcc(model):
+    """xc.jl:37: the Xc term carries a core density when its switch is on and any atom has one."""
+    return ("Xc" in model.term_types and getattr(model, "use_nlcc", True)
+            and any(getattr(a.psp, "has_core_density", lambda: False)() for a in model.atoms))
+
+
+def core_form_factor_table(basis):
+    """ff_core,s(|G|) = hankel(r, r^2 rho_core, 0, |G|) (PspUpf.jl:279-283) per species group and cube point,
+    (n_groups, N); rows of species without a core density are zero (density_methods.jl:265-271).  No normalisation."""
+    from .psp import eval_psp_core_density_fourier
+    q = _cube_norms(basis)
+    rows = []
+    for g in basis.model.atom_groups:
+        el = basis.model.atoms[g[0]]
+        has = getattr(el.psp, "has_core_density", None)
+        if has is None or not has():
+            rows.append(torch.zeros_like(q))
+        elif not is_upf(el.psp):
+            raise NotImplementedError(f"the core density of {el.symbol} ({type(el.psp).__name__}) cannot be evaluated "
+                                      "(non-linear core correction: UPF core channels only)")
+        elif _use_setup_abi(basis):
+            r, wf = el.psp.core_channel()
+            rows.append(radial_transform_abi(basis, 0, 0, r, wf, 0.0, q))
+        else:
+            rows.append(eval_psp_core_density_fourier(el.psp, q))
+    return torch.stack(rows).contiguous()
+
+
+def _superposition_table_torch(basis, ff):
+    """The cube of ``_atomic_superposition_table_abi`` with torch ops (DFTK_MI_TORCH_SETUP)."""
+    model = basis.model
+    nx, ny, nz = basis.fft_size
+    acc = torch.zeros((nz, ny, nx), dtype=torch.complex128, device=basis.device)
+    for row, group in zip(ff, model.atom_groups):
+        sf = torch.zeros_like(acc)
+        for ia in group:
+            sf += _structure_factor_cube(basis, model.positions[ia])
+        acc += sf * row.reshape(nz, ny, nx) / math.sqrt(model.unit_cell_volume)
+    return basis.irfft(acc * basis.enforce_real_mask())
+
+
+def cube_gradient_abi(basis, f):
+    """``dftk_mi_cube_gradient``: the three cubes Re irfft(i G_a fft(f)), shape (3, nz, ny, nx)."""
+    f = f.to(torch.float64).contiguous()
+    out = torch.empty((3,) + tuple(f.shape), dtype=torch.float64, device=basis.device)
+    Bh = np.asfortranarray(basis.model.recip_lattice, dtype=np.float64)
+    basis.pre_call()
+    _lib.check(basis.lib.dftk_mi_cube_gradient(basis._cube_handle, Bh.ctypes.data, f.data_ptr(), out.data_ptr()))
+    return out
+
+
+def _instantiate_core_density(basis, T):
+    """What the Xc term of a model with a non-linear core correction keeps (xc.jl:35-42): the form factors (the forces
+    read them), rho_core = atomic_total_density(basis, CoreDensity()) on the cube and, for GGA functionals, its gradient.
+    Nothing when the switch is off or no atom has a core density."""
+    T.core_ff = T.rho_core = T.grad_core = None
+    if not model_uses_nlcc(basis.model):
+        return
+    T.core_ff = core_form_factor_table(basis)
+    if basis.handle is None:
+        return                                            # (descriptor only: the cube needs the library's FFT)
+    if _use_setup_abi(basis):
+        T.rho_core = _atomic_superposition_table_abi(basis, T.core_ff)
+    else:
+        T.rho_core = _superposition_table_torch(basis, T.core_ff)
+    if any(f in _GGA_BITS for f in basis.model.functionals):
+        T.grad_core = cube_gradient_abi(basis, T.rho_core)
+
+
 def compute_local_potential(basis):
     """local.jl:108-138."""
     model = basis.model
@@ -846,6 +916,7 @@ def instantiate_terms(basis):
         T.exx_kernel = (float(exx.scaling_factor) * compute_kernel_fourier(exx.kernel, basis)).contiguous()
     # terms that need cube FFTs can only be instantiated with the device library
     T.V_loc = T.poisson = None
+    _instantiate_core_density(basis, T)
     if basis.handle is not None:
         if "AtomicLocal" in T.names:
             T.V_loc = compute_local_potential(basis)
@@ -941,7 +1012,22 @@ def _local_potential_call(basis, rho, functionals, with_local_terms, want_potent
     E3 = (C.c_double * 3)() if want_energies or not want_potential else None
     basis.pre_call()
     args = (vloc.data_ptr() if vloc is not None else None, green.data_ptr() if green is not None else None)
-    if rho.dim() == 4:
+    core = getattr(T, "rho_core", None)
+    if core is not None:
+        # non-linear core correction: XC at rho_s + rho_core / n_spin, Hartree and the local term at rho -- the four
+        # entries below in one (``dftk_mi_local_potential_core``)
+        if rho.dim() == 4 and any(f not in _SPIN_LDA + _SPIN_GGA for f in functionals):
+            raise NotImplementedError(f"collinear spin: spin-polarised forms exist for {_SPIN_LDA + _SPIN_GGA} only, got "
+                                      f"{functionals}")
+        grad = getattr(T, "grad_core", None)
+        if (mask & 24) and grad is None:
+            grad = T.grad_core = cube_gradient_abi(basis, core)
+        Bh = np.asfortranarray(basis.model.recip_lattice, dtype=np.float64)
+        _lib.check(basis.lib.dftk_mi_local_potential_core(
+            basis._cube_handle, Bh.ctypes.data, 2 if rho.dim() == 4 else 1, rho.data_ptr(), core.data_ptr(),
+            grad.data_ptr() if grad is not None else None, *args, mask, _DENSITY_THRESHOLD,
+            V.data_ptr() if V is not None else None, E3))
+    elif rho.dim() == 4:
         # collinear spin: (rho_up, rho_down) -> (V_up, V_down); Hartree and the local term see the total density
         if "Xc" in T.names and any(f not in _SPIN_LDA + _SPIN_GGA for f in functionals):
             raise NotImplementedError(f"collinear spin: spin-polarised forms exist for {_SPIN_LDA + _SPIN_GGA} only, got "
@@ -1141,7 +1227,8 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
                 pot = vh if pot is None else pot + vh
             E[name] = float(torch.vdot(pot_G.reshape(-1), rho_G.reshape(-1)).real.item()) / 2
         elif name == "Xc":
-            exc, vxc = xc_energy_potential(basis, rho)
+            core = getattr(T, "rho_core", None)          # (xc.jl:94-97: the core density joins rho in the XC term alone)
+            exc, vxc = xc_energy_potential(basis, rho if core is None else rho + core)
             if not only_energies:
                 pot = vxc if pot is None else pot + vxc
             E[name] = exc

@@ -3,7 +3,9 @@
 UPF 2.0.1 file on a 1141-point logarithmic mesh (the generator of the test-suite, tests/upf_gen.py), read back with
 ``load_psp(path)``, and LDA silicon (two atoms displaced off symmetry, Ecut 15, unreduced 2x2x2 mesh) is converged with both kinds;
 the two total energies and the forces are printed side by side.  Any norm-conserving scalar-relativistic UPF version 2 file
-without a non-linear core correction can be given instead:
+can be given instead.  A third run shows the non-linear core correction: a file with a core density in PP_NLCC (the given
+file if it has one, else the generated file with a made-up Gaussian core of charge 2 and decay length 0.45 bohr), with the
+share of the Xc term in the forces, and the same file with ``use_nlcc=False``:
 
     python examples/silicon_upf.py [path/to/Si.upf]          (needs an MI355X; there is no CPU fallback)
 """
@@ -45,3 +47,22 @@ for name, (E, F) in results.items():
     print("   ", np.array2string(F, precision=8, prefix="    "))
 print(f"difference: {results['UPF'][0] - results['HGH'][0]:+.2e} Ha, "
       f"forces {np.max(np.abs(results['UPF'][1] - results['HGH'][1])):.2e} Ha / bohr")
+
+# ---- non-linear core correction: rho_core joins rho in the XC term alone, and brings Xc forces with it
+if upf.has_core_density():
+    core = upf
+else:
+    r = upf_gen.log_mesh(1141, 1e-5, 60.0)
+    core = dftk.parse_psp_upf(upf_gen.write_upf(hgh, r, rhoatom=upf_gen.gaussian_density_real(4.0, atom_decay_length(10, 4), r),
+                                                core_correction=True, nlcc=upf_gen.gaussian_density_real(2.0, 0.45, r)),
+                              identifier="Si.gth-lda.core.upf")
+for use_nlcc in (True, False):
+    model = dftk.model_DFT(lattice, [dftk.ElementPsp("Si", psp=core)] * 2, positions, functionals=("lda_x", "lda_c_pw"),
+                           use_nlcc=use_nlcc)
+    basis = dftk.PlaneWaveBasis(model, 15, dftk.MonkhorstPack((2, 2, 2)).reducible())
+    scfres = dftk.self_consistent_field(basis, tol=1e-9)
+    F = dftk.compute_forces(scfres)
+    Fxc = dftk.compute_forces_term("Xc", basis, scfres["psi"], scfres["occupation"], rho=scfres["rho"])
+    print(f"core density, use_nlcc={use_nlcc}: total energy {scfres['energies'].total:.10f} Ha, E_xc "
+          f"{scfres['energies']['Xc']:.10f} Ha; largest force {np.max(np.abs(F)):.3e}, Xc share "
+          f"{'none' if Fxc is None else f'{np.max(np.abs(Fxc)):.3e}'} (reduced coordinates)")

@@ -304,6 +304,30 @@ int dftk_mi_local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double*
                                           const double* V_loc_d, const double* poisson_green_d, int xc_functionals,
                                           double density_threshold, double* V_out_d, double* energies_h);
 
+/* Non-linear core correction (src/terms/xc.jl:35-42, 94-97, 184-187): the four entries above in one, with the core density
+ * of the pseudopotentials as one more operand.  n_spin = 1 or 2: rho_d / V_out_d hold that many cubes.  rho_core_d: ONE cube,
+ * the TOTAL core density (atomic_total_density(basis, CoreDensity())); each channel sees rho_core / n_spin
+ * (rho_from_total, src/densities.jl:158-175).  grad_core_d: three cubes (x, y, z), the gradient of the total core density as
+ * dftk_mi_cube_gradient writes it; required with a GGA bit when rho_core_d is given, ignored otherwise.
+ *   E_xc, v_xc: those of rho_s + rho_core / n_spin; gradients grad rho_s + grad rho_core / n_spin, sigma and the flux of
+ *               the divergence term built from those sums; every floor and threshold applies to the summed argument
+ *   Hartree, sum rho V_loc: rho alone
+ * The core rides on passes that stream the cube anyway (the final sum, the point-wise GGA pass, the pass that writes the
+ * gradients): no transform and no launch more than the entry of the same kind.  Masks and their refusals as that entry
+ * (n_spin = 1: LDA bits and TETER93 without a GGA bit, bits 1 .. 16 with one; n_spin = 2: as _collinear_gga);
+ * recip_lattice_h (3x3 column-major) is required with a GGA bit; V_loc_d / poisson_green_d / V_out_d may be NULL and
+ * energies_h == NULL means asynchronous, as above.  With rho_core_d == NULL the results are bit for bit those of the
+ * existing entry.  DFTK_MI_EINVAL, nothing written: n_spin outside {1, 2}, a mask outside the above, a GGA bit with a core
+ * but without grad_core_d, a k-block that does not span the cube. */
+int dftk_mi_local_potential_core(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, int n_spin, const double* rho_d,
+                                 const double* rho_core_d, const double* grad_core_d, const double* V_loc_d,
+                                 const double* poisson_green_d, int xc_functionals, double density_threshold,
+                                 double* V_out_d, double* energies_h);
+/* grad_d[a] = Re irfft(i G_a fft(f_d)), a = x, y, z (three real cubes, one after the other; G cartesian from
+ * recip_lattice_h, 3x3 column-major): exactly the operator chain the GGA pipelines apply to the density, so that
+ * grad(rho + rho_core) and grad rho + grad rho_core agree to rounding.  Set-up entry, asynchronous on the basis' stream. */
+int dftk_mi_cube_gradient(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, const double* f_d, double* grad_d);
+
 /* ---- density-sized operations of the SCF glue ----------------------------------------------
  * symmetrize_rho(basis, rho; symmetries, do_lowpass) for one spin component (src/symmetry.jl:346-357): fft, then
  * accumulate_over_symmetries! (:282-319: out(G) = sum_s e^{-2 pi i G.tau_s} in(S_s^-1 G), terms whose S_s^-1 G leaves
