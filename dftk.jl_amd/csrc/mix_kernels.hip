@@ -81,7 +81,15 @@ __global__ __launch_bounds__(MT) void k_mult_chi0_dielectric(int nx, int ny, int
         const double c2 = L.B[6] * g0 + L.B[7] * g1 + L.B[8] * g2;
         const double G2 = c0 * c0 + c1 * c1 + c2 * c2;
         const double m = C0 * kTF * kTF * G2 / (4.0 * M_PI) / (kTF * kTF - C0 * G2);      // chi0models.jl:66-77
-        const cd v = in[i];
+        cd v = in[i];
+        if (unpaired_nyquist(ix, iy, iz, nx, ny, nz)) {
+            // the model acts on the REAL dV (chi0models.jl:72 transforms a real array).  `in` = poisson(G) F(G) is Hermitian
+            // wherever -G is on the grid; on the Nyquist planes of even axes poisson(G) != poisson(-G) for a sheared cell, and
+            // the transform of Re(dV) is the Hermitian part (in(G) + conj in(-G)) / 2
+            const int64_t j = (int64_t)((nx - ix) % nx) + (int64_t)nx * (((ny - iy) % ny) + (int64_t)ny * ((nz - iz) % nz));
+            const cd u = in[j];
+            v = make_double2(0.5 * (v.x + u.x), 0.5 * (v.y - u.y));
+        }
         out[i] = make_double2(m * v.x, m * v.y);
     }
 }
@@ -415,10 +423,12 @@ extern "C" int dftk_mi_anderson_step(dftk_mi_anderson* a, const double* x_d, dou
     HIPCHK(hipSetDevice(b->device));
     const int64_t n = a->n;
     PtrTable X{}, R{};
-    if (a->m == 0) {
+    if (a->m == 0 || a->errorfactor <= 1.0 || a->maxcond <= 1.0) {
+        // anderson.jl:82: no acceleration -- the plain damped step at every call, nothing enters the history
         hipLaunchKernelGGL(k_anderson_update, grid(), dim3(MT), 0, b->stream, n, x_d, pf_d, alpha, 1.0, 0, X, R, xn_d,
                            (double*)nullptr, (double*)nullptr);
         HIPCHK(hipGetLastError());
+        if (n_history) *n_history = 0;
         return 0;
     }
     auto slot_x = [&](int s) { return a->buf + 2 * (size_t)s * n; };
@@ -735,8 +745,11 @@ extern "C" int dftk_mi_chi0_mix(dftk_mi_kblock* cube_kb, int n_comp, const doubl
             for (double v : h) hh += v * v;
             double rest = ww - hh;
             bool updated = false;
-            if (rest < 1e-2 * ww) {
-                // cancellation: a second pass of Gram-Schmidt ("twice is enough") and the remainder's own norm
+            if (rest < 0.5 * ww) {
+                // |w - V h| < |w| / sqrt 2 (the criterion of Daniel, Gragg, Kaufman and Stewart): a second pass of
+                // Gram-Schmidt ("twice is enough").  A laxer test lets classical Gram-Schmidt lose the orthogonality of the
+                // basis by a constant factor per step: the Givens estimate then stalls above a tight tolerance while the
+                // iterate goes on converging, and the cycle runs to krylovdim
                 for (int i = 0; i <= k; ++i) V.c[i] = h[i];
                 hipLaunchKernelGGL(k_axpy_multi, g, t, 0, b->stream, Nt, wv, k + 1, V, (double*)nullptr, 0.0);
                 hipLaunchKernelGGL(k_center_dots, g, t, 0, b->stream, Nt, wv, (const double*)nullptr, k + 1, V, hpart);

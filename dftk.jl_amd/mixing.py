@@ -104,10 +104,11 @@ def gmres(apply, b: torch.Tensor, rtol: float, krylovdim: int = 30, maxiter: int
             h, ww = vals[:-1].copy(), float(vals[-1])
             w = w - torch.as_tensor(h, device=w.device) @ Vm
             rest = ww - float(np.dot(h, h))
-            if rest < 1e-2 * ww:
-                # cancellation: one pass of classical Gram-Schmidt leaves components of size eps * ||w|| / ||rest|| along
-                # the basis, and Pythagoras has lost its digits -- a second pass ("twice is enough") and the remainder's
-                # own norm; costs one more fetch on the steps where it is needed
+            if rest < 0.5 * ww:
+                # ||w - V h|| < ||w|| / sqrt 2 (Daniel, Gragg, Kaufman, Stewart): one pass of classical Gram-Schmidt leaves
+                # components of size eps * ||w|| / ||rest|| along the basis -- a second pass ("twice is enough") and the
+                # remainder's own norm; one more fetch.  With a laxer test the basis loses its orthogonality by a constant
+                # factor per step and the Givens estimate stalls above a tight tolerance
                 vals2 = torch.cat([Vm @ w, (w @ w).reshape(1)]).cpu().numpy()
                 h2 = vals2[:-1]
                 w = w - torch.as_tensor(h2, device=w.device) @ Vm

@@ -250,7 +250,7 @@ class AndersonAcceleration:
         self.gram = self.gram[np.ix_(keep, keep)]
 
     def __call__(self, x, alpha, Pfx):
-        if self.m == 0:
+        if self.m == 0 or self.errorfactor <= 1 or self.maxcond <= 1:          # anderson.jl:82: disables Anderson
             return x + alpha * Pfx
         pf = Pfx.reshape(-1)
         xf = x.reshape(-1)

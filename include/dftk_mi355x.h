@@ -756,7 +756,8 @@ int dftk_mi_prof_get(dftk_mi_basis* basis, int family, double* total_ms, double*
  * device; a step = one reduction kernel (the inner products with the new residual; the Gram matrix of the history is
  * kept), ONE host synchronisation, the m x m least-squares problem on the host (conditioning test on cond(R) =
  * sqrt(cond(M'M)), entries with error > errorfactor * min dropped, as the reference), one fused update kernel.
- * x_next_d must not alias the inputs.  m = 0: plain damping x + alpha Pf. */
+ * x_next_d must not alias the inputs.  m = 0, errorfactor <= 1 or maxcond <= 1 (anderson.jl:82): no acceleration, plain
+ * damping x + alpha Pf at every call and an empty history. */
 typedef struct dftk_mi_anderson dftk_mi_anderson;
 int dftk_mi_anderson_create(dftk_mi_basis* basis, int64_t n, int m, double maxcond, double errorfactor,
                             dftk_mi_anderson** out);
@@ -773,8 +774,8 @@ int dftk_mi_anderson_step(dftk_mi_anderson* acc, const double* x_d, double alpha
  * or DielectricModel (dielectric != 0: kTF, eps_r, :54-80, needs recip_lattice_h, column-major 3 x 3).  n_comp = 2:
  * collinear spin, vectors are (up, down) stacked, the Hartree kernel sees the total.  With no term alive d_rho = dF
  * (simple mixing, chi0models.jl:32, mixing.jl:264-266).  Every Krylov step is 12 launches and ONE host
- * synchronisation (all inner products of the classical Gram-Schmidt step in one fetch; a second pass when cancellation
- * asks for it).  *n_applies = applications of the dielectric operator, *converged = 0 if maxiter cycles did not
+ * synchronisation (all inner products of the classical Gram-Schmidt step in one fetch; a second pass, with one more
+ * fetch, when the remainder is shorter than |w| / sqrt 2).  *n_applies = applications of the dielectric operator, *converged = 0 if maxiter cycles did not
  * reach the tolerance (d_rho is the last iterate, as the reference's mixing uses it). */
 int dftk_mi_chi0_mix(dftk_mi_kblock* cube_kblock, int n_comp, const double* recip_lattice_h, const double* poisson_d,
                      const double* ldos_d, double dvol, int dielectric, double kTF, double eps_r, const double* dF_d,

@@ -186,9 +186,10 @@ class AndersonAcceleration:
                 lst.pop(i)
 
     def __call__(self, x, alpha, Pfx):
-        if self.m == 0 or not self.iterates:
-            if self.m != 0:
-                self._push(x, Pfx)
+        if self.m == 0 or self.errorfactor <= 1 or self.maxcond <= 1:          # anderson.jl:82: disables Anderson
+            return x + alpha * Pfx
+        if not self.iterates:
+            self._push(x, Pfx)
             return x + alpha * Pfx
         min_error = min(self.errors + [float(np.linalg.norm(Pfx))])
         drop = [i for i, e in enumerate(self.errors[:-1]) if e > self.errorfactor * min_error]
