@@ -1469,10 +1469,15 @@ extern "C" int dftk_mi_zgemm_plan_host(char transA, int64_t m, int64_t n, int64_
     return zgemm_plan_host(transA, m, n, k, flags, out12);
 }
 
+int zgemm_fold_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int cap, int* items4, int* count);   // gemm_kernels.hip
+extern "C" int dftk_mi_zgemm_fold_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int cap, int* items4, int* count) {
+    return zgemm_fold_host(transA, m, n, k, flags, cap, items4, count);
+}
+
 extern "C" int dftk_mi_zgemm_ex(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, dftk_mi_cplx alpha,
                                 const dftk_mi_cplx* A_d, int64_t lda, const dftk_mi_cplx* B_d, int64_t ldb,
                                 dftk_mi_cplx beta, dftk_mi_cplx* C_d, int64_t ldc, int flags) {
-    if (!b || m < 0 || n < 0 || k < 0 || !C_d || (flags & ~(3 | DFTK_MI_GEMM_REAL))) return DFTK_MI_EINVAL;
+    if (!b || m < 0 || n < 0 || k < 0 || !C_d || (flags & ~(3 | DFTK_MI_GEMM_REAL | DFTK_MI_GEMM_SYM_RESULT))) return DFTK_MI_EINVAL;
     HIPCHK(hipSetDevice(b->device));
     cd al = {alpha.re, alpha.im}, be = {beta.re, beta.im};
     return zgemm(b, transA, m, n, k, al, reinterpret_cast<const cd*>(A_d), lda, reinterpret_cast<const cd*>(B_d), ldb,
@@ -1484,6 +1489,12 @@ extern "C" int dftk_mi_heev(dftk_mi_basis* b, int n, dftk_mi_cplx* A_d, int64_t 
     if (!b || n < 1 || !A_d || !W_h || !V_d || lda < n || ldv < n) return DFTK_MI_EINVAL;
     HIPCHK(hipSetDevice(b->device));
     return dense_heev(b, n, reinterpret_cast<cd*>(A_d), lda, W_h, reinterpret_cast<cd*>(V_d), ldv);
+}
+
+extern "C" int dftk_mi_eig_mirror_tall(dftk_mi_basis* b, int n, int real, dftk_mi_cplx* X_d, int64_t ldt) {
+    if (!b || n < 1 || !X_d || ldt < (real ? (n + 1) / 2 : n) || 2 * ldt > INT32_MAX) return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(b->device));
+    return eig_mirror_tall(b, n, real != 0, reinterpret_cast<cd*>(X_d), ldt);
 }
 
 extern "C" int dftk_mi_heev_lowest(dftk_mi_basis* b, int n, int nev, dftk_mi_cplx* A_d, int64_t lda, double* W_h,

@@ -339,6 +339,12 @@ int launch_kinetic_only(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi
 // upper & 1: only the 128x64 tiles that intersect the upper triangle (i <= j) are computed and
 //            written; the rest of C is left untouched (Gram matrices that are hermitised afterwards)
 // upper & 2: B is upper triangular (B[k][j] = 0 for k > j): the k loop of a tile column stops early
+// upper & DFTK_MI_GEMM_SYM_RESULT ('N' products only): the caller knows that A B is Hermitian and needs only its entries
+//            on and above the diagonal -- only the tiles that hold one are computed and written, the caller mirrors them.
+//            With DFTK_MI_GEMM_REAL the operands are "tall" (a complex row of A and C holds two REAL rows,
+//            eig_kernels.hip): the diagonal is met at REAL row 2 i (+ 1) = j, and the tile test uses REAL rows
+#define GEMM_SYM_RESULT DFTK_MI_GEMM_SYM_RESULT
+bool zgemm_sym_result_pays(int64_t m, int64_t n, int64_t k, bool real);   // (host: does the flag save a round of workgroups?)
 int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alpha, const cd* A,
           int64_t lda, const cd* B, int64_t ldb, cd beta, cd* C, int64_t ldc, int upper = 0);
 int ensure_ws(dftk_mi_basis* b, size_t bytes);
@@ -363,6 +369,7 @@ int dense_input_norms(dftk_mi_basis* b, int n, const cd* A, int64_t lda, double*
 // eig_kernels.hip: the lowest nev eigenpairs only (spectral split on the matrix cores + Jacobi on the projected matrix);
 // falls back to dense_heev where the split does not apply
 int dense_heev_lowest(dftk_mi_basis* b, int n, int nev, cd* A, int64_t lda, double* W_h, cd* V, int64_t ldv);
+int eig_mirror_tall(dftk_mi_basis* b, int n, bool real, cd* X, int64_t ldt);   // eig_kernels.hip
 int eig_choose_sigma_host(int n, const double* diag, int nev, double* sigma, double* gap_guess);
 int eig_hold_iterations_host(double gap_over_norm);
 struct ProfMute {    // RAII: nothing inside is booked (the enclosing scope books the whole routine)

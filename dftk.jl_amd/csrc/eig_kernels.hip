@@ -31,6 +31,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 #include <numeric>
 #include <algorithm>
@@ -131,6 +132,47 @@ __global__ __launch_bounds__(256) void k_eig_poly(int n, cd* __restrict__ Y, int
     (void)ntile;
 }
 
+// Completes the iterate X (tall, n x n) that zgemm wrote with GEMM_SYM_RESULT -- only the tiles that meet the upper triangle
+// hold the product -- to an exactly Hermitian matrix: entry (i, j), i > j, = conj(entry (j, i)); the imaginary part of a
+// diagonal entry (round-off) and the REAL format's padding row become zero.  One workgroup per pair of 32 x 32 tiles
+// (bi <= bj), plain copies in a fixed order: the solver stays deterministic.  T = double (REAL: ld = 2 ldt doubles, `rows`
+// = 2 ldt counts the padding row) or cd (rows = n).
+template <class T>
+__global__ __launch_bounds__(256) void k_eig_mirror(int n, int rows, T* __restrict__ X, int64_t ld) {
+    __shared__ T tile[EPT][EPT + 1];
+    int t = blockIdx.x, bj = 0;
+    while (t > bj) {
+        t -= bj + 1;
+        ++bj;
+    }
+    const int bi = t;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+    constexpr bool CPLX = std::is_same<T, cd>::value;
+#pragma unroll
+    for (int r = 0; r < EPT; r += 8) {
+        const int i = bi * EPT + tx, j = bj * EPT + ty + r;
+        T v = T();
+        if (i < n && j < n && i <= j) v = X[i + (int64_t)j * ld];
+        if constexpr (CPLX) {
+            if (i == j && i < n && v.y != 0.0) {
+                v.y = 0.0;
+                X[i + (int64_t)j * ld] = v;
+            }
+        }
+        tile[ty + r][tx] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < EPT; r += 8) {
+        const int j = bj * EPT + tx, i = bi * EPT + ty + r;      // writes row j (fast), column i
+        if (i < n && j < rows && i < j) {
+            T v = tile[tx][ty + r];                              // (j >= n: the padding row, read as zero above)
+            if constexpr (CPLX) v.y = -v.y;
+            X[j + (int64_t)i * ld] = v;
+        }
+    }
+}
+
 template <bool REAL>
 __global__ void k_eig_diag_tall(int n, const cd* __restrict__ U, int64_t ldt, double* __restrict__ d) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -177,6 +219,19 @@ double a_of(double l) { return std::sqrt(3.0 / (1.0 + l + l * l)); }
 double l_next(double l, double a) { return 0.5 * a * l * (3.0 - a * a * l * l); }
 
 }   // namespace
+
+// The mirror pass of the solver's symmetric-result Newton-Schulz step on a tall n x n iterate X (ldt complex rows per
+// column; `real`: the REAL tall format, ldt >= (n + 1) / 2): k_eig_mirror above.  Also behind dftk_mi_eig_mirror_tall (tests).
+int eig_mirror_tall(dftk_mi_basis* b, int n, bool real, cd* X, int64_t ldt) {
+    const int mrows = real ? 2 * (int)ldt : n, mt1 = (mrows + EPT - 1) / EPT;
+    if (real)
+        hipLaunchKernelGGL(k_eig_mirror<double>, dim3(mt1 * (mt1 + 1) / 2), dim3(256), 0, b->stream, n, mrows,
+                           reinterpret_cast<double*>(X), 2 * ldt);
+    else
+        hipLaunchKernelGGL(k_eig_mirror<cd>, dim3(mt1 * (mt1 + 1) / 2), dim3(256), 0, b->stream, n, mrows, X, ldt);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 
 // Host-only statement of the sigma rule (also exported for the CPU test-suite): the nev-th smallest diagonal entry plus
 // `margin` = half the mean level spacing of the nev smallest diagonal entries; gap_guess = a tenth of that spacing
@@ -280,8 +335,15 @@ static int heev_lowest_impl(dftk_mi_basis* b, int n, int nev, cd* A, int64_t lda
         HIPCHK(hipGetLastError());
         return 0;
     };
-    auto advance = [&]() -> int {             // Xn = Xc * Y
-        CHK(zgemm(b, 'N', ldt, n, n, ONE, Xc, ldt, Y, n, ZERO, Xn, ldt, rf));
+    // Xn = Xc * Y.  Xc is Hermitian and Y a polynomial in it, so the product is Hermitian: only its tiles on and above the
+    // diagonal are computed (GEMM_SYM_RESULT: 84 of 144 tiles at 1509^2 REAL), k_eig_mirror completes it
+    // before anything reads it -- the iterate is then EXACTLY Hermitian, which the full product only was to round-off.  Used
+    // where it saves a round of workgroups (zgemm_sym_result_pays: 1509^2 REAL yes, 1006^2 no -- there the mirror pass costs
+    // more than the shorter K chunks give back); the choice depends on n alone, so every rank of a sharded block makes it alike
+    const bool sym = zgemm_sym_result_pays(ldt, n, n, REAL);
+    auto advance = [&]() -> int {
+        CHK(zgemm(b, 'N', ldt, n, n, ONE, Xc, ldt, Y, n, ZERO, Xn, ldt, rf | (sym ? GEMM_SYM_RESULT : 0)));
+        if (sym) CHK(eig_mirror_tall(b, n, REAL, Xn, ldt));
         Xc = Xn;
         Xn = (Xc == Xa) ? Xb : Xa;
         ++its;

@@ -68,7 +68,23 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 // FULL (MODE 1): launched only over tiles that lie entirely inside C -> no per-sub-tile predicates (runtime
 // predicates become a branch per MFMA and break the MFMA issue stream).  gm x gn is the tile sub-grid of this
 // launch, (rt0, ct0) its origin in tiles (see lsplit below for the border launch).
-template <bool CONJA, int MODE, bool REAL, int RN>
+// FOLD (triangular B, 'N', full tiles, no K split): a workgroup computes TWO column tiles of its row panel back to back, the
+// long one gn - 1 - p first and then the short one p (the middle one alone when gn is odd): every workgroup runs gn + 1
+// diagonal blocks of k instead of 1 ... gn, half as many workgroups start and drain, and the loads of the second tile's first
+// k-tile are in flight while the first tile is stored.  The k order inside a tile is the one of the unfolded kernel.
+// Work item of workgroup `id` of a FOLD launch over gm row panels x gn column tiles (grid = 8 ceil(gm / 8) ceil(gn / 2)): the
+// items of one row panel sit on the same XCD (id & 7), they share the A panel.  false: no work.  col2 < 0: one tile only.
+// (host + device: dftk_mi_zgemm_fold_host lists the items of a launch for the CPU test-suite)
+__host__ __device__ inline bool gemm_fold_item(int id, int gm, int gn, int* row_t, int* col1, int* col2) {
+    const int xcd = id & 7, slot = id >> 3;
+    const int np = (gn + 1) >> 1, p = slot % np;
+    *row_t = (slot / np) * 8 + xcd;
+    *col1 = gn - 1 - p;
+    *col2 = (p != gn - 1 - p) ? p : -1;
+    return *row_t < gm;
+}
+
+template <bool CONJA, int MODE, bool REAL, int RN, bool FOLD = false>
 __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int m, int n, int K, int kchunk, int gm, int gn,
                                                                int rt0, int ct0, int lsplit, int upper,
                                                                int shift_ct, int shift_rt, int nsplit, const cd* __restrict__ A, int64_t lda,
@@ -83,14 +99,18 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
     const int id = blockIdx.x;
     const int xcd = id & 7, slot = id >> 3;
     int z, row_t, col_t;
-    if (upper & 16) {
+    int col2 = -1;   // FOLD: the second tile column of this workgroup
+    if (FOLD) {
+        if (!gemm_fold_item(id, gm, gn, &row_t, &col_t, &col2)) return;   // whole workgroup
+        z = 0;
+    } else if (upper & 16) {
         // compact UPPER launch: only the LIVE tiles exist in the grid (row panel r keeps its column tiles >= r BM / BN), the
         // work items (k-chunk, row panel, live column tile) in this order are dealt to the XCDs in 8 contiguous blocks: an
         // XCD sees at most two k-chunks, the column tiles of a row panel sit next to each other, every XCD gets the same
         // number of items and no dead workgroup passes through the dispatcher (with the full grid below 38-44 % of the
         // workgroups of an UPPER launch leave at once; measured: the live ones then spread unevenly over the CUs as soon
         // as an XCD holds more than ~50 of them)
-        constexpr int q = GEMM_BM / BN;
+        const int q = (GEMM_BM << ((upper >> 5) & 1)) / BN;   // (upper & 32: two REAL rows per row of C, see below)
         int L = 0;
         for (int r = 0; r < gm; ++r) L += max(0, gn - r * q);
         const int N = L * nsplit, per = (N + 7) >> 3;
@@ -135,22 +155,24 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
     // rectangle of tiles at (rt0, ct0), or (lsplit >= 0) the L-shaped ragged border as a list:
     // entries < lsplit are the right strip (tile column ct0), the rest the bottom strip (tile row rt0)
     const int tr = lsplit < 0 ? row_t + rt0 : (row_t < lsplit ? row_t : rt0);
-    const int tcn = lsplit < 0 ? col_t + ct0 : (row_t < lsplit ? ct0 : row_t - lsplit);
+    int tcn = lsplit < 0 ? col_t + ct0 : (row_t < lsplit ? ct0 : row_t - lsplit);
     // tile column shift_ct (the one past the last full column) is SHIFTED LEFT to end at column n: it overlaps
     // its neighbour, recomputes up to 31 columns and stores only columns >= jmin.  A ragged n then needs no
     // right-strip launch (which would stream all of A a second time for a handful of columns).
-    const bool shifted = tcn == shift_ct;
+    bool shifted = tcn == shift_ct;
     // likewise tile row shift_rt (the one past the last full row) is SHIFTED UP to end at row m and stores only
     // rows >= imin: a ragged m needs no bottom-strip launch (a second, serialized launch of slow predicated
     // workgroups whose k chains are as long as the interior's)
     const bool rshifted = tr == shift_rt;
-    const int I0 = rshifted ? m - GEMM_BM : tr * GEMM_BM, J0 = shifted ? n - BN : tcn * BN;
-    const int jmin = shifted ? tcn * BN : 0, imin = tr * GEMM_BM;
-    if ((upper & 1) && imin >= J0 + BN) return;   // no needed entry (i <= j) in this tile (whole workgroup)
+    const int I0 = rshifted ? m - GEMM_BM : tr * GEMM_BM, imin = tr * GEMM_BM;
+    int J0 = shifted ? n - BN : tcn * BN, jmin = shifted ? tcn * BN : 0;   // (not const: FOLD moves to a second tile column)
+    // upper & 32 (with upper & 1): the rows of C are pairs of REAL rows (symmetric result of a "tall" REAL 'N' product,
+    // GEMM_SYM_RESULT): the first REAL row of the tile is 2 imin
+    if ((upper & 1) && (imin << ((upper >> 5) & 1)) >= J0 + BN) return;   // no needed entry (i <= j) in this tile (whole workgroup)
     const int i0 = I0 + wave * (GEMM_RM * 16);
     const int kbeg = z * kchunk;
     // bit 1 of `upper`: B is upper triangular (B[k][j] = 0 for k > j) -> this tile column stops at k = J0 + BN
-    const int kend = min(min(K, kbeg + kchunk), (upper & 2) ? J0 + BN : K);
+    int kend = min(min(K, kbeg + kchunk), (upper & 2) ? J0 + BN : K);
     // MODE 1: every tile of the launch is full (no predicates anywhere).  MODE 0: predicated only.
     constexpr bool FULL = MODE == 1;
     const int rmv = FULL ? GEMM_RM : min(GEMM_RM, max(0, (m - i0 + 15) >> 4));
@@ -177,7 +199,7 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
     // running per-thread source pointers (named scalars: arrays captured by lambdas end up in scratch);
     // every load advances them by one k-tile
     const cd *pA0, *pA1, *pA2, *pA3, *pB0, *pB1;
-    {
+    auto init_ptrs = [&]() {
         auto a_ptr = [&](int r) -> const cd* {
             if (CONJA) {
                 int c = I0 + tc + 32 * r;
@@ -200,7 +222,8 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
         pA3 = a_ptr(3);
         pB0 = b_ptr(0);
         pB1 = b_ptr(RN == 4 ? 1 : 0);
-    }
+    };
+    init_ptrs();
     const int64_t stepA = CONJA ? (int64_t)LT_KT : (int64_t)LT_KT * lda;
     struct Stage {
         cd a0, a1, a2, a3, b0, b1;
@@ -262,7 +285,12 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
         if (!vB) st.b0 = st.b1 = czero;
         return st;
     };
-    auto store_tile = [&](int buf, const Stage& st) {
+    // Triangular B (upper & 2): inside the diagonal block of a tile column (its last BN k) the entries below the diagonal
+    // (k > j) are staged as ZEROS, whatever B holds there -- the call equals the dense product with triu(B) bit for bit
+    // (the k order of a tile is the same and the dense product adds exact zeros), and the strict lower triangle of B never
+    // reaches C.  k0 is the first k of the tile stored; this thread holds the entries (k0 + tk, J0 + tc) and (., J0 + tc + 32).
+    int cB0 = (upper & 2) ? J0 + tc - tk : INT32_MAX, cB1 = (upper & 2) ? J0 + tc + 32 - tk : INT32_MAX;
+    auto store_tile = [&](int buf, const Stage& st, int k0) {
         if (CONJA) {
             sA[buf][tk][(tc) ^ tk] = st.a0;
             sA[buf][tk][(tc + 32) ^ tk] = st.a1;
@@ -275,8 +303,17 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
             sA[buf][kk + 4][ii] = st.a2;
             sA[buf][kk + 6][ii] = st.a3;
         }
-        sB[buf][tk][(tc) ^ tk] = st.b0;
-        if (RN == 4) sB[buf][tk][(tc + 32) ^ tk] = st.b1;
+        // (selects on the VALUES: a conditional between two cd lvalues becomes a select of addresses and sends st to scratch)
+        // 'N' products only (X inv(R)): in the 'C' kernels the extra selects pushed the LDS writes out of their MFMA shadows
+        // (Gram products 3-5 % slower, measured); a 'C' call with a triangular B still expects the zeros in B itself
+        if (!CONJA) {
+            const bool z0 = k0 > cB0, z1 = k0 > cB1;
+            sB[buf][tk][(tc) ^ tk] = make_double2(z0 ? 0.0 : st.b0.x, z0 ? 0.0 : st.b0.y);
+            if (RN == 4) sB[buf][tk][(tc + 32) ^ tk] = make_double2(z1 ? 0.0 : st.b1.x, z1 ? 0.0 : st.b1.y);
+        } else {
+            sB[buf][tk][(tc) ^ tk] = st.b0;
+            if (RN == 4) sB[buf][tk][(tc + 32) ^ tk] = st.b1;
+        }
     };
     // MFMA fragments of one k-half of a tile: half h holds k = 2*lk + h (lk = lane >> 4)
     struct Frag {
@@ -333,93 +370,120 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
     //   iteration t:  read half-1 fragments of tile t | write tile t+1 (registers) to the other buffer,
     //                 issue the global loads of tile t+2 | MFMAs on half 0 | barrier |
     //                 read half-0 fragments of tile t+1 | MFMAs on half 1
-    const int nt = (kend - kbeg + LT_KT - 1) / LT_KT;
-    if (nt > 0) {
-        Stage st = load_tile(kbeg);
-        if (nt == 1) st = mask_tile(st, kbeg);
-        store_tile(0, st);
-        if (nt > 1) st = load_tile(kbeg + LT_KT);
-        __syncthreads();
-        Frag f0 = read_frag(0, 0);
-        int t = 0;
-        if (FULL) {
-            // steady state (tiles t+1, t+2, t+3 exist): one branch-free block, and the
-            // scheduler is told to drop one memory instruction into the shadow of each MFMA so that this
-            // wave alone keeps the matrix pipe fed (the two workgroups of a CU run in lockstep, so
-            // "the other wave covers my memory phase" does not happen by itself).
-            for (; t + 3 < nt; ++t) {   // tile t+2 is not the last one: it lies entirely inside the chunk
-                Frag f1 = read_frag(t & 1, 1);
-                store_tile((t + 1) & 1, st);
-                st = load_fast();
-                mfma_half(f0, std::true_type{});
-#pragma unroll
-                for (int i = 0; i < GEMM_RM + RN; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 DS read
-                }
-#pragma unroll
-                for (int i = 0; i < 4 + RN / 2; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // 1 DS write
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // 1 VMEM read
-                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // pointer advance
-                }
-                __syncthreads();
-                f0 = read_frag((t + 1) & 1, 0);
-                mfma_half(f1, std::true_type{});
-#pragma unroll
-                for (int i = 0; i < GEMM_RM + RN; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 1);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
-                }
-            }
-        }
-        for (; t < nt; ++t) {
-            const bool more = (t + 1) < nt;
-            Frag f1 = read_frag(t & 1, 1);
-            if (more) {
-                if (t + 2 == nt) st = mask_tile(st, kbeg + (t + 1) * LT_KT);
-                store_tile((t + 1) & 1, st);
-                if (t + 2 < nt) st = load_tile(kbeg + (t + 2) * LT_KT);
-            }
-            if (active) mfma_half(f0, std::integral_constant<bool, FULL>{});
-            __syncthreads();
-            if (more) f0 = read_frag((t + 1) & 1, 0);
-            if (active) mfma_half(f1, std::integral_constant<bool, FULL>{});
-        }
-    }
-    if (!active) return;
-
-    // epilogue
-    const int j0 = J0;
+    int nt = (kend - kbeg + LT_KT - 1) / LT_KT;
+    Stage st;
+    if (nt > 0) st = load_tile(kbeg);
     const bool direct = (slab == nullptr);
     cd* sl = direct ? nullptr : slab + (int64_t)z * m * n;
+    for (int pass = 0;; ++pass) {
+        if (nt > 0) {
+            if (nt == 1) st = mask_tile(st, kbeg);
+            store_tile(0, st, kbeg);
+            if (nt > 1) st = load_tile(kbeg + LT_KT);
+            __syncthreads();
+            Frag f0 = read_frag(0, 0);
+            int t = 0;
+            if (FULL) {
+                // steady state (tiles t+1, t+2, t+3 exist): one branch-free block, and the
+                // scheduler is told to drop one memory instruction into the shadow of each MFMA so that this
+                // wave alone keeps the matrix pipe fed (the two workgroups of a CU run in lockstep, so
+                // "the other wave covers my memory phase" does not happen by itself).
+                for (; t + 3 < nt; ++t) {   // tile t+2 is not the last one: it lies entirely inside the chunk
+                    Frag f1 = read_frag(t & 1, 1);
+                    store_tile((t + 1) & 1, st, kbeg + (t + 1) * LT_KT);
+                    st = load_fast();
+                    mfma_half(f0, std::true_type{});
 #pragma unroll
-    for (int a = 0; a < GEMM_RM; ++a)
+                    for (int i = 0; i < GEMM_RM + RN; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 DS read
+                    }
 #pragma unroll
-        for (int b = 0; b < RN; ++b)
+                    for (int i = 0; i < 4 + RN / 2; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
+                        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // 1 DS write
+                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // 1 VMEM read
+                        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // pointer advance
+                    }
+                    __syncthreads();
+                    f0 = read_frag((t + 1) & 1, 0);
+                    mfma_half(f1, std::true_type{});
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int gi = i0 + a * 16 + lk + 4 * r;
-                const int gj = j0 + b * 16 + li;
-                if (gi < m && gj < n && gj >= jmin && gi >= imin) {
-                    const double p1 = acc1[a][b][r], p2 = acc2[a][b][r], p3 = acc3[a][b][r];
-                    const double vr = REAL ? p1 : (CONJA ? p1 + p2 : p1 - p2);
-                    const double vi = REAL ? (CONJA ? 0.0 : p2) : (CONJA ? p3 - p1 + p2 : p3 - p1 - p2);
-                    if (direct) {
-                        cd* c = C + gi + (int64_t)gj * ldc;
-                        cd o = make_double2(alpha.x * vr - alpha.y * vi, alpha.x * vi + alpha.y * vr);
-                        if (beta.x != 0.0 || beta.y != 0.0) {
-                            const cd old = *c;
-                            o.x += beta.x * old.x - beta.y * old.y;
-                            o.y += beta.x * old.y + beta.y * old.x;
-                        }
-                        *c = o;
-                    } else {
-                        sl[gi + (int64_t)gj * m] = make_double2(vr, vi);
+                    for (int i = 0; i < GEMM_RM + RN; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 2, 1);
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
                     }
                 }
             }
+            for (; t < nt; ++t) {
+                const bool more = (t + 1) < nt;
+                Frag f1 = read_frag(t & 1, 1);
+                if (more) {
+                    if (t + 2 == nt) st = mask_tile(st, kbeg + (t + 1) * LT_KT);
+                    store_tile((t + 1) & 1, st, kbeg + (t + 1) * LT_KT);
+                    if (t + 2 < nt) st = load_tile(kbeg + (t + 2) * LT_KT);
+                }
+                if (active) mfma_half(f0, std::integral_constant<bool, FULL>{});
+                __syncthreads();
+                if (more) f0 = read_frag((t + 1) & 1, 0);
+                if (active) mfma_half(f1, std::integral_constant<bool, FULL>{});
+            }
+        }
+        if (!active) return;
+
+        // epilogue
+        const int j0 = J0, jm = jmin;
+        const bool again = FOLD && pass == 0 && col2 >= 0;
+        if (again) {
+            // the second tile column: its first k-tile is loaded while the stores below drain.  (Every wave is past the last
+            // barrier of the first tile and nothing reads LDS after it: the buffers are free.)
+            tcn = col2 + ct0;
+            shifted = tcn == shift_ct;
+            J0 = shifted ? n - BN : tcn * BN;
+            jmin = shifted ? tcn * BN : 0;
+            kend = min(min(K, kbeg + kchunk), (upper & 2) ? J0 + BN : K);
+            nt = (kend - kbeg + LT_KT - 1) / LT_KT;
+            cB0 = (upper & 2) ? J0 + tc - tk : INT32_MAX;
+            cB1 = (upper & 2) ? J0 + tc + 32 - tk : INT32_MAX;
+            init_ptrs();
+            if (nt > 0) st = load_tile(kbeg);
+        }
+#pragma unroll
+        for (int a = 0; a < GEMM_RM; ++a)
+#pragma unroll
+            for (int b = 0; b < RN; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int gi = i0 + a * 16 + lk + 4 * r;
+                    const int gj = j0 + b * 16 + li;
+                    if (gi < m && gj < n && gj >= jm && gi >= imin) {
+                        const double p1 = acc1[a][b][r], p2 = acc2[a][b][r], p3 = acc3[a][b][r];
+                        const double vr = REAL ? p1 : (CONJA ? p1 + p2 : p1 - p2);
+                        const double vi = REAL ? (CONJA ? 0.0 : p2) : (CONJA ? p3 - p1 + p2 : p3 - p1 - p2);
+                        if (direct) {
+                            cd* c = C + gi + (int64_t)gj * ldc;
+                            cd o = make_double2(alpha.x * vr - alpha.y * vi, alpha.x * vi + alpha.y * vr);
+                            if (beta.x != 0.0 || beta.y != 0.0) {
+                                const cd old = *c;
+                                o.x += beta.x * old.x - beta.y * old.y;
+                                o.y += beta.x * old.y + beta.y * old.x;
+                            }
+                            *c = o;
+                        } else {
+                            sl[gi + (int64_t)gj * m] = make_double2(vr, vi);
+                        }
+                    }
+                }
+        if (!again) break;
+#pragma unroll
+        for (int a = 0; a < GEMM_RM; ++a)
+#pragma unroll
+            for (int b = 0; b < RN; ++b) {
+                acc1[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
+                acc2[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
+                acc3[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
+            }
+    }
 }
 
 // C = alpha * sum_z slab[z] + beta * C   (fixed summation order).  The interior (i < mi, j < nj) and
@@ -435,8 +499,9 @@ __global__ void k_zgemm_reduce(int m, int n, int mi, int nj, int nsI, const cd* 
     if (idx >= (int64_t)m * n) return;
     const int j = (int)(idx / m);
     const int i = (int)(idx - (int64_t)j * m);
-    if ((upper & 1) && (i / GEMM_BM) * GEMM_BM >= (j / REDUCE_UPPER_BN) * REDUCE_UPPER_BN + REDUCE_UPPER_BN)
-        return;   // tile not computed
+    if ((upper & 1) &&
+        (((i / GEMM_BM) * GEMM_BM) << ((upper >> 5) & 1)) >= min(n, (j / REDUCE_UPPER_BN) * REDUCE_UPPER_BN + REDUCE_UPPER_BN))
+        return;   // tile not computed (a shifted last tile column ends at n: the kernel's own test)
     const bool interior = i < mi && j < nj;
     const int nsplit = interior ? nsI : nsB;
     const cd* slab = interior ? slabI : slabB;
@@ -581,7 +646,7 @@ struct Split {
 // `border`: the plan of a border launch (the plan cache key does not hold `live_rows`, which differ between the
 // interior and the border launch of one shape)
 static Split gemm_plan_split(int64_t m, int64_t n, int64_t k, int upper, const std::vector<int>& live_rows, bool border,
-                             bool compact_ok = false) {
+                             bool compact_ok = false, int rsc = 1) {
     const int64_t slots = GEMM_SLOTS;
     const int64_t plane = (int64_t)m * n * (int64_t)sizeof(cd);
     static std::map<std::vector<int64_t>, std::pair<int, int>> plan_cache;   // key -> (nsplit, zmajor)
@@ -599,7 +664,7 @@ static Split gemm_plan_split(int64_t m, int64_t n, int64_t k, int upper, const s
     int best_ns = 1, best_zm = compact_ok ? 2 : 0;
     if (k >= 128 && total > 0 && total < slots) {
         const std::vector<int64_t> key = {m, n, k, (int64_t)(upper & 1), (int64_t)border, (int64_t)rot_rows,
-                                          (int64_t)compact_ok};
+                                          (int64_t)compact_ok, (int64_t)rsc};
         auto it = plan_cache.find(key);
         if (it != plan_cache.end()) {
             best_ns = it->second.first;
@@ -669,7 +734,9 @@ struct GemmTiling {
     int gmI;     // tile rows of the interior launch = gmf + shift_r
     Split I, B;
 };
-static GemmTiling gemm_tiling(int64_t m, int64_t n, int64_t k, int upper, bool real) {
+// rsc: REAL rows per row of C in the (upper & 1) tile test -- 2 for the symmetric result of a tall REAL 'N' product
+// (GEMM_SYM_RESULT), 1 otherwise
+static GemmTiling gemm_tiling(int64_t m, int64_t n, int64_t k, int upper, bool real, int rsc = 1) {
     GemmTiling t;
     t.BNt = real ? M3_BN_REAL : M3_BN;
     t.gm = (int)((m + GEMM_BM - 1) / GEMM_BM);
@@ -685,7 +752,7 @@ static GemmTiling gemm_tiling(int64_t m, int64_t n, int64_t k, int upper, bool r
     // live column tiles per tile row of each launch (upper: only tiles that intersect the upper triangle)
     auto live = [&](int tr, int tc) {
         const int64_t jend = (t.shift && tc == t.gnf) ? n : (int64_t)tc * t.BNt + t.BNt;
-        return !(upper & 1) || (int64_t)tr * GEMM_BM < jend;
+        return !(upper & 1) || (int64_t)tr * GEMM_BM * rsc < jend;
     };
     std::vector<int> rowsI(t.gmI, 0), rowsB(t.nright + t.nbottom, 0);
     for (int tr = 0; tr < t.gmI; ++tr)
@@ -694,17 +761,58 @@ static GemmTiling gemm_tiling(int64_t m, int64_t n, int64_t k, int upper, bool r
     for (int e = 0; e < t.nbottom; ++e) rowsB[t.nright + e] = live(t.gmf, e) ? 1 : 0;
     // compact UPPER launches (k_zgemm_3m, `upper & 16`): the kernel rebuilds the live tile list as "row panel r keeps its
     // column tiles >= r BM / BN" -- only used when that is exactly the list above
-    bool compact_ok = (upper & 1) && GEMM_BM % t.BNt == 0;
+    bool compact_ok = (upper & 1) && (GEMM_BM * rsc) % t.BNt == 0;
     for (int tr = 0; tr < t.gmI && compact_ok; ++tr)
-        compact_ok = rowsI[tr] == std::max(0, t.gnI - tr * (GEMM_BM / t.BNt));
-    t.I = gemm_plan_split(m, n, k, upper, rowsI, false, compact_ok);
-    t.B = gemm_plan_split(m, n, k, upper, rowsB, true);
+        compact_ok = rowsI[tr] == std::max(0, t.gnI - tr * (GEMM_BM * rsc / t.BNt));
+    t.I = gemm_plan_split(m, n, k, upper, rowsI, false, compact_ok, rsc);
+    t.B = gemm_plan_split(m, n, k, upper, rowsB, true, false, rsc);
     return t;
 }
-int zgemm_plan_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int* out) {
-    if (m <= 0 || n <= 0 || k <= 0 || (flags & ~(3 | DFTK_MI_GEMM_REAL)) || !out) return DFTK_MI_EINVAL;
-    (void)transA;   // both operand layouts share one plan
+// Does GEMM_SYM_RESULT pay for the 'N' product m x n x k?  Only where the FULL product, at the K split its plan chooses, holds
+// more workgroups than are resident at once: the flag then saves a whole round of workgroups.  Below that the K split
+// already fills the chip in one round, the flag only shortens the chunks a little, and the caller's mirror pass costs more
+// (measured, REAL tall: 1006^2 -- 64 tiles x 8 chunks = one round -- heev 5.60 -> 5.99 ms per call with the flag;
+// 1509^2 -- 144 tiles x 6 chunks, two rounds -> 84 x 6, one -- 8.55 -> 7.35 and 19.7 -> 17.6 ms)
+bool zgemm_sym_result_pays(int64_t m, int64_t n, int64_t k, bool real) {
+    if (m <= 0 || n <= 0 || k <= 0) return false;
+    const GemmTiling t = gemm_tiling(m, n, k, 0, real);
+    return (int64_t)t.gmI * t.gnI * t.I.nsplit > GEMM_SLOTS;
+}
+
+// Triangular B ('N', no UPPER) whose interior launch has no K split: two column tiles per workgroup (k_zgemm_3m, FOLD)
+static bool gemm_folds(const GemmTiling& t, bool conja, int upper) {
+    return !conja && (upper & 3) == 2 && t.I.nsplit == 1 && !t.I.zmajor && t.gmI >= 1 && t.gnI >= 2;
+}
+// Host-only: the (tile row, tile column, first k, end k) of every tile a FOLD launch runs, in workgroup order, 4 ints per
+// tile; *count = 0 when the shape does not take the folded launch (CPU test-suite: every tile of the plan exactly once)
+int zgemm_fold_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int cap, int* items4, int* count) {
+    if (m <= 0 || n <= 0 || k <= 0 || (flags & ~(3 | DFTK_MI_GEMM_REAL)) || cap < 0 || !count || (cap > 0 && !items4))
+        return DFTK_MI_EINVAL;
     const GemmTiling t = gemm_tiling(m, n, k, flags & 3, (flags & DFTK_MI_GEMM_REAL) != 0);
+    *count = 0;
+    if (!gemm_folds(t, transA == 'C' || transA == 'c', flags & 3)) return 0;
+    const int nblk = ((t.gmI + 7) / 8) * 8 * ((t.gnI + 1) / 2);
+    for (int id = 0; id < nblk; ++id) {
+        int row, c[2];
+        if (!gemm_fold_item(id, t.gmI, t.gnI, &row, &c[0], &c[1])) continue;
+        for (int i = 0; i < 2; ++i) {
+            if (c[i] < 0) continue;
+            if (*count < cap) {
+                const int64_t j0 = (t.shift && c[i] == t.gnf) ? n - t.BNt : (int64_t)c[i] * t.BNt;
+                int* e = items4 + 4 * (int64_t)*count;
+                e[0] = row; e[1] = c[i]; e[2] = 0; e[3] = (int)std::min<int64_t>(k, j0 + t.BNt);
+            }
+            ++*count;
+        }
+    }
+    return 0;
+}
+
+int zgemm_plan_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int* out) {
+    if (m <= 0 || n <= 0 || k <= 0 || (flags & ~(3 | DFTK_MI_GEMM_REAL | DFTK_MI_GEMM_SYM_RESULT)) || !out) return DFTK_MI_EINVAL;
+    (void)transA;   // both operand layouts share one plan
+    const bool real = (flags & DFTK_MI_GEMM_REAL) != 0, sym = (flags & DFTK_MI_GEMM_SYM_RESULT) != 0;
+    const GemmTiling t = gemm_tiling(m, n, k, (flags & 3) | (sym ? 1 : 0), real, (sym && real) ? 2 : 1);
     const int v[12] = {t.BNt, t.gmf, t.gnf, t.nright, t.nbottom, t.I.nsplit, t.I.kchunk, t.I.compact ? 2 : t.I.zmajor ? 1 : 0,
                        t.B.nsplit, t.B.kchunk, t.B.zmajor ? 1 : 0, t.shift};
     for (int i = 0; i < 12; ++i) out[i] = v[i];
@@ -713,10 +821,17 @@ int zgemm_plan_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int
 
 int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alpha, const cd* A, int64_t lda,
           const cd* B, int64_t ldb, cd beta, cd* C, int64_t ldc, int upper_in) {
-    const int upper = upper_in & 3;
     const bool real = (upper_in & DFTK_MI_GEMM_REAL) != 0;   // operands are real-symmetric half-sphere blocks
     if (m <= 0 || n <= 0) return 0;
     const bool conja = (transA == 'C' || transA == 'c');
+    // GEMM_SYM_RESULT ('N' only): the tile test of UPPER, on REAL rows (two per row of C) for a REAL product
+    const bool sym = (upper_in & GEMM_SYM_RESULT) != 0;
+    if (sym && conja) {
+        dftk_set_error("zgemm: GEMM_SYM_RESULT is a flag of 'N' products");
+        return DFTK_MI_EINVAL;
+    }
+    const int upper = (upper_in & 3) | (sym ? 1 : 0);
+    const int rsc = (sym && real) ? 2 : 1;
     if (!conja && !(transA == 'N' || transA == 'n')) {
         dftk_set_error("zgemm: transA must be 'N' or 'C'");
         return DFTK_MI_EINVAL;
@@ -726,7 +841,8 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
         BOp o;
         o.b = b;
         o.type = BOP_ZGEMM; o.trans = conja ? 'C' : 'N'; o.gm = m; o.gn = n; o.gk = k; o.alpha = alpha; o.A = A; o.lda = lda;
-        o.B = B; o.ldb = ldb; o.beta = beta; o.C = C; o.ldc = ldc; o.flags = upper_in;
+        o.B = B; o.ldb = ldb; o.beta = beta; o.C = C; o.ldc = ldc;
+        o.flags = upper_in & ~GEMM_SYM_RESULT;   // (the merged products know no symmetric result: the full product is computed)
         return batch_record(std::move(o));
     }
     if (k <= 0) {   // C = beta * C : run the reduce kernel over zero slabs
@@ -744,7 +860,7 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
                                  : ((uint64_t)conja << 63) | ((uint64_t)(m & 0x7FFFF) << 42) | ((uint64_t)(real ? 1 : 0) << 61) |
                                        ((uint64_t)(n & 0x3FFFF) << 22) | ((uint64_t)(upper_in & 3) << 40) |
                                        (uint64_t)(k & 0x3FFFFF) | (1ull << 62);
-    const GemmTiling til = gemm_tiling(m, n, k, upper, real);
+    const GemmTiling til = gemm_tiling(m, n, k, upper, real, rsc);
     // Flop booking (bench.py roofline).  `useful` = the part of the product that is mathematically needed:
     // 8mnk for an unstructured call, only the (i <= j) entries of C for UPPER, only k <= j for a triangular B.
     // `executed` = what the launched tiles really run on the matrix pipe (whole tiles, shifted-tile and border
@@ -757,7 +873,8 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
             useful = mac_useful * (double)m * (double)n * (double)k;
         } else {
             for (int64_t j = 0; j < n; ++j) {
-                const double rows = (upper & 1) ? (double)std::min<int64_t>(m, j + 1) : (double)m;
+                // (symmetric tall REAL result: the j + 1 REAL rows at or above the diagonal are (j + 1) / 2 rows of C)
+                const double rows = (upper & 1) ? std::min((double)m, (double)(j + 1) / rsc) : (double)m;
                 const double kk = (upper & 2) ? (double)std::min<int64_t>(k, j + 1) : (double)k;
                 useful += mac_useful * rows * kk;
             }
@@ -770,7 +887,7 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
         };
         auto live = [&](int64_t i0, int tc) {
             const int64_t jend = (til.shift && tc == til.gnf) ? n : std::min<int64_t>(n, (int64_t)tc * BNt + BNt);
-            return !(upper & 1) || i0 < jend;
+            return !(upper & 1) || i0 * rsc < jend;
         };
         for (int tr = 0; tr < til.gmI; ++tr)
             for (int tc = 0; tc < til.gnI; ++tc)
@@ -831,25 +948,31 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
         if (gm_s <= 0 || gn_s <= 0) return 0;
         const bool zmajor = sp.zmajor;
         const bool compact = sp.compact && mode == 1 && lsplit < 0;
-        const int64_t nblk = compact  ? (((int64_t)sp.live * sp.nsplit + 7) / 8) * 8
-                             : zmajor ? (int64_t)((sp.nsplit + 7) / 8) * 8 * gm_s * gn_s
-                                      : grid_for(gm_s, gn_s, sp.nsplit);
+        // triangular B without a K split: two column tiles per workgroup (k_zgemm_3m, FOLD)
+        const bool fold = mode == 1 && lsplit < 0 && gemm_folds(til, conja, upper);
+        const int64_t nblk = fold      ? grid_for(gm_s, (gn_s + 1) / 2, 1)
+                             : compact ? (((int64_t)sp.live * sp.nsplit + 7) / 8) * 8
+                             : zmajor  ? (int64_t)((sp.nsplit + 7) / 8) * 8 * gm_s * gn_s
+                                       : grid_for(gm_s, gn_s, sp.nsplit);
         if (nblk > INT32_MAX) return DFTK_MI_EINVAL;
         dim3 grid((unsigned)nblk);
-        const int upper = (upper_in & 3) | (compact ? 16 : zmajor ? 4 : 0) |
-                          ((!compact && !zmajor && (upper_in & 1) && gm_s <= 4) ? 8 : 0);
+        const int kupper = upper | (compact ? 16 : zmajor ? 4 : 0) | ((!compact && !zmajor && (upper & 1) && gm_s <= 4) ? 8 : 0) |
+                           (rsc == 2 ? 32 : 0);
 #define DFTK_LAUNCH_3M(CJ, MD)                                                                                         \
-    if (real) DFTK_LAUNCH_3M_(CJ, MD, true, M3_RN_REAL);                                                               \
-    else DFTK_LAUNCH_3M_(CJ, MD, false, M3_RN)
-#define DFTK_LAUNCH_3M_(CJ, MD, RL, RNN)                                                                               \
-    hipLaunchKernelGGL((k_zgemm_3m<CJ, MD, RL, RNN>), grid, dim3(GEMM_WAVES * 64), 0, b->stream, (int)m, (int)n, (int)k,  \
-                       sp.kchunk, gm_s, gn_s, rt0, ct0, lsplit, upper, til.shift ? gnf : -1,                           \
+    if (real) DFTK_LAUNCH_3M_(CJ, MD, true, M3_RN_REAL, false);                                                        \
+    else DFTK_LAUNCH_3M_(CJ, MD, false, M3_RN, false)
+#define DFTK_LAUNCH_3M_(CJ, MD, RL, RNN, FD)                                                                           \
+    hipLaunchKernelGGL((k_zgemm_3m<CJ, MD, RL, RNN, FD>), grid, dim3(GEMM_WAVES * 64), 0, b->stream, (int)m, (int)n, (int)k,  \
+                       sp.kchunk, gm_s, gn_s, rt0, ct0, lsplit, kupper, til.shift ? gnf : -1,                          \
                        (til.shift_r && lsplit < 0) ? gmf : -1, sp.nsplit, A, lda, B, ldb, C,                           \
                        ldc, alpha, beta, sp.slab)
         // mode 1 = full tiles, 0 = predicated border
         if (conja) {
             if (mode == 1) { DFTK_LAUNCH_3M(true, 1); }
             else { DFTK_LAUNCH_3M(true, 0); }
+        } else if (fold) {
+            if (real) DFTK_LAUNCH_3M_(false, 1, true, M3_RN_REAL, true);
+            else DFTK_LAUNCH_3M_(false, 1, false, M3_RN, true);
         } else {
             if (mode == 1) { DFTK_LAUNCH_3M(false, 1); }
             else { DFTK_LAUNCH_3M(false, 0); }
@@ -863,7 +986,7 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
     if (spI.slab || spB.slab)
         hipLaunchKernelGGL(k_zgemm_reduce, dim3((unsigned)((m * n + 255) / 256)), dim3(256), 0, b->stream, (int)m,
                            (int)n, til.shift_r ? (int)m : gmf * GEMM_BM, til.shift ? (int)n : gnf * BNt, spI.slab ? spI.nsplit : -1, spI.slab,
-                           spB.slab ? spB.nsplit : -1, spB.slab, C, ldc, alpha, beta, upper);
+                           spB.slab ? spB.nsplit : -1, spB.slab, C, ldc, alpha, beta, upper | (rsc == 2 ? 32 : 0));
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -614,14 +614,24 @@ int dftk_mi_zgemm(dftk_mi_basis* basis, char transA, int64_t m, int64_t n, int64
  *   DFTK_MI_GEMM_UPPER     only the tiles of C (128x32 for complex products, 128x64 with DFTK_MI_GEMM_REAL)
  *                          that intersect the upper triangle (i <= j) are computed and written, the rest of C is
  *                          left untouched;
- *   DFTK_MI_GEMM_B_UPPER   B is upper triangular (B[k][j] = 0 for k > j): the k loop stops at the diagonal;
+ *   DFTK_MI_GEMM_B_UPPER   B is upper triangular (B[k][j] = 0 for k > j): the k loop stops at the diagonal.  'N' products
+ *                          take the entries below the diagonal as zeros whatever the array holds (the call is the dense
+ *                          call on triu(B), bit for bit); 'C' products read them inside the diagonal block of a tile
+ *                          column and REQUIRE the zeros in the array;
  *   DFTK_MI_GEMM_REAL      the long operands are blocks of real-symmetric vectors in the half-sphere format of
  *                          dftk_mi_kblock_set_gamma_real, i.e. real matrices with two real rows per complex entry:
  *                          'C' computes Re(A^H B) (imaginary part stored as 0), 'N' computes A * Re(B); two real
- *                          matrix-core products per complex entry instead of three. */
+ *                          matrix-core products per complex entry instead of three;
+ *   DFTK_MI_GEMM_SYM_RESULT  'N' products whose result is known to be Hermitian (the Newton-Schulz step X p(X) of
+ *                          dftk_mi_heev_lowest): only the tiles of C that hold an entry on or above the diagonal are
+ *                          computed and written, the rest of C is left untouched and the caller mirrors the result.
+ *                          With DFTK_MI_GEMM_REAL a row of A and C holds two consecutive REAL rows (2 i, 2 i + 1) of
+ *                          a real symmetric matrix with 2 m (or 2 m - 1) rows, and the diagonal is counted in those;
+ *                          refused with 'C'. */
 #define DFTK_MI_GEMM_UPPER 1
 #define DFTK_MI_GEMM_B_UPPER 2
 #define DFTK_MI_GEMM_REAL 8
+#define DFTK_MI_GEMM_SYM_RESULT 32
 int dftk_mi_zgemm_ex(dftk_mi_basis* basis, char transA, int64_t m, int64_t n, int64_t k,
                      dftk_mi_cplx alpha, const dftk_mi_cplx* A_d, int64_t lda,
                      const dftk_mi_cplx* B_d, int64_t ldb, dftk_mi_cplx beta,
@@ -639,6 +649,12 @@ int dftk_mi_heev(dftk_mi_basis* basis, int n, dftk_mi_cplx* A_d, int64_t lda, do
  * the split off, DFTK_MI_HEEV_PARTIAL_MIN=<n> moves the size threshold. */
 int dftk_mi_heev_lowest(dftk_mi_basis* basis, int n, int nev, dftk_mi_cplx* A_d, int64_t lda, double* W_h,
                         dftk_mi_cplx* V_d, int64_t ldv);
+/* Exposed for tests: the mirror pass of dftk_mi_heev_lowest's Newton-Schulz step.  X_d is an n x n matrix whose entries on
+ * and above the diagonal are valid (the output of a DFTK_MI_GEMM_SYM_RESULT product), ldt rows per column.  real = 0: entry
+ * (i, j), i > j, becomes conj(entry (j, i)) and the imaginary part of the diagonal becomes zero.  real = 1: the REAL "tall"
+ * layout (complex row i = REAL rows 2 i, 2 i + 1; ldt >= (n + 1) / 2): REAL entry (r, c), r > c, becomes entry (c, r), and
+ * every REAL row from n to 2 ldt - 1 (padding) becomes zero.  Plain copies in a fixed order, no atomics. */
+int dftk_mi_eig_mirror_tall(dftk_mi_basis* basis, int n, int real, dftk_mi_cplx* X_d, int64_t ldt);
 /* Host-only: the shift rule of dftk_mi_heev_lowest on a diagonal (sigma, estimated distance to the nearest
  * eigenvalue) and, for a norm bound of A - sigma I, the number of held iterations (CPU test-suite). */
 int dftk_mi_heev_sigma_host(int n, const double* diag_h, int nev, double* sigma, double* gap_guess,
@@ -808,7 +824,9 @@ int dftk_mi_step_sums(dftk_mi_basis* basis, int64_t n, const double* a_d, const 
 int dftk_mi_fermi_bisection(int n_k, const int* n_bands, const double* eig, const double* kweights, int smearing,
                             double temperature, double filled, double n_electrons, double lo, double hi, double* eF_out);
 /* dftk_mi_prof_enable(basis, 3) also books every zgemm call per SHAPE; this returns (and clears) that table: row i of
- * rows6 = { transA ('N' = 0, 'C' = 1), m, n, k, flags (UPPER | B_UPPER | DFTK_MI_GEMM_REAL), calls }, ms[i] = summed time; *count = shapes seen (<= cap
+ * rows6 = { transA ('N' = 0, 'C' = 1), m, n, k, flags (UPPER | B_UPPER | DFTK_MI_GEMM_REAL; the shape key holds no bit for
+ * DFTK_MI_GEMM_SYM_RESULT: such a call is listed with the dense call of the same m, n, k, while its time is booked to the
+ * structured family 11), calls }, ms[i] = summed time; *count = shapes seen (<= cap
  * rows are written).  bench.py replays the table at 1 / N of the rows for its sharded-step measurement. */
 int dftk_mi_prof_zgemm_shapes(dftk_mi_basis* basis, int cap, int64_t* rows6, double* ms, int* count);
 
@@ -822,6 +840,11 @@ int dftk_mi_diag_mfma_peak(dftk_mi_basis* basis, int waves_per_simd, int iters, 
  * one more FULL tile in the interior launch, shifted left to end at column n (it stores only the new columns),
  * instead of a right-strip launch. */
 int dftk_mi_zgemm_plan_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int* out12);
+/* Host-only, for the CPU test-suite (not part of the computing ABI; it may change with the launch plan).
+ * A DFTK_MI_GEMM_B_UPPER product ('N') whose plan has no K split runs TWO column tiles of a row panel per workgroup
+ * (tile gn - 1 - p, then tile p): the tiles of that launch in workgroup order, 4 ints each { tile row, tile column,
+ * first k, end k } (at most cap are written), *count = their number, 0 when the shape does not take that launch. */
+int dftk_mi_zgemm_fold_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int cap, int* items4, int* count);
 /* Schedule of the blocked Jacobi eigensolver for an n x n matrix: *n_blocks = number of 16-wide blocks (even,
  * padded); for round in [-1, *n_blocks - 2] (pass pairs = where = NULL to query n_blocks only):
  * pairs[2k], pairs[2k+1] = the k-th disjoint block pair of the round (round -1: (2k, 2k+1), then a round-robin
