@@ -45,5 +45,7 @@ from .response import (occupation_divided_difference, compute_alpha_mn, is_effec
                        apply_kernel, solve_OmegaPlusK_split, solve_OmegaPlusK, compute_chi0,
                        multiply_psi_by_potential)
 from .terms import dynmat_ewald  # noqa: F401,E402
+from .bands import (KPath, kpath_interpolate, compute_bands, default_n_bands_bandstructure,  # noqa: F401,E402
+                    atomic_orbital_projectors, atomic_orbital_projections, compute_pdos, sum_pdos)
 from .phonon import (compute_dynmat, compute_dynmat_term, compute_delta_H_psi_alpha_s, phonon_modes,  # noqa: F401,E402
                      dynmat_red_to_cart, mass_matrix)

@@ -40,6 +40,13 @@ class PspHgh:
             return sum(self.count_n_proj(ll) for ll in range(self.lmax + 1))
         return self.count_n_proj_radial(l) * (2 * l + 1)
 
+    def count_n_pswfc_radial(self, l):
+        """HGH tables carry no pseudo-atomic wavefunctions (NormConservingPsp.jl: ``count_n_pswfc_radial`` is 0)."""
+        return 0
+
+    def count_n_pswfc(self):
+        return 0
+
     def has_core_density(self):
         """PspHgh.jl:16: HGH pseudopotentials carry no non-linear core correction."""
         return False
@@ -190,6 +197,13 @@ def eval_psp_projector_fourier(psp, i: int, l: int, p: torch.Tensor) -> torch.Te
     if (l, i) not in table:
         raise NotImplementedError(f"HGH projector l={l}, i={i}")
     return table[(l, i)]()
+
+
+def eval_psp_pswfc_fourier(psp, i: int, l: int, p: torch.Tensor) -> torch.Tensor:
+    """PspUpf.jl:218-224: the Hankel transform of pseudo-atomic wavefunction i (1-based) of angular momentum l."""
+    if not isinstance(psp, PspUpf) or i > psp.count_n_pswfc_radial(l):
+        raise ValueError("the pseudopotential carries no such pseudo-atomic wavefunction")
+    return _on_host(lambda q: psp_upf.eval_psp_pswfc_fourier_upf(psp, i, l, q), p)
 
 
 def eval_psp_valence_density_fourier(psp, p: torch.Tensor) -> torch.Tensor:

@@ -126,6 +126,17 @@ class PspUpf:
             self.r2_projs[l].append(self.rgrid[:cut] * (beta[:cut] / 2))      # r beta / 2 (Ry -> Ha) * r
             order[l].append(ib)
         self.h = tuple(f["dij"][np.ix_(idx, idx)] * 2 if idx else np.zeros((0, 0)) for idx in order)
+        # pseudo-atomic wavefunctions (PspUpf.jl:140-154): per l, in the file's order, r chi -> r^2 chi
+        self.r2_pswfcs = [[] for _ in range(self.lmax + 1)]
+        self.pswfc_occs = [[] for _ in range(self.lmax + 1)]
+        self.pswfc_energies = [[] for _ in range(self.lmax + 1)]
+        self.pswfc_labels = [[] for _ in range(self.lmax + 1)]
+        for l, chi, label, occ, energy in f["pswfc"]:
+            if l <= self.lmax:                                      # (the reference's loop runs over l = 0..lmax)
+                self.r2_pswfcs[l].append(self.rgrid * chi)
+                self.pswfc_occs[l].append(occ)
+                self.pswfc_energies[l].append(energy)
+                self.pswfc_labels[l].append(label)
         self.r2_rhoion = f["rhoatom"] / (4 * math.pi)
         self.r2_rhocore = self.rgrid ** 2 * f["nlcc"]               # PP_NLCC is rho_core(r) itself (PspUpf.jl:147-151)
         self.identifier = "" if identifier is None else identifier
@@ -143,6 +154,24 @@ class PspUpf:
             return sum(self.count_n_proj(ll) for ll in range(self.lmax + 1))
         return self.count_n_proj_radial(l) * (2 * l + 1)
 
+    # -- pseudo-atomic wavefunctions (PspUpf.jl:210-212); i is 1-based in the label functions, as the reference's
+    def count_n_pswfc_radial(self, l):
+        return len(self.r2_pswfcs[l]) if 0 <= l <= self.lmax else 0
+
+    def count_n_pswfc(self):
+        return sum((2 * l + 1) * len(w) for l, w in enumerate(self.r2_pswfcs))
+
+    def pswfc_label(self, i, l):
+        return self.pswfc_labels[l][i - 1]
+
+    def find_pswfc(self, label):
+        """``(l, i)`` (i 1-based) of the orbital called ``label``."""
+        for l, labels in enumerate(self.pswfc_labels):
+            for i, name in enumerate(labels):
+                if name == label:
+                    return l, i + 1
+        raise ValueError(f"could not find pseudo-atomic orbital with label {label!r}")
+
     def has_core_density(self):
         return bool(np.any(self.r2_rhocore != 0))
 
@@ -159,6 +188,12 @@ class PspUpf:
         """``(r, wf)`` of projector i (0-based) of angular momentum l, cut as PspUpf.jl:190."""
         n = min(self.ircut, len(self.r2_projs[l][i]))
         return self.rgrid[:n], self.weights(n) * self.r2_projs[l][i][:n]
+
+    def pswfc_channel(self, l, i):
+        """``(r, wf)`` of pseudo-atomic wavefunction i (0-based) of angular momentum l on the WHOLE mesh: the reference does
+        not cut these at rcut (PspUpf.jl:218-224)."""
+        n = len(self.rgrid)
+        return self.rgrid, self.weights(n) * self.r2_pswfcs[l][i]
 
     def local_channel(self):
         """``(r, wf)`` with wf_i = w_i (r_i vloc_i + Zion erf(r_i)) (PspUpf.jl:237-240)."""
@@ -281,11 +316,32 @@ def _read_upf(text):
                                   "PP_NLCC block is not as long as the mesh")
     if len(nlcc) != len(r):
         nlcc = np.zeros(len(r))
+    # PP_PSWFC: the PP_CHI.n elements in index order, each with its l, label, occupation and (optional) pseudo_energy
+    pswfc = []
+    wfc = root.find("PP_PSWFC")
+    if wfc is not None:
+        found = []
+        for el in wfc:
+            mm = re.fullmatch(r"PP_CHI\.(\d+)", el.tag)
+            if mm:
+                found.append((int(el.attrib.get("index", mm.group(1))), el))
+        for _, el in sorted(found, key=lambda t: t[0]):
+            chi = _numbers(el)
+            if len(chi) < len(r):                # shorter than the mesh: zero beyond what the file gives
+                chi = np.concatenate([chi, np.zeros(len(r) - len(chi))])
+
+            def _float(name):
+                v = el.attrib.get(name)
+                return None if v is None or not v.strip() else float(re.sub(r"[dD]", "E", v))
+            occ = _float("occupation")
+            pswfc.append((int(el.attrib["l"]), chi[:len(r)], (el.attrib.get("label") or "").strip(),
+                          0.0 if occ is None else occ, _float("pseudo_energy")))
     rho = _numbers(root.find("PP_RHOATOM"))
     if len(rho) < len(r):                    # absent, or shorter than the mesh: zero beyond what the file gives
         rho = np.concatenate([rho, np.zeros(len(r) - len(rho))])
     return {"Zion": int(round(float(re.sub(r"[dD]", "E", a["z_valence"])))), "lmax": lmax, "r": r, "rab": rab,
-            "vloc": vloc, "betas": betas, "dij": dij, "rhoatom": rho[:len(r)], "nlcc": nlcc, "comment": a.get("comment", "") or ""}
+            "vloc": vloc, "betas": betas, "dij": dij, "rhoatom": rho[:len(r)], "nlcc": nlcc, "comment": a.get("comment", "") or "",
+            "pswfc": pswfc}
 
 
 # ------------------------------------------------------------------------------------------ host values
@@ -342,6 +398,12 @@ def eval_psp_local_fourier_upf(psp, q):
 def eval_psp_projector_fourier_upf(psp, i, l, q):
     """i is 1-based, as for the HGH function."""
     r, wf = psp.projector_channel(l, i - 1)
+    return hankel_host(r, wf, l, q)
+
+
+def eval_psp_pswfc_fourier_upf(psp, i, l, q):
+    """PspUpf.jl:218-224: hankel(rgrid, r2_pswfc, l, q) on the whole mesh; i is 1-based."""
+    r, wf = psp.pswfc_channel(l, i - 1)
     return hankel_host(r, wf, l, q)
 
 

@@ -50,6 +50,7 @@ typedef struct dftk_mi_comm   dftk_mi_comm;    /* comm_kpts (RCCL communicator) 
 #define DFTK_MI_NUM_NORMALIZATION   3   /* "LOBPCG is badly failing to keep the vectors normalized"*/
 #define DFTK_MI_NUM_EIGEN           4   /* dense Hermitian eigensolver did not converge          */
 #define DFTK_MI_NUM_TOO_SMALL       5   /* N > 3M violated (lobpcg_hyper_impl.jl:363)            */
+#define DFTK_MI_NUM_RANK_DEFICIENT  6   /* linearly dependent columns (ortho.jl:14 @assert)      */
 
 const char* dftk_mi_last_error(void);
 /* Library / build identification: "dftk_mi355x <version> gfx950 ..." */
@@ -667,6 +668,33 @@ int dftk_mi_potrf_trtri(dftk_mi_basis* basis, int n, dftk_mi_cplx* A_d, int64_t 
  * triangle is exactly zero (the Gram matrices of the real-symmetric Gamma iteration); they are not read. */
 int dftk_mi_potrf_trtri_real(dftk_mi_basis* basis, int n, dftk_mi_cplx* A_d, int64_t lda,
                              dftk_mi_cplx* invR_d, int64_t ldi);
+
+/* ---- atomic-orbital projections and the projected density of states (src/postprocess/dos.jl:70-212; pdos_kernels.hip) ----
+ * ortho_lowdin (src/common/ortho.jl:11-17) of the n_rows x n_cols block Phi_d (leading dimension ld), in place:
+ * S = Phi' Phi by the library's zgemm, S = V diag(lambda) V' by the Hermitian eigensolver behind the heev entry,
+ * Phi <- Phi V diag(lambda^-1/2) V' panel by panel (extra workspace: one panel of rows and three n_cols^2 matrices).
+ * evals_h (optional, [n_cols]) receives lambda, ascending.  Linearly dependent columns -- min |lambda| <= 2^-52 max |lambda|,
+ * the reference's assertion -- return DFTK_MI_NUM_RANK_DEFICIENT with Phi_d untouched; the error text names the ratio.
+ * DFTK_MI_EINVAL: n_cols < 1, n_cols > n_rows, ld < n_rows, a call inside a batched multi-k call.  Fixed reduction order:
+ * two calls give bitwise identical results. */
+int dftk_mi_lowdin_ortho(dftk_mi_basis* basis, int64_t n_rows, int n_cols, dftk_mi_cplx* Phi_d, int64_t ld,
+                         double* evals_h);
+/* One k-block of atomic_orbital_projections / compute_pdos.  psi_d: n_rows x n_bands, Phi_d: n_rows x n_proj (orthonormal
+ * orbitals), both column-major in the caller's full-sphere complex layout (the orbitals of a Gamma-real block included).
+ * C = Phi' psi is one zgemm.
+ *   proj_d (optional, device, n_proj x n_bands column-major) is OVERWRITTEN with |C_pn|^2, the fat-band weights;
+ *   pdos_d (optional, device, n_eps x n_proj column-major) is ACCUMULATED:
+ *       pdos[e, p] += weight sum_n g(eps_h[e], eig_h[n]) |C_pn|^2,  g(e, x) = -occupation_derivative((x - e) / T) / T,
+ *       weight = filled_occupation * kweight; smearing_kind 1 = Fermi-Dirac, 2 = Gaussian (Smearing.jl:66-92), whose
+ *       Fermi-Dirac derivative is written so that |x - e| / T of several hundred gives exactly 0.
+ * The accumulation is a tiled real product (a workgroup per tile of energies x projectors, bands in ascending order,
+ * |C|^2 staged through LDS), no atomics: reproducible bit for bit.  DFTK_MI_EINVAL, nothing written: both outputs NULL, a
+ * leading dimension below n_rows, a size below 1 and, when pdos_d is given, temperature <= 0, an unknown smearing kind or
+ * n_eps < 1; a call inside a batched multi-k call. */
+int dftk_mi_pdos_accumulate(dftk_mi_basis* basis, int64_t n_rows, int n_bands, const dftk_mi_cplx* psi_d, int64_t ld_psi,
+                            int n_proj, const dftk_mi_cplx* Phi_d, int64_t ld_phi, const double* eig_h, double weight,
+                            int smearing_kind, double temperature, int n_eps, const double* eps_h, double* proj_d,
+                            double* pdos_d);
 
 /* ---- comm_kpts: replaces MPI.Init / mpi_sum!(rho, comm_kpts)
  *      (src/common/mpi.jl:19-32 at src/densities.jl:46) with RCCL over xGMI ---------------------
