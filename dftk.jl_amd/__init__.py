@@ -49,3 +49,5 @@ from .bands import (KPath, kpath_interpolate, compute_bands, default_n_bands_ban
                     atomic_orbital_projectors, atomic_orbital_projections, compute_pdos, sum_pdos)
 from .phonon import (compute_dynmat, compute_dynmat_term, compute_delta_H_psi_alpha_s, phonon_modes,  # noqa: F401,E402
                      dynmat_red_to_cart, mass_matrix)
+from .hubbard import (OrbitalManifold, Hubbard, resolve_hubbard_manifold, wigner_d_matrix,  # noqa: F401,E402
+                      symmetrize_hubbard_n, compute_hubbard_n)

@@ -176,6 +176,10 @@ _SIGNATURES = {
     "dftk_mi_lowdin_ortho": (C.c_int, [C.c_void_p, _i64, C.c_int, C.c_void_p, _i64, C.c_void_p]),
     "dftk_mi_pdos_accumulate": (C.c_int, [C.c_void_p, _i64, C.c_int, C.c_void_p, _i64, C.c_int, C.c_void_p, _i64, C.c_void_p,
                                           C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dftk_mi_hubbard_occupation": (C.c_int, [C.c_void_p, _i64, C.c_int, C.c_void_p, _i64, C.c_int, C.c_void_p, _i64, C.c_void_p,
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dftk_mi_hubbard_rotate": (C.c_int, [C.c_void_p, _i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _i64, C.c_void_p,
+                                         C.c_void_p, _i64]),
     "dftk_mi_comm_get_unique_id": (C.c_int, [C.c_char_p]),
     "dftk_mi_comm_init_rank": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dftk_mi_comm_create_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -278,6 +278,11 @@ class PlaneWaveBasis:
             self.lane_handles.append(h)
         self.n_lanes = n_lanes
         self._pool = None
+        # DFT+U: a Gamma-real block takes REAL occupation matrices (hubbard.hubbard_energy_ops).  Those of a mesh with further
+        # k-points are real only to the accuracy of its diagonalisations (if the mesh is closed under k -> -k at all), so the
+        # automatic choice is off there; gamma_real=True is still taken as asked for
+        if getattr(model, "hubbard", None) is not None and self.gamma_real is None and len(self.kcoords_global) > 1:
+            self.gamma_real = False
         self.kpoints = [Kpoint(self, k, lane=i % n_lanes) for i, k in enumerate(kc)]
         self.n_kcoords_local = len(kc)
         if model.n_spin_components == 2:

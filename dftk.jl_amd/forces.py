@@ -148,6 +148,8 @@ def compute_forces_term(name, basis, psi, occupation, rho=None):
     """``compute_forces(term, basis, psi, occupation; rho)`` for the term named ``name``: an (n_atoms, 3) array of
     reduced-coordinate forces, or None for terms without explicit position dependence."""
     model = basis.model
+    from .hubbard import refuse as refuse_hubbard
+    refuse_hubbard(model, "forces (the Hubbard term has no force yet: the sum of the other terms would be wrong)")
     if name not in model.term_types:
         raise ValueError(f"term {name} is not part of the model")
     if name in _NO_FORCES:

@@ -21,18 +21,24 @@ class DftHamiltonianBlock:
         # the exchange term of this block (exchange.ExchangeOperator; models with ExactExchange only): like the potential,
         # the device handle holds one at a time -- in its projector slot -- and bind() puts this block's back
         self.exchange = None
+        # the Hubbard term of this block (hubbard.HubbardOperator; models with a Hubbard term and occupation matrices only):
+        # rotated orbitals behind P in the same projector slot
+        self.hubbard = None
         if bind:
             self.bind(force=True)
 
     @staticmethod
-    def for_all_kpoints(basis, potential, exchange=None):
+    def for_all_kpoints(basis, potential, exchange=None, hubbard=None):
         """The blocks of every local k-point for ONE summed potential (Hamiltonian.jl:36-57), bound with a single library
         call (``dftk_mi_kblocks_set_potential``) instead of one host round trip per k-point.  ``exchange`` (models with
         ExactExchange): {k-block index: ExchangeOperator}, attached BEFORE the blocks are bound, so that the projector slot is
-        set once per Hamiltonian."""
+        set once per Hamiltonian.  ``hubbard`` (models with a Hubbard term): {k-block index: HubbardOperator}, likewise."""
         import ctypes as C
 
         def attach(blocks):
+            if hubbard is not None:
+                for ik, b_ in enumerate(blocks):
+                    b_.hubbard = hubbard.get(ik)
             if exchange is not None:
                 for ik, b_ in enumerate(blocks):
                     b_.exchange = exchange.get(ik)
@@ -81,6 +87,11 @@ class DftHamiltonianBlock:
             xi = self.exchange.xi if self.exchange is not None else None
             bind_projectors(self.basis, self.basis.kpoints.index(kpt), xi)
             kpt._exx_owner = self
+        # (a model without Hubbard term never leaves the first test: its blocks carry None and the slot holds None)
+        if getattr(kpt, "_hubbard_bound", None) is not self.hubbard:
+            from .hubbard import bind_projector_rows
+            bind_projector_rows(self.basis, self.basis.kpoints.index(kpt), self.hubbard)
+            kpt._hubbard_bound = self.hubbard
 
     def _has_exchange_term(self):
         return getattr(self.basis.terms, "exx_kernel", None) is not None

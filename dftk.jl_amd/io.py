@@ -56,7 +56,20 @@ def model_to_dict(model) -> dict:
         "terms": list(model.term_types), "functionals": list(model.functionals),
         "use_nlcc": bool(getattr(model, "use_nlcc", True)),
         **_hybrid_to_dict(model),
+        **_hubbard_to_dict(model),
     }
+
+
+def _hubbard_to_dict(model) -> dict:
+    """What the term name "Hubbard" does not say: the manifolds (atoms as a symbol or 0-based indices, the orbital as a
+    label or (l, i)) and their U in Hartree, so that saved occupation matrices name the U they belong to."""
+    hub = getattr(model, "hubbard", None)
+    if hub is None:
+        return {}
+    return {"hubbard": {"manifolds": [{"atoms": m.atoms if isinstance(m.atoms, str) else list(m.atoms),
+                                       "projectors": m.projectors if isinstance(m.projectors, str)
+                                       else {"l": m.projectors[0], "i": m.projectors[1]}} for m in hub.manifolds],
+                        "U": list(hub.U)}}
 
 
 def _hybrid_to_dict(model) -> dict:
@@ -131,6 +144,8 @@ def scfres_to_dict(scfres: dict, save_psi: bool = False, save_rho: bool = True) 
         rho_ = scfres["rho"]
         d["ρ"] = _tolist(rho_) if rho_.dim() == 4 else [_tolist(rho_)]       # [spin][iz][iy][ix]
         d["τ"] = None
+    if scfres.get("hubbard_n") is not None:
+        d["hubbard_n"] = hubbard_n_to_lists(scfres["hubbard_n"])
     d["energies"] = {k: float(v) for k, v in scfres["energies"].items()}
     d["energies"]["total"] = float(scfres["energies"].total)
     extra = {"converged": bool(scfres["converged"]), "norm_Δρ": float(scfres["history_drho"][-1]),
@@ -148,6 +163,21 @@ def scfres_to_dict(scfres: dict, save_psi: bool = False, save_rho: bool = True) 
         d["kpt_n_G_vectors"] = _by_spin(basis, n_G)
         d["kpt_max_n_G"] = int(basis.comm_kpts.max_scalar(max(n_G)))
     return d
+
+
+def hubbard_n_to_lists(hubbard_n):
+    """The occupation matrices of a Hubbard term (one array per manifold, input_output.jl:355-365) as nested lists
+    ``[manifold][spin][atom][atom][m1][m2] = [re, im]``."""
+    return [np.stack([np.asarray(n).real, np.asarray(n).imag], axis=-1).tolist() for n in hubbard_n]
+
+
+def hubbard_n_from_lists(lists):
+    """The arrays ``hubbard_n_to_lists`` wrote."""
+    out = []
+    for n in lists:
+        a = np.asarray(n, dtype=float)
+        out.append(a[..., 0] + 1j * a[..., 1])
+    return out
 
 
 def save_scfres(filename: str, scfres: dict, save_psi=None, save_rho=None, extra_data=None):
@@ -190,9 +220,14 @@ def load_scfres(filename: str, basis=None) -> dict:
     ext = os.path.splitext(filename)[1].lower()
     if ext == ".json":
         with open(filename) as fh:
-            return json.load(fh)
+            out = json.load(fh)
+        if out.get("hubbard_n") is not None:
+            out["hubbard_n"] = hubbard_n_from_lists(out["hubbard_n"])
+        return out
     data = np.load(filename, allow_pickle=False)
     out = json.loads(str(data["meta_json"]))
+    if out.get("hubbard_n") is not None:
+        out["hubbard_n"] = hubbard_n_from_lists(out["hubbard_n"])
     if basis is not None:
         if list(basis.fft_size) != out["fft_size"] or abs(basis.Ecut - out["Ecut"]) > 1e-12 \
                 or len(basis.kcoords_global) != out["n_kpoints"]:

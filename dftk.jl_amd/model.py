@@ -13,6 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .exchange import Coulomb
+from .hubbard import Hubbard
 from .psp import AMU_IN_ELECTRON_MASSES, ATOMIC_NUMBER, ATOMIC_WEIGHT, PspHgh, load_psp
 
 
@@ -80,7 +81,16 @@ class Model:
         if len(exx) > 1:
             raise ValueError("Model with more than one ExactExchange term not supported.")
         self.exact_exchange = (ExactExchange() if exx[0] == "ExactExchange" else exx[0]) if exx else None
-        self.term_types = tuple("ExactExchange" if isinstance(t, ExactExchange) else t for t in terms)
+        # likewise the Hubbard term (hubbard.py): the object carries the manifolds and their U
+        hub = [t for t in terms if isinstance(t, Hubbard) or (isinstance(t, str) and t == "Hubbard")]
+        if len(hub) > 1:
+            raise ValueError("Model with more than one Hubbard term not supported.")
+        self.hubbard = (Hubbard() if isinstance(hub[0], str) else hub[0]) if hub else None
+        if self.hubbard is not None and self.exact_exchange is not None:
+            raise NotImplementedError("a Hubbard term together with ExactExchange is not implemented (both use the "
+                                      "k-block's projector slot)")
+        self.term_types = tuple("ExactExchange" if isinstance(t, ExactExchange) else "Hubbard" if isinstance(t, Hubbard)
+                                else t for t in terms)
         if not self.term_types:
             raise ValueError("Model without terms not supported.")
         self.functionals = tuple(functionals)
@@ -160,9 +170,11 @@ def model_DFT(lattice, atoms, positions, functionals=("lda_x", "lda_c_pw"), **kw
     if isinstance(functionals, PBE0):
         a = 0.25 if functionals.exx_fraction is None else float(functionals.exx_fraction)
         kernel = Coulomb() if functionals.exx_kernel is None else functionals.exx_kernel
-        return model_atomic(lattice, atoms, positions, extra_terms=("Hartree", "Xc", ExactExchange(a, kernel)),
+        extra = tuple(kw.pop("extra_terms", ()))
+        return model_atomic(lattice, atoms, positions, extra_terms=("Hartree", "Xc", ExactExchange(a, kernel)) + extra,
                             functionals=("gga_x_pbe", "gga_c_pbe"), functional_scales=(1.0 - a, 1.0), **kw)
-    return model_atomic(lattice, atoms, positions, extra_terms=("Hartree", "Xc"),
+    extra = tuple(kw.pop("extra_terms", ()))              # (e.g. a Hubbard(...) term, as the reference's extra_terms)
+    return model_atomic(lattice, atoms, positions, extra_terms=("Hartree", "Xc") + extra,
                         functionals=tuple(functionals), **kw)
 
 

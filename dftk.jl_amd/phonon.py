@@ -34,6 +34,8 @@ def _check_supported(basis, q=None):
     from .exchange import refuse
     model = basis.model
     refuse(model, "the dynamical matrix (no response with the Fock operator)")
+    from .hubbard import refuse as refuse_hubbard
+    refuse_hubbard(model, "the dynamical matrix")
     from .psp_upf import refuse_upf
     refuse_upf(model, "the dynamical matrix and the displacement perturbation")
     if q is not None and np.any(np.asarray(q, dtype=float) != 0):

@@ -175,6 +175,8 @@ def determine_band_tolerances(alg, density_tol):
 def _check_supported(basis, q=None):
     from .exchange import refuse
     refuse(basis.model, "the density response (no exchange kernel term, no Sternheimer solve with the Fock operator)")
+    from .hubbard import refuse as refuse_hubbard
+    refuse_hubbard(basis.model, "the density response (no Hubbard kernel term)")
     if q is not None and np.any(np.asarray(q, dtype=float) != 0):
         raise NotImplementedError("response at q != 0 (phonons) is not implemented: q = 0 only")
     if basis.model.n_spin_components != 1:

@@ -390,9 +390,14 @@ class ScfStepper:
 
     def __init__(self, basis, rho=None, psi=None, tol=1e-6, damping=0.8, nbandsalg=None, is_converged=None,
                  eigensolver=lobpcg_hyper, anderson_m=None, seed=0, determine_tol=determine_diagtol, mixing=None,
-                 phase_timers=None, coarse_start=True, exxalg=None):
+                 phase_timers=None, coarse_start=True, exxalg=None, hubbard_n=None):
         basis._require_gpu()
         self.basis = basis
+        # DFT+U: the occupation matrices are recomputed from every step's output orbitals, not mixed, and build the next
+        # step's Hamiltonian (self_consistent_field.jl:218-224); a cold start's first step carries no Hubbard operator
+        self.has_hubbard = getattr(basis.model, "hubbard", None) is not None
+        if hubbard_n is not None and not self.has_hubbard:
+            raise ValueError("hubbard_n given, but the model has no Hubbard term")
         # exact exchange: the Hamiltonian of a step is built from the previous step's orbitals (self_consistent_field.jl:207)
         self.has_exx = getattr(basis.model, "exact_exchange", None) is not None
         self.exxalg = exxalg
@@ -403,8 +408,9 @@ class ScfStepper:
         self.mixing = mixing if mixing is not None else LdosMixing()
         # per-step nonlocal energy from the Ritz values (terms.energy_hamiltonian); the energies returned by
         # finalize() / self_consistent_field always come from the projections themselves
-        # (off with exact exchange: the Ritz values contain the exchange operator)
-        self.ritz_energies = os.environ.get("DFTK_MI_EXACT_STEP_ENERGIES") is None and not self.has_exx
+        # (off with exact exchange: the Ritz values contain the exchange operator; off with a Hubbard term likewise)
+        self.ritz_energies = (os.environ.get("DFTK_MI_EXACT_STEP_ENERGIES") is None and not self.has_exx
+                              and not self.has_hubbard)
         self.gen = torch.Generator(device=basis.device)
         self.gen.manual_seed(seed + 7919 * basis.comm_kpts.rank)
         self.seed = seed
@@ -425,6 +431,8 @@ class ScfStepper:
         self.sqrt_dvol = math.sqrt(basis.dvol)
         self.info = dict(psi=psi, occupation=None, eigenvalues=None, eF=None, n_iter=0, n_matvec=0, converged=False,
                          history_Etot=[], history_drho=[], rho=self.rho_in, timings=[])
+        if self.has_hubbard:                  # (the key exists for models with the term only)
+            self.info["hubbard_n"] = hubbard_n
 
     def step(self):
         # the whole step runs with the library's stream as torch's current stream: torch kernels and library kernels are
@@ -451,8 +459,9 @@ class ScfStepper:
         # only the Hamiltonian of rho_in is needed here; the psi-dependent energy terms of this call
         # would be thrown away (the energies reported for the step are those of (psi_out, rho_out) below)
         exx = (dict(exxalg=self.exxalg, occupation_threshold=self.nbandsalg.occupation_threshold) if self.has_exx else {})
+        hub = dict(hubbard_n=info["hubbard_n"]) if self.has_hubbard else {}
         _, ham = energy_hamiltonian(basis, info["psi"] if self.has_exx else None, info["occupation"] if self.has_exx else None,
-                                    rho=self.rho_in, only_hamiltonian=True, **exx)
+                                    rho=self.rho_in, only_hamiltonian=True, **exx, **hub)
         t = lap("energy_hamiltonian", t)
         diagtol = self.determine_tol(info["n_iter"], info["history_drho"])
         nxt = next_density(ham, self.nbandsalg, self.eigensolver, psi=info["psi"], eigenvalues=info["eigenvalues"],
@@ -463,10 +472,15 @@ class ScfStepper:
         # int V_in rho_out (Ritz-value form of the nonlocal energy) and ||rho_out - rho_in||^2 in one library call / one fetch
         ritz_pot = self._ritz_potential(ham) if self.ritz_energies else None
         sums = self._step_sums(nxt["rho"], ritz_pot, self.rho_in)
+        if self.has_hubbard:
+            from .hubbard import compute_hubbard_n
+            nxt["hubbard_n"] = compute_hubbard_n(basis, nxt["psi"], nxt["occupation"])
+            hub = dict(hubbard_n=nxt["hubbard_n"])
         energies, _ = energy_hamiltonian(basis, nxt["psi"], nxt["occupation"], rho=nxt["rho"], only_energies=True,
                                          eigenvalues=nxt["eigenvalues"], eF=nxt["eF"], ritz_potential=ritz_pot,
                                          ritz_occupation_threshold=self.nbandsalg.occupation_threshold,
-                                         ritz_potential_dot=None if sums is None or ritz_pot is None else sums[0], **exx)
+                                         ritz_potential_dot=None if sums is None or ritz_pot is None else sums[0], **exx,
+                                         **hub)
         t = lap("energies", t)
         drho = nxt["rho"] - self.rho_in
         n_matvec_total = info["n_matvec"] + nxt["n_matvec"]
@@ -527,8 +541,9 @@ class ScfStepper:
         with self.basis.on_library_stream():
             exx = (dict(exxalg=self.exxalg, occupation_threshold=self.nbandsalg.occupation_threshold) if self.has_exx
                    else {})
+            hub = dict(hubbard_n=info["hubbard_n"]) if self.has_hubbard else {}
             energies, ham = energy_hamiltonian(self.basis, info["psi"], info["occupation"], rho=info["rho"],
-                                               eigenvalues=info["eigenvalues"], eF=info["eF"], **exx)
+                                               eigenvalues=info["eigenvalues"], eF=info["eF"], **exx, **hub)
             self.basis.sync()
         info.update(energies=energies, ham=ham)
         return info
@@ -536,15 +551,18 @@ class ScfStepper:
 
 def self_consistent_field(basis, rho=None, psi=None, tol=1e-6, maxiter=100, damping=0.8, nbandsalg=None,
                           is_converged=None, callback=None, eigensolver=lobpcg_hyper, anderson_m=None, seed=0,
-                          determine_tol=determine_diagtol, mixing=None, coarse_start=True, exxalg=None):
+                          determine_tol=determine_diagtol, mixing=None, coarse_start=True, exxalg=None, hubbard_n=None):
     """``self_consistent_field(basis; rho, psi, tol, maxiter, damping, nbandsalg, is_converged, callback,
     eigensolver, exxalg)`` (self_consistent_field.jl:164-289).  ``exxalg``: ``AceExx()`` unless given (models with exact
     exchange; the final Hamiltonian carries the compressed operator of all computed bands).  ``anderson_m``:
-    10 unless given, 0 (plain damping) for models with exact exchange."""
+    10 unless given, 0 (plain damping) for models with exact exchange.  ``hubbard_n`` (models with a Hubbard term): the
+    occupation matrices of the first step's Hamiltonian (a restart); the result of such a model, and every step's ``info``,
+    carries the last ones under the key ``hubbard_n`` (models without the term have no such key)."""
     t0 = time.time()
     stepper = ScfStepper(basis, rho=rho, psi=psi, tol=tol, damping=damping, nbandsalg=nbandsalg,
                          is_converged=is_converged, eigensolver=eigensolver, anderson_m=anderson_m, seed=seed,
-                         determine_tol=determine_tol, mixing=mixing, coarse_start=coarse_start, exxalg=exxalg)
+                         determine_tol=determine_tol, mixing=mixing, coarse_start=coarse_start, exxalg=exxalg,
+                         hubbard_n=hubbard_n)
     for _ in range(maxiter):
         info = stepper.step()
         if callback is not None:

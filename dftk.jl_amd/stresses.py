@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .forces import _check_nlcc
+from .hubbard import refuse as refuse_hubbard
 from .psp_upf import refuse_upf
 from .symmetry import symmetrize_stresses
 from .terms import (_DENSITY_THRESHOLD, _GGA_BITS, _LDA_BITS, _SPIN_LDA, local_species_tables, occupied_block,
@@ -209,6 +210,7 @@ def compute_stresses_term(name, basis, psi, occupation, rho=None):
     ``occupation`` (the definition recomputes it from the orbitals)."""
     if name not in basis.model.term_types:
         raise ValueError(f"term {name} is not part of the model")
+    refuse_hubbard(basis.model, "the stress tensor")
     refuse_upf(basis.model, "the stress tensor")
     if name == "Entropy":
         return None
@@ -226,6 +228,7 @@ def compute_stresses_cart(basis_or_scfres, psi=None, occupation=None, rho=None):
         basis, psi, occupation, rho = res["basis"], res["psi"], res["occupation"], res["rho"]
     else:
         basis = basis_or_scfres
+    refuse_hubbard(basis.model, "the stress tensor")
     refuse_upf(basis.model, "the stress tensor")
     _check_unsharded(basis)
     names = [n for n in basis.model.term_types if n != "Entropy"]

@@ -1077,7 +1077,7 @@ def smearing_entropy(kind, x):
 
 def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, eigenvalues=None, eF=None,
                        ritz_potential=None, ritz_occupation_threshold=0.0, only_hamiltonian=False, ritz_potential_dot=None,
-                       exxalg=None, occupation_threshold=0.0):
+                       exxalg=None, occupation_threshold=0.0, hubbard_n=None):
     """``energy_hamiltonian(basis, psi, occupation; rho, eigenvalues, eF)`` (Hamiltonian.jl:200-227); with
     ``only_energies`` it is ``energy(...)`` (:232-236).  Returns (Energies, [DftHamiltonianBlock]).  The entropy
     term -TS (terms/entropy.jl:11-42) needs this rank's eigenvalues and the Fermi level, else it is Inf.
@@ -1085,7 +1085,9 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
     returns no energies and does not synchronise; Hartree / Xc / AtomicLocal are NaN in the returned Energies.
     ``exxalg`` (``AceExx()`` unless given; ``VanillaExx()``) and ``occupation_threshold``: how the exchange operator of a
     model with ExactExchange is built from ``psi`` (exact_exchange.jl:36-58); without orbitals the term contributes E = 0 and
-    no operator, like the reference's NoopOperator."""
+    no operator, like the reference's NoopOperator.  ``hubbard_n`` (models with a Hubbard term; one array per manifold as
+    ``compute_hubbard_n`` returns them): the occupation matrices the Hubbard energy and operator are built from
+    (hubbard.jl:149-184); without them, or with an empty term, E = 0 and there is no operator."""
     basis._require_gpu()
     T = basis.terms
     E = Energies()
@@ -1094,6 +1096,7 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
     reduce_kpts = []       # terms that are sums over this rank's k-points: ONE fused reduction at the end
     ritz_fix = None
     exx_ops = {}            # per k-block: the exchange operator built from psi (absent: the term has no operator)
+    hub_ops = None          # per k-block: the Hubbard operator built from hubbard_n (None: the term has no operator)
     kin_bands = []          # per k-point: kinetic energy of every band (library reduction), or None
     # local-potential pipeline behind the C ABI (LDA and PBE); DFTK_MI_TORCH_LOCAL=1 keeps the torch formulation
     # (the parity twin of tests/test_gpu_scf.py)
@@ -1215,6 +1218,11 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
                         e += e_k
                         exx_ops[ik] = op
             E[name] = e
+        elif name == "Hubbard":
+            E[name] = 0.0
+            if hubbard_n is not None and basis.model.hubbard.U:
+                from .hubbard import hubbard_energy_ops
+                E[name], hub_ops = hubbard_energy_ops(basis, hubbard_n, want_ops=not only_energies)
         elif name == "Ewald":
             E[name] = T.E_ewald
         elif name == "PspCorrection":
@@ -1256,5 +1264,6 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
         E["AtomicNonlocal"] = E["AtomicNonlocal"] - (0.0 if ritz_fix[1] else E["Kinetic"]) - ritz_fix[0]
     if only_energies:
         return E, None
-    ham = DftHamiltonianBlock.for_all_kpoints(basis, pot, exchange=exx_ops if T.exx_kernel is not None else None)
+    ham = DftHamiltonianBlock.for_all_kpoints(basis, pot, exchange=exx_ops if T.exx_kernel is not None else None,
+                                              hubbard=hub_ops)
     return E, ham

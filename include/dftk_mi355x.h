@@ -696,6 +696,33 @@ int dftk_mi_pdos_accumulate(dftk_mi_basis* basis, int64_t n_rows, int n_bands, c
                             int smearing_kind, double temperature, int n_eps, const double* eps_h, double* proj_d,
                             double* pdos_d);
 
+/* ---- DFT+U: the Hubbard occupation matrix and the rotation of a manifold's orbitals (src/terms/hubbard.jl:149-228;
+ *      hubbard_kernels.hip) ----
+ * One k-block of compute_hubbard_n.  psi_d: n_rows x n_bands, Phi_d: n_rows x n_proj (orthonormal orbitals), both
+ * column-major in the caller's full-sphere complex layout, as for dftk_mi_pdos_accumulate.  C = Phi' psi is one zgemm into
+ * basis scratch.  Block b is the s = block_size_h[b] <= 7 consecutive columns of Phi_d that start at block_first_h[b] (the
+ * 2 l + 1 orbitals of one atom); blocks may come in any order and need not cover Phi_d.  n_d (device) holds the blocks one
+ * after the other, block b as a column-major s x s complex matrix, and is ACCUMULATED:
+ *     n_b[m1, m2] += sum_n w_h[n] C[p0 + m1, n] conj(C[p0 + m2, n]),      w_h[n] = kweight occupation_n / filled_occupation
+ * (i_projection * diagm(occupation / filled_occ) * j_projection of hubbard.jl:217-222), so that one buffer per spin channel
+ * collects every k-block and is fetched once.  One workgroup per block, the bands strided over its threads, a fixed-order
+ * tree through LDS, no atomics: reproducible bit for bit.  DFTK_MI_EINVAL, nothing written: a size below 1, a block that
+ * is not inside [0, n_proj), a block of more than 7 orbitals, a leading dimension below n_rows, a call inside a batched
+ * multi-k call. */
+int dftk_mi_hubbard_occupation(dftk_mi_basis* basis, int64_t n_rows, int n_bands, const dftk_mi_cplx* psi_d, int64_t ld_psi,
+                               int n_proj, const dftk_mi_cplx* Phi_d, int64_t ld_phi, const double* w_h, int n_blocks,
+                               const int* block_first_h, const int* block_size_h, dftk_mi_cplx* n_d);
+/* Out[:, block b] = Phi[:, block b] V_b for every block in one launch: V_h (host) holds the column-major s x s complex
+ * matrices one after the other, Out_d is laid out like Phi_d (leading dimension ld_out) and may not overlap it; the blocks
+ * must be disjoint; columns of Out_d outside every block are left untouched.  With n_b = V nu V' the rotated orbitals carry
+ * the Hubbard operator with REAL DIAGONAL couplings, Phi_b (U / 2)(1 - 2 n_b) Phi_b' = (Phi_b V) diag(U / 2 (1 - 2 nu))
+ * (Phi_b V)', which is what dftk_mi_kblock_set_projectors takes.  DFTK_MI_EINVAL, nothing written: a size below 1, a block
+ * that starts below 0 or holds more than 7 orbitals, two blocks that share a column, a leading dimension below n_rows,
+ * overlapping Out_d and Phi_d, a call inside a batched multi-k call. */
+int dftk_mi_hubbard_rotate(dftk_mi_basis* basis, int64_t n_rows, int n_blocks, const int* block_first_h,
+                           const int* block_size_h, const dftk_mi_cplx* Phi_d, int64_t ld_phi, const dftk_mi_cplx* V_h,
+                           dftk_mi_cplx* Out_d, int64_t ld_out);
+
 /* ---- comm_kpts: replaces MPI.Init / mpi_sum!(rho, comm_kpts)
  *      (src/common/mpi.jl:19-32 at src/densities.jl:46) with RCCL over xGMI ---------------------
  * Rank 0 calls get_unique_id and ships the 128 bytes to the other ranks by any side channel. */
