@@ -165,6 +165,13 @@ extern "C" int dftk_mi_launch_count(int64_t* launches, int64_t* host_syncs) {
     if (host_syncs) *host_syncs = g_dftk_host_syncs.load(std::memory_order_relaxed);
     return 0;
 }
+// DFTK_MI_LAND_IN_PLACE (read per call; default on): results of the Gamma-real / general LOBPCG driver and of the density pass
+// are written where they are needed instead of being copied or added there afterwards.  0 restores the launch sequence with
+// the copies; both sequences perform the same floating-point operations on the same operands.
+bool land_in_place() {
+    const char* e = getenv("DFTK_MI_LAND_IN_PLACE");
+    return !(e && atoi(e) == 0);
+}
 extern "C" int dftk_mi_prof_get(dftk_mi_basis* b, int family, double* total_ms, double* work, int64_t* launches) {
     if (!b || family < 0 || family >= PROF_NFAM) return DFTK_MI_EINVAL;
     CHK(prof_resolve(b));
@@ -1482,6 +1489,17 @@ extern "C" int dftk_mi_zgemm_ex(dftk_mi_basis* b, char transA, int64_t m, int64_
     cd al = {alpha.re, alpha.im}, be = {beta.re, beta.im};
     return zgemm(b, transA, m, n, k, al, reinterpret_cast<const cd*>(A_d), lda, reinterpret_cast<const cd*>(B_d), ldb,
                  be, reinterpret_cast<cd*>(C_d), ldc, flags);
+}
+
+extern "C" int dftk_mi_zgemm_to(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, dftk_mi_cplx alpha,
+                                const dftk_mi_cplx* A_d, int64_t lda, const dftk_mi_cplx* B_d, int64_t ldb,
+                                dftk_mi_cplx beta, const dftk_mi_cplx* C_d, int64_t ldc, dftk_mi_cplx* D_d, int flags) {
+    if (!b || m < 0 || n < 0 || k < 0 || !C_d || !D_d || (flags & ~(3 | DFTK_MI_GEMM_REAL | DFTK_MI_GEMM_SYM_RESULT)))
+        return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(b->device));
+    cd al = {alpha.re, alpha.im}, be = {beta.re, beta.im};
+    return zgemm_to(b, transA, m, n, k, al, reinterpret_cast<const cd*>(A_d), lda, reinterpret_cast<const cd*>(B_d), ldb,
+                    be, reinterpret_cast<const cd*>(C_d), ldc, reinterpret_cast<cd*>(D_d), flags);
 }
 
 extern "C" int dftk_mi_heev(dftk_mi_basis* b, int n, dftk_mi_cplx* A_d, int64_t lda, double* W_h, dftk_mi_cplx* V_d,

@@ -30,6 +30,7 @@ inline hipError_t dftk_counted_stream_sync(hipStream_t s) {
     } while (0)
 
 void dftk_set_error(const char* fmt, ...);
+bool land_in_place();   // api.cpp: the switch DFTK_MI_LAND_IN_PLACE (default on)
 // hipMalloc for library-owned scratch (behind DevBuf, devbuf.h); DFTK_MI_POISON=1 fills it with 0xFF bytes (NaN doubles) so
 // that any read of scratch that was not written in the current call shows up as a non-finite result (debugging aid)
 hipError_t dftk_scratch_malloc(void** p, size_t bytes);
@@ -322,10 +323,13 @@ int launch_fft_from_cube(dftk_mi_kblock* kb, const cd* cube, cd* c, int nb = 1);
 // marked there (the caller has begun the pass and sized the buffer; never inside a batched call)
 int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho,
                    const double* w_im_h = nullptr, const double* w2_h = nullptr, double* rho2 = nullptr,
-                   bool keep_planes = false);
+                   bool keep_planes = false, int pair_nb = 0);
+// (pair_nb > 0: psi holds pair_nb FULL-SPHERE columns of real-symmetric orbitals and transform i is column 2 i + i column
+//  2 i + 1, formed by stage A itself; nb = ceil(pair_nb / 2), w_h / w_im_h per transform as before.  Single block only.)
 int fft_group_size(const dftk_mi_basis* b);      // bands per launch group of the one-slot pipelines
 // stages A and B of bands [b0, b0 + nbb) of psi (column 0 = band b0) into slots b0 ... of `planes`
-int launch_planes_fill(dftk_mi_kblock* kb, int b0, int nbb, const cd* psi, int64_t ldpsi, cd* planes);
+// (pair_nb > 0: column 0 of psi is the first of the pair_nb columns that make up these nbb transforms, as in launch_density)
+int launch_planes_fill(dftk_mi_kblock* kb, int b0, int nbb, const cd* psi, int64_t ldpsi, cd* planes, int pair_nb = 0);
 // out = V_loc psi for nb bands whose y-planes sit in `planes` (slot = band): stages C (in place: the planes are consumed), D
 // and E without the kinetic term; T1 stays scratch
 int launch_local_apply_from_planes(dftk_mi_kblock* kb, int nb, cd* planes, cd* out, int64_t ldout);
@@ -347,6 +351,11 @@ int launch_kinetic_only(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi
 bool zgemm_sym_result_pays(int64_t m, int64_t n, int64_t k, bool real);   // (host: does the flag save a round of workgroups?)
 int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alpha, const cd* A,
           int64_t lda, const cd* B, int64_t ldb, cd beta, cd* C, int64_t ldc, int upper = 0);
+// D = alpha op(A) B + beta C with D != C allowed (D has C's shape and leading dimension; same flags, same arithmetic: `old`
+// is read from C, the store goes to D).  With UPPER / SYM_RESULT only the computed tiles of D are written.  Not recorded
+// in a batched call unless D == C.
+int zgemm_to(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alpha, const cd* A, int64_t lda, const cd* B,
+             int64_t ldb, cd beta, const cd* C, int64_t ldc, cd* D, int upper = 0);
 int ensure_ws(dftk_mi_basis* b, size_t bytes);
 // grow a buffer that work on the basis' stream may still use: if `need` exceeds what it holds, synchronise the stream, then
 // reserve (exactly `need` bytes unless `slack` adds some; the contents are not kept; a failure leaves the owner empty)
@@ -388,6 +397,9 @@ int ew_colreduce(dftk_mi_basis* b, int mode, int64_t n, int m, const cd* X, int6
 int ew_colnorms(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, double* out_d);
 int ew_coldots(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, const cd* Y, int64_t ldy,
                double* out_re_d);
+// out_xy = Re <X, Y> and out_xx = <X, X> per column from one read of X (bit for bit ew_coldots(X, Y) and ew_coldots(X, X))
+int ew_coldots2(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, const cd* Y, int64_t ldy, double* out_xy_d,
+                double* out_xx_d);
 // R = AX - X diag(lam), norms = column norms of R; optionally (kin / xx non-null) mean_kin = sum kin |X|^2 and
 // xx = sum |X|^2 per column in the same pass
 int ew_residual(dftk_mi_basis* b, int64_t n, int m, const cd* AX, int64_t lda, const cd* X, int64_t ldx,
@@ -495,19 +507,24 @@ int gamma_compress(dftk_mi_kblock* kb, int m, const cd* X, int64_t ldx, cd* H, i
 // ... after rotating every column by the global phase that maximises its real-symmetric part (LOBPCG entry)
 int gamma_compress_aligned(dftk_mi_kblock* kb, int m, const cd* X, int64_t ldx, cd* H, int64_t ldh);
 int gamma_expand(dftk_mi_kblock* kb, int m, const cd* H, int64_t ldh, cd* X, int64_t ldx);
-int gamma_apply_H(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t ldpsi, cd* Hpsi, int64_t ldH);
+// add (optional, un-sharded blocks with which == 1 only): Hpsi = add + H psi in the pass that writes Hpsi (add may be Hpsi)
+int gamma_apply_H(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t ldpsi, cd* Hpsi, int64_t ldH,
+                  const cd* add = nullptr, int64_t ldadd = 0);
 int gamma_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho);
 // local building blocks (whole bands on this rank)
 int gamma_ensure_buf(dftk_mi_kblock* kb, size_t elems);
 int gamma_pack_pairs(dftk_mi_kblock* kb, int nb, const cd* H, int64_t ldh, cd* Z, int64_t ldz);
-int gamma_unpack_pairs(dftk_mi_kblock* kb, int nb, const cd* W, int64_t ldw, cd* H, int64_t ldh);
+// (add, optional: H = add + unpack(W), one rounding per entry; add may be H itself)
+int gamma_unpack_pairs(dftk_mi_kblock* kb, int nb, const cd* W, int64_t ldw, cd* H, int64_t ldh, const cd* add = nullptr,
+                       int64_t ldadd = 0);
 int gamma_pack_full(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Z, int64_t ldz);
 int gamma_gather_P(dftk_mi_kblock* kb, int ncols, const cd* P, int64_t ldP, cd* Ph, int64_t ldh, double* asym_mag_h);
 int gamma_density_bands(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho);
 // y-planes kept by the density pass over the block the general LOBPCG driver returned (kb->ho): may this
 // block keep and use them now (DFTK_MI_PLANES_REUSE, Gamma-real format on, un-sharded, outside a batched call)?
 bool planes_eligible(const dftk_mi_kblock* kb);
-int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Hpsi, int64_t ldH);
+int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Hpsi, int64_t ldH,
+                                  const cd* add = nullptr, int64_t ldadd = 0);   // (add: as gamma_unpack_pairs)
 int64_t gamma_local_rows(const dftk_mi_kblock* kb);     // half-format rows held by this rank
 int64_t gamma_row0(const dftk_mi_kblock* kb);
 int gamma_projectors(dftk_mi_kblock* kb);               // half-format projectors of this rank (built on first use)

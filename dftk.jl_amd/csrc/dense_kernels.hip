@@ -28,6 +28,12 @@ __global__ __launch_bounds__(NT) void k_col_reduce(int mode, int64_t n, const cd
     ew_col_reduce<NT>(mode, n, X + (int64_t)c * ldx, Y ? Y + (int64_t)c * ldy : nullptr, w, out + c);
 }
 template <int NT>
+__global__ __launch_bounds__(NT) void k_col_dots2(int64_t n, const cd* __restrict__ X, int64_t ldx, const cd* __restrict__ Y,
+                                                  int64_t ldy, double* __restrict__ out_xy, double* __restrict__ out_xx) {
+    const int c = blockIdx.x;
+    ew_col_dots2<NT>(n, X + (int64_t)c * ldx, Y + (int64_t)c * ldy, out_xy + c, out_xx + c);
+}
+template <int NT>
 __global__ __launch_bounds__(NT) void k_residual(int64_t n, const cd* __restrict__ AX, int64_t lda,
                                                  const cd* __restrict__ X, int64_t ldx,
                                                  const double* __restrict__ lam, cd* __restrict__ R, int64_t ldr,
@@ -1597,6 +1603,18 @@ int ew_colnorms(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, do
 int ew_coldots(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, const cd* Y, int64_t ldy,
                double* out_re_d) {
     return ew_colreduce(b, 1, n, m, X, ldx, Y, ldy, nullptr, out_re_d);
+}
+int ew_coldots2(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, const cd* Y, int64_t ldy, double* out_xy_d,
+                double* out_xx_d) {
+    if (m <= 0) return 0;
+    if (batching()) {     // (a recorded call keeps the two reductions: the batch table has no entry for the pair)
+        CHK(ew_coldots(b, n, m, X, ldx, Y, ldy, out_xy_d));
+        return ew_coldots(b, n, m, X, ldx, X, ldx, out_xx_d);
+    }
+    ProfScope prof_scope(b, PROF_EW, n >= 4096 ? 32.0 * (double)n * m : 0.0);
+    EW_LAUNCH_COLS(k_col_dots2, n, m, b->stream, n, X, ldx, Y, ldy, out_xy_d, out_xx_d);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 int ew_coldots_im(dftk_mi_basis* b, int64_t n, int m, const cd* X, int64_t ldx, const cd* Y, int64_t ldy,
                   double* out_im_d) {

@@ -53,6 +53,36 @@ __device__ __forceinline__ void ew_col_reduce(int mode, int64_t n, const cd* __r
     if (threadIdx.x == 0) *out = (mode == 0) ? sqrt(r) : r;
 }
 
+// *out_xy = Re sum conj(x) y and *out_xx = sum |x|^2 from ONE read of x: per quantity the loop and the tree of
+// ew_col_reduce<NT> (modes 1 and 3), so both results are bit for bit those of two separate reductions
+template <int NT>
+__device__ __forceinline__ void ew_col_dots2(int64_t n, const cd* __restrict__ x, const cd* __restrict__ y,
+                                             double* __restrict__ out_xy, double* __restrict__ out_xx) {
+    __shared__ double sh[NT / 64];
+    double acc = 0.0, accx = 0.0;
+    for (int64_t i0 = threadIdx.x; i0 < n; i0 += (int64_t)NT * EW_UNR) {
+        cd a[EW_UNR], bb[EW_UNR];
+#pragma unroll
+        for (int u = 0; u < EW_UNR; ++u) {
+            const int64_t i = i0 + (int64_t)u * NT;
+            const bool in = i < n;
+            a[u] = in ? x[i] : make_double2(0.0, 0.0);
+            bb[u] = in ? y[i] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int u = 0; u < EW_UNR; ++u) {
+            acc += ew_dot2(a[u].x, bb[u].x, a[u].y, bb[u].y);
+            accx += ew_dot2(a[u].x, a[u].x, a[u].y, a[u].y);
+        }
+    }
+    const double s = block_sum<NT>(acc, sh);
+    const double sx = block_sum<NT>(accx, sh);
+    if (threadIdx.x == 0) {
+        *out_xy = s;
+        *out_xx = sx;
+    }
+}
+
 // r = ax - l x ; *norm = ||r|| ; in the same pass over x (optional, kin != null / xx != null):
 // *mk = sum kin |x|^2 (precondprep! of the TPA preconditioner) and *xx = sum |x|^2 (normalisation check)
 template <int NT>

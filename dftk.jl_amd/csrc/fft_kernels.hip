@@ -341,21 +341,24 @@ struct FftJob {
 };
 
 // ---------------------------------------------------------------------------------------- stage A
-template <bool GEN>
+// PAIR (single-block pipeline only; density of real-symmetric orbitals): transform `band` is a + i b of the two full-sphere
+// columns a = psi[:, 2 band], b = psi[:, 2 band + 1] (b = 0 past the last of the pair_nb columns), formed while scattering
+// with the arithmetic of k_gr_pack_full (gamma_kernels.hip), whose packed copy this replaces.
+template <bool GEN, bool PAIR = false>
 __global__ __launch_bounds__(FFT_THREADS) void k_xbwd_scatter(FftAxis ax, int nxp, int n_lines,
                                                               const int* __restrict__ line_start,
                                                               const int* __restrict__ cpos,
                                                               const cd* __restrict__ psi, int64_t ldpsi,
                                                               cd* __restrict__ T1, int64_t T1_stride,
-                                                              const FftJob* __restrict__ jobs) {
+                                                              const FftJob* __restrict__ jobs, int pair_nb) {
     constexpr int FFT_LS = FFT_LS_X;
     cd* buf = reinterpret_cast<cd*>(dftk_smem);
     cd* tw = buf + ax.n * FFT_LS;
     const int tid = threadIdx.x, l = tid & (FFT_L - 1), j = tid >> 3;
     const int band = blockIdx.y;
     const int l0 = blockIdx.x * FFT_L;
-    const cd* p = psi + (int64_t)band * ldpsi;
-    if (jobs) {
+    const cd* p = psi + (int64_t)(PAIR ? 2 * band : band) * ldpsi;
+    if (!PAIR && jobs) {
         const FftJob jb = jobs[band];
         n_lines = jb.n_lines;
         line_start = jb.line_start;
@@ -368,7 +371,17 @@ __global__ __launch_bounds__(FFT_THREADS) void k_xbwd_scatter(FftAxis ax, int nx
     const int line = l0 + l;
     if (line < n_lines) {
         const int c0 = line_start[line], c1 = line_start[line + 1];
-        for (int c = c0 + j; c < c1; c += FFT_TPL) buf[cpos[c] * FFT_LS + l] = p[c];
+        if (PAIR) {
+            const bool has_b = 2 * band + 1 < pair_nb;
+            const cd* pb = p + ldpsi;
+            for (int c = c0 + j; c < c1; c += FFT_TPL) {
+                const cd a = p[c];
+                const cd bb = has_b ? pb[c] : make_double2(0.0, 0.0);
+                buf[cpos[c] * FFT_LS + l] = make_double2(a.x - bb.y, a.y + bb.x);
+            }
+        } else {
+            for (int c = c0 + j; c < c1; c += FFT_TPL) buf[cpos[c] * FFT_LS + l] = p[c];
+        }
     }
     __syncthreads();
     fft_tile<FFT_LS, false, GEN>(buf, tw, ax, +1.0, l, j);
@@ -1277,11 +1290,23 @@ static double t1_bytes(const FftPipe& p) { return 16.0 * (double)p.s1; }
 static double t2_bytes(const FftPipe& p) { return 16.0 * (double)p.s2; }
 static int book(const FftPipe& p, int fam, double bytes) { return p.book ? prof_begin(p.b, fam, bytes) : -1; }
 
-static int stage_A(const FftPipe& p, const cd* psi, int64_t ldpsi) {
+// pair_nb > 0: psi holds pair_nb full-sphere columns of real-symmetric orbitals, two per transform (k_xbwd_scatter, PAIR)
+static int stage_A(const FftPipe& p, const cd* psi, int64_t ldpsi, int pair_nb = 0) {
     const dftk_mi_basis* b = p.b;
+    if (pair_nb > 0) {
+        if (p.jobs || (pair_nb + 1) / 2 != p.nb) {
+            dftk_set_error("stage A: a band pair per transform needs the single-block pipeline and nb = ceil(pair_nb / 2)");
+            return DFTK_MI_EINVAL;
+        }
+        const int ps = book(p, PROF_FFT_A, 16.0 * p.n_G * pair_nb + t1_bytes(p) * p.nb);
+        LAUNCH_FFT((k_xbwd_scatter<GEN, true>), b->ax[0], dim3((p.n_lines + FFT_L - 1) / FFT_L, p.nb), lds_bytes(b->nx, FFT_LS_X),
+                   p.stream, b->ax[0], b->nxp, p.tab.n_lines, p.tab.line_start, p.tab.cpos, psi, ldpsi, p.T1, p.s1, p.jobs, pair_nb);
+        prof_end(p.b, ps);
+        return 0;
+    }
     const int ps = book(p, PROF_FFT_A, (16.0 * p.n_G + t1_bytes(p)) * p.nb);
     LAUNCH_FFT((k_xbwd_scatter<GEN>), b->ax[0], dim3((p.n_lines + FFT_L - 1) / FFT_L, p.nb), lds_bytes(b->nx, FFT_LS_X),
-               p.stream, b->ax[0], b->nxp, p.tab.n_lines, p.tab.line_start, p.tab.cpos, psi, ldpsi, p.T1, p.s1, p.jobs);
+               p.stream, b->ax[0], b->nxp, p.tab.n_lines, p.tab.line_start, p.tab.cpos, psi, ldpsi, p.T1, p.s1, p.jobs, 0);
     prof_end(p.b, ps);
     return 0;
 }
@@ -1446,13 +1471,13 @@ int launch_local_apply(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi,
     });
 }
 
-int launch_planes_fill(dftk_mi_kblock* kb, int b0, int nbb, const cd* psi, int64_t ldpsi, cd* planes) {
+int launch_planes_fill(dftk_mi_kblock* kb, int b0, int nbb, const cd* psi, int64_t ldpsi, cd* planes, int pair_nb) {
     dftk_mi_basis* b = kb->basis;
     CHK(check_lds(b));
     CHK(fft_ensure_scratch(b, kb, nbb));
     const int64_t s2 = (int64_t)kb->nzx * b->ny * b->nxp;
     const FftPipe p = kblock_pipe(kb, nbb, 0, planes + (int64_t)b0 * s2);
-    CHK(stage_A(p, psi, ldpsi));
+    CHK(stage_A(p, psi, ldpsi, pair_nb));
     CHK(stage_B(p));
     HIPCHK(hipGetLastError());
     return 0;
@@ -1495,8 +1520,13 @@ static int check_density_nz(const dftk_mi_basis* b) {
 }
 
 int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* rho,
-                   const double* w_im_h, const double* w2_h, double* rho2, bool keep_planes) {
+                   const double* w_im_h, const double* w2_h, double* rho2, bool keep_planes, int pair_nb) {
     dftk_mi_basis* b = kb->basis;
+    if (pair_nb > 0 && (batching() || w2_h || (pair_nb + 1) / 2 != nb)) {
+        dftk_set_error("launch_density: a band pair per transform is a one-weight pass of nb = ceil(pair_nb / 2) transforms "
+                       "outside a batched call");
+        return DFTK_MI_EINVAL;
+    }
     if (!keep_planes) kb->ho.planes_off();     // planes kept by an earlier pass belong to another block or shape
     if (batching() && nb > 0) {   // part of a batched multi-k call: the bands of all k-blocks share one pipeline later
         // payload: [w | wim (flags & 1) | w2 (flags & 2)]; D = the second cube of a two-weight pass
@@ -1524,7 +1554,10 @@ int launch_density(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, con
     const int64_t s2 = (int64_t)kb->nzx * b->ny * b->nxp;
     return band_groups(kb, nb, 1, w_h, w_im_h, [&](int b0, int nbb, const double* w_d, const double* wim_d) -> int {
         const FftPipe p = kblock_pipe(kb, nbb, 0, keep_planes ? kb->ho.planes + (int64_t)b0 * s2 : nullptr);
-        CHK(stage_A(p, psi + (int64_t)b0 * ldpsi, ldpsi));
+        if (pair_nb > 0)    // (transform b0 + i is the pair of columns 2 (b0 + i), 2 (b0 + i) + 1 of psi)
+            CHK(stage_A(p, psi + (int64_t)(2 * b0) * ldpsi, ldpsi, std::min(2 * nbb, pair_nb - 2 * b0)));
+        else
+            CHK(stage_A(p, psi + (int64_t)b0 * ldpsi, ldpsi));
         CHK(stage_B(p));
         if (keep_planes) kb->ho.planes_mark(b0, nbb);
         return stage_density(p, w_d, wim_d, rho);

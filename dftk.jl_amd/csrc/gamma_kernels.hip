@@ -256,13 +256,20 @@ __global__ __launch_bounds__(256) void k_gr_pack(int64_t nh, int nb, const int* 
 }
 
 // inverse of k_gr_pack on the pipeline's output W: A = (W(G) + conj W(-G)) / 2, B = (W(G) - conj W(-G)) / (2i)
+// ADD: H = Add + (the unpacked pair), each entry rounded once after the products (no fused multiply-add: the sum is the one
+// of an element-wise addition of the finished block).  Add may be H itself -- a thread reads exactly the entries it writes,
+// and reads them first -- so neither pointer is declared restrict.
+template <bool ADD>
 __global__ __launch_bounds__(256) void k_gr_unpack(int64_t nh, int nb, const int* __restrict__ g, const int* __restrict__ mg,
-                                                   const cd* __restrict__ W, int64_t ldw, cd* __restrict__ H, int64_t ldh) {
+                                                   const cd* __restrict__ W, int64_t ldw, cd* H, int64_t ldh, const cd* Add,
+                                                   int64_t ldadd) {
+#pragma clang fp contract(off)   // the sum below must not fuse with the product before it (the only candidate in this body)
     const int64_t j0 = (int64_t)blockIdx.x * GR_ROWS + threadIdx.x;
     const int p = blockIdx.y;
     const cd* w = W + (int64_t)p * ldw;
+    const bool has_b = 2 * p + 1 < nb;
     int ig[GR_UNR], im[GR_UNR];
-    cd wg[GR_UNR], wm[GR_UNR];
+    cd wg[GR_UNR], wm[GR_UNR], da[GR_UNR], db[GR_UNR];
 #pragma unroll
     for (int u = 0; u < GR_UNR; ++u) {
         const int64_t j = j0 + u * 256;
@@ -273,14 +280,25 @@ __global__ __launch_bounds__(256) void k_gr_unpack(int64_t nh, int nb, const int
     for (int u = 0; u < GR_UNR; ++u) {
         wg[u] = w[ig[u]];
         wm[u] = w[im[u]];
+        if (ADD) {
+            const int64_t j = j0 + u * 256;
+            da[u] = j < nh ? Add[j + (int64_t)(2 * p) * ldadd] : make_double2(0.0, 0.0);
+            db[u] = (j < nh && has_b) ? Add[j + (int64_t)(2 * p + 1) * ldadd] : make_double2(0.0, 0.0);
+        }
     }
 #pragma unroll
     for (int u = 0; u < GR_UNR; ++u) {
         const int64_t j = j0 + u * 256;
         if (j >= nh) continue;
         const double s = j ? GR_ISQRT2 : 0.5;            // sqrt(2) / 2, row 0: 1 / 2 (wg == wm)
-        H[j + (int64_t)(2 * p) * ldh] = make_double2(s * (wg[u].x + wm[u].x), s * (wg[u].y - wm[u].y));
-        if (2 * p + 1 < nb) H[j + (int64_t)(2 * p + 1) * ldh] = make_double2(s * (wg[u].y + wm[u].y), s * (wm[u].x - wg[u].x));
+        cd a = make_double2(s * (wg[u].x + wm[u].x), s * (wg[u].y - wm[u].y));
+        cd c = make_double2(s * (wg[u].y + wm[u].y), s * (wm[u].x - wg[u].x));
+        if (ADD) {
+            a = make_double2(da[u].x + a.x, da[u].y + a.y);
+            c = make_double2(db[u].x + c.x, db[u].y + c.y);
+        }
+        H[j + (int64_t)(2 * p) * ldh] = a;
+        if (has_b) H[j + (int64_t)(2 * p + 1) * ldh] = c;
     }
 }
 
@@ -489,12 +507,16 @@ int gamma_pack_pairs(dftk_mi_kblock* kb, int nb, const cd* H, int64_t ldh, cd* Z
     HIPCHK(hipGetLastError());
     return 0;
 }
-int gamma_unpack_pairs(dftk_mi_kblock* kb, int nb, const cd* W, int64_t ldw, cd* H, int64_t ldh) {
+int gamma_unpack_pairs(dftk_mi_kblock* kb, int nb, const cd* W, int64_t ldw, cd* H, int64_t ldh, const cd* add, int64_t ldadd) {
     if (nb <= 0) return 0;
     GammaReal* gr = kb->gr.get();
-    ProfScope prof_scope(kb->basis, PROF_EW, 32.0 * (double)gr->n_half * nb);
-    hipLaunchKernelGGL(k_gr_unpack, gr_grid_unr(gr->n_half, (nb + 1) / 2), dim3(256), 0, kb->basis->stream, gr->n_half, nb,
-                       gr->d_g, gr->d_mg, W, ldw, H, ldh);
+    ProfScope prof_scope(kb->basis, PROF_EW, (add ? 48.0 : 32.0) * (double)gr->n_half * nb);
+    if (add)
+        hipLaunchKernelGGL(k_gr_unpack<true>, gr_grid_unr(gr->n_half, (nb + 1) / 2), dim3(256), 0, kb->basis->stream, gr->n_half,
+                           nb, gr->d_g, gr->d_mg, W, ldw, H, ldh, add, ldadd);
+    else
+        hipLaunchKernelGGL(k_gr_unpack<false>, gr_grid_unr(gr->n_half, (nb + 1) / 2), dim3(256), 0, kb->basis->stream, gr->n_half,
+                           nb, gr->d_g, gr->d_mg, W, ldw, H, ldh, add, ldadd);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -508,8 +530,13 @@ int gamma_pack_full(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Z,
 }
 
 // H psi in the half-sphere format (which: bit 0 local, 1 kinetic, 2 nonlocal as dftk_mi_apply_H_parts)
-int gamma_apply_H(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t ldpsi, cd* Hpsi, int64_t ldH) {
+int gamma_apply_H(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t ldpsi, cd* Hpsi, int64_t ldH, const cd* add,
+                  int64_t ldadd) {
     if (nb <= 0) return 0;
+    if (add && (kb->sh_comm || (which & 4))) {
+        dftk_set_error("gamma_apply_H: an addend goes with the local and kinetic parts of an un-sharded block only");
+        return DFTK_MI_EINVAL;
+    }
     if (kb->sh_comm) return gamma_apply_H_sharded(kb, which, nb, psi, ldpsi, Hpsi, ldH);
     GammaReal* gr = kb->gr.get();
     dftk_mi_basis* b = kb->basis;
@@ -531,7 +558,7 @@ int gamma_apply_H(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t 
     if ((which & 4) && kb->n_p > 0) prof_count(b, PROF_AR_MODEL, 16.0 * (double)kb->n_p * nb);   // P' psi partial sums
     CHK(gamma_pack_pairs(kb, nb, psi, ldpsi, Z, kb->n_G));
     CHK(launch_local_apply(kb, nb2, Z, kb->n_G, W, kb->n_G, kinetic, local));
-    CHK(gamma_unpack_pairs(kb, nb, W, kb->n_G, Hpsi, ldH));
+    CHK(gamma_unpack_pairs(kb, nb, W, kb->n_G, Hpsi, ldH, add, ldadd));
     if ((which & 4) && kb->n_p > 0) {
         CHK(gr_projectors(kb));
         CHK(apply_nonlocal_rows(kb, nb, gr->P_half, gr->n_half, gr->n_half, psi, ldpsi, Hpsi, ldH, true,
@@ -592,21 +619,28 @@ int gamma_density_bands(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi
     const int nb2 = (nb + 1) / 2;
     bool keep = false;
     CHK(planes_prepare(kb, nb, psi, ldpsi, &keep));
-    CHK(gamma_ensure_buf(kb, (size_t)kb->n_G * nb2));
-    CHK(gamma_pack_full(kb, nb, psi, ldpsi, kb->gr->buf, kb->n_G));
+    // stage A forms a + i b of a band pair while it scatters; DFTK_MI_LAND_IN_PLACE=0 (and a batched call, whose merged
+    // pipeline takes one column per transform) packs the pairs into the scratch block first
+    const bool pairs_in_A = land_in_place() && !batching();
+    if (!pairs_in_A) {
+        CHK(gamma_ensure_buf(kb, (size_t)kb->n_G * nb2));
+        CHK(gamma_pack_full(kb, nb, psi, ldpsi, kb->gr->buf, kb->n_G));
+    }
     std::vector<double> wre(nb2), wim(nb2);
     for (int p = 0; p < nb2; ++p) {
         wre[p] = w_h[2 * p];
         wim[p] = (2 * p + 1 < nb) ? w_h[2 * p + 1] : 0.0;
     }
     if (keep) kb->ho.planes_begin(nb, kb->basis->fft_batch);   // (a pass that keeps nothing: launch_density switches them off)
+    if (pairs_in_A) return launch_density(kb, nb2, psi, ldpsi, wre.data(), rho, wim.data(), nullptr, nullptr, keep, nb);
     return launch_density(kb, nb2, kb->gr->buf, kb->n_G, wre.data(), rho, wim.data(), nullptr, nullptr, keep);
 }
 
 // The local part of H psi (the bound potential) in the half-sphere format for the nb bands whose y-planes the density pass
 // kept: the pipeline starts at stage C.  A launch group the density pass skipped (all weights zero) gets its planes here
 // first, from the caller's full-format block X (the block those planes belong to).  The planes are consumed.
-int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Hpsi, int64_t ldH) {
+int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Hpsi, int64_t ldH, const cd* add,
+                                  int64_t ldadd) {
     if (nb <= 0) return 0;
     GammaReal* gr = kb->gr.get();
     dftk_mi_basis* b = kb->basis;
@@ -618,18 +652,26 @@ int gamma_apply_local_from_planes(dftk_mi_kblock* kb, int nb, const cd* X, int64
         int s;
         ~G() { prof_end(b, s); }
     } guard{b, slot};
-    CHK(gamma_ensure_buf(kb, 2 * (size_t)kb->n_G * nb2));
+    // W: the pipeline's output; Z: the packed pairs of a launch group the density pass skipped -- not needed where stage A
+    // forms the pairs itself (DFTK_MI_LAND_IN_PLACE)
+    const bool pairs_in_A = land_in_place();
+    CHK(gamma_ensure_buf(kb, (pairs_in_A ? 1 : 2) * (size_t)kb->n_G * nb2));
     cd* Z = gr->buf;
-    cd* W = gr->buf + (size_t)kb->n_G * nb2;
+    cd* W = pairs_in_A ? gr->buf.get() : gr->buf + (size_t)kb->n_G * nb2;
     prof_count(b, PROF_A2A_MODEL, 16.0 * (double)gr->n_half * nb);   // (as gamma_apply_H: what a sharded run of the call moves)
     prof_count(b, PROF_A2A_MODEL, 16.0 * (double)gr->n_half * nb);
     const int group = fft_group_size(b);
     for (int b0 = 0; b0 < nb2; b0 += group) {
         const int nbb = std::min(group, nb2 - b0);
         if (std::all_of(valid.begin() + b0, valid.begin() + b0 + nbb, [](char v) { return v != 0; })) continue;
-        CHK(gamma_pack_full(kb, std::min(2 * nbb, nb - 2 * b0), X + (int64_t)(2 * b0) * ldx, ldx, Z, kb->n_G));
+        const int ncol = std::min(2 * nbb, nb - 2 * b0);
+        if (pairs_in_A) {     // (as gamma_density_bands)
+            CHK(launch_planes_fill(kb, b0, nbb, X + (int64_t)(2 * b0) * ldx, ldx, kb->ho.planes, ncol));
+            continue;
+        }
+        CHK(gamma_pack_full(kb, ncol, X + (int64_t)(2 * b0) * ldx, ldx, Z, kb->n_G));
         CHK(launch_planes_fill(kb, b0, nbb, Z, kb->n_G, kb->ho.planes));
     }
     CHK(launch_local_apply_from_planes(kb, nb2, kb->ho.planes, W, kb->n_G));
-    return gamma_unpack_pairs(kb, nb, W, kb->n_G, Hpsi, ldH);
+    return gamma_unpack_pairs(kb, nb, W, kb->n_G, Hpsi, ldH, add, ldadd);
 }

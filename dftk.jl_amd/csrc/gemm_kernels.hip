@@ -89,8 +89,10 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
                                                                int rt0, int ct0, int lsplit, int upper,
                                                                int shift_ct, int shift_rt, int nsplit, const cd* __restrict__ A, int64_t lda,
                                                                const cd* __restrict__ B, int64_t ldb,
-                                                               cd* __restrict__ C, int64_t ldc, cd alpha, cd beta,
+                                                               const cd* C, cd* D, int64_t ldc, cd alpha, cd beta,
                                                                cd* __restrict__ slab) {
+    // C, D: the epilogue reads `old` from C and stores to D, entry by entry at the same offset (leading dimension ldc for
+    // both).  D == C is the in-place product, so the two are not declared restrict.
     constexpr int BN = 16 * RN;      // column-tile width: 32 (3M complex), 64 (REAL: the third product's registers
                                      // hold a second pair of accumulator columns -> 1.7x the flops per operand byte)
     static_assert(RN == 2 || RN == 4, "B staging handles one or two columns per thread");
@@ -461,14 +463,14 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
                         const double vr = REAL ? p1 : (CONJA ? p1 + p2 : p1 - p2);
                         const double vi = REAL ? (CONJA ? 0.0 : p2) : (CONJA ? p3 - p1 + p2 : p3 - p1 - p2);
                         if (direct) {
-                            cd* c = C + gi + (int64_t)gj * ldc;
+                            const int64_t off = gi + (int64_t)gj * ldc;
                             cd o = make_double2(alpha.x * vr - alpha.y * vi, alpha.x * vi + alpha.y * vr);
                             if (beta.x != 0.0 || beta.y != 0.0) {
-                                const cd old = *c;
+                                const cd old = C[off];
                                 o.x += beta.x * old.x - beta.y * old.y;
                                 o.y += beta.x * old.y + beta.y * old.x;
                             }
-                            *c = o;
+                            D[off] = o;
                         } else {
                             sl[gi + (int64_t)gj * m] = make_double2(vr, vi);
                         }
@@ -493,7 +495,7 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
 // 128 x 32 tiles of the complex products.
 #define REDUCE_UPPER_BN 64
 __global__ void k_zgemm_reduce(int m, int n, int mi, int nj, int nsI, const cd* __restrict__ slabI, int nsB,
-                               const cd* __restrict__ slabB, cd* __restrict__ C, int64_t ldc, cd alpha, cd beta,
+                               const cd* __restrict__ slabB, const cd* C, cd* D, int64_t ldc, cd alpha, cd beta,
                                int upper) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)m * n) return;
@@ -512,20 +514,20 @@ __global__ void k_zgemm_reduce(int m, int n, int mi, int nj, int nsI, const cd* 
         sr += v.x;
         si += v.y;
     }
-    cd* c = C + i + (int64_t)j * ldc;
+    const int64_t off = i + (int64_t)j * ldc;
     cd o = make_double2(alpha.x * sr - alpha.y * si, alpha.x * si + alpha.y * sr);
     if (beta.x != 0.0 || beta.y != 0.0) {
-        const cd old = *c;
+        const cd old = C[off];
         o.x += beta.x * old.x - beta.y * old.y;
         o.y += beta.x * old.y + beta.y * old.x;
     }
-    *c = o;
+    D[off] = o;
 }
 
 // Reference kernel without matrix cores (debug path, env DFTK_MI_GEMM=naive): one thread per C entry.
 template <bool CONJA>
 __global__ void k_zgemm_naive(int m, int n, int K, const cd* __restrict__ A, int64_t lda,
-                              const cd* __restrict__ B, int64_t ldb, cd* __restrict__ C, int64_t ldc, cd alpha,
+                              const cd* __restrict__ B, int64_t ldb, const cd* C, cd* D, int64_t ldc, cd alpha,
                               cd beta, int real) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)m * n) return;
@@ -541,14 +543,14 @@ __global__ void k_zgemm_naive(int m, int n, int K, const cd* __restrict__ A, int
         si += a.x * b.y + a.y * b.x;
     }
     if (real && CONJA) si = 0.0;
-    cd* c = C + i + (int64_t)j * ldc;
+    const int64_t off = i + (int64_t)j * ldc;
     cd o = make_double2(alpha.x * sr - alpha.y * si, alpha.x * si + alpha.y * sr);
     if (beta.x != 0.0 || beta.y != 0.0) {
-        const cd old = *c;
+        const cd old = C[off];
         o.x += beta.x * old.x - beta.y * old.y;
         o.y += beta.x * old.y + beta.y * old.x;
     }
-    *c = o;
+    D[off] = o;
 }
 
 // ---- diagnostic: pure v_mfma_f64_16x16x4_f64 issue rate (no memory traffic) -> measured ceiling
@@ -821,6 +823,13 @@ int zgemm_plan_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int
 
 int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alpha, const cd* A, int64_t lda,
           const cd* B, int64_t ldb, cd beta, cd* C, int64_t ldc, int upper_in) {
+    return zgemm_to(b, transA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, C, upper_in);
+}
+
+// D = alpha op(A) B + beta C: the product above with its result in a second array of C's shape and leading dimension.  The
+// k order and the epilogue arithmetic are those of the in-place product (D == C); C is only read, and only where beta != 0.
+int zgemm_to(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alpha, const cd* A, int64_t lda,
+             const cd* B, int64_t ldb, cd beta, const cd* C, int64_t ldc, cd* D, int upper_in) {
     const bool real = (upper_in & DFTK_MI_GEMM_REAL) != 0;   // operands are real-symmetric half-sphere blocks
     if (m <= 0 || n <= 0) return 0;
     const bool conja = (transA == 'C' || transA == 'c');
@@ -838,16 +847,20 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
     }
     if (m > INT32_MAX || n > INT32_MAX || k > INT32_MAX) return DFTK_MI_EINVAL;
     if (batching()) {   // a fiber of a batched multi-k call: recorded, merged with its siblings' products later
+        if (D != C) {
+            dftk_set_error("zgemm: a recorded product of a batched call writes its result in place");
+            return DFTK_MI_EINVAL;
+        }
         BOp o;
         o.b = b;
         o.type = BOP_ZGEMM; o.trans = conja ? 'C' : 'N'; o.gm = m; o.gn = n; o.gk = k; o.alpha = alpha; o.A = A; o.lda = lda;
-        o.B = B; o.ldb = ldb; o.beta = beta; o.C = C; o.ldc = ldc;
+        o.B = B; o.ldb = ldb; o.beta = beta; o.C = D; o.ldc = ldc;
         o.flags = upper_in & ~GEMM_SYM_RESULT;   // (the merged products know no symmetric result: the full product is computed)
         return batch_record(std::move(o));
     }
     if (k <= 0) {   // C = beta * C : run the reduce kernel over zero slabs
         hipLaunchKernelGGL(k_zgemm_reduce, dim3((unsigned)((m * n + 255) / 256)), dim3(256), 0, b->stream, (int)m,
-                           (int)n, (int)m, (int)n, 0, (const cd*)nullptr, 0, (const cd*)nullptr, C, ldc, alpha, beta, 0);
+                           (int)n, (int)m, (int)n, 0, (const cd*)nullptr, 0, (const cd*)nullptr, C, D, ldc, alpha, beta, 0);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -918,10 +931,10 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
         const unsigned blocks = (unsigned)((m * n + 255) / 256);
         if (conja)
             hipLaunchKernelGGL(k_zgemm_naive<true>, dim3(blocks), dim3(256), 0, b->stream, (int)m, (int)n, (int)k, A,
-                               lda, B, ldb, C, ldc, alpha, beta, real ? 1 : 0);
+                               lda, B, ldb, C, D, ldc, alpha, beta, real ? 1 : 0);
         else
             hipLaunchKernelGGL(k_zgemm_naive<false>, dim3(blocks), dim3(256), 0, b->stream, (int)m, (int)n, (int)k,
-                               A, lda, B, ldb, C, ldc, alpha, beta, real ? 1 : 0);
+                               A, lda, B, ldb, C, D, ldc, alpha, beta, real ? 1 : 0);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -964,7 +977,7 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
 #define DFTK_LAUNCH_3M_(CJ, MD, RL, RNN, FD)                                                                           \
     hipLaunchKernelGGL((k_zgemm_3m<CJ, MD, RL, RNN, FD>), grid, dim3(GEMM_WAVES * 64), 0, b->stream, (int)m, (int)n, (int)k,  \
                        sp.kchunk, gm_s, gn_s, rt0, ct0, lsplit, kupper, til.shift ? gnf : -1,                          \
-                       (til.shift_r && lsplit < 0) ? gmf : -1, sp.nsplit, A, lda, B, ldb, C,                           \
+                       (til.shift_r && lsplit < 0) ? gmf : -1, sp.nsplit, A, lda, B, ldb, C, D,                        \
                        ldc, alpha, beta, sp.slab)
         // mode 1 = full tiles, 0 = predicated border
         if (conja) {
@@ -986,7 +999,7 @@ int zgemm(dftk_mi_basis* b, char transA, int64_t m, int64_t n, int64_t k, cd alp
     if (spI.slab || spB.slab)
         hipLaunchKernelGGL(k_zgemm_reduce, dim3((unsigned)((m * n + 255) / 256)), dim3(256), 0, b->stream, (int)m,
                            (int)n, til.shift_r ? (int)m : gmf * GEMM_BM, til.shift ? (int)n : gnf * BNt, spI.slab ? spI.nsplit : -1, spI.slab,
-                           spB.slab ? spB.nsplit : -1, spB.slab, C, ldc, alpha, beta, upper | (rsc == 2 ? 32 : 0));
+                           spB.slab ? spB.nsplit : -1, spB.slab, C, D, ldc, alpha, beta, upper | (rsc == 2 ? 32 : 0));
     HIPCHK(hipGetLastError());
     return 0;
 }

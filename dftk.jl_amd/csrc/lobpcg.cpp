@@ -70,6 +70,11 @@ struct Ctx {
            cd beta, cd* C, int64_t ldc, int upper = 0) {
         return zgemm(b, transA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, upper | rf);
     }
+    // ... with the result in D (C's shape and leading dimension; C is read where beta != 0): zgemm_to
+    int mm_to(char transA, int64_t m, int64_t n, int64_t k, cd alpha, const cd* A, int64_t lda, const cd* B, int64_t ldb,
+              cd beta, const cd* C, int64_t ldc, cd* D, int upper = 0) {
+        return zgemm_to(b, transA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, D, upper | rf);
+    }
     // Row-slab (plane-wave) sharding: every product with the long dimension n_G as its inner dimension and
     // every column reduction is a LOCAL partial sum followed by an all-reduce over the block's communicator
     // (no-ops for an unsharded block).  reduce_norms: the buffer holds sqrt(local sums).
@@ -152,8 +157,12 @@ int svd_polar(Ctx& c, Mat X, cd* scratch, int64_t scratch_ld);
 // `hook` (optional): called once, right after the first Cholesky factorisation has come back (the first host
 // synchronisation of the call) and before X is touched; a non-zero result is handed to the caller in *hook_out and the call
 // returns at once with X unchanged (ortho_XY lets a fetch of its own ride on that synchronisation).
+// `start` (optional; X.p or tmp): where the block lives on entry.  The result is always left in X; a caller that expects an
+// ODD number of passes (one, for a block that is orthonormal up to round-off) hands the block over in tmp and the last pass
+// lands in X without a copy -- an even count then costs the one copy an odd count costs from X.
 int ortho_X(Ctx& c, Mat X, cd* tmp, double tol, int* nchol_total_out, double* growth_out, bool allow_svd = true,
-            int64_t tmp_ld = 0, bool force_svd = false, const std::function<int()>* hook = nullptr, int* hook_out = nullptr) {
+            int64_t tmp_ld = 0, bool force_svd = false, const std::function<int()>* hook = nullptr, int* hook_out = nullptr,
+            const cd* start = nullptr) {
     double growth = 1.0;
     int nchol_total = 0;
     const int m = X.cols;
@@ -166,6 +175,7 @@ int ortho_X(Ctx& c, Mat X, cd* tmp, double tol, int* nchol_total_out, double* gr
     // the passes alternate between X and tmp (X * invR cannot be formed in place); one copy at the end
     // if the result happens to sit in tmp
     Mat src = X, dst{tmp, tmp_ld, X.rows, m};
+    if (start != nullptr && start != X.p) std::swap(src, dst);   // (start == tmp)
     for (int pass = 0;; ++pass) {
         if (pass >= 30) {
             dftk_set_error("ortho!(X) did not reach the orthogonality tolerance in 30 Cholesky-QR passes");
@@ -303,7 +313,14 @@ int ortho_XY(Ctx& c, Mat X, const std::vector<Mat>& Ys, cd* tmp, double tol, con
     const std::vector<Mat>& Yl = merged.empty() ? Ys : merged;
     int niter = 1;
     std::vector<double> hb;     // landing zone of the (possibly deferred) fetch below: outlives every round of the loop
+    // From the second round on the ortho!(X) that closes the round takes ONE Cholesky-QR pass (X left it orthonormal a round
+    // ago and the projection moves it by round-off), and X inv(R) cannot be formed in place: the round writes X - Y BYX into
+    // tmp, works on it there and the pass lands in X (DFTK_MI_LAND_IN_PLACE; large blocks outside a batched call).
+    const bool via_tmp = land_in_place() && !batching() && ny > 0 && X.ld == X.rows &&
+                         (int64_t)X.rows * X.cols > DEFER_FETCH_MAX_ELEMS;
     for (;;) {
+        const bool in_tmp = via_tmp && niter > 1;
+        const Mat W = in_tmp ? Mat{tmp, X.ld, X.rows, X.cols} : X;   // where this round's block lives until ortho!(X)
         // BYX = Y' X ; X -= Y BYX
         int off = 0;
         for (auto& Y : Yl) {
@@ -313,14 +330,16 @@ int ortho_XY(Ctx& c, Mat X, const std::vector<Mat>& Ys, cd* tmp, double tol, con
         }
         CHK(c.reduce_c(c.BYX, (size_t)ny * X.cols));
         off = 0;
+        const cd* from = X.p;     // (the first product reads X and writes W, the others update W)
         for (auto& Y : Yl) {
             if (Y.cols == 0) continue;
-            CHK(c.mm('N', X.rows, X.cols, Y.cols, MONE, Y.p, Y.ld, c.BYX + off, ny, ONE, X.p, X.ld));
+            CHK(c.mm_to('N', X.rows, X.cols, Y.cols, MONE, Y.p, Y.ld, c.BYX + off, ny, ONE, from, X.ld, W.p));
+            from = W.p;
             off += Y.cols;
         }
         // drop_small!  (the column sums of |BYX|^2 for the convergence test below ride on the same fetch: every host
         // synchronisation of this loop is a round of latency, in the batched multi-k driver a whole scheduling round)
-        CHK(ew_colnorms(c.b, X.rows, X.cols, X.p, X.ld, c.d_a));
+        CHK(ew_colnorms(c.b, W.rows, W.cols, W.p, W.ld, c.d_a));
         CHK(c.reduce_norms(c.d_a, X.cols));
         const bool one_fetch = c.dstride > 0 && c.d_b == c.d_a + c.dstride && X.cols <= c.dstride;
         // Small blocks (the k-point workloads): the fetch does not get a synchronisation of its own -- it rides on the first
@@ -375,8 +394,8 @@ int ortho_XY(Ctx& c, Mat X, const std::vector<Mat>& Ys, cd* tmp, double tol, con
             if (nonfinite) return DFTK_MI_NUM_NONFINITE;
         }
         for (int j : dropped) {
-            CHK(randomize_column(c, X, j));
-            Mat xj = X.cols_from(j, 1);
+            CHK(randomize_column(c, W, j));
+            Mat xj = W.cols_from(j, 1);
             int o2 = 0;
             // X[:, j] -= Y (Y' X[:, j])   (uses the tail of BYX as scratch: ny x 1 beyond the block)
             cd* scr = c.BYX + (int64_t)ny * X.cols;
@@ -395,8 +414,11 @@ int ortho_XY(Ctx& c, Mat X, const std::vector<Mat>& Ys, cd* tmp, double tol, con
         }
         if (!one_fetch) CHK(frob2(c, Mat{c.BYX, ny, ny, X.cols}, &byx2));
         if (!speculated) {
-            if (std::sqrt(byx2) < tol && niter > 1) break;
-            CHK(ortho_X(c, X, tmp, tol, &ninner, &growth));
+            if (std::sqrt(byx2) < tol && niter > 1) {
+                if (in_tmp) CHK(ew_copy(c.b, X.rows, X.cols, W.p, W.ld, X.p, X.ld));   // (no pass follows: back as it is)
+                break;
+            }
+            CHK(ortho_X(c, X, tmp, tol, &ninner, &growth, true, 0, false, nullptr, nullptr, W.p));
         }
         if (growth * EPS < tol) break;
         if (niter > 10) {
@@ -734,6 +756,7 @@ struct Lob {
     }
 
     // (A_old X) inv(R) -> AX: straight into place unless the kept block IS AX's storage (through newR then)
+    // (the launch sequence of DFTK_MI_LAND_IN_PLACE=0; start_AX states the other one)
     int kept_times_invR() {
         if (kept_AX != AX.p) return c.mm('N', N, M, M, ONE, kept_AX, kept_ld, c.invR, M, ZERO, AX.p, AX.ld, /*B upper triangular=*/2);
         CHK(c.mm('N', N, M, M, ONE, kept_AX, kept_ld, c.invR, M, ZERO, newR.p, newR.ld, /*B upper triangular=*/2));
@@ -745,14 +768,18 @@ struct Lob {
     int start_AX(const cd* Xp, int64_t ldX) {
         LobHandover& ho = kb->ho;
         bool reuse_ax = kept_AX != nullptr && kb->d_Vs != nullptr && ho.V_kept != nullptr;
+        // The start block of an SCF step comes back orthonormal to round-off: ortho!(X) is ONE Cholesky-QR pass, and X inv(R)
+        // cannot be formed in place.  The block is therefore loaded into tmp (leading dimension N, as X) and the pass lands in X.
+        const bool lip = land_in_place();
+        cd* const X0 = lip ? tmp : X.p;
         if (c.real_mode)
-            CHK(gamma_lobpcg_load(kb, M, Xp, ldX, X.p, X.ld, /*align=*/true));
+            CHK(gamma_lobpcg_load(kb, M, Xp, ldX, X0, X.ld, /*align=*/true));
         else
-            CHK(ew_copy(b, N, M, Xp, ldX, X.p, X.ld));
+            CHK(ew_copy(b, N, M, Xp, ldX, X0, X.ld));
         {
             int nch;
             double gr;
-            CHK(ortho_X(c, X, tmp, ORTHO_TOL, &nch, &gr));
+            CHK(ortho_X(c, X, tmp, ORTHO_TOL, &nch, &gr, true, 0, false, nullptr, nullptr, X0));
             // the kept A X follows X through ONE plain Cholesky-QR pass (X <- X inv(R), the common case: X comes back orthonormal
             // to round-off from the previous step); anything else (several passes, shifts, the SVD fallback) takes the full H X
             if (reuse_ax && !(nch == 1)) reuse_ax = false;
@@ -772,11 +799,43 @@ struct Lob {
             // A_new X = (A_old X_ret + (V_new - V_old) X_ret) inv(R), the same operator before the triangular factor.
             g_planes_reuse_count.fetch_add(1);
             kb->d_Vs = ho.dV;
-            const int st_dv = gamma_apply_local_from_planes(kb, M, Xp, ldX, newR.p, newR.ld);
-            kb->d_Vs = Vs_bound;
-            CHK(st_dv);
-            CHK(ew_add(b, N, M, newR.p, newR.ld, kept_AX, kept_ld));
-            CHK(kept_times_invR());
+            if (lip) {
+                // the unpack of the pipeline's output adds the kept block as it writes: the sum goes to newR where the kept
+                // block is AX's own storage (the product below cannot run in place), else back into the kept block
+                const Mat S = kept_AX == AX.p ? newR : Mat{kept_AX, kept_ld, N, M};
+                const int st_dv = gamma_apply_local_from_planes(kb, M, Xp, ldX, S.p, S.ld, kept_AX, kept_ld);
+                kb->d_Vs = Vs_bound;
+                CHK(st_dv);
+                CHK(c.mm('N', N, M, M, ONE, S.p, S.ld, c.invR, M, ZERO, AX.p, AX.ld, /*B upper triangular=*/2));
+            } else {
+                const int st_dv = gamma_apply_local_from_planes(kb, M, Xp, ldX, newR.p, newR.ld);
+                kb->d_Vs = Vs_bound;
+                CHK(st_dv);
+                CHK(ew_add(b, N, M, newR.p, newR.ld, kept_AX, kept_ld));
+                CHK(kept_times_invR());
+            }
+        } else if (lip) {
+            // (A_old X) inv(R) goes to AX, or to newR where the kept block is AX's own storage; (V_new - V_old) X is added as
+            // it is written.  An un-sharded Gamma-real block adds in the unpack of its pipeline.  The general complex pipeline
+            // and the sharded Gamma-real one end in kernels shared with every H psi (the sphere gather of stage E, the
+            // all-to-all): they write beside the product and keep the one trailing addition.
+            const Mat Pr = kept_AX == AX.p ? newR : AX;
+            CHK(c.mm('N', N, M, M, ONE, kept_AX, kept_ld, c.invR, M, ZERO, Pr.p, Pr.ld, /*B upper triangular=*/2));
+            kb->d_Vs = ho.dV;                                     // (the kernels take the pointer at launch)
+            int st_dv;
+            if (c.real_mode && !kb->sh_comm) {
+                st_dv = gamma_apply_H(kb, 1, M, X.p, X.ld, AX.p, AX.ld, Pr.p, Pr.ld);
+                kb->d_Vs = Vs_bound;
+                CHK(st_dv);
+            } else {
+                const Mat Dl = kept_AX == AX.p ? AX : newR;       // the block the product did not take
+                st_dv = c.real_mode ? gamma_apply_H(kb, 1, M, X.p, X.ld, Dl.p, Dl.ld)
+                                    : dftk_mi_apply_H_parts(kb, 1, M, reinterpret_cast<const dftk_mi_cplx*>(X.p), X.ld,
+                                                            reinterpret_cast<dftk_mi_cplx*>(Dl.p), Dl.ld);
+                kb->d_Vs = Vs_bound;
+                CHK(st_dv);
+                CHK(ew_add(b, N, M, newR.p, newR.ld, AX.p, AX.ld));
+            }
         } else {
             CHK(kept_times_invR());
             kb->d_Vs = ho.dV;                                     // (the kernels take the pointer at launch)
@@ -994,6 +1053,17 @@ struct Lob {
         if (*permuted) {
             std::stable_sort(perm.begin(), perm.end(), [&](int a, int d) { return full_lam[a] < full_lam[d]; });
             CHK(h2d(b, d_perm, perm.data(), M * sizeof(int)));
+            if (land_in_place()) {
+                // the other pair is free once the iteration is over: gather X and AX into it and make it the current one
+                cur ^= 1;
+                const Mat Xs = Yb[cur].cols_from(0, M), AXs = AYb[cur].cols_from(0, M);
+                CHK(ew_gather_cols(b, N, M, X.p, X.ld, d_perm, Xs.p, Xs.ld));
+                CHK(ew_gather_cols(b, N, M, AX.p, AX.ld, d_perm, AXs.p, AXs.ld));
+                X = Xs;
+                AX = AXs;
+                kb->ho.set_last_AX(c.real_mode ? nullptr : AX.p);
+                return 0;
+            }
             CHK(ew_gather_cols(b, N, M, X.p, X.ld, d_perm, tmp, N));
             CHK(ew_copy(b, N, M, tmp, N, X.p, X.ld));
             CHK(ew_gather_cols(b, N, M, AX.p, AX.ld, d_perm, tmp, N));
@@ -1046,7 +1116,15 @@ int lobpcg_ortho(dftk_mi_basis* b, int64_t n, int m, cd* X, int64_t ldx, int for
     c.rng.seed(0x9E3779B97F4A7C15ull);
     int nch = 0;
     double gr = 1.0;
-    int st = ortho_X(c, Mat{X, ldx, n, m}, tmp, 2 * EPS, &nch, &gr, true, n, force_svd != 0);
+    // force_svd & 2: enter as the LOBPCG driver does under DFTK_MI_LAND_IN_PLACE -- the block is moved to the scratch copy
+    // and the passes start there, so that an odd number of them ends in X
+    const cd* start = X;
+    if ((force_svd & 2) && land_in_place()) {
+        int st0 = ew_copy(b, n, m, X, ldx, tmp, n);
+        if (st0 != 0) return st0;
+        start = tmp;
+    }
+    int st = ortho_X(c, Mat{X, ldx, n, m}, tmp, 2 * EPS, &nch, &gr, true, n, (force_svd & 1) != 0, nullptr, nullptr, start);
     if (st == 0 && hipStreamSynchronize(b->stream) != hipSuccess) st = DFTK_MI_EHIP;
     if (n_chol) *n_chol = nch;
     if (used_svd) *used_svd = c.n_svd;
@@ -1083,8 +1161,12 @@ static int lobpcg_run_general(dftk_mi_kblock* kb, int M, cd* Xp, int64_t ldX, do
     Ctx& c = s.c;
     CHK(s.start_AX(Xp, ldX));
     // (R is written at the end of iteration 0 and P at the end of iteration 1, before their first use)
-    CHK(ew_coldots(b, N, M, s.X.p, s.X.ld, s.AX.p, s.AX.ld, c.d_a));
-    CHK(ew_coldots(b, N, M, s.X.p, s.X.ld, s.X.p, s.X.ld, c.d_b));
+    if (land_in_place()) {
+        CHK(ew_coldots2(b, N, M, s.X.p, s.X.ld, s.AX.p, s.AX.ld, c.d_a, c.d_b));   // <x, Ax> and <x, x> from one read of X
+    } else {
+        CHK(ew_coldots(b, N, M, s.X.p, s.X.ld, s.AX.p, s.AX.ld, c.d_a));
+        CHK(ew_coldots(b, N, M, s.X.p, s.X.ld, s.X.p, s.X.ld, c.d_b));
+    }
     CHK(c.reduce_d(c.d_a, 2 * (size_t)DS));
     CHK(d2h_sync(b, s.hf.data(), c.d_a, 2 * (size_t)DS * sizeof(double)));
     CHK(s.rayleigh_quotients());

@@ -587,7 +587,9 @@ int dftk_mi_columnwise_dots(dftk_mi_basis* basis, int64_t n, int m, const dftk_m
                             const dftk_mi_cplx* B_d, int64_t ldb, dftk_mi_cplx* dots_h /* [m]: dot(A[:,i], B[:,i]) */);
 /* ortho_qr (src/common/ortho.jl:1-9) / ortho!(X) (lobpcg_hyper_impl.jl:216-261): orthonormalise the columns of X
  * in place by Cholesky-QR with the reference's shift-and-retry and SVD fallback (same column space as Householder
- * QR; Q differs from LAPACK's by a unitary diagonal).  force_svd = 1 takes the SVD branch (X = U V').
+ * QR; Q differs from LAPACK's by a unitary diagonal).  force_svd = 1 takes the SVD branch (X = U V').  force_svd | 2 (while
+ * DFTK_MI_LAND_IN_PLACE is on): the block is first moved to the routine's scratch copy and the passes start from there, as
+ * the LOBPCG driver enters them -- an odd number of passes then ends in X without a copy back; same result bit for bit.
  * *n_chol = Cholesky factorizations used (100 after an SVD fallback, as the reference reports). */
 int dftk_mi_ortho_qr(dftk_mi_basis* basis, int64_t n, int m, dftk_mi_cplx* X_d, int64_t ldx, int force_svd,
                      int* n_chol, int* used_svd);
@@ -637,6 +639,14 @@ int dftk_mi_zgemm_ex(dftk_mi_basis* basis, char transA, int64_t m, int64_t n, in
                      dftk_mi_cplx alpha, const dftk_mi_cplx* A_d, int64_t lda,
                      const dftk_mi_cplx* B_d, int64_t ldb, dftk_mi_cplx beta,
                      dftk_mi_cplx* C_d, int64_t ldc, int flags);
+/* D = alpha * op(A) * B + beta * C with the result in a second array D of C's shape and leading dimension (D == C is
+ * dftk_mi_zgemm_ex).  Same flags, same launch plan, same arithmetic in the same order: the result is bit for bit the one the
+ * in-place call leaves in C.  C is read only where beta != 0 and never written; with DFTK_MI_GEMM_UPPER /
+ * DFTK_MI_GEMM_SYM_RESULT only the computed tiles of D are written. */
+int dftk_mi_zgemm_to(dftk_mi_basis* basis, char transA, int64_t m, int64_t n, int64_t k,
+                     dftk_mi_cplx alpha, const dftk_mi_cplx* A_d, int64_t lda,
+                     const dftk_mi_cplx* B_d, int64_t ldb, dftk_mi_cplx beta,
+                     const dftk_mi_cplx* C_d, int64_t ldc, dftk_mi_cplx* D_d, int flags);
 /* Hermitian eigen-decomposition (blocked parallel Jacobi): A (n x n, full storage, destroyed),
  * W_h[n] ascending eigenvalues (host), V_d n x n eigenvectors (columns, sorted like W). */
 int dftk_mi_heev(dftk_mi_basis* basis, int n, dftk_mi_cplx* A_d, int64_t lda, double* W_h,
