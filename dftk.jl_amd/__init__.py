@@ -51,3 +51,6 @@ from .phonon import (compute_dynmat, compute_dynmat_term, compute_delta_H_psi_al
                      dynmat_red_to_cart, mass_matrix)
 from .hubbard import (OrbitalManifold, Hubbard, resolve_hubbard_manifold, wigner_d_matrix,  # noqa: F401,E402
                       symmetrize_hubbard_n, compute_hubbard_n)
+from .transfer import transfer_blochwave_kpt, transfer_blochwave, transfer_density  # noqa: F401,E402
+from .refine import (RefinementResult, refine_scfres, refine_energies, refine_forces, invert_refinement_metric,  # noqa: F401,E402
+                     select_occupied_orbitals, check_full_occupation, compute_projected_gradient, apply_Omega, apply_K)

@@ -465,6 +465,7 @@ extern "C" int dftk_mi_kblock_create(dftk_mi_basis* b, int64_t n_G, const int64_
     CHK(upload(kin, kb->d_kin));
     kb->h_mapping.assign(mapping0_h, mapping0_h + n_G);
     kb->h_kin = std::move(kin);
+    kb->kin_given = kinetic_h != nullptr;
     *out = kb.release();
     return 0;
 }

@@ -135,11 +135,19 @@ struct StreamOwner {     // the basis' stream: declared before every buffer of t
     ~StreamOwner() { if (s) hipStreamDestroy(s); }
     operator hipStream_t() const { return s; }
 };
+struct EventOwner {      // one timing-less event, created on first use (transfer_kernels.hip orders two bases' streams with it)
+    hipEvent_t e = nullptr;
+    EventOwner() = default;
+    EventOwner(const EventOwner&) = delete;
+    EventOwner& operator=(const EventOwner&) = delete;
+    ~EventOwner() { if (e) hipEventDestroy(e); }
+};
 struct dftk_mi_basis {
     int nx = 0, ny = 0, nz = 0, nxp = 0;   // nxp = nx rounded up to a multiple of FFT_L (padded x pitch)
     double volume = 0.0;
     int device = 0;
     StreamOwner stream;
+    EventOwner order_ev;          // recorded on `stream` when another basis' stream has to wait for this one
     FftAxis ax[3] = {};           // x, y, z (tw / pos point into d_tables)
     DevTable<void> d_tables[6];   // device tw/pos buffers
     int fft_batch = 0;            // bands per launch group
@@ -260,6 +268,7 @@ struct GammaReal {
     std::vector<int64_t> half_rows;
 };
 
+inline std::atomic<uint64_t> g_kblock_serial{0};
 struct dftk_mi_kblock {
     dftk_mi_basis* basis = nullptr;   // borrowed
     int device = 0;               // copy of basis->device (destroy must not touch the basis)
@@ -308,6 +317,15 @@ struct dftk_mi_kblock {
     std::vector<double> h_kin;
     std::unique_ptr<GammaReal> gr;   // null until dftk_mi_kblock_set_gamma_real / density_accumulate_real
     DevTable<int32_t> d_G3;          // [3 n_G] integer G of every sphere row (built by the first forces call)
+    // inverse of the mapping: sphere row of every cube index, -1 where the sphere has none (built by the first
+    // dftk_mi_transfer_blochwave call that reads from this block, transfer_kernels.hip)
+    DevTable<int32_t> d_inv;
+    // every block has its own number (a new block at the address of a destroyed one gets another), and remembers the last
+    // (input block, dG) that dftk_mi_transfer_blochwave has checked against it as OUTPUT block: the check runs once per pair
+    uint64_t serial = g_kblock_serial.fetch_add(1, std::memory_order_relaxed) + 1;
+    uint64_t transfer_in_serial = 0;
+    int transfer_dG[3] = {0, 0, 0};
+    bool kin_given = false;          // dftk_mi_kblock_create was handed kinetic energies (h_kin is not a row of zeros)
 };
 
 // ------------------------------------------------------------------------------------ internal API
@@ -589,6 +607,18 @@ int sternheimer_run(dftk_mi_kblock* kb, int n_occ, const cd* psi_occ, int64_t ld
 // dftk_mi_dynmat_nonlocal (the entry points are the whole interface: see include/dftk_mi355x.h)
 
 // exx_kernels.hip: dftk_mi_exx_apply (the entry point is the whole interface: see include/dftk_mi355x.h)
+
+// transfer_kernels.hip: dftk_mi_transfer_blochwave / dftk_mi_transfer_density (the entry points are the whole interface)
+
+// refine_kernels.hip: the per-column element-wise kernels of the refinement metric (refine.cpp)
+// Y[:, c] = f_c(kin) X[:, c] with t = kin + mean_kin[c]: mode 0 f = sqrt(t), mode 1 f = 1 / t   (X == Y allowed)
+int refine_scale_T(dftk_mi_basis* b, int64_t n, int m, int mode, const double* kin_d, const double* mean_kin_d, const cd* X,
+                   int64_t ldx, cd* Y, int64_t ldy);
+// gamma[c] = 0 where res[c] <= tol: the CG kernels of response_kernels.hip then leave x and r of column c as they are
+int refine_lock(dftk_mi_basis* b, int m, const double* res_d, double tol, double* gamma_d);
+// refine.cpp
+int refinement_metric_solve(dftk_mi_kblock* kb, int m, const cd* psi, int64_t ld_psi, const cd* res, int64_t ld_res,
+                            double tol, int maxiter, cd* out, int64_t ld_out, int* iters_h, double* resnorm_h);
 
 // lobpcg.cpp
 // ortho!(X) (Cholesky-QR with the reference's shift-and-retry and SVD fallback) on a stand-alone block;

@@ -181,6 +181,28 @@ __device__ __forceinline__ void ew_rows(int64_t n, int64_t rb, const cd* x, cd* 
     }
 }
 
+// y = f(kin + shift) x row by row, f(t) = 1 / t (INV) or sqrt(t): the diagonal operators T_n^{-1} and T_n^{1/2} of the
+// refinement metric (T_n = kin + mean_kin[n], refine.jl:20-25); same row tile and load pattern as ew_rows, x == y allowed
+template <bool INV>
+__device__ __forceinline__ void ew_rows_kin(int64_t n, int64_t rb, const cd* x, cd* y, const double* __restrict__ kin,
+                                            double shift) {
+    const int64_t i0 = rb * EW_ROWS + threadIdx.x;
+    cd v[EW_UNR];
+    double t[EW_UNR];
+#pragma unroll
+    for (int u = 0; u < EW_UNR; ++u) {
+        const int64_t i = i0 + u * 256;
+        v[u] = i < n ? x[i] : make_double2(0.0, 0.0);
+        t[u] = i < n ? kin[i] + shift : 1.0;
+    }
+#pragma unroll
+    for (int u = 0; u < EW_UNR; ++u) {
+        const int64_t i = i0 + u * 256;
+        const double f = INV ? 1.0 / t[u] : sqrt(t[u]);
+        if (i < n) y[i] = make_double2(v[u].x * f, v[u].y * f);
+    }
+}
+
 // ---------------------------------------------------------------------------- small matrices: one thread per entry idx
 // C[row0 + a, a] -= 1 for a in [0, cols)   (the "e" matrix of lobpcg_hyper_impl.jl:493-499)
 __device__ __forceinline__ void ew_sub_identity_at(int64_t a, int64_t rows, int cols, cd* __restrict__ C, int64_t ldc,

@@ -129,7 +129,13 @@ def _forces_xc(basis, rho):
             vxc.sub_(part["V"], alpha=1.0 - s)
     if vxc.dim() == 4:
         vxc = 0.5 * (vxc[0] + vxc[1])
-    vxc = vxc.contiguous()
+    return _forces_xc_of_potential(basis, vxc.contiguous())
+
+
+def _forces_xc_of_potential(basis, vxc):
+    """The Xc force sum for a given potential cube: linear in ``vxc`` (refine.refine_forces hands it f_xc d_rho)."""
+    model = basis.model
+    T = basis.terms
     ff = T.core_ff if getattr(T, "core_ff", None) is not None else core_form_factor_table(basis)
     order = _group_order(model)
     _, species, positions = local_species_tables(model, lambda el: [])

@@ -426,6 +426,57 @@ int dftk_mi_density_response_accumulate(dftk_mi_kblock* kb, int n_bands, const d
 int dftk_mi_apply_kernel(dftk_mi_kblock* cube_kb, const double* rho_d, const double* drho_d, const double* poisson_green_d,
                          int xc_functionals, double* dV_d);
 
+/* ---- transfer between two bases of the same lattice (src/transfer.jl) ----------------------------------------------------
+ * transfer_blochwave_kpt (transfer.jl:46-124) for all bands of one k-block in ONE launch.  kb_in and kb_out are k-blocks of
+ * the same lattice whose k-points differ by the integer vector dG_h[3] = k_out - k_in (0 0 0 for the same k-point); they may
+ * belong to two different basis handles (other Ecut, other FFT grid) of the same device.  in_d: n_G(kb_in) x n_bands,
+ * out_d: n_G(kb_out) x n_bands, both in the caller's full-sphere complex layout (a Gamma-real block included); they must
+ * not overlap.  Row r of the output, carrying the plane wave G, receives the input row that carries G + dG; if G + dG lies
+ * outside the input cube or outside the input sphere the row is set to zero, and input rows whose plane wave the output
+ * sphere lacks are dropped -- the same rule small -> large and large -> small.  A gather over the output rows through the
+ * input block's inverse cube -> row map (built at the first call that reads from the block, kept with it): every entry
+ * of the n_G(kb_out) x n_bands output is written exactly once, rows from n_G(kb_out) to ld_out are not touched, no atomics,
+ * results are bit-for-bit reproducible and equal to the moved numbers.
+ * Streams: the kernel runs on the stream of kb_out's basis after a device-side wait for the work queued on the stream of
+ * kb_in's basis, and that stream in turn waits for the kernel; the host does not block (one handle on both sides: one
+ * stream, no event).
+ * DFTK_MI_EINVAL, outputs untouched: n_bands < 0, a leading dimension below the rows of its sphere, blocks on different
+ * devices, a plane-wave sharded block, or a dG that does not fit the blocks -- where both blocks were created with kinetic
+ * energies, partners must carry the same |k + G|^2 / 2 (a host pass over the output rows, made once per input block
+ * and dG and remembered on the output block). */
+int dftk_mi_transfer_blochwave(dftk_mi_kblock* kb_in, dftk_mi_kblock* kb_out, const int* dG_h /* [3] */, int n_bands,
+                               const dftk_mi_cplx* in_d, int64_t ld_in, dftk_mi_cplx* out_d, int64_t ld_out);
+/* transfer_density (transfer.jl:165-178): rho_out = irfft(basis_out, T fft(basis_in, rho_in)) for n_spin (1 or 2) real cubes
+ * stored one after the other.  cube_kb_in / cube_kb_out: full-cube k-blocks (n_G = nx ny nz, identity mapping) of the two
+ * bases.  T copies the eight index blocks of transfer_mapping (transfer.jl:10-31) and zeroes the rest: per axis, indices
+ * of equal signed frequency correspond over the frequency range of the shorter axis -- the unmatched frequency -n/2 of an
+ * even shorter axis is carried to -n/2 of the longer one, whose +n/2 stays zero, so small -> large -> small is not the
+ * identity on such a grid (transfer.jl:158-163).  The inverse transform is the library's complex cube transform followed
+ * by the real part (as everywhere in this library), where the reference's half-spectrum transform reads the x >= 0
+ * half only: the two differ in the contribution of that unmatched plane along x alone, which the density of orbitals
+ * on a sphere inside the grid does not populate.  Normalisation: 1 / N_in overall; the integral of the density is preserved
+ * small -> large.  Streams: as above (forward transform on the input basis' stream, the rest on the output basis').
+ * Asynchronous. */
+int dftk_mi_transfer_density(dftk_mi_kblock* cube_kb_in, dftk_mi_kblock* cube_kb_out, int n_spin, const double* rho_in_d,
+                             double* rho_out_d);
+
+/* ---- refinement metric (src/postprocess/refine.jl:20-84) -----------------------------------------------------------------
+ * invert_refinement_metric for ONE k-block, all columns in one call: solves
+ *     M_c x_c = P res_c,   M_c = P T_c^{1/2} P T_c^{1/2} P,   T_c = kinetic + mean_kin[c],   P = 1 - psi psi',   c = 0 .. n - 1
+ * with mean_kin[c] = sum_G kinetic_G |psi_Gc|^2 (precondprep!, computed here on the device), by conjugate gradients from
+ * x = 0 preconditioned with P T_c^{-1} P, until ||r_c|| <= tol (the reference: 100 eps) or maxiter passes (the reference:
+ * 20), and projects the result once more: psi' x = 0.  psi_d: n orthonormal columns; res_d: n columns (their components along
+ * psi are projected out); out_d: n_G x n.  Every column has its own alpha and beta and is frozen bit for bit once it has
+ * converged; iters_h[c] is the reference's n_iter of column c (the pass in which its residual norm was first seen at or
+ * below tol; 1 = at the start), or the number of passes made if it never was, and resnorm_h[c] its last residual norm -- a
+ * column that did not converge is REPORTED (resnorm_h[c] > tol), the call still returns 0.  Projections are zgemm calls,
+ * the scalings one launch for all columns; ONE host synchronisation per CG pass (the fetch of the residual norms).
+ * Workspace: 5 n_G n complex numbers of the basis' response workspace.  Unsharded blocks only, not inside a batched
+ * multi-k call (DFTK_MI_EINVAL). */
+int dftk_mi_refinement_metric_solve(dftk_mi_kblock* kb, int n, const dftk_mi_cplx* psi_d, int64_t ld_psi,
+                                    const dftk_mi_cplx* res_d, int64_t ld_res, double tol, int maxiter, dftk_mi_cplx* out_d,
+                                    int64_t ld_out, int* iters_h, double* resnorm_h);
+
 /* ---- exact exchange at the Gamma point (src/terms/exact_exchange.jl, ExchangeOperator of src/terms/operators.jl:184-210) --
  * The Fock operator built from n_occ orbitals phi (n_G x n_occ) applied to n_bands columns psi:
  *     W_m (+)= - sum_n weight_h[n] FFT[ phi_n(r) IFFT[ K(G) FFT[ conj(phi_n(r)) psi_m(r) ] ] ]
