@@ -1478,6 +1478,10 @@ extern "C" int dftk_mi_zgemm_plan_host(char transA, int64_t m, int64_t n, int64_
 }
 
 int zgemm_fold_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int cap, int* items4, int* count);   // gemm_kernels.hip
+int zgemm_compact_host(int gm, int gn, int q, int nsplit, int cap, int* items3, int* count);   // gemm_kernels.hip
+extern "C" int dftk_mi_zgemm_compact_host(int gm, int gn, int q, int nsplit, int cap, int* items3, int* count) {
+    return zgemm_compact_host(gm, gn, q, nsplit, cap, items3, count);
+}
 extern "C" int dftk_mi_zgemm_fold_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int cap, int* items4, int* count) {
     return zgemm_fold_host(transA, m, n, k, flags, cap, items4, count);
 }

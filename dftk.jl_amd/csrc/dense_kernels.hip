@@ -306,8 +306,9 @@ __global__ __launch_bounds__(256) void k_trtri_upper_blk(int n, const cd* __rest
 // factor L (A = L L^H, R = L^H is what the caller gets), keeps its rows in REGISTERS (two rows of 16 per thread), consumes
 // the panels j < l as their owners publish them (global buffer + release / acquire flag at agent scope: the workgroups sit
 // on different XCDs), then factors its own diagonal block, scales its column panel and publishes it.  The critical path per
-// panel is: read 16 columns from L2, 256 complex multiply-adds per row, a 16-step Cholesky of the diagonal block in LDS, a
-// 16-step substitution per row, publish: ~10 us.  The inverse follows in the same launch: workgroup l forward-substitutes
+// panel is: read 16 columns from L2, 256 complex multiply-adds per row, a 16-step Cholesky of the diagonal block in the
+// registers of the first wave, a 16-step substitution per row, publish: ~13 us measured as call time / panels at n = 503
+// (real entry).  The inverse follows in the same launch: workgroup l forward-substitutes
 // block column l of X = L^{-1} (X_kl = -W_k sum_j L_kj X_jl with the published inverse diagonal blocks W_k), and
 // R^{-1} = X^H.  All nb <= 32 workgroups are resident at once (1 per CU), which is what makes the flag waits safe.
 #define CCB 16
@@ -332,17 +333,39 @@ __device__ __forceinline__ void e_load_conj(cd& dst, cd a, bool diag) { dst = ma
 __device__ __forceinline__ void e_load_conj(double& dst, cd a, bool) { dst = a.x; }
 __device__ __forceinline__ cd e_out_conj(cd a) { return make_double2(a.x, -a.y); }
 __device__ __forceinline__ cd e_out_conj(double a) { return make_double2(a, 0.0); }
+// Hand-off of a published panel between workgroups (they sit on different XCDs: private L2s, a vector L1 per CU that no
+// other CU's store refreshes).  ONE lane pays the agent-scope fences, on both sides: the consumer's lane 0 polls the flag
+// relaxed, invalidates this CU's L1 once and holds the workgroup barrier until the invalidate has completed, then every
+// wave reads the panel with plain loads; on the producer every storing wave drains its stores, the barrier collects them and
+// lane 0 writes the XCD's L2 back once before the relaxed flag store.  (Before: __threadfence() -- write-back AND
+// invalidate -- in all 512 threads on both sides, 2-4 times one lane's cost per hand-off.)  The waits are inline
+// assembly so that no compiler pass can drop them as redundant.  Correctness leans on __syncthreads() being a barrier WITH
+// the workgroup-scope release / acquire fences: they make lane 0's agent-scope fence cover the other waves' accesses
+// (the chain is transitive; L1 and L2 are shared by the waves of the workgroup).  A bare s_barrier in its place carries
+// no fence and would let the compiler and the hardware move the other waves' loads and stores across the hand-off.
 __device__ __forceinline__ void coop_wait(const int* flag) {
-    if (threadIdx.x == 0)
-        while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0) __builtin_amdgcn_s_sleep(1);
+    if (threadIdx.x == 0) {
+        while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) __builtin_amdgcn_s_sleep(1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     __syncthreads();
-    __threadfence();
 }
 __device__ __forceinline__ void coop_signal(int* flag) {
-    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave: its stores have left the CU
     __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
+// value of lane `l` (a compile-time constant after unrolling) for the whole wave, through the scalar registers
+__device__ __forceinline__ double lane_bcast(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ cd lane_bcast(cd v, int l) { return make_double2(lane_bcast(v.x, l), lane_bcast(v.y, l)); }
 template <typename T>
 __global__ __launch_bounds__(CCT, 1) void k_potrf_trtri_coop(int n, cd* __restrict__ A, int64_t lda, cd* __restrict__ Z,
                                                              int64_t ldz, T* __restrict__ Lbuf, T* __restrict__ Wbuf,
@@ -351,7 +374,8 @@ __global__ __launch_bounds__(CCT, 1) void k_potrf_trtri_coop(int n, cd* __restri
     T* Xs = reinterpret_cast<T*>(sm);                   // phase 2: [rows][16] block column of X = L^{-1}
     __shared__ T Dm[CCB][CCB + 1];                       // diagonal block (lower), then scratch
     __shared__ T Wm[CCB][CCB + 1];                       // its inverse
-    __shared__ T Lj[CCB][CCB + 1];                       // L_{l,j} of the panel being consumed
+    __shared__ __attribute__((aligned(16))) T Lj[CCB][CCB];   // L_{l,j} of the panel being consumed (read as broadcasts only)
+    __shared__ double Dinv[CCB];                         // 1 / diagonal of the factored block
     const int l = blockIdx.x, nb = gridDim.x, tid = threadIdx.x;
     const int r0 = CCB * l;                              // first global row / column of this block
     const int np = CCB * nb;                             // padded order
@@ -379,12 +403,16 @@ __global__ __launch_bounds__(CCT, 1) void k_potrf_trtri_coop(int n, cd* __restri
     for (int j = 0; j < l; ++j) {
         coop_wait(flags + j);
         const T* P = panel(j) + (size_t)(r0 - CCB * j) * CCB;      // my first row inside panel j
-        if (tid < CCB * CCB) Lj[tid >> 4][tid & 15] = P[tid];      // rows r0 .. r0+15 of the panel = L_{l,j}
+        // rows r0 .. r0+15 of the panel = L_{l,j}: loaded together with my own row (one round trip to L2, not two)
+        T lj;
+        e_set(lj, 0.0);
+        if (tid < CCB * CCB) lj = P[tid];
         T p[CCB];
         if (have_row) {
 #pragma unroll
             for (int t = 0; t < CCB; ++t) p[t] = P[(size_t)i * CCB + t];
         }
+        if (tid < CCB * CCB) Lj[tid >> 4][tid & 15] = lj;
         __syncthreads();
         if (have_row) {
 #pragma unroll
@@ -396,68 +424,55 @@ __global__ __launch_bounds__(CCT, 1) void k_potrf_trtri_coop(int n, cd* __restri
                 e_sub(row[c], s);
             }
         }
-        __syncthreads();   // Lj is rewritten by the next panel
+        // (no barrier here: Lj is rewritten behind the barrier of the next coop_wait, which every thread reaches after
+        //  its last read of this panel's Lj)
     }
-    // ---- factor the diagonal block (threads 0..15 hold its rows): wave 0 alone, LDS, no workgroup barriers
-    if (tid < CCB) {
-#pragma unroll
-        for (int c = 0; c < CCB; ++c) Dm[tid][c] = row[c];
-    }
-    __syncthreads();
+    // ---- factor the diagonal block: lanes 0..15 of wave 0 hold its rows in REGISTERS.  The 16 steps run without LDS, fences
+    // or barriers; the pivot and the multipliers of a step reach the other lanes through the scalar registers (lane_bcast).
+    // Element by element the operations and their order are those of the right-looking factorisation in place (scale
+    // column c, then subtract its outer product from the lower triangle of the trailing block), so the factor is bit for
+    // bit the one of the earlier LDS form -- which spent ~1000 cycles per step on four dependent LDS round trips.
     if (tid < 64) {
-        // lane owns elements (k, m) = (4 q + (lane >> 4), lane & 15), q = 0..3
-        const int m = tid & 15, kb = tid >> 4;
+        const bool mine = tid < CCB;   // (lanes 16..63 hold rows below the block: they follow the control flow only)
+        double my_inv = 1.0;
+#pragma unroll
         for (int c = 0; c < CCB; ++c) {
-            const double d = e_re(Dm[c][c]);
+            const double d = e_re(lane_bcast(row[c], c));
             const bool ok = d > 0.0 && isfinite(d);
             if (!ok && tid == 0) atomicCAS(info, 0, r0 + c + 1);
             const double sd = ok ? sqrt(d) : 1.0, inv = 1.0 / sd;
-            __builtin_amdgcn_wave_barrier();
-            if (m == c) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int k = 4 * q + kb;
-                    if (k == c)
-                        e_set(Dm[k][c], sd);
-                    else if (k > c)
-                        Dm[k][c] = e_scale(Dm[k][c], inv);
-                }
+            if (tid == c) {
+                e_set(row[c], sd);
+                my_inv = inv;
+            } else if (mine && tid > c) {
+                row[c] = e_scale(row[c], inv);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (m > c) {
-                const T lm = Dm[m][c];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int k = 4 * q + kb;
-                    if (k >= m) e_sub(Dm[k][m], e_mulc(Dm[k][c], lm));
-                }
+            for (int m = c + 1; m < CCB; ++m) {
+                const T lm = lane_bcast(row[c], m);
+                if (mine && tid >= m) e_sub(row[m], e_mulc(row[c], lm));
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
+        if (mine) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int k = 4 * q + kb;
-            if (m > k) e_set(Dm[k][m], 0.0);
+            for (int m = 0; m < CCB; ++m) {
+                if (m > tid) e_set(row[m], 0.0);
+                Dm[tid][m] = row[m];
+            }
+            Dinv[tid] = my_inv;
         }
     }
     __syncthreads();
-    // ---- column panel below the diagonal block: y D^H = x  per row;  the diagonal block rows take D itself
+    // ---- column panel below the diagonal block: y D^H = x  per row
     if (have_row) {
-        if (i < CCB) {
-#pragma unroll
-            for (int c = 0; c < CCB; ++c) row[c] = Dm[i][c];
-        } else {
+        if (i >= CCB) {   // (the rows of the diagonal block are in their registers already)
 #pragma unroll
             for (int c = 0; c < CCB; ++c) {
                 T acc = row[c];
 #pragma unroll
                 for (int t = 0; t < CCB; ++t)
                     if (t < c) e_sub(acc, e_mulc(row[t], Dm[c][t]));
-                row[c] = e_scale(acc, 1.0 / e_re(Dm[c][c]));
+                row[c] = e_scale(acc, Dinv[c]);   // Dinv[c] = 1 / Dm[c][c], the factor's own quotient
             }
         }
         // ---- publish my row of panel l
@@ -484,7 +499,7 @@ __global__ __launch_bounds__(CCT, 1) void k_potrf_trtri_coop(int n, cd* __restri
 #pragma unroll
             for (int t = 0; t < CCB; ++t)
                 if (t < k) e_sub(acc, e_mul(Dm[k][t], w[t]));
-            w[k] = e_scale(acc, 1.0 / e_re(Dm[k][k]));
+            w[k] = e_scale(acc, Dinv[k]);
             if (k < m) e_set(w[k], 0.0);
         }
 #pragma unroll

@@ -84,6 +84,28 @@ __host__ __device__ inline bool gemm_fold_item(int id, int gm, int gn, int* row_
     return *row_t < gm;
 }
 
+// Work item of workgroup `id` of a compact UPPER launch over gm row panels x gn column tiles x nsplit k-chunks, q = column
+// tiles per row panel (grid = 8 ceil(L nsplit / 8), L = live tiles): row panel r keeps its column tiles >= r q; the items
+// (k-chunk, row panel, live column tile) in this order are dealt to the XCDs (id & 7) in 8 contiguous blocks.  false: no work.
+// (host + device: dftk_mi_zgemm_compact_host lists the items of a launch for the CPU test-suite)
+__host__ __device__ inline bool gemm_compact_item(int id, int gm, int gn, int q, int nsplit, int* z, int* row_t, int* col_t) {
+    const int xcd = id & 7, slot = id >> 3;
+    int L = 0;
+    for (int r = 0; r < gm; ++r) L += (gn - r * q > 0) ? gn - r * q : 0;
+    const int N = L * nsplit, per = (N + 7) >> 3;
+    const int item = xcd * per + slot;
+    if (slot >= per || item >= N) return false;
+    *z = item / L;
+    int t = item - *z * L, r = 0;
+    while (t >= gn - r * q) {
+        t -= gn - r * q;
+        ++r;
+    }
+    *row_t = r;
+    *col_t = r * q + t;
+    return true;
+}
+
 template <bool CONJA, int MODE, bool REAL, int RN, bool FOLD = false>
 __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int m, int n, int K, int kchunk, int gm, int gn,
                                                                int rt0, int ct0, int lsplit, int upper,
@@ -113,19 +135,7 @@ __global__ __launch_bounds__(GEMM_WAVES * 64, M3_MIN_BLOCKS) void k_zgemm_3m(int
         // workgroups of an UPPER launch leave at once; measured: the live ones then spread unevenly over the CUs as soon
         // as an XCD holds more than ~50 of them)
         const int q = (GEMM_BM << ((upper >> 5) & 1)) / BN;   // (upper & 32: two REAL rows per row of C, see below)
-        int L = 0;
-        for (int r = 0; r < gm; ++r) L += max(0, gn - r * q);
-        const int N = L * nsplit, per = (N + 7) >> 3;
-        const int item = xcd * per + slot;
-        if (slot >= per || item >= N) return;   // whole workgroup
-        z = item / L;
-        int t = item - z * L, r = 0;
-        while (t >= gn - r * q) {
-            t -= gn - r * q;
-            ++r;
-        }
-        row_t = r;
-        col_t = r * q + t;
+        if (!gemm_compact_item(id, gm, gn, q, nsplit, &z, &row_t, &col_t)) return;   // whole workgroup
     } else if (upper & 4) {
         // K-split launches: all tiles of one k-chunk on the SAME XCD, so that both the A chunk and the
         // B chunk are fetched from HBM once and shared through that XCD's L2
@@ -806,6 +816,27 @@ int zgemm_fold_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int
             }
             ++*count;
         }
+    }
+    return 0;
+}
+
+// Host-only: the (k-chunk, tile row, tile column) of every workgroup with work of a compact UPPER launch, in workgroup
+// order, 3 ints per item (CPU test-suite: every live (chunk, tile) exactly once, no dead one)
+int zgemm_compact_host(int gm, int gn, int q, int nsplit, int cap, int* items3, int* count) {
+    if (gm <= 0 || gn <= 0 || q <= 0 || nsplit <= 0 || cap < 0 || !count || (cap > 0 && !items3)) return DFTK_MI_EINVAL;
+    int64_t live = 0;
+    for (int r = 0; r < gm; ++r) live += std::max(0, gn - r * q);
+    const int64_t nblk = ((live * nsplit + 7) / 8) * 8;   // the grid of the launch (zgemm_to)
+    if (nblk > INT32_MAX) return DFTK_MI_EINVAL;
+    *count = 0;
+    for (int id = 0; id < (int)nblk; ++id) {
+        int z, row, col;
+        if (!gemm_compact_item(id, gm, gn, q, nsplit, &z, &row, &col)) continue;
+        if (*count < cap) {
+            int* e = items3 + 3 * (int64_t)*count;
+            e[0] = z; e[1] = row; e[2] = col;
+        }
+        ++*count;
     }
     return 0;
 }

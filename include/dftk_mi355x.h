@@ -961,6 +961,12 @@ int dftk_mi_zgemm_plan_host(char transA, int64_t m, int64_t n, int64_t k, int fl
  * (tile gn - 1 - p, then tile p): the tiles of that launch in workgroup order, 4 ints each { tile row, tile column,
  * first k, end k } (at most cap are written), *count = their number, 0 when the shape does not take that launch. */
 int dftk_mi_zgemm_fold_host(char transA, int64_t m, int64_t n, int64_t k, int flags, int cap, int* items4, int* count);
+/* Host-only, for the CPU test-suite (not part of the computing ABI; it may change with the launch plan).
+ * A DFTK_MI_GEMM_UPPER product whose interior launch runs over its LIVE tiles only (dftk_mi_zgemm_plan_host: placement 2):
+ * gm row panels x gn column tiles x nsplit K chunks, q = column tiles per row panel (row panel r keeps its column
+ * tiles >= r q).  The work items of that launch in workgroup order, 3 ints each { K chunk, tile row, tile column } (at
+ * most cap are written), *count = their number. */
+int dftk_mi_zgemm_compact_host(int gm, int gn, int q, int nsplit, int cap, int* items3, int* count);
 /* Schedule of the blocked Jacobi eigensolver for an n x n matrix: *n_blocks = number of 16-wide blocks (even,
  * padded); for round in [-1, *n_blocks - 2] (pass pairs = where = NULL to query n_blocks only):
  * pairs[2k], pairs[2k+1] = the k-th disjoint block pair of the round (round -1: (2k, 2k+1), then a round-robin
