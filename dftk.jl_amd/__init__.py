@@ -54,3 +54,4 @@ from .hubbard import (OrbitalManifold, Hubbard, resolve_hubbard_manifold, wigner
 from .transfer import transfer_blochwave_kpt, transfer_blochwave, transfer_density  # noqa: F401,E402
 from .refine import (RefinementResult, refine_scfres, refine_energies, refine_forces, invert_refinement_metric,  # noqa: F401,E402
                      select_occupied_orbitals, check_full_occupation, compute_projected_gradient, apply_Omega, apply_K)
+from .direct_minimization import direct_minimization, backtracking, LbfgsNative  # noqa: F401,E402

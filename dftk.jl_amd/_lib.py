@@ -203,6 +203,15 @@ _SIGNATURES = {
     "dftk_mi_anderson_destroy": (C.c_int, [C.c_void_p]),
     "dftk_mi_anderson_reset": (C.c_int, [C.c_void_p]),
     "dftk_mi_anderson_history": (C.c_int, [C.c_void_p]),
+    "dftk_mi_stiefel_project_tangent": (C.c_int, [C.c_void_p, _i64, C.c_int, C.c_void_p, _i64, C.c_void_p, _i64]),
+    "dftk_mi_lbfgs_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "dftk_mi_lbfgs_destroy": (C.c_int, [C.c_void_p]),
+    "dftk_mi_lbfgs_reset": (C.c_int, [C.c_void_p]),
+    "dftk_mi_lbfgs_history": (C.c_int, [C.c_void_p]),
+    "dftk_mi_lbfgs_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                                       C.POINTER(C.c_int)]),
+    "dftk_mi_lbfgs_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "dftk_mi_anderson_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dftk_mi_chi0_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_double,
                                    C.c_double, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int),

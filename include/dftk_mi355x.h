@@ -913,6 +913,58 @@ int dftk_mi_chi0_mix(dftk_mi_kblock* cube_kblock, int n_comp, const double* reci
                      const double* ldos_d, double dvol, int dielectric, double kTF, double eps_r, const double* dF_d,
                      double reltol, int krylovdim, int maxiter, double* drho_d, int* n_applies, int* converged);
 
+/* ---- the optimiser of direct_minimization (dm_kernels.hip; src/scf/direct_minimization.jl, which hands these steps to
+ * Optim.jl's L-BFGS on a product of Stiefel manifolds) ---------------------------------------------------------------
+ * Optim's project_tangent!(Stiefel(), g, x): G <- G - X (X'G + G'X) / 2 in place, X and G n x m column-major.  One zgemm,
+ * one kernel that symmetrises the m x m matrix on the device, one zgemm; no host synchronisation (beyond a first-use
+ * growth of the workspace).  DFTK_MI_EINVAL, G untouched: n < 1, m < 1, a leading dimension below n, X_d == G_d, a call
+ * inside a batched multi-k call. */
+int dftk_mi_stiefel_project_tangent(dftk_mi_basis* basis, int64_t n, int m, const dftk_mi_cplx* X_d, int64_t ldx,
+                                    dftk_mi_cplx* G_d, int64_t ldg);
+/* L-BFGS on packed vectors.  A packed vector is a list of n_blocks column-major complex blocks, block b of n_rows[b] x
+ * n_cols[b] entries with a leading dimension >= n_rows[b], given as HOST arrays of device pointers and of leading
+ * dimensions.  The inner product is Optim's: <a, b> = sum over blocks and entries of Re(conj(a) b), no k-weights.
+ *
+ * The handle holds on the device memory + 1 slots of pairs (s, y), the previous point and the previous gradient, each
+ * stored block after block without padding ((2 memory + 4) packed vectors: the spare slot receives the candidate pair of an
+ * update, so that a rejected pair leaves a full history as it was), the loop coefficients alpha_i and two buffers of
+ * partial sums.  rho_i = 1 / <s_i, y_i> is kept with the history and reaches the kernels through device memory.
+ *
+ * update: the first call after create / reset only stores (x, g): *kept = 0, *sy_h = 0, no synchronisation.  Every later
+ * call is ONE fused pass (reads x, g, x_prev, g_prev; writes s = x - x_prev and y = g - g_prev into the spare slot and the
+ * new x_prev, g_prev; block partial sums of <s, y> in a fixed order) and ONE host synchronisation, after which *sy_h =
+ * <s, y>.  The pair enters the history (the oldest one leaves when memory pairs are held) only if <s, y> is finite and
+ * > 0 -- stricter than Optim, which skips the infinite case only; otherwise the history is unchanged and *kept = 0.
+ *
+ * direction: d = -H g by the two-loop recursion; g is not modified, d_d must not alias g_d and serves as the work vector.
+ *   newest to oldest: alpha_i = rho_i <s_i, q>, q -= alpha_i y_i;
+ *   middle step     : r = P^-1 q / scale_b, where P^-1 is the Teter-Payne-Allan ldiv! of the block's kinetic vector with
+ *                     mean_kin_h[b][n] for column n, kin-wise mean_kin / (mean_kin + kin) exactly as dftk_mi_tpa_ldiv
+ *                     applies it (the reference's DMPreconditioner.ldiv!, the caller passes scale_b = the k-weight);
+ *                     kblocks == NULL: r = q / scale_b;
+ *   oldest to newest: beta = rho_i <y_i, r>, r += (alpha_i - beta) s_i;     d = -r.
+ * Every step is one launch of one kernel body: it sums the partial inner products the previous launch left (fixed order),
+ * reads rho_i / alpha_i from device memory, applies its axpy and leaves the partial sums of the next inner product, so that
+ * every history vector is read once per loop: 2 k + 1 launches with k pairs held (1 with an empty history, where the result
+ * is exactly the middle step, negated), whatever n_blocks (one grid walks a table of work items over all blocks).  No host
+ * synchronisation and no host read of a device result, no atomics: two calls give bitwise identical results.  The
+ * pointer tables, mean_kin_h and rho travel through two pinned staging buffers used in turn; only a third call while the
+ * first is still in flight waits (counted as a host synchronisation).  Runs on the basis' stream.
+ *
+ * DFTK_MI_EINVAL, every output untouched: sizes below 1, memory < 1, a null pointer or a leading dimension below the rows
+ * given at creation, a k-block whose sphere is not n_rows[b] long, scale_b <= 0, a call inside a batched multi-k call. */
+typedef struct dftk_mi_lbfgs dftk_mi_lbfgs;
+int dftk_mi_lbfgs_create(dftk_mi_basis* basis, int n_blocks, const int64_t* n_rows_h, const int* n_cols_h, int memory,
+                         dftk_mi_lbfgs** out);
+int dftk_mi_lbfgs_destroy(dftk_mi_lbfgs* acc);
+int dftk_mi_lbfgs_reset(dftk_mi_lbfgs* acc);
+int dftk_mi_lbfgs_history(const dftk_mi_lbfgs* acc);   /* pairs held */
+int dftk_mi_lbfgs_update(dftk_mi_lbfgs* acc, const dftk_mi_cplx* const* x_d, const int64_t* ldx_h,
+                         const dftk_mi_cplx* const* g_d, const int64_t* ldg_h, double* sy_h, int* kept);
+int dftk_mi_lbfgs_direction(dftk_mi_lbfgs* acc, const dftk_mi_cplx* const* g_d, const int64_t* ldg_h,
+                            dftk_mi_kblock* const* kblocks /* or NULL */, const double* const* mean_kin_h /* per block, or NULL */,
+                            const double* scale_h /* [n_blocks] */, dftk_mi_cplx* const* d_d, const int64_t* ldd_h);
+
 /* Process-wide counters since load: kernel launches issued by the library and host synchronisations it waited on
  * (stream synchronisations of its drivers, result fetches, scheduling rounds of the batched k-point driver).  For the
  * many-small-k workloads these two ARE the cost model; either pointer may be NULL. */
