@@ -23,7 +23,8 @@ from .hamiltonian import DftHamiltonianBlock, mul_  # noqa: F401,E402
 from .terms import energy_hamiltonian, guess_density  # noqa: F401,E402
 from .eigen import (lobpcg_hyper, diagonalize_all_kblocks, PreconditionerTPA, random_orbitals,  # noqa: F401,E402
                     columnwise_norms, columnwise_dots, ortho_qr, interpolate_kpoint, lobpcg_residual_history)
-from .densities import compute_density  # noqa: F401,E402
+from .densities import (compute_density, compute_kinetic_energy_density,  # noqa: F401,E402
+                        von_weizsaecker_kinetic_energy_density, guess_kinetic_energy_density)
 from .mixing import (SimpleMixing, KerkerMixing, KerkerDosMixing, DielectricMixing, LdosMixing, HybridMixing,  # noqa: F401,E402
                      Chi0Mixing, compute_dos, compute_ldos)
 from .scf import (self_consistent_field, next_density, compute_occupation, AdaptiveBands, FixedBands,  # noqa: F401,E402

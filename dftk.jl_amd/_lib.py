@@ -121,6 +121,14 @@ _SIGNATURES = {
     "dftk_mi_cube_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dftk_mi_xc_gga_spin": (C.c_int, [C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "dftk_mi_kblock_set_kpoint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dftk_mi_kblock_set_tau_potential": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dftk_mi_kblocks_set_tau_potential": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
+    "dftk_mi_kinetic_energy_density_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, C.c_void_p]),
+    "dftk_mi_local_potential_mgga": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dftk_mi_xc_mgga": (C.c_int, [C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "dftk_mi_symmetrize_rho": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dftk_mi_mix_kerker": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "dftk_mi_mix_dielectric": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),

@@ -101,10 +101,10 @@ def _basis_on(basis, kgrid, build_terms=True):
                           use_symmetries_for_kpoint_reduction=basis.use_symmetries_for_kpoint_reduction)
 
 
-def _solve(bs_basis, rho, n_bands, n_extra, tol, seed, diag_kwargs, hubbard_n=None):
+def _solve(bs_basis, rho, n_bands, n_extra, tol, seed, diag_kwargs, hubbard_n=None, tau=None):
     with bs_basis.on_library_stream():
         # (the Hubbard term of bs_basis builds the manifold's orbitals at the new k-points)
-        _, ham = energy_hamiltonian(bs_basis, None, None, rho=rho, only_hamiltonian=True, hubbard_n=hubbard_n)
+        _, ham = energy_hamiltonian(bs_basis, None, None, rho=rho, only_hamiltonian=True, hubbard_n=hubbard_n, tau=tau)
         gen = torch.Generator(device=bs_basis.device)
         gen.manual_seed(seed)
         eig = diagonalize_all_kblocks(lobpcg_hyper, ham, n_bands + n_extra, n_conv_check=n_bands, tol=tol, generator=gen,
@@ -118,7 +118,7 @@ def _solve(bs_basis, rho, n_bands, n_extra, tol, seed, diag_kwargs, hubbard_n=No
 
 
 def compute_bands(basis_or_scfres, kgrid_or_kpath, n_bands=None, n_extra=3, rho=None, eF=None, tol=1e-3,
-                  kline_density=40, kchunk=None, keep_psi=True, seed=0, hubbard_n=None, **diag_kwargs):
+                  kline_density=40, kchunk=None, keep_psi=True, seed=0, hubbard_n=None, tau=None, **diag_kwargs):
     """``compute_bands(basis | scfres, kgrid | kpath; n_bands, n_extra, rho, eF, tol, kline_density)``
     (band_structure.jl:14-92): ``n_bands`` eigenpairs of the Hamiltonian of ``rho`` at other k-points.  From an ``scfres`` the
     density and the Fermi level are its own and ``n_bands`` defaults to ``default_n_bands_bandstructure(scfres)``.  Returns a
@@ -135,6 +135,7 @@ def compute_bands(basis_or_scfres, kgrid_or_kpath, n_bands=None, n_extra=3, rho=
         rho = scfres["rho"] if rho is None else rho
         eF = scfres.get("eF") if eF is None else eF
         hubbard_n = scfres.get("hubbard_n") if hubbard_n is None else hubbard_n
+        tau = scfres.get("tau") if tau is None else tau      # (meta-GGA: the kinetic energy density beside rho)
         if n_bands is None:
             n_bands = default_n_bands_bandstructure(scfres)
     else:
@@ -161,7 +162,7 @@ def compute_bands(basis_or_scfres, kgrid_or_kpath, n_bands=None, n_extra=3, rho=
 
     if kchunk is None:
         bs_basis = _basis_on(basis, kgrid)
-        eig = _solve(bs_basis, rho, n_bands, n_extra, tol, seed, diag_kwargs, hubbard_n)
+        eig = _solve(bs_basis, rho, n_bands, n_extra, tol, seed, diag_kwargs, hubbard_n, tau)
         X = eig.pop("X")
         eigenvalues, psi, diag = eig["λ"], X if keep_psi else None, [eig]
     else:
@@ -176,7 +177,7 @@ def compute_bands(basis_or_scfres, kgrid_or_kpath, n_bands=None, n_extra=3, rho=
         for c0 in range(0, len(kc), kchunk):
             sub = ExplicitKpoints([list(k) for k in kc[c0:c0 + kchunk]], list(kw[c0:c0 + kchunk]))
             cb = _basis_on(basis, sub)
-            eig = _solve(cb, rho, n_bands, n_extra, tol, seed + c0, diag_kwargs, hubbard_n)
+            eig = _solve(cb, rho, n_bands, n_extra, tol, seed + c0, diag_kwargs, hubbard_n, tau)
             nc = len(sub.kcoords)
             for s in range(n_spin):
                 per_spin[s][0].extend(eig["λ"][s * nc:(s + 1) * nc])

@@ -173,6 +173,13 @@ class PlaneWaveBasis:
             if gamma_real is True:
                 raise NotImplementedError("gamma_real=True is not available for models with exact exchange")
             gamma_real = False
+        # meta-GGA: the Gamma-real format and the sharded pipelines do not know the div-A-grad term
+        if getattr(model, "uses_tau", False):
+            if gamma_real is True:
+                raise NotImplementedError("gamma_real=True is not available for meta-GGA functionals")
+            if (comm_pw is not None and comm_pw.size > 1) or (comm_kpts is not None and comm_kpts.size > 1):
+                raise NotImplementedError("meta-GGA functionals run on one rank (comm_pw and comm_kpts of size 1)")
+            gamma_real = False
         self.gamma_real = gamma_real
         self.model = model
         self.Ecut = float(Ecut)

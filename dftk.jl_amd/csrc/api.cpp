@@ -823,6 +823,85 @@ extern "C" int dftk_mi_kblocks_set_potential(int n_kblocks, dftk_mi_kblock* cons
     return launch_pad_potential(kbs[0], V_d);     // asynchronous on the basis' stream
 }
 
+// ---- meta-GGA: the second padded cube of a k-block, v_tau = de/dtau (layout and sharing rule of the local potential above)
+static void release_Vtau(dftk_mi_kblock* kb) {
+    kb->Vtau_buf.reset();
+    kb->Vtau_shared = false;
+    kb->d_Vtau = nullptr;
+}
+
+extern "C" int dftk_mi_kblock_set_kpoint(dftk_mi_kblock* kb, const double* recip_lattice_h, const double* kcoord_h) {
+    if (!kb || !recip_lattice_h || !kcoord_h) return DFTK_MI_EINVAL;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) kb->frame_B[3 * i + j] = recip_lattice_h[i + 3 * j];
+        kb->frame_k[i] = kcoord_h[i];
+    }
+    kb->frame_set = true;
+    return 0;
+}
+
+extern "C" int dftk_mi_kblock_set_tau_potential(dftk_mi_kblock* kb, const double* Vtau_d) {
+    if (!kb) return DFTK_MI_EINVAL;
+    dftk_mi_basis* b = kb->basis;
+    HIPCHK(hipSetDevice(b->device));
+    kb->ho.forget();               // (a kept A X is corrected with (V_new - V_old) X only: it does not follow this term)
+    if (!Vtau_d || kb->Vtau_shared) {
+        HIPCHK(hipStreamSynchronize(b->stream));
+        release_Vtau(kb);
+        if (!Vtau_d) return 0;
+    }
+    if (!kb->frame_set) {
+        dftk_set_error("dftk_mi_kblock_set_tau_potential: the block does not know its k-point (dftk_mi_kblock_set_kpoint)");
+        return DFTK_MI_EINVAL;
+    }
+    if (kb->sh_comm || (kb->gr && kb->gr->on)) {
+        dftk_set_error("dftk_mi_kblock_set_tau_potential: meta-GGA runs on un-sharded blocks of complex orbitals only");
+        return DFTK_MI_EINVAL;
+    }
+    if (!kb->Vtau_buf) {
+        auto own = std::make_shared<DevTable<double>>();
+        HIPCHK(own->alloc((size_t)b->nz * b->ny * b->nxp * sizeof(double)));
+        kb->Vtau_buf = std::move(own);
+        kb->d_Vtau = kb->Vtau_buf->get();
+    }
+    return launch_pad_potential(kb, Vtau_d, kb->d_Vtau);
+}
+
+extern "C" int dftk_mi_kblocks_set_tau_potential(int n_kblocks, dftk_mi_kblock* const* kbs, const double* Vtau_d) {
+    if (n_kblocks < 0 || (n_kblocks > 0 && !kbs)) return DFTK_MI_EINVAL;
+    for (int i = 0; i < n_kblocks; ++i)
+        if (!kbs[i]) return DFTK_MI_EINVAL;
+    bool one_basis = n_kblocks >= 2 && Vtau_d != nullptr;
+    for (int i = 1; i < n_kblocks && one_basis; ++i) one_basis = kbs[i]->basis == kbs[0]->basis;
+    for (int i = 0; i < n_kblocks && one_basis; ++i)
+        one_basis = kbs[i]->frame_set && !kbs[i]->sh_comm && !(kbs[i]->gr && kbs[i]->gr->on);
+    if (!one_basis) {              // (unbinding, a single block, several bases, or a block that must refuse: one by one)
+        for (int i = 0; i < n_kblocks; ++i) CHK(dftk_mi_kblock_set_tau_potential(kbs[i], Vtau_d));
+        return 0;
+    }
+    dftk_mi_basis* b = kbs[0]->basis;
+    HIPCHK(hipSetDevice(b->device));
+    std::shared_ptr<DevTable<double>> sh = kbs[0]->Vtau_shared ? kbs[0]->Vtau_buf : nullptr;
+    bool reuse = sh != nullptr && sh.use_count() == n_kblocks + 1;   // (+ 1: the local copy)
+    for (int i = 0; i < n_kblocks && reuse; ++i) reuse = kbs[i]->Vtau_shared && kbs[i]->Vtau_buf == sh;
+    for (int i = 0; i < n_kblocks; ++i) kbs[i]->ho.forget();
+    if (!reuse) {
+        HIPCHK(hipStreamSynchronize(b->stream));
+        for (int i = 0; i < n_kblocks; ++i) release_Vtau(kbs[i]);
+        sh = std::make_shared<DevTable<double>>();
+        if (sh->alloc((size_t)b->nz * b->ny * b->nxp * sizeof(double)) != hipSuccess) {
+            dftk_set_error("dftk_mi_kblocks_set_tau_potential: out of device memory");
+            return DFTK_MI_EHIP;
+        }
+        for (int i = 0; i < n_kblocks; ++i) {
+            kbs[i]->Vtau_buf = sh;
+            kbs[i]->Vtau_shared = true;
+            kbs[i]->d_Vtau = sh->get();
+        }
+    }
+    return launch_pad_potential(kbs[0], Vtau_d, sh->get());     // asynchronous on the basis' stream
+}
+
 // ------------------------------------------------------------------------------------ H psi
 int apply_nonlocal_rows(dftk_mi_kblock* kb, int nb, const cd* P, int64_t ldP, int64_t rows, const cd* psi,
                         int64_t ldpsi, cd* Hpsi, int64_t ldH, bool accumulate, int gemm_flags, dftk_mi_comm* comm) {
@@ -859,6 +938,12 @@ extern "C" int dftk_mi_apply_H_parts(dftk_mi_kblock* kb, int which, int n_bands,
     const int64_t rows = local_rows(kb);
     if (ld_psi < rows || ld_Hpsi < rows) return DFTK_MI_EINVAL;
     if (n_bands == 0) return 0;   // "Nothing to do if psi empty" (Hamiltonian.jl:141)
+    const bool tau_term = (which & 1) && kb->d_Vtau != nullptr;
+    if (tau_term && (batching() || kb->sh_comm)) {
+        dftk_set_error("dftk_mi_apply_H_parts: the block has a tau potential bound (meta-GGA): the %s does not know the "
+                       "div-A-grad term", batching() ? "batched executor" : "sharded pipeline");
+        return DFTK_MI_EINVAL;
+    }
     if (batching() && !kb->sh_comm) {   // fiber of a batched multi-k call: all k-blocks' bands go through ONE pipeline later
         BOp o;
         o.b = kb->basis;
@@ -886,6 +971,7 @@ extern "C" int dftk_mi_apply_H_parts(dftk_mi_kblock* kb, int which, int n_bands,
         }
         if (nonlocal && kb->n_p > 0) prof_count(kb->basis, PROF_AR_MODEL, 16.0 * (double)kb->n_p * n_bands);
         CHK(launch_local_apply(kb, n_bands, psi, ld_psi, H, ld_Hpsi, kinetic, local));
+        if (tau_term) CHK(mgga_div_a_grad(kb, n_bands, psi, ld_psi, H, ld_Hpsi));
     } else {
         // row-slab sharded block: the FFT pipeline needs whole bands -> slab -> band all-to-all, every rank
         // transforms its share of the bands, band -> slab all-to-all back
@@ -942,6 +1028,20 @@ extern "C" int dftk_mi_local_potential_gga(dftk_mi_kblock* cube_kb, const double
     if (recip_lattice_h) rowmajor3(recip_lattice_h, B);
     return local_potential_lda(cube_kb, B, rho_d, nullptr, nullptr, V_loc_d, poisson_green_d, xc_functionals,
                                density_threshold, V_out_d, energies_h);
+}
+
+extern "C" int dftk_mi_local_potential_mgga(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, const double* rho_d,
+                                            const double* tau_d, const double* V_loc_d, const double* poisson_green_d,
+                                            int xc_functionals, double density_threshold, double* V_out_d, double* Vtau_out_d,
+                                            double* energies_h) {
+    if (!cube_kb || !recip_lattice_h || !rho_d || !tau_d || (!energies_h && !V_out_d) || (V_out_d && !Vtau_out_d) ||
+        (xc_functionals & ~(31 | 192)) || !(xc_functionals & 192) || cube_kb->sh_comm)
+        return DFTK_MI_EINVAL;
+    HIPCHK(hipSetDevice(cube_kb->basis->device));
+    double B[9];
+    rowmajor3(recip_lattice_h, B);
+    return local_potential_lda(cube_kb, B, rho_d, nullptr, nullptr, V_loc_d, poisson_green_d, xc_functionals,
+                               density_threshold, V_out_d, energies_h, tau_d, Vtau_out_d);
 }
 
 extern "C" int dftk_mi_local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_lattice_h,
@@ -1188,6 +1288,17 @@ extern "C" int dftk_mi_xc_gga_spin(dftk_mi_basis* b, int64_t n, const double* rh
     return xc_gga_spin_pointwise(b, n, rho_d, sigma_d, xc_functionals, density_threshold, e_d, vrho_d, vsigma_d);
 }
 
+extern "C" int dftk_mi_xc_mgga(dftk_mi_basis* b, int64_t n, const double* rho_d, const double* sigma_d, const double* tau_d,
+                               int xc_functionals, double density_threshold, double* e_d, double* vrho_d, double* vsigma_d,
+                               double* vtau_d) {
+    if (!b || n < 0 || !rho_d || !sigma_d || !tau_d || !e_d || !vrho_d || !vsigma_d || !vtau_d ||
+        (xc_functionals & ~(DFTK_MI_XC_MGGA_X_SCAN | DFTK_MI_XC_MGGA_C_SCAN)) || !xc_functionals)
+        return DFTK_MI_EINVAL;
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(b->device));
+    return xc_mgga_pointwise(b, n, rho_d, sigma_d, tau_d, xc_functionals, density_threshold, e_d, vrho_d, vsigma_d, vtau_d);
+}
+
 extern "C" int dftk_mi_ifft_sphere(dftk_mi_kblock* kb, const dftk_mi_cplx* c_d, dftk_mi_cplx* cube_d) {
     if (!kb || !c_d || !cube_d) return DFTK_MI_EINVAL;
     HIPCHK(hipSetDevice(kb->basis->device));
@@ -1221,6 +1332,15 @@ extern "C" int dftk_mi_density_accumulate(dftk_mi_kblock* kb, int n_bands, const
     CHK(t.to_bands(reinterpret_cast<const cd*>(psi_d), R1, F));
     if (t.mine == 0) return 0;
     return launch_density(kb, t.mine, F, kb->n_G, weight_h + t.c0[t.me], rho_d);
+}
+
+// compute_kinetic_energy_density's inner loop (src/densities.jl:110-125) for one k-block
+extern "C" int dftk_mi_kinetic_energy_density_accumulate(dftk_mi_kblock* kb, int n_bands, const dftk_mi_cplx* psi_d,
+                                                         int64_t ld_psi, const double* weight_h, double* tau_d) {
+    if (!kb || !psi_d || !weight_h || !tau_d || n_bands < 0 || ld_psi < local_rows(kb)) return DFTK_MI_EINVAL;
+    if (n_bands == 0) return 0;
+    HIPCHK(hipSetDevice(kb->basis->device));
+    return mgga_tau_accumulate(kb, n_bands, reinterpret_cast<const cd*>(psi_d), ld_psi, weight_h, tau_d);
 }
 
 // compute_density's accumulation with the spin index of the k-block spelled out (densities.jl:39:

@@ -293,6 +293,17 @@ struct dftk_mi_kblock {
     bool Vs_shared = false;       // attached by dftk_mi_kblocks_set_potential (stays set when the other holders have left)
     double* d_Vs = nullptr;       // the potential the kernels apply (borrowed: Vs_buf, or ho.dV while the LOBPCG start applies
                                   // V_new - V_old), or null
+    // meta-GGA: [nz*ny*nxp] v_tau = de/dtau / N, layout and sharing rule of Vs_buf (dftk_mi_kblock[s]_set_tau_potential); with
+    // one bound, H psi gains -1/2 div(v_tau grad psi) (mgga_kernels.hip) and the block stays off the batched executor, the
+    // Gamma-real format and the LOBPCG handover, which do not know the term
+    std::shared_ptr<DevTable<double>> Vtau_buf;
+    bool Vtau_shared = false;
+    double* d_Vtau = nullptr;
+    // the frame that turns the integer G of a row into (G + k) in cartesian coordinates (dftk_mi_kblock_set_kpoint)
+    bool frame_set = false;
+    double frame_B[9] = {0};      // recip_lattice, row-major
+    double frame_k[3] = {0};      // the k-point, fractional
+    DevBuf<cd> mgga_buf;          // n_G x nb scratch of the scaled orbitals (grown on demand)
     // nonlocal
     int n_p = 0;
     const cd* P = nullptr;        // borrowed device pointer, n_G x n_p
@@ -353,7 +364,11 @@ int launch_planes_fill(dftk_mi_kblock* kb, int b0, int nbb, const cd* psi, int64
 int launch_local_apply_from_planes(dftk_mi_kblock* kb, int nb, cd* planes, cd* out, int64_t ldout);
 int launch_density_response(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const cd* dpsi, int64_t lddpsi,
                             const double* wo_h, const double* wd_h, double* drho);
-int launch_pad_potential(dftk_mi_kblock* kb, const double* V);
+// dst: the padded cube to fill (null: the block's bound local potential)
+int launch_pad_potential(dftk_mi_kblock* kb, const double* V, double* dst = nullptr);
+// mgga_kernels.hip: tau += sum_n (w_n / 2) sum_a |ifft((G + k)_a psi_n)|^2 and H += -1/2 div(v_tau grad psi) of the bound tau cube
+int mgga_tau_accumulate(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, const double* w_h, double* tau);
+int mgga_div_a_grad(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, cd* H, int64_t ldH);
 int launch_kinetic_only(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t ldpsi, cd* out,
                         int64_t ldout, bool accumulate, bool use_kin);
 
@@ -463,7 +478,7 @@ int local_potential_collinear(dftk_mi_kblock* cube_kb, const double* rho, const 
                               const double* green, int fun_mask, double* V_out, double* energies_h);
 int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* core,
                         const double* grad_core, const double* vloc, const double* green, int fun_mask, double threshold,
-                        double* V_out, double* energies_h);
+                        double* V_out, double* energies_h, const double* tau = nullptr, double* Vtau_out = nullptr);
 int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* core,
                                   const double* grad_core, const double* vloc, const double* green, int fun_mask,
                                   double threshold, double* V_out, double* energies_h);
@@ -483,6 +498,8 @@ int cube_fourier_filter(dftk_mi_kblock* cube_kb, int kind, const double* recip_h
 int cube_gradient(dftk_mi_kblock* cube_kb, const double* recip_h, const double* f, double* grad);
 int xc_gga_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, int fun_mask,
                      double threshold, double* e, double* vrho, double* vsigma);
+int xc_mgga_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, const double* tau, int fun_mask,
+                      double threshold, double* e, double* vrho, double* vsigma, double* vtau);
 
 // setup_kernels.hip
 int sphere_enumerate_host(int nx, int ny, int nz, const double* B, const double* k, double Ecut, int64_t cap,

@@ -1581,13 +1581,13 @@ int launch_density_response(dftk_mi_kblock* kb, int nb, const cd* psi, int64_t l
     });
 }
 
-int launch_pad_potential(dftk_mi_kblock* kb, const double* V) {
+int launch_pad_potential(dftk_mi_kblock* kb, const double* V, double* dst) {
     dftk_mi_basis* b = kb->basis;
     const int64_t rows = (int64_t)b->ny * b->nz;
     const int64_t total = rows * b->nxp;
     const double scale = 1.0 / ((double)b->nx * b->ny * b->nz);
     hipLaunchKernelGGL(k_pad_potential, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, b->stream, b->nx,
-                       b->nxp, rows, scale, V, kb->d_Vs);
+                       b->nxp, rows, scale, V, dst ? dst : kb->d_Vs);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -533,6 +533,11 @@ int gamma_pack_full(dftk_mi_kblock* kb, int nb, const cd* X, int64_t ldx, cd* Z,
 int gamma_apply_H(dftk_mi_kblock* kb, int which, int nb, const cd* psi, int64_t ldpsi, cd* Hpsi, int64_t ldH, const cd* add,
                   int64_t ldadd) {
     if (nb <= 0) return 0;
+    if (kb->d_Vtau) {
+        dftk_set_error("gamma_apply_H: the block has a tau potential bound (meta-GGA): the Gamma-real format does not know the "
+                       "div-A-grad term");
+        return DFTK_MI_EINVAL;
+    }
     if (add && (kb->sh_comm || (which & 4))) {
         dftk_set_error("gamma_apply_H: an addend goes with the local and kinetic parts of an un-sharded block only");
         return DFTK_MI_EINVAL;

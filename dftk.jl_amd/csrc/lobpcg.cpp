@@ -767,7 +767,8 @@ struct Lob {
     // one (LobHandover::take), by a full application otherwise.  Xp, ldX: the caller's start block.
     int start_AX(const cd* Xp, int64_t ldX) {
         LobHandover& ho = kb->ho;
-        bool reuse_ax = kept_AX != nullptr && kb->d_Vs != nullptr && ho.V_kept != nullptr;
+        // (a block with a tau potential never takes the handover: the kept A X is corrected with (V_new - V_old) X only)
+        bool reuse_ax = kept_AX != nullptr && kb->d_Vs != nullptr && ho.V_kept != nullptr && kb->d_Vtau == nullptr;
         // The start block of an SCF step comes back orthonormal to round-off: ortho!(X) is ONE Cholesky-QR pass, and X inv(R)
         // cannot be formed in place.  The block is therefore loaded into tmp (leading dimension N, as X) and the pass lands in X.
         const bool lip = land_in_place();
@@ -1253,7 +1254,9 @@ bool lobpcg_small_eligible(const dftk_mi_kblock* kb, int M) {
     static const bool off = getenv("DFTK_MI_LOBPCG_SMALL") && atoi(getenv("DFTK_MI_LOBPCG_SMALL")) == 0;
     // (DFTK_MI_KBATCH_SEQUENTIAL -- read per call, like the recorder reads it -- runs every recorded operation through its
     //  original entry point, and the fused kernels have none: the general driver then)
-    if (off || getenv("DFTK_MI_KBATCH_SEQUENTIAL") != nullptr || kb->sh_comm || (kb->gr && kb->gr->on)) return false;
+    // (a block with a tau potential, meta-GGA: the small-block driver records its H psi for the batched executor, which does
+    //  not know the div-A-grad term)
+    if (off || getenv("DFTK_MI_KBATCH_SEQUENTIAL") != nullptr || kb->sh_comm || (kb->gr && kb->gr->on) || kb->d_Vtau) return false;
     return M >= 1 && M <= 8 && kb->n_G * (int64_t)M <= DEFER_FETCH_MAX_ELEMS && kb->n_G > 3 * (int64_t)M;
 }
 

@@ -45,6 +45,11 @@ struct Solver {
     }
     // OUT = (H - diag(eps)) Y for m columns (eps: device, m values)
     int apply_H_minus_eps(const cd* Y, cd* OUT, int m, const double* e_d) {
+        if (kb->d_Vtau) {
+            dftk_set_error("sternheimer: the block has a tau potential bound (meta-GGA): the solver does not know the "
+                           "div-A-grad term");
+            return DFTK_MI_EINVAL;
+        }
         const int slot = prof_begin(b, PROF_APPLY_H, (double)m);
         int st = 0;
         if (kb->d_Vs) {

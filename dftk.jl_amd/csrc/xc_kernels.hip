@@ -114,6 +114,7 @@ struct Dual {
     friend __device__ __forceinline__ Dual dcbrt(Dual a) { const double r = cbrt(a.v); return dchain(a, r, r / (3.0 * a.v)); }
     friend __device__ __forceinline__ Dual dlog1p(Dual a) { return dchain(a, log1p(a.v), 1.0 / (1.0 + a.v)); }
     friend __device__ __forceinline__ Dual dexpm1(Dual a) { const double e = expm1(a.v); return dchain(a, e, e + 1.0); }
+    friend __device__ __forceinline__ Dual dexp(Dual a) { const double e = exp(a.v); return dchain(a, e, e); }
 };
 typedef Dual<2> D3;
 typedef Dual<3> D4;
@@ -296,6 +297,92 @@ __global__ __launch_bounds__(256) void k_gga_spin(int64_t n, const double* __res
         vsuu[i] = wuu;
         vsud[i] = wud;
         vsdd[i] = wdd;
+    }
+}
+
+// ---- meta-GGA (SCAN): e(rho, sigma, tau), slots (d/d rho, d/d sigma, d/d tau) of D4.  Closed forms of Sun, Ruzsinszky,
+// Perdew, PRL 115, 036402 (2015) as libxc's unpolarised mgga_x_scan / mgga_c_scan:
+//   p = s^2 = sigma / (4 k_F^2 rho^2),  alpha = (tau - sigma / (8 rho)) / tau_unif,  tau_unif = 3/10 k_F^2 rho
+// sigma is not clamped against 8 rho tau: alpha may be negative, the forms are smooth there.
+__device__ __forceinline__ D4 dinv_root4(D4 a) { return dc<D4>(1.0) / dsqrt(dsqrt(a)); }      // a^(-1/4)
+// the switching function: exp(-c1 alpha / (1 - alpha)) below alpha = 1, -d exp(c2 / (1 - alpha)) above, 0 with zero slope at 1.
+// Next to 1 the exponential underflows to 0 while the slope of its argument stays finite (|1 - alpha| >= 2^-53): no 0 * inf.
+__device__ __forceinline__ D4 scan_switch(D4 alpha, double c1, double c2, double d) {
+    const D4 oma = dc<D4>(1.0) - alpha;
+    if (alpha.v < 1.0) return dexp((-c1) * (alpha / oma));
+    if (alpha.v > 1.0) return (-d) * dexp(dc<D4>(c2) / oma);
+    return dc<D4>(0.0);
+}
+__device__ __forceinline__ void scan_variables(D4 rho, D4 sigma, D4 tau, D4& p, D4& alpha) {
+    const D4 kf = dcbrt(3.0 * M_PI * M_PI * rho);
+    const D4 kf2r = kf * kf * rho;
+    p = sigma / (4.0 * (kf2r * rho));
+    // tau - tau_W cancels (tau_W = 5/3 s^2 tau_unif: 167 tau_unif at s = 10) and the switching function is steep in alpha,
+    // so the value of the difference takes the rounding error of the quotient tau_W = sigma / (8 rho) back in (one fma
+    // gives the remainder exactly); the slots are those of the plain expression
+    D4 num = tau - sigma / (8.0 * rho);
+    const double r8 = 8.0 * rho.v, tw = sigma.v / r8;
+    num.v = (tau.v - tw) - fma(-tw, r8, sigma.v) / r8;
+    alpha = num / (0.3 * kf2r);
+}
+__device__ __forceinline__ D4 mgga_x_scan(D4 rho, D4 sigma, D4 tau) {
+    const double cx = -0.73855876638202240588;                       // -3/4 (3/pi)^(1/3)
+    const double k1 = 0.065, h0 = 1.174, a1 = 4.9479, mu = 10.0 / 81.0;
+    const double b2 = 0.12083045973594572;                           // sqrt(5913 / 405000)
+    const double b1 = (511.0 / 13500.0) / (2.0 * b2), b3 = 0.5;
+    const double b4 = mu * mu / k1 - 1606.0 / 18225.0 - b1 * b1;
+    D4 p, alpha;
+    scan_variables(rho, sigma, tau, p, alpha);
+    const D4 oma = dc<D4>(1.0) - alpha;
+    const D4 w = b1 * p + b2 * (oma * dexp((-b3) * (oma * oma)));
+    const D4 y = mu * p + b4 * ((p * p) * dexp((-b4 / mu) * p)) + w * w;
+    const D4 h1 = (1.0 + k1) + (-k1 * k1) * (dc<D4>(1.0) / (k1 + y));
+    // g_x = 1 - exp(-a1 / p^(1/4)); where the exponential underflows (sigma = 0 included) g_x is the constant 1: the dual of
+    // p^(-1/4) would multiply an infinite slope by a zero there
+    D4 gx = dc<D4>(1.0);
+    if (a1 / sqrt(sqrt(p.v)) <= 708.0) gx = dc<D4>(1.0) - dexp((-a1) * dinv_root4(p));
+    const D4 fx = scan_switch(alpha, 0.667, 0.8, 1.24);
+    const D4 Fx = (h1 + fx * (dc<D4>(h0) - h1)) * gx;
+    return cx * (rho * dcbrt(rho)) * Fx;
+}
+__device__ __forceinline__ D4 mgga_c_scan(D4 rho, D4 sigma, D4 tau) {
+    const double gamma = 0.031090690869654895;                       // (1 - ln 2) / pi^2
+    const double b1c = 0.0285764, b2c = 0.0889, b3c = 0.125541, chi = 0.12802585262625815;
+    D4 p, alpha;
+    scan_variables(rho, sigma, tau, p, alpha);
+    const D4 rs = dcbrt(dc<D4>(3.0 / (4.0 * M_PI)) / rho);
+    const D4 sq = dsqrt(rs);
+    const D4 eps = pw92_G(rs, sq, 0.0310907, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294);   // lda_c_pw_mod
+    const D4 beta = 0.066725 * ((1.0 + 0.1 * rs) / (1.0 + 0.1778 * rs));
+    const D4 kf = dcbrt(3.0 * M_PI * M_PI * rho);
+    const D4 t2 = (M_PI / 16.0) * (sigma / (kf * rho * rho));
+    const D4 w1 = dexpm1((-1.0 / gamma) * eps);
+    const D4 A = beta / (gamma * w1);
+    const D4 eps1 = eps + gamma * dlog1p(w1 * (dc<D4>(1.0) - dinv_root4(1.0 + 4.0 * (A * t2))));
+    const D4 e0 = dc<D4>(-b1c) / (1.0 + (b2c * sq + b3c * rs));
+    const D4 w0 = dexpm1((-1.0 / b1c) * e0);
+    const D4 eps0 = e0 + b1c * dlog1p(w0 * (dc<D4>(1.0) - dinv_root4(1.0 + (4.0 * chi) * p)));
+    const D4 fc = scan_switch(alpha, 0.64, 1.5, 0.7);
+    return rho * (eps1 + fc * (eps0 - eps1));
+}
+// e, de/drho, de/dsigma, de/dtau per grid point; points with rho <= threshold give zeros, as in k_gga
+// add: e, vrho, vsigma already hold the GGA part of the same points (k_gga) and are added to
+__global__ __launch_bounds__(256) void k_mgga(int64_t n, const double* __restrict__ rho, const double* __restrict__ sigma,
+                                              const double* __restrict__ tau, int fun_mask, double threshold, bool add,
+                                              double* __restrict__ e, double* __restrict__ vrho, double* __restrict__ vsigma,
+                                              double* __restrict__ vtau) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        D4 acc = dc<D4>(0.0);
+        const double r = rho[i];
+        if (r > threshold) {
+            const D4 dr = D4{r, {1.0, 0.0, 0.0}}, dsg = D4{sigma[i], {0.0, 1.0, 0.0}}, dt = D4{tau[i], {0.0, 0.0, 1.0}};
+            if (fun_mask & DFTK_MI_XC_MGGA_X_SCAN) acc = acc + mgga_x_scan(dr, dsg, dt);
+            if (fun_mask & DFTK_MI_XC_MGGA_C_SCAN) acc = acc + mgga_c_scan(dr, dsg, dt);
+        }
+        e[i] = add ? e[i] + acc.v : acc.v;
+        vrho[i] = add ? vrho[i] + acc.d[0] : acc.d[0];
+        vsigma[i] = add ? vsigma[i] + acc.d[1] : acc.d[1];
+        vtau[i] = acc.d[2];
     }
 }
 
@@ -557,6 +644,15 @@ int xc_gga_spin_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const 
     return 0;
 }
 
+int xc_mgga_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, const double* tau, int fun_mask,
+                      double threshold, double* e, double* vrho, double* vsigma, double* vtau) {
+    hipLaunchKernelGGL(k_mgga, dim3(XC_BLOCKS), dim3(256), 0, b->stream, n, rho, sigma, tau, fun_mask, threshold, false, e,
+                       vrho, vsigma, vtau);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
 int xc_gga_pointwise(dftk_mi_basis* b, int64_t n, const double* rho, const double* sigma, int fun_mask,
                      double threshold, double* e, double* vrho, double* vsigma) {
     hipLaunchKernelGGL(k_gga, dim3(XC_BLOCKS), dim3(256), 0, b->stream, n, rho, (const double*)nullptr, sigma, fun_mask,
@@ -693,9 +789,12 @@ int local_potential_collinear_gga(dftk_mi_kblock* cube_kb, const double* recip_h
 // core / grad_core (optional: one cube and its three gradient cubes, non-linear core correction): the XC forms are evaluated
 // at rho + core with grad rho + grad core in sigma and the flux; Hartree and the local energy see rho alone.  The core is
 // one more operand of passes that run anyway: no transform and no launch more.
+// Meta-GGA bits (64, 128; dftk_mi_local_potential_mgga): tau is one more operand of the point-wise pass (k_mgga, after k_gga
+// where GGA bits are mixed in) and Vtau_out = de/dtau one more output of it; V_out gets v_rho - 2 div(v_sigma grad rho) of the
+// summed forms through the same two pipelines.  No transform more.
 int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const double* rho, const double* core,
                         const double* grad_core, const double* vloc, const double* green, int fun_mask, double threshold,
-                        double* V_out, double* energies_h) {
+                        double* V_out, double* energies_h, const double* tau, double* Vtau_out) {
     dftk_mi_basis* b = cube_kb->basis;
     const int64_t N = (int64_t)b->nx * b->ny * b->nz;
     if (cube_kb->n_G != N) {
@@ -703,7 +802,13 @@ int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const do
                        (long long)cube_kb->n_G, (long long)N);
         return DFTK_MI_EINVAL;
     }
-    const int gga_mask = fun_mask & 24;
+    const int mgga_mask = fun_mask & 192;
+    if (mgga_mask && (!tau || core)) {
+        dftk_set_error("local_potential: a meta-GGA functional needs tau and has no core correction (mask %d)", fun_mask);
+        return DFTK_MI_EINVAL;
+    }
+    const int pbe_mask = fun_mask & 24;
+    const int gga_mask = pbe_mask | mgga_mask;       // everything that takes the gradient branch
     // complex cubes c1, c2 (+ three more and 7 real cubes for GGA) + reduction partials in the basis' dense workspace
     const size_t need = (gga_mask ? 5 : 2) * (size_t)N * sizeof(cd) + (gga_mask ? 7 : 0) * (size_t)N * sizeof(double) +
                         3 * XC_BLOCKS * sizeof(double);
@@ -738,8 +843,15 @@ int local_potential_lda(dftk_mi_kblock* cube_kb, const double* recip_h, const do
                            core ? grad_core : (const double*)nullptr, 1.0, 3 * N,
                            grad[0]);                                                   // the three gradients are adjacent
         CHK(cube_sigma(b, N, grad[0], grad[1], grad[2], sigma));
-        hipLaunchKernelGGL(k_gga, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, rho, core, (const double*)sigma, gga_mask,
-                           threshold, e_g, vrho, vsig);
+        if (pbe_mask)
+            hipLaunchKernelGGL(k_gga, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, rho, core, (const double*)sigma, pbe_mask,
+                               threshold, e_g, vrho, vsig);
+        if (mgga_mask) {
+            // without a caller's cube for it (energies only) v_tau lands in c2's storage, dead until the divergence below
+            double* vt = Vtau_out ? Vtau_out : reinterpret_cast<double*>(c2);
+            hipLaunchKernelGGL(k_mgga, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, rho, (const double*)sigma, tau, mgga_mask,
+                               threshold, pbe_mask != 0, e_g, vrho, vsig, vt);
+        }
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_product3_to_complex, dim3(XC_BLOCKS), dim3(256), 0, b->stream, N, (const double*)vsig,
                            (const double*)grad[0], g3);                                // v_sigma d_a rho, a = 0, 1, 2

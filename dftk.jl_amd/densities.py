@@ -116,3 +116,64 @@ def compute_density(basis, psi, occupation, occupation_threshold: float = 0.0, r
             rho2 = symmetrize_rho(basis, rho2, do_lowpass=False)
     out = rho if n_spin == 2 else rho[0]
     return out if rho2 is None else (out, rho2)
+
+
+def compute_kinetic_energy_density(basis, psi, occupation, occupation_threshold: float = 0.0):
+    """``compute_kinetic_energy_density`` (src/densities.jl:110-125): tau = 1/2 sum_k w_k sum_n f_n |grad psi_nk|^2, the
+    density of a meta-GGA beside rho.  Per band three pruned transforms of (G + k)_a psi through the density stages
+    (``dftk_mi_kinetic_energy_density_accumulate``), then the symmetrisation of ``compute_density`` without low-pass."""
+    basis._require_gpu()
+    if basis.model.n_spin_components != 1 or basis.comm_pw.size > 1 or basis.comm_kpts.size > 1:
+        raise NotImplementedError("compute_kinetic_energy_density (meta-GGA): unpolarised models on one rank only")
+    nx, ny, nz = basis.fft_size
+    taus = [torch.zeros((nz, ny, nx), dtype=torch.float64, device=basis.device) for _ in range(basis.n_lanes)]
+    Bh = np.asfortranarray(basis.model.recip_lattice, dtype=np.float64)
+    basis.pre_call()
+
+    def accumulate(ik, kpt):
+        occ = np.asarray(occupation[ik], dtype=np.float64)
+        w = np.where(np.abs(occ) >= occupation_threshold, occ, 0.0) * basis.kweights[ik] * basis.ifft_normalization ** 2
+        w = np.ascontiguousarray(w)
+        psik = psi[ik]
+        if not (psik.is_cuda and psik.dtype == torch.complex128 and psik.stride(1) == 1):
+            raise TypeError("compute_kinetic_energy_density: complex128 CUDA band-major blocks required")
+        if getattr(kpt, "gamma_real", False):
+            raise NotImplementedError("compute_kinetic_energy_density (meta-GGA) on a Gamma-real k-block")
+        if not getattr(kpt, "_frame_set", False):
+            kc = np.ascontiguousarray(kpt.coordinate, dtype=np.float64)
+            _lib.check(basis.lib.dftk_mi_kblock_set_kpoint(kpt.handle, Bh.ctypes.data, kc.ctypes.data))
+            kpt._frame_set = True
+        _lib.check(basis.lib.dftk_mi_kinetic_energy_density_accumulate(kpt.handle, len(w), psik.data_ptr(), psik.stride(0),
+                                                                       w.ctypes.data, taus[kpt.lane].data_ptr()))
+    basis.run_on_lanes(accumulate, basis.kpoints)
+    tau = taus[0]
+    if basis.n_lanes > 1:
+        basis.post_call()
+        for t in taus[1:]:
+            tau += t
+        basis.pre_call()
+    basis.post_call()
+    if any(not s.isone() for s in basis.symmetries):
+        from .symmetry import symmetrize_rho
+        tau = symmetrize_rho(basis, tau, do_lowpass=False)
+    return tau
+
+
+def von_weizsaecker_kinetic_energy_density(basis, rho):
+    """tau_W = |grad rho|^2 / (8 rho) with rho floored at 10 eps (src/densities.jl:131-146): the kinetic energy density of a
+    single-orbital density, the guess of a meta-GGA calculation."""
+    from .terms import cube_gradient_abi
+    if rho.dim() == 4:
+        raise NotImplementedError("von_weizsaecker_kinetic_energy_density (meta-GGA): unpolarised densities only")
+    grad = cube_gradient_abi(basis, rho.to(torch.float64).contiguous())
+    sigma = (grad.reshape(3, *rho.shape) ** 2).sum(dim=0)
+    eps = 10 * np.finfo(np.float64).eps
+    return sigma / (8.0 * torch.clamp(rho, min=eps))
+
+
+def guess_kinetic_energy_density(basis, rho):
+    """The tau an SCF starts from when the caller has none: tau_W of the starting density for a model with a functional of
+    tau, None for every other model."""
+    if not getattr(basis.model, "uses_tau", False):
+        return None
+    return von_weizsaecker_kinetic_energy_density(basis, rho)

@@ -81,6 +81,8 @@ def n_bands_full(model):
 def check_supported(basis, psi=None, who="direct_minimization"):
     """The refusals of this solver, on descriptors alone (no device work)."""
     model = basis.model
+    from .model import refuse_meta_gga
+    refuse_meta_gga(model, f"{who} (the gradient has no div-A-grad term, the line search no tau)")
     if model.temperature != 0:
         raise ValueError(f"{who}: only full occupations are supported (the model has a temperature)")
     per_band = model.n_spin_components * model.filled_occupation

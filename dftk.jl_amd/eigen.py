@@ -358,6 +358,9 @@ def diagonalize_all_kblocks(eigensolver, ham, nev_per_kpoint: int, psiguess=None
     # k-points that start from random orbitals when no guess is given (the others interpolate): the first W of the k loop, or --
     # batched small blocks, two waves -- W k-points SPREAD over the list, so that every other k-point has a solved neighbour
     guesses = []
+    # a Hamiltonian with a tau potential (meta-GGA) takes the per-block path: the batched executor does not know the
+    # div-A-grad term, and the two-level start builds its coarse Hamiltonian from the local potential alone
+    mgga = any(getattr(Hk, "tau_potential", None) is not None for Hk in ham)
     basis_ = ham[0].basis if ham else None
     W_ = _chain_width(basis_) if ham else 1
     two_waves = (bool(ham) and eigensolver is lobpcg_hyper and getattr(basis_, "kbatch", False) and basis_.n_lanes == 1
@@ -381,7 +384,7 @@ def diagonalize_all_kblocks(eigensolver, ham, nev_per_kpoint: int, psiguess=None
                 g = torch.cat([g, extra * np.sqrt(2 * kpt.n_G)], dim=0)
         elif interpolate_kpoints and ik not in in_first and basis.comm_pw.size == 1:
             g = None                                   # filled in by the lane from its previous k-point
-        elif (coarse_start and getattr(basis, "coarse", None) is not None and eigensolver is lobpcg_hyper
+        elif (coarse_start and not mgga and getattr(basis, "coarse", None) is not None and eigensolver is lobpcg_hyper
               and kpt.spin == 1 and getattr(Hk, "potential", None) is not None and kpt.n_G >= 8 * nev_per_kpoint):
             # two-level start: solve on the companion basis first (counted in n_matvec_coarse, inside the caller's timing)
             g, nmv_c = _coarse_start_vectors(eigensolver, Hk, ik, nev_per_kpoint, prec_type, tol, miniter, maxiter,
@@ -394,7 +397,7 @@ def diagonalize_all_kblocks(eigensolver, ham, nev_per_kpoint: int, psiguess=None
         ham[0].basis.pre_call()
 
     basis0 = ham[0].basis if ham else None
-    if ham and eigensolver is lobpcg_hyper and getattr(basis0, "kbatch", False) and basis0.n_lanes == 1:
+    if ham and eigensolver is lobpcg_hyper and getattr(basis0, "kbatch", False) and basis0.n_lanes == 1 and not mgga:
         # many small k-blocks: ONE library call iterates a whole wave of them in lock-step (dftk_mi_lobpcg_multi); the
         # Gamma point, if it runs the real-symmetric iteration, keeps its own call.  With guesses for everybody (every
         # SCF step but the first) there is one wave; without, k-point ik starts from the interpolated solution of

@@ -24,18 +24,27 @@ class DftHamiltonianBlock:
         # the Hubbard term of this block (hubbard.HubbardOperator; models with a Hubbard term and occupation matrices only):
         # rotated orbitals behind P in the same projector slot
         self.hubbard = None
+        # the cube v_tau = de/dtau of a meta-GGA (None otherwise): with it bound the handle adds -1/2 div(v_tau grad psi)
+        self.tau_potential = None
         if bind:
             self.bind(force=True)
 
     @staticmethod
-    def for_all_kpoints(basis, potential, exchange=None, hubbard=None):
+    def for_all_kpoints(basis, potential, exchange=None, hubbard=None, tau_potential=None):
         """The blocks of every local k-point for ONE summed potential (Hamiltonian.jl:36-57), bound with a single library
         call (``dftk_mi_kblocks_set_potential``) instead of one host round trip per k-point.  ``exchange`` (models with
         ExactExchange): {k-block index: ExchangeOperator}, attached BEFORE the blocks are bound, so that the projector slot is
-        set once per Hamiltonian.  ``hubbard`` (models with a Hubbard term): {k-block index: HubbardOperator}, likewise."""
+        set once per Hamiltonian.  ``hubbard`` (models with a Hubbard term): {k-block index: HubbardOperator}, likewise.
+        ``tau_potential`` (meta-GGA): the cube de/dtau of all blocks, bound with a single library call as well
+        (``dftk_mi_kblocks_set_tau_potential``: the blocks of a basis handle share ONE padded copy, like the potential); a block
+        that is bound again later, by its own ``bind()``, gets a copy of its own."""
         import ctypes as C
 
         def attach(blocks):
+            if tau_potential is not None:
+                vt = tau_potential.to(torch.float64).contiguous()
+                for b_ in blocks:
+                    b_.tau_potential = vt
             if hubbard is not None:
                 for ik, b_ in enumerate(blocks):
                     b_.hubbard = hubbard.get(ik)
@@ -67,10 +76,28 @@ class DftHamiltonianBlock:
         kbs = (C.c_void_p * n)(*[b_.kpoint.handle.value for b_ in blocks])
         basis.pre_call()
         _lib.check(basis.lib.dftk_mi_kblocks_set_potential(n, kbs, pot.data_ptr()))
+        if tau_potential is not None:
+            vt = blocks[0].tau_potential
+            for b_ in blocks:
+                b_._set_frame()
+            _lib.check(basis.lib.dftk_mi_kblocks_set_tau_potential(n, kbs, vt.data_ptr()))
+            for b_ in blocks:
+                b_.kpoint._tau_bound = vt
         for b_ in blocks:
             b_.kpoint._pot_owner = b_
             b_.bind()
         return blocks
+
+    def _set_frame(self):
+        """Tell the device handle its k-point and the reciprocal lattice (once): what turns the integer G of a row into
+        (G + k) in cartesian coordinates for the div-A-grad term."""
+        kpt = self.kpoint
+        if not getattr(kpt, "_frame_set", False):
+            import numpy as np
+            Bh = np.asfortranarray(self.basis.model.recip_lattice, dtype=np.float64)
+            kc = np.ascontiguousarray(kpt.coordinate, dtype=np.float64)
+            _lib.check(self.basis.lib.dftk_mi_kblock_set_kpoint(kpt.handle, Bh.ctypes.data, kc.ctypes.data))
+            kpt._frame_set = True
 
     def bind(self, force: bool = False):
         """Make the device handle of the k-point apply THIS block's potential."""
@@ -87,6 +114,16 @@ class DftHamiltonianBlock:
             xi = self.exchange.xi if self.exchange is not None else None
             bind_projectors(self.basis, self.basis.kpoints.index(kpt), xi)
             kpt._exx_owner = self
+        # (likewise without a meta-GGA: the blocks carry None and nothing is bound)
+        if getattr(kpt, "_tau_bound", None) is not self.tau_potential:
+            lib = self.basis.lib
+            if self.tau_potential is not None:
+                self._set_frame()
+                self.basis.pre_call()
+                _lib.check(lib.dftk_mi_kblock_set_tau_potential(kpt.handle, self.tau_potential.data_ptr()))
+            else:
+                _lib.check(lib.dftk_mi_kblock_set_tau_potential(kpt.handle, None))
+            kpt._tau_bound = self.tau_potential
         # (a model without Hubbard term never leaves the first test: its blocks carry None and the slot holds None)
         if getattr(kpt, "_hubbard_bound", None) is not self.hubbard:
             from .hubbard import bind_projector_rows

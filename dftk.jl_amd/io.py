@@ -143,7 +143,8 @@ def scfres_to_dict(scfres: dict, save_psi: bool = False, save_rho: bool = True) 
     if save_rho:
         rho_ = scfres["rho"]
         d["ρ"] = _tolist(rho_) if rho_.dim() == 4 else [_tolist(rho_)]       # [spin][iz][iy][ix]
-        d["τ"] = None
+        tau_ = scfres.get("tau")             # (models with a meta-GGA functional; [spin][iz][iy][ix] like the density)
+        d["τ"] = [_tolist(tau_)] if tau_ is not None else None
     if scfres.get("hubbard_n") is not None:
         d["hubbard_n"] = hubbard_n_to_lists(scfres["hubbard_n"])
     d["energies"] = {k: float(v) for k, v in scfres["energies"].items()}
@@ -204,6 +205,8 @@ def save_scfres(filename: str, scfres: dict, save_psi=None, save_rho=None, extra
     arrays = {"meta_json": np.array(json.dumps(d))}
     if save_rho:
         arrays["rho"] = scfres["rho"].detach().cpu().numpy()
+        if scfres.get("tau") is not None:      # the kinetic energy density of a meta-GGA calculation
+            arrays["tau"] = scfres["tau"].detach().cpu().numpy()
     if save_psi:
         for ik, p in enumerate(scfres["psi"]):
             arrays[f"psi_{ik}"] = p.detach().cpu().numpy()
@@ -246,6 +249,8 @@ def load_scfres(filename: str, basis=None) -> dict:
         dev = basis.device
         if "rho" in data:
             out["rho"] = torch.from_numpy(data["rho"]).to(dev)
+        if "tau" in data:
+            out["tau"] = torch.from_numpy(data["tau"]).to(dev)
         # one block per (k-point, spin component): psi_0 .. psi_{n_spin n_k - 1} in the order of basis.kpoints
         psi = [torch.from_numpy(data[f"psi_{ik}"]).to(dev) for ik in range(len(basis.kpoints)) if f"psi_{ik}" in data]
         if psi:

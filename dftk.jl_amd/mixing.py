@@ -337,6 +337,14 @@ class Chi0Mixing:
         self.chi0terms, self.reltol = list(chi0terms), float(reltol)
         self.last_gmres_applies = 0
 
+    def refuse_meta_gga(self, basis):
+        """A meta-GGA model takes the reference's default, ``LdosMixing()`` (this class with the LDOS model alone), and the
+        mixings that are no chi0 models; every other ``Chi0Mixing`` is refused."""
+        if len(self.chi0terms) == 1 and type(self.chi0terms[0]) is LdosModel:
+            return
+        from .model import refuse_meta_gga
+        refuse_meta_gga(basis, "Chi0Mixing with other chi0 terms than the LdosModel of LdosMixing()")
+
     def _native(self, basis, dF, info):
         """The whole solve behind the C ABI (``dftk_mi_chi0_mix``: the LDOS / dielectric models and the restarted GMRES
         of this class as ONE library call, 12 launches and one host synchronisation per Krylov step); None when a chi0
@@ -398,6 +406,7 @@ class Chi0Mixing:
         return ldos_weights(eF, basis, eigenvalues, psi, sm, T), EPS
 
     def mix_density(self, basis, dF, **info):
+        self.refuse_meta_gga(basis)
         if not _torch_mix():
             out = self._native(basis, dF, info)
             if out is not None:

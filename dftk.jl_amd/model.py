@@ -63,6 +63,16 @@ def compute_recip_lattice(lattice):
     return 2 * math.pi * np.linalg.inv(np.asarray(lattice, dtype=float).T)
 
 
+MGGA_FUNCTIONALS = ("mgga_x_scan", "mgga_c_scan")      # the functionals of tau = 1/2 sum f |grad psi|^2 with a kernel
+
+
+def refuse_meta_gga(model_or_basis, what):
+    """``what`` does not know the kinetic energy density or the div-A-grad term: NotImplementedError for a meta-GGA model"""
+    model = getattr(model_or_basis, "model", model_or_basis)
+    if getattr(model, "uses_tau", False):
+        raise NotImplementedError(f"{what} is not implemented for meta-GGA functionals {model.functionals}")
+
+
 class Model:
     """``Model`` (src/Model.jl): lattice (columns), atoms, fractional positions, term list, XC functionals,
     temperature / smearing, and the spin polarisation -- ``:none`` or ``:collinear`` (Model.jl:29-39), inferred from the
@@ -116,6 +126,21 @@ class Model:
                                       "supported by the reference either; :spinless is outside the hot path)")
         self.spin_polarization = spin_polarization
         self.n_spin_components = 2 if spin_polarization == "collinear" else 1          # Model.jl:196, :366-372
+        # meta-GGA: SCAN, unpolarised, alone with the standard terms -- everything else is refused here, by name
+        self.uses_tau = any(f in MGGA_FUNCTIONALS for f in self.functionals)
+        other = [f for f in self.functionals if f.startswith(("mgga_", "hyb_mgga_")) and f not in MGGA_FUNCTIONALS]
+        if other:
+            raise NotImplementedError(f"meta-GGA: {MGGA_FUNCTIONALS} (SCAN) are the functionals with a kernel, got {other}")
+        if self.uses_tau:
+            if spin_polarization == "collinear":
+                raise NotImplementedError("meta-GGA with collinear spin is not implemented (the SCAN forms are unpolarised)")
+            if self.hubbard is not None or self.exact_exchange is not None:
+                raise NotImplementedError("meta-GGA together with a Hubbard or ExactExchange term is not implemented")
+            if any(s != 1.0 for s in self.functional_scales):
+                raise NotImplementedError("meta-GGA with scaled functionals (hybrids) is not implemented")
+            if self.use_nlcc and any(getattr(getattr(a, "psp", None), "has_core_density", lambda: False)() for a in self.atoms):
+                raise NotImplementedError("meta-GGA with a pseudopotential that carries a core correction is not implemented "
+                                          "(no tau_core); pass use_nlcc=False to drop the correction")
         # atom_groups (Model.jl:169): indices of identical elements, in order of first appearance
         self.atom_groups = []
         reps = []

@@ -32,7 +32,9 @@ _NO_DYNMAT = ("Kinetic", "Hartree", "Xc", "PspCorrection", "Entropy")
 # ------------------------------------------------------------------------------------------ checks
 def _check_supported(basis, q=None):
     from .exchange import refuse
+    from .model import refuse_meta_gga
     model = basis.model
+    refuse_meta_gga(model, "the dynamical matrix (compute_dynmat)")
     refuse(model, "the dynamical matrix (no response with the Fock operator)")
     from .hubbard import refuse as refuse_hubbard
     refuse_hubbard(model, "the dynamical matrix")

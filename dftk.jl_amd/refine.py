@@ -36,6 +36,8 @@ METRIC_MAXITER = 20
 def check_supported(basis, who="refine_scfres"):
     """The refusals of this layer, on descriptors alone (no device work): ``NotImplementedError`` names the reason."""
     model = basis.model
+    from .model import refuse_meta_gga
+    refuse_meta_gga(model, who)
     if model.n_spin_components != 1:
         raise NotImplementedError(f"{who}: collinear spin is not implemented (the exchange-correlation kernel is "
                                   "spin-unpolarised)")

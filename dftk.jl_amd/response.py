@@ -173,6 +173,8 @@ def determine_band_tolerances(alg, density_tol):
 
 # ------------------------------------------------------------------------------------------ checks
 def _check_supported(basis, q=None):
+    from .model import refuse_meta_gga
+    refuse_meta_gga(basis, "the density response (no meta-GGA kernel, no Sternheimer solve with the div-A-grad term)")
     from .exchange import refuse
     refuse(basis.model, "the density response (no exchange kernel term, no Sternheimer solve with the Fock operator)")
     from .hubbard import refuse as refuse_hubbard

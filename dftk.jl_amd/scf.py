@@ -19,7 +19,7 @@ from scipy.special import erfc
 
 from .densities import compute_density
 from .eigen import diagonalize_all_kblocks, lobpcg_hyper
-from .mixing import LdosMixing
+from .mixing import Chi0Mixing, LdosMixing
 from .terms import energy_hamiltonian, guess_density
 
 EPS = float(np.finfo(np.float64).eps)
@@ -390,7 +390,15 @@ class ScfStepper:
 
     def __init__(self, basis, rho=None, psi=None, tol=1e-6, damping=0.8, nbandsalg=None, is_converged=None,
                  eigensolver=lobpcg_hyper, anderson_m=None, seed=0, determine_tol=determine_diagtol, mixing=None,
-                 phase_timers=None, coarse_start=True, exxalg=None, hubbard_n=None):
+                 phase_timers=None, coarse_start=True, exxalg=None, hubbard_n=None, tau=None):
+        # meta-GGA: the kinetic energy density is carried like hubbard_n (scf_solvers.jl:95-99: "tau is just patched through
+        # without any changes") -- tau_in of a step is the tau of the previous step's output orbitals, neither mixed nor
+        # accelerated; the first step takes the caller's, or the von Weizsaecker guess of the starting density
+        self.has_tau = bool(getattr(basis.model, "uses_tau", False))
+        if tau is not None and not self.has_tau:
+            raise ValueError("tau given, but the model has no meta-GGA functional")
+        if self.has_tau and isinstance(mixing, Chi0Mixing):
+            mixing.refuse_meta_gga(basis)
         basis._require_gpu()
         self.basis = basis
         # DFT+U: the occupation matrices are recomputed from every step's output orbitals, not mixed, and build the next
@@ -409,8 +417,9 @@ class ScfStepper:
         # per-step nonlocal energy from the Ritz values (terms.energy_hamiltonian); the energies returned by
         # finalize() / self_consistent_field always come from the projections themselves
         # (off with exact exchange: the Ritz values contain the exchange operator; off with a Hubbard term likewise)
+        # (off with a meta-GGA: the Ritz values contain the div-A-grad term)
         self.ritz_energies = (os.environ.get("DFTK_MI_EXACT_STEP_ENERGIES") is None and not self.has_exx
-                              and not self.has_hubbard)
+                              and not self.has_hubbard and not self.has_tau)
         self.gen = torch.Generator(device=basis.device)
         self.gen.manual_seed(seed + 7919 * basis.comm_kpts.rank)
         self.seed = seed
@@ -433,6 +442,9 @@ class ScfStepper:
                          history_Etot=[], history_drho=[], rho=self.rho_in, timings=[])
         if self.has_hubbard:                  # (the key exists for models with the term only)
             self.info["hubbard_n"] = hubbard_n
+        if self.has_tau:                      # (likewise)
+            from .densities import guess_kinetic_energy_density
+            self.info["tau"] = tau if tau is not None else guess_kinetic_energy_density(basis, self.rho_in)
 
     def step(self):
         # the whole step runs with the library's stream as torch's current stream: torch kernels and library kernels are
@@ -460,6 +472,8 @@ class ScfStepper:
         # would be thrown away (the energies reported for the step are those of (psi_out, rho_out) below)
         exx = (dict(exxalg=self.exxalg, occupation_threshold=self.nbandsalg.occupation_threshold) if self.has_exx else {})
         hub = dict(hubbard_n=info["hubbard_n"]) if self.has_hubbard else {}
+        if self.has_tau:
+            hub = dict(tau=info["tau"])
         _, ham = energy_hamiltonian(basis, info["psi"] if self.has_exx else None, info["occupation"] if self.has_exx else None,
                                     rho=self.rho_in, only_hamiltonian=True, **exx, **hub)
         t = lap("energy_hamiltonian", t)
@@ -476,6 +490,11 @@ class ScfStepper:
             from .hubbard import compute_hubbard_n
             nxt["hubbard_n"] = compute_hubbard_n(basis, nxt["psi"], nxt["occupation"])
             hub = dict(hubbard_n=nxt["hubbard_n"])
+        if self.has_tau:
+            from .densities import compute_kinetic_energy_density
+            nxt["tau"] = compute_kinetic_energy_density(basis, nxt["psi"], nxt["occupation"],
+                                                        self.nbandsalg.occupation_threshold)
+            hub = dict(tau=nxt["tau"])
         energies, _ = energy_hamiltonian(basis, nxt["psi"], nxt["occupation"], rho=nxt["rho"], only_energies=True,
                                          eigenvalues=nxt["eigenvalues"], eF=nxt["eF"], ritz_potential=ritz_pot,
                                          ritz_occupation_threshold=self.nbandsalg.occupation_threshold,
@@ -542,6 +561,8 @@ class ScfStepper:
             exx = (dict(exxalg=self.exxalg, occupation_threshold=self.nbandsalg.occupation_threshold) if self.has_exx
                    else {})
             hub = dict(hubbard_n=info["hubbard_n"]) if self.has_hubbard else {}
+            if self.has_tau:
+                hub = dict(tau=info["tau"])
             energies, ham = energy_hamiltonian(self.basis, info["psi"], info["occupation"], rho=info["rho"],
                                                eigenvalues=info["eigenvalues"], eF=info["eF"], **exx, **hub)
             self.basis.sync()
@@ -551,18 +572,21 @@ class ScfStepper:
 
 def self_consistent_field(basis, rho=None, psi=None, tol=1e-6, maxiter=100, damping=0.8, nbandsalg=None,
                           is_converged=None, callback=None, eigensolver=lobpcg_hyper, anderson_m=None, seed=0,
-                          determine_tol=determine_diagtol, mixing=None, coarse_start=True, exxalg=None, hubbard_n=None):
+                          determine_tol=determine_diagtol, mixing=None, coarse_start=True, exxalg=None, hubbard_n=None,
+                          tau=None):
     """``self_consistent_field(basis; rho, psi, tol, maxiter, damping, nbandsalg, is_converged, callback,
     eigensolver, exxalg)`` (self_consistent_field.jl:164-289).  ``exxalg``: ``AceExx()`` unless given (models with exact
     exchange; the final Hamiltonian carries the compressed operator of all computed bands).  ``anderson_m``:
     10 unless given, 0 (plain damping) for models with exact exchange.  ``hubbard_n`` (models with a Hubbard term): the
     occupation matrices of the first step's Hamiltonian (a restart); the result of such a model, and every step's ``info``,
-    carries the last ones under the key ``hubbard_n`` (models without the term have no such key)."""
+    carries the last ones under the key ``hubbard_n`` (models without the term have no such key).  ``tau`` (models with a
+    meta-GGA functional): the kinetic energy density of the first step's Hamiltonian (a restart; the von Weizsaecker guess of
+    the starting density otherwise); the result and every step's ``info`` carry the one of the last orbitals as ``tau``."""
     t0 = time.time()
     stepper = ScfStepper(basis, rho=rho, psi=psi, tol=tol, damping=damping, nbandsalg=nbandsalg,
                          is_converged=is_converged, eigensolver=eigensolver, anderson_m=anderson_m, seed=seed,
                          determine_tol=determine_tol, mixing=mixing, coarse_start=coarse_start, exxalg=exxalg,
-                         hubbard_n=hubbard_n)
+                         hubbard_n=hubbard_n, tau=tau)
     for _ in range(maxiter):
         info = stepper.step()
         if callback is not None:

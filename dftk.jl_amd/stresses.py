@@ -228,6 +228,8 @@ def compute_stresses_cart(basis_or_scfres, psi=None, occupation=None, rho=None):
         basis, psi, occupation, rho = res["basis"], res["psi"], res["occupation"], res["rho"]
     else:
         basis = basis_or_scfres
+    from .model import refuse_meta_gga
+    refuse_meta_gga(basis.model, "the stress tensor (compute_stresses_cart; the reference has no meta-GGA stress either)")
     refuse_hubbard(basis.model, "the stress tensor")
     refuse_upf(basis.model, "the stress tensor")
     _check_unsharded(basis)

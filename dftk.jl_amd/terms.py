@@ -759,7 +759,7 @@ def xc_energy_potential(basis, rho):
             continue
         if name not in _FUNCTIONALS:
             raise NotImplementedError(f"XC functional {name}: LDA (lda_x, lda_c_vwn, lda_c_pw) and PBE "
-                                      f"(gga_x_pbe, gga_c_pbe) are on this path")
+                                      f"(gga_x_pbe, gga_c_pbe) are on this path (meta-GGA: the library's pipeline only)")
         ei, vi = _FUNCTIONALS[name](rc)
         e += ei
         v += vi
@@ -966,14 +966,15 @@ _LDA_BITS = {"lda_x": 1, "lda_c_vwn": 2, "lda_c_pw": 4, "lda_xc_teter93": 32}
 _SPIN_LDA = ("lda_x", "lda_c_pw", "lda_xc_teter93")      # functionals with a spin-polarised closed form in the library
 _GGA_BITS = {"gga_x_pbe": 8, "gga_c_pbe": 16}
 _SPIN_GGA = ("gga_x_pbe", "gga_c_pbe")                   # ... through dftk_mi_local_potential_collinear_gga
+_MGGA_BITS = {"mgga_x_scan": 64, "mgga_c_scan": 128}     # functionals of tau as well: dftk_mi_local_potential_mgga
 
 
-def local_potential_fused(basis, rho, want_potential=True, want_energies=True):
+def local_potential_fused(basis, rho, want_potential=True, want_energies=True, tau=None):
     """``_local_potential_call`` for the model's functionals; a functional scaled by s != 1 (the exchange part of a hybrid)
     is taken out again by a second pass over the Xc part alone, V -= (1 - s) v_f, E_xc -= (1 - s) E_f: the pipeline is
     linear in the functionals and takes a set of them, not multipliers."""
     model = basis.model
-    out = _local_potential_call(basis, rho, model.functionals, True, want_potential, want_energies)
+    out = _local_potential_call(basis, rho, model.functionals, True, want_potential, want_energies, tau=tau)
     if out is None or "Xc" not in basis.terms.names:
         return out
     for name, s in zip(model.functionals, getattr(model, "functional_scales", ())):
@@ -988,12 +989,13 @@ def local_potential_fused(basis, rho, want_potential=True, want_energies=True):
     return out
 
 
-def _local_potential_call(basis, rho, functionals, with_local_terms, want_potential=True, want_energies=True):
+def _local_potential_call(basis, rho, functionals, with_local_terms, want_potential=True, want_energies=True, tau=None):
     """Hartree + XC (LDA point-wise; PBE with its gradient / divergence Fourier passes) + V_loc summed into one
     potential and their three energies by ONE library call (``dftk_mi_local_potential`` / ``_gga``; a collinear density
     (rho.dim() == 4) goes to ``_collinear`` / ``_collinear_gga``: hartree.jl:50-59, xc.jl:84-160,356-409,576-584,
     local.jl:15-16, operators.jl:213-222).  Returns None for functionals the library does
-    not evaluate.  ``want_energies=False`` (potential only): the call does not synchronise, the three energies are NaN."""
+    not evaluate.  ``want_energies=False`` (potential only): the call does not synchronise, the three energies are NaN.
+    Meta-GGA functionals (``dftk_mi_local_potential_mgga``) take ``tau`` as one more cube and return ``Vtau`` = de/dtau."""
     import ctypes as C
     T = basis.terms
     mask = 0
@@ -1003,17 +1005,31 @@ def _local_potential_call(basis, rho, functionals, with_local_terms, want_potent
                 mask |= _LDA_BITS[name]
             elif name in _GGA_BITS:
                 mask |= _GGA_BITS[name]
+            elif name in _MGGA_BITS:
+                mask |= _MGGA_BITS[name]
             else:
                 return None
     rho = rho.to(torch.float64).contiguous()
     V = torch.empty_like(rho) if want_potential else None
+    Vtau = None
     vloc = T.V_loc if "AtomicLocal" in T.names and with_local_terms else None
     green = T.poisson if "Hartree" in T.names and with_local_terms else None
     E3 = (C.c_double * 3)() if want_energies or not want_potential else None
     basis.pre_call()
     args = (vloc.data_ptr() if vloc is not None else None, green.data_ptr() if green is not None else None)
     core = getattr(T, "rho_core", None)
-    if core is not None:
+    if mask & 192:
+        if tau is None:
+            raise ValueError(f"the functionals {tuple(functionals)} need the kinetic energy density: pass tau=")
+        if rho.dim() == 4 or core is not None:
+            raise NotImplementedError("meta-GGA: unpolarised densities without core correction only")
+        tau = tau.to(torch.float64).contiguous()
+        Vtau = torch.empty_like(rho) if want_potential else None
+        Bh = np.asfortranarray(basis.model.recip_lattice, dtype=np.float64)
+        _lib.check(basis.lib.dftk_mi_local_potential_mgga(
+            basis._cube_handle, Bh.ctypes.data, rho.data_ptr(), tau.data_ptr(), *args, mask, _DENSITY_THRESHOLD,
+            V.data_ptr() if V is not None else None, Vtau.data_ptr() if Vtau is not None else None, E3))
+    elif core is not None:
         # non-linear core correction: XC at rho_s + rho_core / n_spin, Hartree and the local term at rho -- the four
         # entries below in one (``dftk_mi_local_potential_core``)
         if rho.dim() == 4 and any(f not in _SPIN_LDA + _SPIN_GGA for f in functionals):
@@ -1048,8 +1064,8 @@ def _local_potential_call(basis, rho, functionals, with_local_terms, want_potent
         _lib.check(basis.lib.dftk_mi_local_potential(basis._cube_handle, rho.data_ptr(), *args, mask,
                                                      V.data_ptr() if V is not None else None, E3))
     if E3 is None:
-        return dict(Hartree=math.nan, Xc=math.nan, AtomicLocal=math.nan, V=V)
-    return dict(Hartree=E3[0], Xc=E3[1], AtomicLocal=E3[2], V=V)
+        return dict(Hartree=math.nan, Xc=math.nan, AtomicLocal=math.nan, V=V, Vtau=Vtau)
+    return dict(Hartree=E3[0], Xc=E3[1], AtomicLocal=E3[2], V=V, Vtau=Vtau)
 
 
 class Energies(dict):
@@ -1077,7 +1093,7 @@ def smearing_entropy(kind, x):
 
 def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, eigenvalues=None, eF=None,
                        ritz_potential=None, ritz_occupation_threshold=0.0, only_hamiltonian=False, ritz_potential_dot=None,
-                       exxalg=None, occupation_threshold=0.0, hubbard_n=None):
+                       exxalg=None, occupation_threshold=0.0, hubbard_n=None, tau=None):
     """``energy_hamiltonian(basis, psi, occupation; rho, eigenvalues, eF)`` (Hamiltonian.jl:200-227); with
     ``only_energies`` it is ``energy(...)`` (:232-236).  Returns (Energies, [DftHamiltonianBlock]).  The entropy
     term -TS (terms/entropy.jl:11-42) needs this rank's eigenvalues and the Fermi level, else it is Inf.
@@ -1087,9 +1103,17 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
     model with ExactExchange is built from ``psi`` (exact_exchange.jl:36-58); without orbitals the term contributes E = 0 and
     no operator, like the reference's NoopOperator.  ``hubbard_n`` (models with a Hubbard term; one array per manifold as
     ``compute_hubbard_n`` returns them): the occupation matrices the Hubbard energy and operator are built from
-    (hubbard.jl:149-184); without them, or with an empty term, E = 0 and there is no operator."""
+    (hubbard.jl:149-184); without them, or with an empty term, E = 0 and there is no operator.  ``tau`` (models with a
+    meta-GGA functional; ``compute_kinetic_energy_density``): the kinetic energy density the Xc energy and potential are
+    evaluated at; the blocks then carry ``tau_potential`` = de/dtau and apply -1/2 div(v_tau grad psi) with it."""
     basis._require_gpu()
     T = basis.terms
+    mgga = getattr(basis.model, "uses_tau", False) and "Xc" in T.names
+    if mgga and rho is not None and tau is None:
+        raise ValueError(f"energy_hamiltonian: the functionals {basis.model.functionals} need the kinetic energy density; "
+                         "pass tau= (compute_kinetic_energy_density, guess_kinetic_energy_density)")
+    if mgga and os.environ.get("DFTK_MI_TORCH_LOCAL") is not None:
+        raise NotImplementedError("meta-GGA functionals have no torch formulation (DFTK_MI_TORCH_LOCAL)")
     E = Energies()
     pot = None
     have_psi = psi is not None and occupation is not None
@@ -1104,7 +1128,7 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
     if rho is not None and os.environ.get("DFTK_MI_TORCH_LOCAL") is None and \
             any(n in T.names for n in ("AtomicLocal", "Hartree", "Xc")):
         fused = local_potential_fused(basis, rho, want_potential=not only_energies,
-                                      want_energies=not (only_hamiltonian and not only_energies))
+                                      want_energies=not (only_hamiltonian and not only_energies), tau=tau if mgga else None)
         if fused is not None and not only_energies:
             pot = fused["V"]
     if rho is not None and rho.dim() == 4 and fused is None and any(n in T.names for n in ("Hartree", "Xc")):
@@ -1163,7 +1187,7 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
         elif name == "AtomicNonlocal":
             if T.P is None:
                 E[name] = 0.0
-            elif (have_psi and ritz_potential is not None and eigenvalues is not None and "Kinetic" in E
+            elif (have_psi and ritz_potential is not None and eigenvalues is not None and "Kinetic" in E and not mgga
                   and (basis.model.temperature == 0 or (kin_bands and all(kb_ is not None for kb_ in kin_bands)))):
                 # psi are the Ritz vectors of H[V_in] with Ritz values eps_n = <psi_n|H|psi_n> (kinetic + local +
                 # nonlocal): sum_n f_n <psi_n|V_nl|psi_n> = sum f eps - sum f kin_n - int V_in rho[psi].  Exact up to the
@@ -1264,6 +1288,8 @@ def energy_hamiltonian(basis, psi, occupation, rho=None, only_energies=False, ei
         E["AtomicNonlocal"] = E["AtomicNonlocal"] - (0.0 if ritz_fix[1] else E["Kinetic"]) - ritz_fix[0]
     if only_energies:
         return E, None
+    # (the Ritz-value form of the nonlocal energy above is off for a meta-GGA: its Ritz values hold <psi|A_tau|psi> as well)
     ham = DftHamiltonianBlock.for_all_kpoints(basis, pot, exchange=exx_ops if T.exx_kernel is not None else None,
-                                              hubbard=hub_ops)
+                                              hubbard=hub_ops,
+                                              tau_potential=fused["Vtau"] if mgga and fused is not None else None)
     return E, ham

@@ -85,6 +85,18 @@ int dftk_mi_kblock_set_potential(dftk_mi_kblock* kb, const double* V_d);
 /* The same potential for n k-blocks (all k-points of a basis apply ONE summed local potential, Hamiltonian.jl:36-57):
  * one call instead of one host round trip per k-block.  V_d must stay unchanged until the blocks' streams have run. */
 int dftk_mi_kblocks_set_potential(int n_kblocks, dftk_mi_kblock* const* kbs, const double* V_d);
+/* Meta-GGA (DivAgradOperator, src/terms/operators.jl): a second cube, v_tau = de/dtau, bound like the local potential (copied,
+ * un-normalised, NULL unbinds; the plural form shares one padded copy among the blocks of a basis).  With one bound,
+ * dftk_mi_apply_H_parts(which & 1) adds  -1/2 div(v_tau grad psi) = 1/2 sum_a (G + k)_a fft(v_tau ifft((G + k)_a psi)),
+ * (G + k) cartesian: three more transform pairs per band through the local-apply pipeline.  The block must know its k-point
+ * first: dftk_mi_kblock_set_kpoint(kb, recip_lattice_h (3x3 column-major), kcoord_h (fractional)).  Un-sharded blocks of
+ * complex orbitals only.  A block with a tau potential is refused (DFTK_MI_EINVAL, with a message) by the batched executor
+ * (apply_H inside dftk_mi_lobpcg_multi) and by the Gamma-real format, which do not know the term, and never takes the A X
+ * handover of dftk_mi_kblock_reuse_AX (binding or unbinding forgets a kept one).  With nothing bound every path runs as
+ * before. */
+int dftk_mi_kblock_set_kpoint(dftk_mi_kblock* kb, const double* recip_lattice_h, const double* kcoord_h);
+int dftk_mi_kblock_set_tau_potential(dftk_mi_kblock* kb, const double* Vtau_d);
+int dftk_mi_kblocks_set_tau_potential(int n_kblocks, dftk_mi_kblock* const* kbs, const double* Vtau_d);
 
 /* ---- mul!(Hpsi, H::DftHamiltonianBlock, psi)  (src/terms/Hamiltonian.jl:137-192) ------------- */
 int dftk_mi_apply_H(dftk_mi_kblock* kb, int n_bands, const dftk_mi_cplx* psi_d, int64_t ld_psi,
@@ -292,6 +304,16 @@ int dftk_mi_local_potential_gga(dftk_mi_kblock* cube_kb, const double* recip_lat
                                 const double* V_loc_d, const double* poisson_green_d, int xc_functionals,
                                 double density_threshold, double* V_out_d, double* energies_h);
 
+/* The same pipeline with meta-GGA functionals (SCAN: DFTK_MI_XC_MGGA_X_SCAN | DFTK_MI_XC_MGGA_C_SCAN, at least one of them; LDA
+ * and GGA bits may be mixed in as above).  tau_d: the kinetic energy density (real cube), one more operand of the point-wise
+ * pass; Vtau_out_d = de/dtau (real cube), one more output of it: the cube to bind with dftk_mi_kblocks_set_tau_potential.
+ *   V_out = V_loc + V_H + de/drho - 2 div(de/dsigma grad rho)
+ * No transform more than dftk_mi_local_potential_gga.  recip_lattice_h is required; Vtau_out_d is required with V_out_d;
+ * unpolarised, no core correction.  Point-wise forms and threshold: dftk_mi_xc_mgga. */
+int dftk_mi_local_potential_mgga(dftk_mi_kblock* cube_kb, const double* recip_lattice_h, const double* rho_d,
+                                 const double* tau_d, const double* V_loc_d, const double* poisson_green_d, int xc_functionals,
+                                 double density_threshold, double* V_out_d, double* Vtau_out_d, double* energies_h);
+
 /* Collinear spin with GGA functionals (PBE on a magnetic system, the reference's test/iron_pbe.jl): the semantics of
  * dftk_mi_local_potential_collinear (two cubes in rho_d and V_out_d, Hartree and V_loc on the total density, three
  * energies, energies_h == NULL: asynchronous) with the gradient terms of src/terms/xc.jl:120-137 for two spin components,
@@ -373,6 +395,18 @@ int dftk_mi_xc_gga(dftk_mi_basis* basis, int64_t n, const double* rho_d, const d
 int dftk_mi_xc_gga_spin(dftk_mi_basis* basis, int64_t n, const double* rho_d, const double* sigma_d, int xc_functionals,
                         double density_threshold, double* e_d, double* vrho_d, double* vsigma_d);
 
+/* Meta-GGA exchange-correlation point by point (SCAN: libxc's unpolarised mgga_x_scan / mgga_c_scan; Sun, Ruzsinszky, Perdew,
+ * PRL 115, 036402 (2015)): e_d = energy density per volume, vrho_d = de/drho, vsigma_d = de/dsigma, vtau_d = de/dtau for n grid
+ * points, tau_d = 1/2 sum_n f_n |grad psi_n|^2 the kinetic energy density; derivatives by forward-mode differentiation of the
+ * closed forms on the device.  alpha = (tau - sigma / (8 rho)) / tau_unif is not clamped (sigma may exceed 8 rho tau).  Points
+ * with rho <= density_threshold give zeros in all four outputs.  xc_functionals: DFTK_MI_XC_MGGA_X_SCAN, DFTK_MI_XC_MGGA_C_SCAN or
+ * both; anything else: DFTK_MI_EINVAL, nothing written.  No other entry point accepts these two bits. */
+#define DFTK_MI_XC_MGGA_X_SCAN 64
+#define DFTK_MI_XC_MGGA_C_SCAN 128
+int dftk_mi_xc_mgga(dftk_mi_basis* basis, int64_t n, const double* rho_d, const double* sigma_d, const double* tau_d,
+                    int xc_functionals, double density_threshold, double* e_d, double* vrho_d, double* vsigma_d,
+                    double* vtau_d);
+
 /* ---- sphere <-> cube transforms  (src/fft.jl:110-122 ifft!, :162-172 fft!; normalize=false) --
  * cube_d is nx*ny*nz complex, x fastest.  Test/diagnostic entry points (the hot path never
  * materialises the full cube in the caller's layout). */
@@ -384,6 +418,13 @@ int dftk_mi_fft_sphere(dftk_mi_kblock* kb, const dftk_mi_cplx* cube_d, dftk_mi_c
  * occupation[n] * kweight * ifft_normalization^2 (bands with weight 0 are skipped). */
 int dftk_mi_density_accumulate(dftk_mi_kblock* kb, int n_bands, const dftk_mi_cplx* psi_d,
                                int64_t ld_psi, const double* weight_h, double* rho_d);
+
+/* compute_kinetic_energy_density inner loop (src/densities.jl:110-125):
+ * tau_d[nx*ny*nz] += sum_n weight_h[n] / 2 * sum_a |BFFT(pad((G + k)_a psi[:,n]))|^2, a = x, y, z cartesian, weights as above.
+ * Three transforms per band through the density stages.  Needs dftk_mi_kblock_set_kpoint; un-sharded blocks of complex
+ * orbitals outside a batched call only (anything else: DFTK_MI_EINVAL with a message, nothing written). */
+int dftk_mi_kinetic_energy_density_accumulate(dftk_mi_kblock* kb, int n_bands, const dftk_mi_cplx* psi_d,
+                                              int64_t ld_psi, const double* weight_h, double* tau_d);
 
 /* The same with the spin index of the k-block spelled out: rho_d holds n_spin cubes (n_spin = 1 or 2,
  * model.n_spin_components), the bands of this block are added to cube `spin` (0-based: kpt.spin - 1) --

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Multiprecision reference of the point-wise exchange-correlation forms: writes tests/golden/xc_mp_*.json.
+"""Multiprecision reference of the point-wise exchange-correlation forms: writes tests/golden/xc_mp_*.json and, for the
+meta-GGA forms, tests/golden/mgga_mp_*.json.
 
 Only the energy density per volume e of each functional is written down here, from its paper (or the libxc
 definition of the same form), with every constant parsed from a decimal string:
@@ -10,6 +11,8 @@ definition of the same form), with every constant parsed from a decimal string:
   lda_xc_teter93  Goedecker, Teter, Hutter, PRB 54, 1703 (1996), appendix: Pade fit with coefficients linear in f(zeta)
   gga_x_pbe       Perdew, Burke, Ernzerhof, PRL 77, 3865 (1996), eq. (14), kappa = 0.8040, mu = 0.2195149727645171
   gga_c_pbe       ibid. eqs. (7), (8) on lda_c_pw_mod (a = 0.0310907), unpolarised (phi = 1)
+  mgga_x_scan     Sun, Ruzsinszky, Perdew, PRL 115, 036402 (2015), eq. (2) with the supplement's constants, unpolarised
+  mgga_c_scan     ibid. eq. (3) at zeta = 0 (phi = d_x = G_c = 1) on lda_c_pw_mod
 
 Every derivative is a numerical one (``mpmath.diff``, central differences in 800+ bit arithmetic): v = de/drho,
 v_sigma = de/dsigma, v_up, v_down, f_xc = d2e/drho2.  No hand-derived formula appears in this file.  Results are good to
@@ -21,6 +24,11 @@ Semantics of the collinear forms (those of ``dftk_mi_local_potential_collinear``
 evaluated at max(rho_s, 1e-20), the derivative is taken with respect to that clamped variable, and everything is zero
 when rho_up + rho_down <= 2e-20.  The unpolarised lda_xc_teter93 is the collinear form at rho_up = rho_down = rho / 2, so
 it is zero for rho <= 2e-20 as well.  The other unpolarised forms are the plain functions of rho > 0.
+
+Semantics of the meta-GGA forms (those of ``dftk_mi_xc_mgga``): e(rho, sigma, tau) with alpha = (tau - tau_W) / tau_unif and
+no clamp of sigma against 8 rho tau; the switching function is the one of the paper, f(1) = 0; the exchange factor
+g_x = 1 - exp(-a1 / p^(1/4)) is 1 for p <= 0, the limit from the right (all its derivatives vanish there).  The kernel
+replaces g_x by 1 where the exponential underflows a double, which these values do not distinguish.
 
 The grid helpers at the top need NumPy only; tests/test_xc_reference.py and tests/test_gpu_xc_pointwise.py rebuild the
 inputs of a fixture from its "grid" entry with them.  Running this file rewrites the fixtures byte for byte.
@@ -91,6 +99,39 @@ def spin_even_index(grid):
     """(index of |zeta| among the zeta >= 0 of the list, for every zeta of the list; number of zeta >= 0)"""
     nonneg = [z for z in grid["zeta"] if z >= 0]
     return [nonneg.index(abs(z)) for z in grid["zeta"]], len(nonneg)
+
+
+MGGA_GRID = {"decades": [-10, 3], "mantissas": ["1"], "s": [0.0, 1e-3, 0.1, 1.0, 3.0, 10.0],
+             "alpha": [0.0, 0.1, 0.5, 0.9, 0.99, 1.0, 1.01, 1.1, 2.0, 10.0, 100.0], "tau_zero": True}
+MGGA_FUNCTIONALS = ("mgga_x_scan", "mgga_c_scan")   # both bits together: the sum of the two, no fixture of its own
+MGGA_QUANTITIES = ("e", "vrho", "vsigma", "vtau")
+
+
+def tau_unif(rho):
+    """(3/10) (3 pi^2)^(2/3) rho^(5/3), the kinetic energy density of the uniform gas"""
+    return 0.3 * np.cbrt(3.0 * math.pi ** 2) ** 2 * rho * np.cbrt(rho) ** 2
+
+
+def mgga_grid(grid):
+    """(rho, sigma, tau, decade), flat, index = (i_rho * n_s + i_s) * n_t + i_t; tau = tau_W + alpha tau_unif with
+    tau_W = sigma / (8 rho) for every alpha of the list, then tau = 0"""
+    rho, dec = rho_grid(grid)
+    s = np.array(grid["s"])
+    n_t = len(grid["alpha"]) + (1 if grid["tau_zero"] else 0)
+    sigma = ((s * s)[None, :] * sigma_unit(rho)[:, None]).ravel()
+    rho_s = np.repeat(rho, len(s))
+    tau = np.zeros((len(rho_s), n_t))
+    tau[:, :len(grid["alpha"])] = (sigma / (8.0 * rho_s))[:, None] + np.array(grid["alpha"])[None, :] * tau_unif(rho_s)[:, None]
+    return np.repeat(rho_s, n_t), np.repeat(sigma, n_t), tau.ravel(), np.repeat(np.repeat(dec, len(s)), n_t)
+
+
+def mgga_fixture_path(functional, quantity):
+    return os.path.normpath(os.path.join(GOLDEN, f"mgga_mp_{functional}_{quantity}.json"))
+
+
+def load_mgga_fixture(functional, quantity):
+    with open(mgga_fixture_path(functional, quantity)) as fh:
+        return json.load(fh)
 
 
 def fixture_path(family, functional, quantity=None):
@@ -206,6 +247,57 @@ def e_gga_xc_pbe(mp, rho, sigma):
     return e_gga_x_pbe(mp, rho, sigma) + e_gga_c_pbe(mp, rho, sigma)
 
 
+def _scan_common(mp, rho, sigma, tau):
+    """(p, alpha) = (s^2, (tau - tau_W) / tau_unif)"""
+    kf = mp.cbrt(3 * mp.pi ** 2 * rho)
+    p = sigma / (2 * kf * rho) ** 2
+    t_unif = mp.mpf(3) / 10 * kf ** 2 * rho
+    return p, (tau - sigma / (8 * rho)) / t_unif
+
+
+def _scan_switch(mp, alpha, c1, c2, d):
+    if alpha < 1:
+        return mp.exp(-mp.mpf(c1) * alpha / (1 - alpha))
+    if alpha == 1:
+        return mp.mpf(0)
+    return -mp.mpf(d) * mp.exp(mp.mpf(c2) / (1 - alpha))
+
+
+def e_mgga_x_scan(mp, rho, sigma, tau):
+    p, alpha = _scan_common(mp, rho, sigma, tau)
+    k1, h0, a1, mu = mp.mpf("0.065"), mp.mpf("1.174"), mp.mpf("4.9479"), mp.mpf(10) / 81
+    b2 = mp.sqrt(mp.mpf(5913) / 405000)
+    b1 = mp.mpf(511) / 13500 / (2 * b2)
+    b3 = mp.mpf("0.5")
+    b4 = mu * mu / k1 - mp.mpf(1606) / 18225 - b1 * b1
+    oma = 1 - alpha
+    y = mu * p + b4 * p * p * mp.exp(-b4 * p / mu) + (b1 * p + b2 * oma * mp.exp(-b3 * oma * oma)) ** 2
+    h1 = 1 + k1 - k1 / (1 + y / k1)
+    gx = 1 - mp.exp(-a1 / mp.sqrt(mp.sqrt(p))) if p > 0 else mp.mpf(1)
+    fx = _scan_switch(mp, alpha, "0.667", "0.8", "1.24")
+    return e_lda_x(mp, rho) * (h1 + fx * (h0 - h1)) * gx
+
+
+def e_mgga_c_scan(mp, rho, sigma, tau):
+    p, alpha = _scan_common(mp, rho, sigma, tau)
+    rs = _rs(mp, rho)
+    gamma = (1 - mp.log(2)) / mp.pi ** 2
+    b1c, b2c, b3c, chi = mp.mpf("0.0285764"), mp.mpf("0.0889"), mp.mpf("0.125541"), mp.mpf("0.12802585262625815")
+    eps = _pw92_G(mp, rs, "eps0_mod")
+    beta = mp.mpf("0.066725") * (1 + mp.mpf("0.1") * rs) / (1 + mp.mpf("0.1778") * rs)
+    kf = mp.cbrt(3 * mp.pi ** 2 * rho)
+    t2 = mp.pi * sigma / (16 * kf * rho * rho)
+    w1 = mp.expm1(-eps / gamma)
+    A = beta / (gamma * w1)
+    eps1 = eps + gamma * mp.log1p(w1 * (1 - 1 / mp.sqrt(mp.sqrt(1 + 4 * A * t2))))
+    e0 = -b1c / (1 + b2c * mp.sqrt(rs) + b3c * rs)
+    w0 = mp.expm1(-e0 / b1c)
+    eps0 = e0 + b1c * mp.log1p(w0 * (1 - 1 / mp.sqrt(mp.sqrt(1 + 4 * chi * p))))
+    fc = _scan_switch(mp, alpha, "0.64", "1.5", "0.7")
+    return rho * (eps1 + fc * (eps0 - eps1))
+
+
+E_MGGA = {"mgga_x_scan": e_mgga_x_scan, "mgga_c_scan": e_mgga_c_scan}
 E_UNPOL = {"lda_x": e_lda_x, "lda_c_vwn": e_lda_c_vwn, "lda_c_pw": e_lda_c_pw}
 E_SPIN = {"lda_x": e_spin_lda_x, "lda_c_pw": e_spin_lda_c_pw, "lda_xc_teter93": e_spin_lda_xc_teter93}
 E_GGA = {"gga_x_pbe": e_gga_x_pbe, "gga_c_pbe": e_gga_c_pbe, "gga_xc_pbe": e_gga_xc_pbe}
@@ -245,6 +337,17 @@ def ref_gga(functional, rho, sigma):
             "vsigma": float(_diff(mp, lambda x: fun(mp, r, x), sigma, 1, max(sigma, float(sigma_unit(rho)))))}
 
 
+def ref_mgga(functional, rho, sigma, tau):
+    """{"e", "vrho", "vsigma", "vtau"} at one point (doubles)"""
+    mp = _mp()
+    fun = E_MGGA[functional]
+    r, sg, tu = mp.mpf(rho), mp.mpf(sigma), mp.mpf(tau)
+    return {"e": float(_diff(mp, lambda x: fun(mp, x, sg, tu), rho, 0, rho)),
+            "vrho": float(_diff(mp, lambda x: fun(mp, x, sg, tu), rho, 1, rho)),
+            "vsigma": float(_diff(mp, lambda x: fun(mp, r, x, tu), sigma, 1, max(sigma, float(sigma_unit(rho))))),
+            "vtau": float(_diff(mp, lambda x: fun(mp, r, sg, x), tau, 1, max(tau, float(tau_unif(rho)))))}
+
+
 def ref_spin(functional, up, dn):
     """{"e", "vup", "vdn"} at one point (doubles), with the clamp and the threshold of the module docstring"""
     mp = _mp()
@@ -276,7 +379,18 @@ def _dump(path, head, values):
     print(f"{os.path.relpath(path)}: {len(text)} bytes")
 
 
+def main_mgga():
+    head = {"generator": "tools/make_golden_xc.py", "mp_dps": DPS}
+    rho, sigma, tau, _ = mgga_grid(MGGA_GRID)
+    for fun in MGGA_FUNCTIONALS:
+        rows = [ref_mgga(fun, float(r), float(s), float(t)) for r, s, t in zip(rho, sigma, tau)]
+        for q in MGGA_QUANTITIES:
+            _dump(mgga_fixture_path(fun, q), dict(head, family="mgga", functional=fun, grid=MGGA_GRID), {q: [row[q] for row in rows]})
+
+
 def main():
+    if sys.argv[1:] == ["mgga"]:        # the meta-GGA fixtures alone
+        return main_mgga()
     head = {"generator": "tools/make_golden_xc.py", "mp_dps": DPS}
     rho, _ = rho_grid(LDA_GRID)
     for fun, quantities in LDA_FUNCTIONALS.items():
@@ -295,6 +409,7 @@ def main():
         values = {"e": [row["e"] for row, z in zip(rows, zeta) if z >= 0], "vup": [row["vup"] for row in rows]}
         for q in SPIN_QUANTITIES:
             _dump(fixture_path("spin", fun, q), dict(head, family="spin", functional=fun, grid=SPIN_GRID), {q: values[q]})
+    main_mgga()
 
 
 if __name__ == "__main__":
