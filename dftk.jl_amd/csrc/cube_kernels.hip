@@ -16,7 +16,7 @@
 
 namespace dftk_cube {   // (named: kernels of an anonymous namespace lose their names in rocprofv3 traces)
 const int CUBE_BLOCKS = 2048;
-const int MAX_SYMM = 192;     // 48 point operations x up to 4 centring translations
+const int MAX_SYMM = 192;     // operations per launch (LDS tables): 48 point operations x up to 4 centring translations
 
 struct Lat9 {                 // recip_lattice, row-major: G_cart[a] = sum_j B[3 a + j] G_red[j]
     double B[9];
@@ -24,6 +24,10 @@ struct Lat9 {                 // recip_lattice, row-major: G_cart[a] = sum_j B[3
 
 __device__ __forceinline__ bool in_range(int g, int n) { return g >= -((n - 1) - (n - 1) / 2) && g <= (n - 1) / 2; }
 __device__ __forceinline__ int wrap(int g, int n) { return g < 0 ? g + n : g; }
+__device__ __forceinline__ bool stays_on_grid(const int* F, int g0, int g1, int g2, int nx, int ny, int nz) {   // F G
+    return in_range(F[0] * g0 + F[1] * g1 + F[2] * g2, nx) && in_range(F[3] * g0 + F[4] * g1 + F[5] * g2, ny) &&
+           in_range(F[6] * g0 + F[7] * g1 + F[8] * g2, nz);
+}
 
 __global__ __launch_bounds__(256) void k_r2c(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
                                              cd* __restrict__ out) {
@@ -41,6 +45,9 @@ __global__ __launch_bounds__(256) void k_c2r(int64_t n, const cd* __restrict__ c
 // accumulate_over_symmetries! (symmetry.jl:282-319) and lowpass_for_symmetry! (:323-343) fused, one thread per G:
 //   out(G) = keep(G) * scale * sum_s [ S_s^-1 G on the grid ] e^{-2 pi i G.tau_s} in(S_s^-1 G),
 //   keep(G) = prod_s [ S_s G on the grid ]          (only when lowpass != 0)
+// n_sym <= MAX_SYMM per launch.  ACCUMULATE: out(G) += the sum of this launch (a group of more than MAX_SYMM operations goes
+// through in chunks, the first with ACCUMULATE = false; its low-pass follows in k_symm_lowpass once every chunk is in).
+template <bool ACCUMULATE>
 __global__ __launch_bounds__(256) void k_symmetrize(int nx, int ny, int nz, int n_sym, const int* __restrict__ invS,
                                                     const int* __restrict__ S, const double* __restrict__ tau,
                                                     const cd* __restrict__ in, cd* __restrict__ out, int lowpass,
@@ -78,13 +85,29 @@ __global__ __launch_bounds__(256) void k_symmetrize(int nx, int ny, int nz, int 
                     ai += cs * v.y + sn * v.x;
                 }
             }
-            if (lowpass) {
-                const int* F = s_S + 9 * s;
-                keep = keep && in_range(F[0] * g0 + F[1] * g1 + F[2] * g2, nx) &&
-                       in_range(F[3] * g0 + F[4] * g1 + F[5] * g2, ny) && in_range(F[6] * g0 + F[7] * g1 + F[8] * g2, nz);
-            }
+            if (lowpass) keep = keep && stays_on_grid(s_S + 9 * s, g0, g1, g2, nx, ny, nz);
         }
-        out[i] = keep ? make_double2(scale * ar, scale * ai) : make_double2(0.0, 0.0);
+        if (ACCUMULATE)
+            out[i] = make_double2(out[i].x + scale * ar, out[i].y + scale * ai);
+        else
+            out[i] = keep ? make_double2(scale * ar, scale * ai) : make_double2(0.0, 0.0);
+    }
+}
+
+// the low-pass of one chunk of a chunked symmetrisation: c(G) = 0 where some S_s G of the chunk leaves the grid.  It only
+// ever clears, so an entry cleared by one chunk stays cleared by the others.
+__global__ __launch_bounds__(256) void k_symm_lowpass(int nx, int ny, int nz, int n_sym, const int* __restrict__ S,
+                                                      cd* __restrict__ c) {
+    __shared__ int s_S[MAX_SYMM * 9];
+    for (int t = threadIdx.x; t < n_sym * 9; t += 256) s_S[t] = S[t];
+    __syncthreads();
+    const int64_t N = (int64_t)nx * ny * nz;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
+        const int ix = (int)(i % nx), iy = (int)((i / nx) % ny), iz = (int)(i / ((int64_t)nx * ny));
+        const int g0 = signed_freq(ix, nx), g1 = signed_freq(iy, ny), g2 = signed_freq(iz, nz);
+        bool keep = true;
+        for (int s = 0; s < n_sym; ++s) keep = keep && stays_on_grid(s_S + 9 * s, g0, g1, g2, nx, ny, nz);
+        if (!keep) c[i] = make_double2(0.0, 0.0);
     }
 }
 
@@ -230,8 +253,8 @@ int cube_symmetrize(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, cons
     int64_t N;
     CHK(check_cube(cube_kb, &N));
     dftk_mi_basis* b = cube_kb->basis;
-    if (n_sym < 1 || n_sym > MAX_SYMM) {
-        dftk_set_error("symmetrize_rho: %d symmetry operations (1 .. %d supported)", n_sym, MAX_SYMM);
+    if (n_sym < 1) {
+        dftk_set_error("symmetrize_rho: %d symmetry operations (at least 1 needed)", n_sym);
         return DFTK_MI_EINVAL;
     }
     bool all_one = true;
@@ -290,9 +313,31 @@ int cube_symmetrize(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, cons
     const int* d_invS = reinterpret_cast<const int*>(d_tau + 3 * (size_t)n_sym);
     const int* d_S = d_invS + 9 * (size_t)n_sym;
     CHK(cube_forward_real(cube_kb, rho_in, nullptr, c1, c2));                       // c2 = F[rho]
-    hipLaunchKernelGGL(k_symmetrize, dim3(CUBE_BLOCKS), dim3(256), 0, b->stream, b->nx, b->ny, b->nz, n_sym, d_invS, d_S,
-                       d_tau, c2, c1, do_lowpass, 1.0 / (double)n_sym);
-    HIPCHK(hipGetLastError());
+    const dim3 g(CUBE_BLOCKS), t(256);
+    const double scale = 1.0 / (double)n_sym;
+    if (n_sym <= MAX_SYMM) {
+        hipLaunchKernelGGL(k_symmetrize<false>, g, t, 0, b->stream, b->nx, b->ny, b->nz, n_sym, d_invS, d_S, d_tau, c2, c1,
+                           do_lowpass, scale);
+        HIPCHK(hipGetLastError());
+    } else {
+        // more operations than one launch holds in LDS (supercells): chunks of MAX_SYMM accumulate into c1, then every
+        // chunk's low-pass clears its entries -- only after the last accumulation, which would refill a cleared entry
+        for (int s0 = 0; s0 < n_sym; s0 += MAX_SYMM) {
+            const int n = n_sym - s0 < MAX_SYMM ? n_sym - s0 : MAX_SYMM;
+            if (s0 == 0)
+                hipLaunchKernelGGL(k_symmetrize<false>, g, t, 0, b->stream, b->nx, b->ny, b->nz, n, d_invS, d_S, d_tau, c2,
+                                   c1, 0, scale);
+            else
+                hipLaunchKernelGGL(k_symmetrize<true>, g, t, 0, b->stream, b->nx, b->ny, b->nz, n, d_invS + 9 * s0,
+                                   d_S + 9 * s0, d_tau + 3 * s0, c2, c1, 0, scale);
+            HIPCHK(hipGetLastError());
+        }
+        for (int s0 = 0; do_lowpass && s0 < n_sym; s0 += MAX_SYMM) {
+            hipLaunchKernelGGL(k_symm_lowpass, g, t, 0, b->stream, b->nx, b->ny, b->nz,
+                               n_sym - s0 < MAX_SYMM ? n_sym - s0 : MAX_SYMM, d_S + 9 * s0, c1);
+            HIPCHK(hipGetLastError());
+        }
+    }
     CHK(cube_backward_real(cube_kb, c1, c2, 1.0 / (double)N, rho_out));
     return 0;            // asynchronous on the basis' stream (header conventions)
 }

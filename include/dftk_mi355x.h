@@ -356,7 +356,10 @@ int dftk_mi_cube_gradient(dftk_mi_kblock* cube_kb, const double* recip_lattice_h
  * accumulate_over_symmetries! (:282-319: out(G) = sum_s e^{-2 pi i G.tau_s} in(S_s^-1 G), terms whose S_s^-1 G leaves
  * the grid dropped) and lowpass_for_symmetry! (:323-343) as ONE kernel over G, / n_sym, irfft.  S_h: n_sym 3x3 integer
  * matrices, column-major (Julia's symop.S = W'); tau_h: 3 doubles each (symop.tau = -W^-1 w).  rho_out_d may alias
- * rho_in_d.  With identity-only symmetries the density is copied (all(isone, symmetries), :292-295). */
+ * rho_in_d.  With identity-only symmetries the density is copied (all(isone, symmetries), :292-295).  Any n_sym >= 1: up to
+ * 192 operations are one kernel; a larger group (supercells: 384 for 2x2x2 primitive Si) goes through in chunks of 192
+ * between the same two FFTs, accumulating first and low-passing once every chunk is in.  DFTK_MI_EINVAL, nothing written:
+ * n_sym < 1, a matrix with det S != +-1, a k-block that does not span the cube. */
 int dftk_mi_symmetrize_rho(dftk_mi_kblock* cube_kb, int n_sym, const int32_t* S_h, const double* tau_h, int do_lowpass,
                            const double* rho_in_d, double* rho_out_d);
 /* mix_density(::KerkerMixing, basis, dF) (src/scf/mixing.jl:61-72, spin-unpolarised):
