@@ -56,3 +56,4 @@ from .transfer import transfer_blochwave_kpt, transfer_blochwave, transfer_densi
 from .refine import (RefinementResult, refine_scfres, refine_energies, refine_forces, invert_refinement_metric,  # noqa: F401,E402
                      select_occupied_orbitals, check_full_occupation, compute_projected_gradient, apply_Omega, apply_K)
 from .direct_minimization import direct_minimization, backtracking, LbfgsNative  # noqa: F401,E402
+from .newton import newton, solve_OmegaPlusK_cg, TangentSpace, apply_OmegaPlusK, TangentCgNative  # noqa: F401,E402

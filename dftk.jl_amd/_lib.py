@@ -220,6 +220,16 @@ _SIGNATURES = {
                                        C.POINTER(C.c_int)]),
     "dftk_mi_lbfgs_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "dftk_mi_orbitals_realspace": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p]),
+    "dftk_mi_tangent_density": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _i64, C.c_void_p, C.c_void_p]),
+    "dftk_mi_tangent_potential": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _i64, C.c_int]),
+    "dftk_mi_tangent_cg_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "dftk_mi_tangent_cg_destroy": (C.c_int, [C.c_void_p]),
+    "dftk_mi_tangent_cg_dot": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dftk_mi_tangent_cg_update_xr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dftk_mi_tangent_cg_update_p": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "dftk_mi_tangent_cg_read": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dftk_mi_anderson_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dftk_mi_chi0_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_double,
                                    C.c_double, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int),

@@ -177,6 +177,9 @@ struct dftk_mi_basis {
     // workspace of the exact-exchange apply (exx_kernels.hip): the cubes of the occupied orbitals, of a group of columns
     // and of a group of pair densities live across calls into the sphere <-> cube pipelines (T1 / T2)
     DevBuf<void> exx_ws;
+    // workspace of the tangent-space entries (newton_kernels.hip): the cubes and coefficient vectors of one launch group
+    // live across calls into the sphere <-> cube pipelines (T1 / T2)
+    DevBuf<void> newton_ws;
 };
 
 // ------------------------------------------------------------------------------------ profiling
@@ -624,6 +627,9 @@ int sternheimer_run(dftk_mi_kblock* kb, int n_occ, const cd* psi_occ, int64_t ld
 // dftk_mi_dynmat_nonlocal (the entry points are the whole interface: see include/dftk_mi355x.h)
 
 // exx_kernels.hip: dftk_mi_exx_apply (the entry point is the whole interface: see include/dftk_mi355x.h)
+
+// newton_kernels.hip: dftk_mi_orbitals_realspace / dftk_mi_tangent_density / dftk_mi_tangent_potential / dftk_mi_tangent_cg_*
+// (the entry points are the whole interface: see include/dftk_mi355x.h)
 
 // transfer_kernels.hip: dftk_mi_transfer_blochwave / dftk_mi_transfer_density (the entry points are the whole interface)
 

@@ -1009,6 +1009,67 @@ int dftk_mi_lbfgs_direction(dftk_mi_lbfgs* acc, const dftk_mi_cplx* const* g_d, 
                             dftk_mi_kblock* const* kblocks /* or NULL */, const double* const* mean_kin_h /* per block, or NULL */,
                             const double* scale_h /* [n_blocks] */, dftk_mi_cplx* const* d_d, const int64_t* ldd_h);
 
+/* ---- the tangent-space solve of Newton's method (newton_kernels.hip; solve_OmegaPlusK of src/response/hessian.jl:111-176
+ * with cg! of src/response/cg.jl) ------------------------------------------------------------------------------------
+ * The orbitals are fixed for a whole solve, so their real-space values are transformed ONCE and kept by the caller; an
+ * application of K then costs two 3-D transforms per band (the change in, dV psi out) instead of four.  All three entries
+ * are fp64, use a fixed reduction order and no atomics (two calls give bitwise identical results), are asynchronous on the
+ * block's stream and synchronise with the host only when their workspace grows on first use.  A Gamma-real block is
+ * accepted and served in the complex full-sphere layout.  DFTK_MI_EINVAL, every output untouched: a plane-wave sharded
+ * block, a leading dimension below n_G, n_bands < 0, a null pointer (with n_bands > 0), a call inside a batched multi-k
+ * call.  n_bands = 0 is a no-op.
+ *
+ * orbitals_realspace: psi_r_d[n] = the UNNORMALISED backward transform of column n, sum_G psi_n(G) e^{+iG.r}, as a complex
+ *   cube of nx ny nz entries, x fastest, cube n at offset n nx ny nz (what dftk_mi_ifft_sphere gives per column).
+ *   The caller folds ifft_normalization^2 into the weights of tangent_density, as for dftk_mi_density_response_accumulate;
+ *   tangent_potential divides by nx ny nz itself, so that its result is that of the H apply.
+ * tangent_density: drho(r) += sum_n w_h[n] 2 Re[conj psi_n(r) dpsi_n(r)], the quantity dftk_mi_density_response_accumulate
+ *   defines with w_docc = 0.  One backward transform per band (of dpsi), then one streaming kernel per launch group that
+ *   reads both cubes once, sums the bands of the group in ascending order per grid point and updates drho once.  A launch
+ *   group whose weights are all zero is skipped.
+ * tangent_potential: out[:, n] (+)= the sphere rows of FFT(dV psi_n(r)) / (nx ny nz), the quantity
+ *   dftk_mi_apply_H_parts(which = 1) defines for a block with dV bound (dV_d: nz x ny x nx doubles, not padded).  One
+ *   streaming kernel per launch group forms the products, then one forward transform per band.  The block's bound
+ *   potential and its LOBPCG state are not touched. */
+int dftk_mi_orbitals_realspace(dftk_mi_kblock* kblock, int n_bands, const dftk_mi_cplx* psi_d, int64_t ld_psi,
+                               dftk_mi_cplx* psi_r_d);
+int dftk_mi_tangent_density(dftk_mi_kblock* kblock, int n_bands, const dftk_mi_cplx* psi_r_d, const dftk_mi_cplx* dpsi_d,
+                            int64_t ld_dpsi, const double* w_h, double* drho_d);
+int dftk_mi_tangent_potential(dftk_mi_kblock* kblock, int n_bands, const dftk_mi_cplx* psi_r_d, const double* dV_d,
+                              dftk_mi_cplx* out_d, int64_t ld_out, int accumulate);
+/* The packed-vector pieces of cg! for one right-hand side.  Packed vectors are those of dftk_mi_lbfgs_* (host arrays of
+ * device pointers and leading dimensions, block b of n_rows[b] x n_cols[b] entries); the inner product is
+ * <a, b> = sum_b weight[b] Re <a_b, b_b> (the k-weights: Omega + K is self-adjoint with respect to it).
+ *
+ * dot(slot, a, b): one launch that leaves the per-workgroup partial sums of <a, b> in the slot.  GAMMA receives <r, z>;
+ *   the value becomes the current gamma at the next update_p, until then it is the NEXT gamma.  PC receives <p, c>, RR
+ *   <r, r>.
+ * update_xr(p, c, x, r): sums the partials of the current gamma and of PC itself (fixed order, every workgroup for itself),
+ *   alpha = gamma / <p, c>; x += alpha p, r -= alpha c in one launch.
+ * update_p(z, p, first): beta = next gamma / current gamma formed the same way, p = z + beta p; first != 0: p = z, p is
+ *   not read (the start of cg!).  Either way the next gamma becomes the current one.
+ * read(out3_h): out3_h = { <r, r>, current gamma, <p, c> } from the slots; the ONE host synchronisation of an iteration.
+ * alpha and beta never visit the host.  No atomics: two runs give bitwise identical results.  The block tables travel
+ * through pinned staging buffers used in turn (eight; read frees all of them), so no other entry synchronises.
+ *
+ * DFTK_MI_EINVAL, every output untouched: sizes below 1, a null table, a null block pointer or a leading dimension below
+ * the rows given at creation, an unknown slot, a call inside a batched multi-k call. */
+typedef struct dftk_mi_tangent_cg dftk_mi_tangent_cg;
+#define DFTK_MI_CG_GAMMA 0
+#define DFTK_MI_CG_PC 1
+#define DFTK_MI_CG_RR 2
+int dftk_mi_tangent_cg_create(dftk_mi_basis* basis, int n_blocks, const int64_t* n_rows_h, const int* n_cols_h,
+                              const double* weight_h, dftk_mi_tangent_cg** out);
+int dftk_mi_tangent_cg_destroy(dftk_mi_tangent_cg* cg);
+int dftk_mi_tangent_cg_dot(dftk_mi_tangent_cg* cg, int slot, const dftk_mi_cplx* const* a_d, const int64_t* lda_h,
+                           const dftk_mi_cplx* const* b_d, const int64_t* ldb_h);
+int dftk_mi_tangent_cg_update_xr(dftk_mi_tangent_cg* cg, const dftk_mi_cplx* const* p_d, const int64_t* ldp_h,
+                                 const dftk_mi_cplx* const* c_d, const int64_t* ldc_h, dftk_mi_cplx* const* x_d,
+                                 const int64_t* ldx_h, dftk_mi_cplx* const* r_d, const int64_t* ldr_h);
+int dftk_mi_tangent_cg_update_p(dftk_mi_tangent_cg* cg, const dftk_mi_cplx* const* z_d, const int64_t* ldz_h,
+                                dftk_mi_cplx* const* p_d, const int64_t* ldp_h, int first);
+int dftk_mi_tangent_cg_read(dftk_mi_tangent_cg* cg, double* out3_h);
+
 /* Process-wide counters since load: kernel launches issued by the library and host synchronisations it waited on
  * (stream synchronisations of its drivers, result fetches, scheduling rounds of the batched k-point driver).  For the
  * many-small-k workloads these two ARE the cost model; either pointer may be NULL. */
