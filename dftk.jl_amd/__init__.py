@@ -57,3 +57,8 @@ from .refine import (RefinementResult, refine_scfres, refine_energies, refine_fo
                      select_occupied_orbitals, check_full_occupation, compute_projected_gradient, apply_Omega, apply_K)
 from .direct_minimization import direct_minimization, backtracking, LbfgsNative  # noqa: F401,E402
 from .newton import newton, solve_OmegaPlusK_cg, TangentSpace, apply_OmegaPlusK, TangentCgNative  # noqa: F401,E402
+from .unfold import apply_symop, unfold_bz, unfold_mapping, unfold_array  # noqa: F401,E402
+from .wannier import (GaussianWannierProjection, HydrogenicWannierProjection, default_wannier_centers,  # noqa: F401,E402
+                      radial_hydrogenic, overlap_Mmn_k_kpb, compute_mmn, compute_amn_kpoint, compute_amn, compute_nnkp,
+                      complete_nnkp, read_w90_nnkp, write_w90_nnkp, write_w90_win, write_w90_eig, write_w90_amn, write_w90_mmn,
+                      write_w90_unk, write_wannier90_files, wannier_spreads, projection_gauge, rotate_mmn)

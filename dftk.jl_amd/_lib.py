@@ -105,6 +105,13 @@ _SIGNATURES = {
     "dftk_mi_apply_kernel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "dftk_mi_transfer_blochwave": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, _i64]),
     "dftk_mi_transfer_density": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "dftk_mi_apply_symop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64,
+                                      C.c_void_p, _i64]),
+    "dftk_mi_wannier_overlaps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "dftk_mi_wannier_guess_columns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_int, C.c_void_p,
+                                                _i64]),
     "dftk_mi_refinement_metric_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, _i64, C.c_double, C.c_int,
                                                   C.c_void_p, _i64, C.c_void_p, C.c_void_p]),
     "dftk_mi_exx_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64,

@@ -162,7 +162,7 @@ class PlaneWaveBasis:
     def __init__(self, model: Model, Ecut: float, kgrid=None, fft_size=None, device="cuda",
                  comm_kpts: KptComm | None = None, build_terms=True, comm_pw: KptComm | None = None,
                  use_symmetries_for_kpoint_reduction=True, n_lanes: int | None = None, gamma_real: bool | None = None,
-                 coarse_start: bool | None = None):
+                 coarse_start: bool | None = None, symmetries_respect_rgrid: bool | None = None):
         from . import symmetry as _sym
         # gamma_real: None = automatic at k = 0 (env DFTK_MI_GAMMA_REAL=0 switches it off), True = required, False = off
         if gamma_real is None and os.environ.get("DFTK_MI_GAMMA_REAL", "1") == "0":
@@ -189,7 +189,10 @@ class PlaneWaveBasis:
         self.comm_pw = comm_pw if comm_pw is not None else KptComm.single()
         if self.comm_pw.size > 1 and self.comm_kpts.size > 1:
             raise NotImplementedError("k-point and plane-wave sharding cannot be combined yet")
-        symmetries_respect_rgrid = fft_size is None                          # PlaneWaveBasis.jl:330
+        # (symmetries_respect_rgrid given: the inner constructor, PlaneWaveBasis.jl:129-261 -- unfold_bz rebuilds a basis
+        # with the flag of the one it came from, whatever its fft_size argument was)
+        if symmetries_respect_rgrid is None:
+            symmetries_respect_rgrid = fft_size is None                      # PlaneWaveBasis.jl:330
         if fft_size is None:
             # FFT size compatible with the fractional translations of the symmetries (PlaneWaveBasis.jl:349-361)
             factors = (1,)
@@ -216,6 +219,7 @@ class PlaneWaveBasis:
         # k-points: explicit list or unreduced Monkhorst-Pack mesh, split over comm_kpts
         if kgrid is None:
             kgrid = MonkhorstPack((1, 1, 1))
+        self.kgrid = kgrid            # the grid AS GIVEN (basis.kgrid of the reference): unfold_bz and the .win writer read it
         # symmetries that survive the discretisation, irreducible k-points (PlaneWaveBasis.jl:161-173)
         symmetries = list(model.symmetries)
         # what todict(basis) reports (input_output.jl:184-196): the grid AS GIVEN and the two constructor flags

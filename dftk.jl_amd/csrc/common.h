@@ -340,6 +340,10 @@ struct dftk_mi_kblock {
     uint64_t transfer_in_serial = 0;
     int transfer_dG[3] = {0, 0, 0};
     bool kin_given = false;          // dftk_mi_kblock_create was handed kinetic energies (h_kin is not a row of zeros)
+    // the last (input block, S^-1, kshift) that dftk_mi_apply_symop has checked against this block as OUTPUT block
+    // (symop_kernels.hip: every output row has its pre-image in the input sphere; the host pass runs once per triple)
+    uint64_t symop_in_serial = 0;
+    int symop_key[12] = {0};
 };
 
 // ------------------------------------------------------------------------------------ internal API
@@ -631,7 +635,23 @@ int sternheimer_run(dftk_mi_kblock* kb, int n_occ, const cd* psi_occ, int64_t ld
 // newton_kernels.hip: dftk_mi_orbitals_realspace / dftk_mi_tangent_density / dftk_mi_tangent_potential / dftk_mi_tangent_cg_*
 // (the entry points are the whole interface: see include/dftk_mi355x.h)
 
-// transfer_kernels.hip: dftk_mi_transfer_blochwave / dftk_mi_transfer_density (the entry points are the whole interface)
+// transfer_kernels.hip: dftk_mi_transfer_blochwave / dftk_mi_transfer_density; symop_kernels.hip and wannier_kernels.hip share
+// the inverse cube -> row map of a block and the ordering of two bases' streams with them
+namespace dftk_transfer {
+__host__ __device__ inline bool freq_on_axis(int g, int n) { return g >= -((n - 1) - (n - 1) / 2) && g <= (n - 1) / 2; }
+__host__ __device__ inline int freq_index(int g, int n) { return g < 0 ? g + n : g; }
+// cube index of G on an (nx, ny, nz) grid, -1 if G is not on it
+__host__ __device__ inline int64_t cube_index(int g0, int g1, int g2, int nx, int ny, int nz) {
+    if (!(freq_on_axis(g0, nx) && freq_on_axis(g1, ny) && freq_on_axis(g2, nz))) return -1;
+    return freq_index(g0, nx) + (int64_t)nx * (freq_index(g1, ny) + (int64_t)ny * freq_index(g2, nz));
+}
+int order_after(dftk_mi_basis* waiter, dftk_mi_basis* producer);
+int inverse_map_host(const dftk_mi_kblock* kb, std::vector<int32_t>* inv);
+int ensure_inverse_map(dftk_mi_kblock* kb);      // kb->d_inv, built on first use
+}
+
+// symop_kernels.hip: dftk_mi_apply_symop; wannier_kernels.hip: dftk_mi_wannier_overlaps / dftk_mi_wannier_guess_columns (the
+// entry points are the whole interface: see include/dftk_mi355x.h)
 
 // refine_kernels.hip: the per-column element-wise kernels of the refinement metric (refine.cpp)
 // Y[:, c] = f_c(kin) X[:, c] with t = kin + mean_kin[c]: mode 0 f = sqrt(t), mode 1 f = 1 / t   (X == Y allowed)

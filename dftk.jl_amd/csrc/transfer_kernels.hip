@@ -37,14 +37,7 @@ namespace dftk_transfer {
 const int TR_NT = 256;         // rows per workgroup (one thread per output row)
 const int TR_BANDS = 8;        // columns a thread writes after one partner look-up
 
-__host__ __device__ inline bool freq_on_axis(int g, int n) { return g >= -((n - 1) - (n - 1) / 2) && g <= (n - 1) / 2; }
-__host__ __device__ inline int freq_index(int g, int n) { return g < 0 ? g + n : g; }
-
-// cube index of G on an (nx, ny, nz) grid, -1 if G is not on it
-__host__ __device__ inline int64_t cube_index(int g0, int g1, int g2, int nx, int ny, int nz) {
-    if (!(freq_on_axis(g0, nx) && freq_on_axis(g1, ny) && freq_on_axis(g2, nz))) return -1;
-    return freq_index(g0, nx) + (int64_t)nx * (freq_index(g1, ny) + (int64_t)ny * freq_index(g2, nz));
-}
+// (freq_on_axis / freq_index / cube_index: common.h, shared with symop_kernels.hip and wannier_kernels.hip)
 
 __global__ __launch_bounds__(TR_NT) void k_transfer_blochwave(int64_t n_out, const int32_t* __restrict__ G3_out, int d0,
                                                               int d1, int d2, int nx_in, int ny_in, int nz_in,

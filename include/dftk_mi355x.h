@@ -504,6 +504,54 @@ int dftk_mi_transfer_blochwave(dftk_mi_kblock* kb_in, dftk_mi_kblock* kb_out, co
 int dftk_mi_transfer_density(dftk_mi_kblock* cube_kb_in, dftk_mi_kblock* cube_kb_out, int n_spin, const double* rho_in_d,
                              double* rho_out_d);
 
+/* ---- symmetry operations on orbitals and the Wannier90 interface (src/symmetry.jl:229-270, src/external/wannier_shared.jl)
+ * apply_symop (symmetry.jl:229-270) for all bands of one k-block in ONE launch:
+ *   out(G) = e^{-2 pi i (G + kshift).tau} in(S^-1 (G + kshift))     for every plane wave G of kb_out,
+ * kb_in the block of k, kb_out the block of S k reduced to [-0.5, 0.5)^3 by the integer vector kshift_h[3] = reduced - raw.
+ * invS_h: the 3x3 integer matrix S^-1, column-major (as S_h of dftk_mi_symmetrize_rho); tau_h: symop.tau.  in_d: n_G(kb_in)
+ * x n_bands, out_d: n_G(kb_out) x n_bands, both in the caller's full-sphere complex layout (a Gamma-real block included);
+ * they must not overlap.  A gather over the output rows through the input block's inverse cube -> row map (the one
+ * dftk_mi_transfer_blochwave keeps): the phase is computed once per row, every entry of the output is written exactly once,
+ * rows from n_G(kb_out) to ld_out are not touched, no atomics, results repeat bit for bit; with tau = 0 the numbers are
+ * moved, not multiplied.  Streams: as dftk_mi_transfer_blochwave.
+ * DFTK_MI_EINVAL, outputs untouched: n_bands < 0, a leading dimension below the rows of its sphere, blocks on different
+ * devices, a plane-wave sharded block, det S^-1 != +-1, or an output row whose pre-image lies outside the input cube or
+ * sphere -- the operation is then not a symmetry of this discretisation (the reference asserts); a host pass over the output
+ * rows, made once per (input block, S^-1, kshift) and remembered on the output block. */
+int dftk_mi_apply_symop(dftk_mi_kblock* kb_in, dftk_mi_kblock* kb_out, const int* invS_h /* [9] */,
+                        const int* kshift_h /* [3] */, const double* tau_h /* [3] */, int n_bands, const dftk_mi_cplx* in_d,
+                        int64_t ld_in, dftk_mi_cplx* out_d, int64_t ld_out);
+/* overlap_Mmn_k_kpb (wannier_shared.jl:220-241) of one k-point with all n_nb neighbours:
+ *   M_d[m + n_bands (j n_bands + n)] = sum_G conj(psi(G, m)) psi_nb_j(G + dG_j, n),   m, n < n_bands, j < n_nb,
+ * the sum over the plane waves G of kb whose partner G + dG_j (dG_h[3 j ..]: the file's G_shift) is a plane wave of
+ * kb_nb_h[j]; a neighbour that shares none gives a zero matrix (the identity of the reference is the caller's rule).
+ * psi_d: n_G(kb) x n_bands with leading dimension ld; psi_nb_h[j] / ld_nb_h[j]: device block and leading dimension of
+ * neighbour j (host arrays of n_nb entries, read before the call returns; a block may be its own neighbour and appear
+ * several times).  The neighbours may belong to other basis handles of the same device: this basis' stream waits for
+ * theirs and theirs for the kernels (device-side, as dftk_mi_transfer_blochwave).  The partner look-up and the product are
+ * one kernel: one launch per 16 neighbours whatever n_bands, no workspace, no host synchronisation; the summation order is
+ * fixed, results repeat bit for bit.  Sized for the band counts of a Wannierisation (n_bands of tens at most): a workgroup
+ * owns a 4 x 4 tile of one neighbour's matrix and reads both orbital blocks in full, so the blocks are read
+ * ceil(n_bands / 4) times each -- once for 4 bands, 9 times for 33; no crossover against a gathered panel and one zgemm has
+ * been measured, and hundreds of bands are not what this entry is for.  Asynchronous.  DFTK_MI_EINVAL, M_d untouched:
+ * negative counts, a short leading
+ * dimension, a null block, a sharded block or another device. */
+int dftk_mi_wannier_overlaps(dftk_mi_kblock* kb, int n_bands, const dftk_mi_cplx* psi_d, int64_t ld, int n_nb,
+                             dftk_mi_kblock* const* kb_nb_h, const int* dG_h /* [3 n_nb] */,
+                             const dftk_mi_cplx* const* psi_nb_h, const int64_t* ld_nb_h, dftk_mi_cplx* M_d);
+/* The guess orbitals of compute_amn_kpoint (wannier_shared.jl:13-22, :38-71, :278-298) at p = k + G for every plane wave of
+ * kb, n_cols columns in one launch per 32 columns.  recip_lattice_h: 3x3 column-major; kcoord_h[3]: the k-point, reduced;
+ * centers_h[3 c ..]: the centre of column c, reduced.  kind_h[c] = 0: the Gaussian exp(2 pi (-i p.c - |p_cart|^2 / 4));
+ * kind_h[c] = 1: e^{-2 pi i p.c} (-i)^l R_lm(p_cart) T_c(|p_cart|) / 4 pi with (l, m) = lm_h[2 c], lm_h[2 c + 1] (l <= 3,
+ * R_lm = |p|^l Y_lm the real solid harmonic in the reference's ylm_real convention) and T_c = R_d[chan_h[c] * ldR + row],
+ * the kind-0 dftk_mi_radial_transform of the radial function at |p_cart| of every row (n_chan rows of ldR >= n_G values):
+ * the reference's sum_r w f j_l(|p| r) is T |p|^l / 4 pi; an exact zero at p = 0 for l > 0.  normalize != 0: every column
+ * is divided by its 2-norm (wannier_shared.jl:291).  Asynchronous.  DFTK_MI_EINVAL, out_d untouched: a kind outside
+ * {0, 1}, (l, m) or a channel out of range, a short leading dimension, a sharded block. */
+int dftk_mi_wannier_guess_columns(dftk_mi_kblock* kb, const double* recip_lattice_h, const double* kcoord_h, int n_cols,
+                                  const int* kind_h, const int* lm_h, const int* chan_h, const double* centers_h, int n_chan,
+                                  const double* R_d, int64_t ldR, int normalize, dftk_mi_cplx* out_d, int64_t ld_out);
+
 /* ---- refinement metric (src/postprocess/refine.jl:20-84) -----------------------------------------------------------------
  * invert_refinement_metric for ONE k-block, all columns in one call: solves
  *     M_c x_c = P res_c,   M_c = P T_c^{1/2} P T_c^{1/2} P,   T_c = kinetic + mean_kin[c],   P = 1 - psi psi',   c = 0 .. n - 1
