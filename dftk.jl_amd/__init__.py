@@ -57,6 +57,10 @@ from .refine import (RefinementResult, refine_scfres, refine_energies, refine_fo
                      select_occupied_orbitals, check_full_occupation, compute_projected_gradient, apply_Omega, apply_K)
 from .direct_minimization import direct_minimization, backtracking, LbfgsNative  # noqa: F401,E402
 from .newton import newton, solve_OmegaPlusK_cg, TangentSpace, apply_OmegaPlusK, TangentCgNative  # noqa: F401,E402
+from .potential_mixing import (scf_potential_mixing, scf_potential_mixing_adaptive, AdaptiveDamping,  # noqa: F401,E402
+                               FixedDamping, ScfAcceptStepAll, ScfAcceptImprovingStep, scf_damping_quadratic_model,
+                               ensure_damping_within_range, propose_backtrack_damping, trial_damping,
+                               total_local_potential, hamiltonian_with_total_potential)
 from .unfold import apply_symop, unfold_bz, unfold_mapping, unfold_array  # noqa: F401,E402
 from .wannier import (GaussianWannierProjection, HydrogenicWannierProjection, default_wannier_centers,  # noqa: F401,E402
                       radial_hydrogenic, overlap_Mmn_k_kpb, compute_mmn, compute_amn_kpoint, compute_amn, compute_nnkp,

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libdftk_mi355x.so")
-SOURCES = ["api.cpp", "comm.cpp", "lobpcg.cpp", "batch.cpp", "batch_kernels.hip", "fft_kernels.hip", "gemm_kernels.hip", "dense_kernels.hip", "eig_kernels.hip", "xc_kernels.hip", "mgga_kernels.hip", "setup_kernels.hip", "gamma_kernels.hip", "cube_kernels.hip", "mix_kernels.hip", "force_kernels.hip", "stress_kernels.hip", "sternheimer.cpp", "response_kernels.hip", "exx_kernels.hip", "phonon_kernels.hip", "radial_kernels.hip", "pdos_kernels.hip", "hubbard_kernels.hip", "transfer_kernels.hip", "refine.cpp", "refine_kernels.hip", "dm_kernels.hip", "newton_kernels.hip", "symop_kernels.hip", "wannier_kernels.hip"]
+SOURCES = ["api.cpp", "comm.cpp", "lobpcg.cpp", "batch.cpp", "batch_kernels.hip", "fft_kernels.hip", "gemm_kernels.hip", "dense_kernels.hip", "eig_kernels.hip", "xc_kernels.hip", "mgga_kernels.hip", "setup_kernels.hip", "gamma_kernels.hip", "cube_kernels.hip", "mix_kernels.hip", "force_kernels.hip", "stress_kernels.hip", "sternheimer.cpp", "response_kernels.hip", "exx_kernels.hip", "phonon_kernels.hip", "radial_kernels.hip", "pdos_kernels.hip", "hubbard_kernels.hip", "transfer_kernels.hip", "refine.cpp", "refine_kernels.hip", "dm_kernels.hip", "newton_kernels.hip", "potmix_kernels.hip", "symop_kernels.hip", "wannier_kernels.hip"]
 HEADERS = ["common.h", "devbuf.h", "handover.h", "batch.h", "ew_device.h", "hgh_forms.h", "radial_forms.h"]     # every header under csrc/: part of both hashes below
 
 HASHPATH = LIBPATH + ".srchash"

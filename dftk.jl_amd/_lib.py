@@ -247,6 +247,7 @@ _SIGNATURES = {
     "dftk_mi_ax_reuse_count": (C.c_int, [C.POINTER(_i64)]),
     "dftk_mi_planes_reuse_count": (C.c_int, [C.POINTER(_i64)]),
     "dftk_mi_step_sums": (C.c_int, [C.c_void_p, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dftk_mi_diff_dots": (C.c_int, [C.c_void_p, _i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dftk_mi_fermi_bisection": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
                                           C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "dftk_mi_diag_mfma_peak": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),

@@ -180,10 +180,11 @@ class FixedBands:
 
 
 def next_density(ham, nbandsalg, eigensolver=lobpcg_hyper, psi=None, eigenvalues=None, occupation=None,
-                 tol=1e-6, generator=None, seed=0, timers=None, extra_weights=None, coarse_start=True):
+                 tol=1e-6, generator=None, seed=0, timers=None, extra_weights=None, coarse_start=True, miniter=1):
     """self_consistent_field.jl:80-129.  ``extra_weights(basis, eigenvalues, eF, psi) -> (weights, threshold) | None``: a second
     set of band weights accumulated in the density pass (``rho_extra`` of the result; the stepper passes the LDOS weights of
-    its mixing)."""
+    its mixing).  ``miniter``: the eigensolver's minimal number of iterations (:85; ``scf_potential_mixing`` passes its
+    ``diag_miniter``)."""
     basis = ham[0].basis
     n_conv, n_comp = nbandsalg.determine_n_bands(occupation, eigenvalues, psi)
     if psi is not None:
@@ -191,7 +192,7 @@ def next_density(ham, nbandsalg, eigensolver=lobpcg_hyper, psi=None, eigenvalues
     n_comp = int(basis.comm_kpts.max_scalar(n_comp))                       # mpi_max(n_bands_compute)
     t0 = time.time()
     eig = diagonalize_all_kblocks(eigensolver, ham, n_comp, psiguess=psi, n_conv_check=n_conv, tol=tol,
-                                  miniter=1, generator=generator, seed=seed, coarse_start=coarse_start)
+                                  miniter=miniter, generator=generator, seed=seed, coarse_start=coarse_start)
     t1 = time.time()
     occ, eF = compute_occupation(basis, eig["λ"], tol_n_elec=nbandsalg.occupation_threshold)
     # extra_weights (optional callback of the mixing: LdosMixing's local density of states): accumulated in the same pass

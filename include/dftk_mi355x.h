@@ -1136,6 +1136,19 @@ int dftk_mi_device_buffers_live(int64_t* count, int64_t* bytes);
  * src/scf/self_consistent_field.jl:229-236); the caller multiplies by the volume element. */
 int dftk_mi_step_sums(dftk_mi_basis* basis, int64_t n, const double* a_d, const double* b_d, const double* c_d, double* out_h);
 
+/* The cube-sized scalars of one trial step of the potential-mixing SCF (potmix_kernels.hip; slope and curvature of the
+ * quadratic model of src/scf/potential_mixing.jl:54-56, ||P^-1 dV||^2 of :14, ||rho_next - rho_in||^2 of :224), all inner
+ * products of differences of arrays that exist:
+ *   out_h[p] = sum_i (a_p[i] - b_p[i]) * (c_p[i] - d_p[i]),   p < n_pairs, 1 <= n_pairs <= 8,
+ * a_d .. d_d host tables of n_pairs device pointers to n doubles each (n: the whole array, both spin channels of a
+ * collinear one); an entry of b_d / d_d, or the whole table, may be NULL (= 0).  One launch on the basis' stream, block
+ * partials into the pinned landing zone, summed on the host in block order: one synchronisation, no atomics, no
+ * temporary, bitwise repeatable.  An operand (x - y) whose two pointers equal those of an earlier operand of the call is
+ * read once.  The caller multiplies by the volume element.
+ * DFTK_MI_EINVAL, out_h untouched: a null basis, out_h, a_d, c_d, a_d[p] or c_d[p]; n < 1; n_pairs outside [1, 8]. */
+int dftk_mi_diff_dots(dftk_mi_basis* basis, int64_t n, int n_pairs, const double* const* a_d, const double* const* b_d,
+                      const double* const* c_d, const double* const* d_d, double* out_h);
+
 /* compute_occupation's Fermi-level search (src/occupation.jl:99-132, FermiBisection; host-only, no device call): bisection of
  *   excess(eF) = sum_k kweights[k] sum_n filled * smearing((eig[k][n] - eF) / temperature) - n_electrons
  * on the bracket [lo, hi] (excess(lo) < 0 <= excess(hi)) until the midpoint equals an end point (adjacent doubles; at most
