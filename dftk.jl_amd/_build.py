@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libdftk_mi355x.so")
 SOURCES = ["api.cpp", "comm.cpp", "lobpcg.cpp", "batch.cpp", "batch_kernels.hip", "fft_kernels.hip", "gemm_kernels.hip", "dense_kernels.hip", "eig_kernels.hip", "xc_kernels.hip", "mgga_kernels.hip", "setup_kernels.hip", "gamma_kernels.hip", "cube_kernels.hip", "mix_kernels.hip", "force_kernels.hip", "stress_kernels.hip", "sternheimer.cpp", "response_kernels.hip", "exx_kernels.hip", "phonon_kernels.hip", "radial_kernels.hip", "pdos_kernels.hip", "hubbard_kernels.hip", "transfer_kernels.hip", "refine.cpp", "refine_kernels.hip", "dm_kernels.hip", "newton_kernels.hip", "potmix_kernels.hip", "symop_kernels.hip", "wannier_kernels.hip"]
-HEADERS = ["common.h", "devbuf.h", "handover.h", "batch.h", "ew_device.h", "hgh_forms.h", "radial_forms.h"]     # every header under csrc/: part of both hashes below
+HEADERS = ["common.h", "devbuf.h", "handover.h", "batch.h", "ew_device.h", "hgh_forms.h", "radial_forms.h", "packed.h"]     # every header under csrc/: part of both hashes below
 
 HASHPATH = LIBPATH + ".srchash"
 
@@ -206,6 +206,27 @@ def build_host_handover_check(force: bool = False) -> str:
     return HANDOVER_CHECK_BIN
 
 
+PACKED_CHECK_SRC = os.path.join(os.path.dirname(HERE), "tools", "host_packed_check.cpp")
+PACKED_CHECK_BIN = os.path.join(os.path.dirname(HERE), "tools", "bin", "host_packed_check")
+
+
+def build_host_packed_check(force: bool = False) -> str:
+    """tools/host_packed_check.cpp -> tools/bin/host_packed_check: the host-only check of ``packed_items`` (csrc/packed.h:
+    the table of work items of the packed-vector solvers): coverage, offsets, totals and every refusal.  Compiled like the
+    devbuf check (host part under AddressSanitizer and UBSan); it calls no HIP runtime function and runs without a GPU."""
+    src_time = max(os.path.getmtime(p) for p in (PACKED_CHECK_SRC, os.path.join(CSRC, "packed.h")))
+    if not force and os.path.exists(PACKED_CHECK_BIN) and os.path.getmtime(PACKED_CHECK_BIN) >= src_time:
+        return PACKED_CHECK_BIN
+    os.makedirs(os.path.dirname(PACKED_CHECK_BIN), exist_ok=True)
+    cmd = [shutil.which("hipcc") or "/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "hip", "--offload-arch=gfx950",
+           "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+           "-I", CSRC, PACKED_CHECK_SRC, "-o", PACKED_CHECK_BIN, "-fsanitize=address,undefined"]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    if res.returncode != 0:
+        raise RuntimeError("hipcc failed on tools/host_packed_check.cpp:\n" + res.stdout + res.stderr)
+    return PACKED_CHECK_BIN
+
+
 RADIAL_CHECK_SRC = os.path.join(os.path.dirname(HERE), "tools", "host_radial_check.cpp")
 RADIAL_CHECK_BIN = os.path.join(os.path.dirname(HERE), "tools", "bin", "host_radial_check")
 
@@ -236,3 +257,4 @@ if __name__ == "__main__":
     print(build_host_devbuf_check(force=True))
     print(build_host_handover_check(force=True))
     print(build_host_radial_check(force=True))
+    print(build_host_packed_check(force=True))

@@ -11,23 +11,16 @@
 // fft_group_size(b) bands; between them run HBM-bound streams in the form of exx_kernels.hip: 256 threads, grid-stride
 // loop, one complex fp64 number per 16-byte access, NW_UNR independent loads per operand in flight before the first use.
 //
-// The CG pieces are built the way dm_kernels.hip builds L-BFGS: a packed vector is a list of column-major blocks given as
-// host arrays of device pointers and leading dimensions, one grid walks a table of work items over all blocks, an inner
-// product leaves one partial sum per workgroup in a named slot, and the kernel that needs the scalar sums the partials
-// itself (fixed order, every workgroup for itself) -- alpha and beta never visit the host, no atomics.
-#include "common.h"
-#include "batch.h"
-#include <algorithm>
+// The CG pieces stand on packed.h (packed vectors, the table of work items, the parameter ring): an inner product leaves
+// one partial sum per workgroup in a named slot, and the kernel that needs the scalar sums the partials itself -- alpha and
+// beta never visit the host, no atomics.
+#include "packed.h"
 #include <cmath>
-#include <cstring>
-#include <vector>
 
 namespace dftk_newton {
-const int NW_NT = 256;          // threads of a workgroup
+const int NW_NT = PACKED_NT;    // threads of a workgroup
 const int NW_UNR = 4;
 const int NW_MAX_BLOCKS = 4096;
-const int NW_CH = 1024;         // rows of one CG work item (a piece of one column of one block)
-const int NW_MAXG = 1024;       // workgroups of a CG launch at most = partial sums of an inner product
 const int NW_RING = 8;          // staging buffers of the CG call parameters, used in turn
 
 // drho[i] += sum_j w[j] 2 Re(conj(psi[j][i]) dpsi[j][i]) over the nb cubes of a launch group (n apart), j ascending: one
@@ -257,9 +250,6 @@ extern "C" int dftk_mi_tangent_potential(dftk_mi_kblock* kb, int n_bands, const 
 
 // ====================================================================================================== packed-vector CG
 namespace dftk_newton {
-struct CgItem {               // rows [row0, row0 + nrows) of column col of block b
-    int b, col, row0, nrows;
-};
 struct CgBlock {              // one block of the caller's vectors for one call (device copy of the call's parameters)
     const cd* a;              // dot: a          update_xr: p          update_p: z
     int64_t lda;
@@ -272,29 +262,13 @@ struct CgBlock {              // one block of the caller's vectors for one call 
     double w;                 // weight of the block in the inner product
 };
 
-// sum over the workgroup, valid in every thread; two barriers, sh may be reused afterwards
-__device__ __forceinline__ double cg_block_sum(double v, double* sh) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-// the partial sums a dot left, summed in a fixed order by every workgroup for itself
-__device__ __forceinline__ double cg_sum_partials(const double* part, int n_part, double* sh) {
-    double v = 0.0;
-    for (int j = threadIdx.x; j < n_part; j += NW_NT) v += part[j];
-    return cg_block_sum(v, sh);
-}
-
 // part_out[workgroup] = sum over its items of w_b sum_rows Re(conj(a) b)
-__global__ __launch_bounds__(NW_NT) void k_cg_dot(const CgItem* __restrict__ items, int n_items,
+__global__ __launch_bounds__(NW_NT) void k_cg_dot(const PackedItem* __restrict__ items, int n_items,
                                                   const CgBlock* __restrict__ blk, double* __restrict__ part_out) {
     __shared__ double sh[NW_NT / 64];
     double acc = 0.0;
     for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-        const CgItem item = items[it];
+        const PackedItem item = items[it];
         const CgBlock bk = blk[item.b];
         const cd* a = bk.a + (int64_t)item.col * bk.lda + item.row0;
         const cd* c = bk.c + (int64_t)item.col * bk.ldc + item.row0;
@@ -305,20 +279,20 @@ __global__ __launch_bounds__(NW_NT) void k_cg_dot(const CgItem* __restrict__ ite
         }
         acc += bk.w * s;
     }
-    const double t = cg_block_sum(acc, sh);
+    const double t = block_sum_all<NW_NT>(acc, sh);
     if (threadIdx.x == 0) part_out[blockIdx.x] = t;
 }
 
 // alpha = <r, z> / <p, c> from the partial sums of both; x += alpha p, r -= alpha c
-__global__ __launch_bounds__(NW_NT) void k_cg_update_xr(const CgItem* __restrict__ items, int n_items,
+__global__ __launch_bounds__(NW_NT) void k_cg_update_xr(const PackedItem* __restrict__ items, int n_items,
                                                         const CgBlock* __restrict__ blk, const double* __restrict__ part_g,
                                                         const double* __restrict__ part_pc, int n_part) {
     __shared__ double sh[NW_NT / 64];
-    const double gamma = cg_sum_partials(part_g, n_part, sh);
-    const double pc = cg_sum_partials(part_pc, n_part, sh);
+    const double gamma = sum_partials<NW_NT>(part_g, n_part, sh);
+    const double pc = sum_partials<NW_NT>(part_pc, n_part, sh);
     const double alpha = gamma / pc;
     for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-        const CgItem item = items[it];
+        const PackedItem item = items[it];
         const CgBlock bk = blk[item.b];
         const cd* p = bk.a + (int64_t)item.col * bk.lda + item.row0;
         const cd* c = bk.c + (int64_t)item.col * bk.ldc + item.row0;
@@ -338,18 +312,18 @@ __global__ __launch_bounds__(NW_NT) void k_cg_update_xr(const CgItem* __restrict
 }
 
 // beta = gamma_new / gamma_old from the partial sums of both; p = z + beta p (first: p = z, p is not read)
-__global__ __launch_bounds__(NW_NT) void k_cg_update_p(const CgItem* __restrict__ items, int n_items,
+__global__ __launch_bounds__(NW_NT) void k_cg_update_p(const PackedItem* __restrict__ items, int n_items,
                                                        const CgBlock* __restrict__ blk, const double* __restrict__ part_new,
                                                        const double* __restrict__ part_old, int n_part, int first) {
     __shared__ double sh[NW_NT / 64];
     double beta = 0.0;
     if (!first) {
-        const double g_new = cg_sum_partials(part_new, n_part, sh);
-        const double g_old = cg_sum_partials(part_old, n_part, sh);
+        const double g_new = sum_partials<NW_NT>(part_new, n_part, sh);
+        const double g_old = sum_partials<NW_NT>(part_old, n_part, sh);
         beta = g_new / g_old;
     }
     for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-        const CgItem item = items[it];
+        const PackedItem item = items[it];
         const CgBlock bk = blk[item.b];
         const cd* z = bk.a + (int64_t)item.col * bk.lda + item.row0;
         cd* p = bk.x + (int64_t)item.col * bk.ldx + item.row0;
@@ -369,9 +343,9 @@ __global__ __launch_bounds__(NW_NT) void k_cg_update_p(const CgItem* __restrict_
 __global__ __launch_bounds__(NW_NT) void k_cg_read(const double* __restrict__ p0, const double* __restrict__ p1,
                                                    const double* __restrict__ p2, int n_part, double* __restrict__ out) {
     __shared__ double sh[NW_NT / 64];
-    const double a = cg_sum_partials(p0, n_part, sh);
-    const double c = cg_sum_partials(p1, n_part, sh);
-    const double d = cg_sum_partials(p2, n_part, sh);
+    const double a = sum_partials<NW_NT>(p0, n_part, sh);
+    const double c = sum_partials<NW_NT>(p1, n_part, sh);
+    const double d = sum_partials<NW_NT>(p2, n_part, sh);
     if (threadIdx.x == 0) {
         out[0] = a;
         out[1] = c;
@@ -382,80 +356,44 @@ __global__ __launch_bounds__(NW_NT) void k_cg_read(const double* __restrict__ p0
 
 struct dftk_mi_tangent_cg {
     dftk_mi_basis* b = nullptr;          // borrowed
-    int n_blocks = 0;
-    std::vector<int64_t> rows;
-    std::vector<int> cols;
+    PackedTable tab;
     std::vector<double> weight;
-    int n_items = 0, grid = 0;
-    DevTable<CgItem> items;
-    // four buffers of NW_MAXG partial sums: gamma (two, used in turn: the one a dot of slot GAMMA writes is the NEXT gamma
+    // four buffers of PACKED_MAXG partial sums: gamma (two, used in turn: the one a dot of slot GAMMA writes is the NEXT gamma
     // until update_p has used both), <p, c> and <r, r>
     DevTable<double> part;
     int cur = 0;                         // the gamma buffer that holds the current gamma
-    // the parameters of a call (block table) travel through pinned memory into a device table; NW_RING of each, used in
-    // turn, each guarded by an event recorded behind its copy
-    PinnedBuf<char> stage[NW_RING];
-    DevTable<char> params[NW_RING];
-    EventOwner ev[NW_RING];
-    bool ev_pending[NW_RING] = {false};
-    int turn = 0;
-    size_t param_bytes = 0;
+    ParamRing<NW_RING> ring;             // the parameters of a call: the block table (a _read in between frees every slot)
 
-    double* gamma(int i) const { return part + (size_t)i * NW_MAXG; }
-    double* pc() const { return part + 2 * (size_t)NW_MAXG; }
-    double* rr() const { return part + 3 * (size_t)NW_MAXG; }
+    double* gamma(int i) const { return part + (size_t)i * PACKED_MAXG; }
+    double* pc() const { return part + 2 * (size_t)PACKED_MAXG; }
+    double* rr() const { return part + 3 * (size_t)PACKED_MAXG; }
 };
 
 namespace dftk_newton {
-// the call's block table into the next staging buffer; *blk_d = its device address.  No host synchronisation unless the
-// buffer is still in flight from NW_RING calls ago (a _read in between clears all of them).
+// the call's block table into the next slot of the ring; *blk_d = its device address
 template <class Fill>
 int cg_stage(dftk_mi_tangent_cg* a, Fill fill, const CgBlock** blk_d) {
-    dftk_mi_basis* b = a->b;
-    const int t = a->turn;
-    a->turn = (a->turn + 1) % NW_RING;
-    if (a->ev_pending[t] && hipEventQuery(a->ev[t].e) != hipSuccess) {
-        g_dftk_host_syncs.fetch_add(1, std::memory_order_relaxed);
-        HIPCHK(hipEventSynchronize(a->ev[t].e));
-    }
-    a->ev_pending[t] = false;
-    CgBlock* blk = reinterpret_cast<CgBlock*>(a->stage[t].get());
-    for (int i = 0; i < a->n_blocks; ++i) {
+    char *h, *d;
+    HIPCHK(hipSetDevice(a->b->device));
+    CHK(a->ring.begin(&h, &d));
+    CgBlock* blk = reinterpret_cast<CgBlock*>(h);
+    for (int i = 0; i < a->tab.n_blocks; ++i) {
         blk[i] = CgBlock{};
         blk[i].w = a->weight[i];
         fill(i, blk[i]);
     }
-    HIPCHK(hipMemcpyAsync(a->params[t].get(), blk, a->param_bytes, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipEventRecord(a->ev[t].e, b->stream));
-    a->ev_pending[t] = true;
-    *blk_d = reinterpret_cast<const CgBlock*>(a->params[t].get());
+    CHK(a->ring.commit(a->b->stream));
+    *blk_d = reinterpret_cast<const CgBlock*>(d);
     return 0;
 }
 
-// every vector of a call: a non-null pointer table and block pointers, leading dimensions not below the rows of creation
 int cg_check(const char* who, const dftk_mi_tangent_cg* a, int n_vec, const dftk_mi_cplx* const* const* ptr,
              const int64_t* const* ld) {
     if (!a) {
         dftk_set_error("%s: null handle", who);
         return DFTK_MI_EINVAL;
     }
-    for (int v = 0; v < n_vec; ++v) {
-        if (!ptr[v] || !ld[v]) {
-            dftk_set_error("%s: null block table", who);
-            return DFTK_MI_EINVAL;
-        }
-        for (int i = 0; i < a->n_blocks; ++i)
-            if (!ptr[v][i] || ld[v][i] < a->rows[i]) {
-                dftk_set_error("%s: block %d does not match the %lld x %d block given at creation", who, i,
-                               (long long)a->rows[i], a->cols[i]);
-                return DFTK_MI_EINVAL;
-            }
-    }
-    if (batching()) {
-        dftk_set_error("%s: not available inside a batched multi-k call", who);
-        return DFTK_MI_EINVAL;
-    }
-    return 0;
+    return packed_check(who, a->tab.n_blocks, a->tab.rows.data(), a->tab.cols.data(), n_vec, ptr, ld);
 }
 inline const cd* ccd(const dftk_mi_cplx* p) { return reinterpret_cast<const cd*>(p); }
 inline cd* mcd(const dftk_mi_cplx* p) { return const_cast<cd*>(reinterpret_cast<const cd*>(p)); }
@@ -468,57 +406,29 @@ extern "C" int dftk_mi_tangent_cg_create(dftk_mi_basis* b, int n_blocks, const i
         return DFTK_MI_EINVAL;
     }
     for (int i = 0; i < n_blocks; ++i)
-        if (n_rows_h[i] < 1 || n_rows_h[i] > INT32_MAX - NW_CH || n_cols_h[i] < 1 || !std::isfinite(weight_h[i])) {
+        if (!std::isfinite(weight_h[i])) {
             dftk_set_error("tangent_cg_create: block %d is %lld x %d with weight %g", i, (long long)n_rows_h[i], n_cols_h[i],
                            weight_h[i]);
             return DFTK_MI_EINVAL;
         }
-    if (batching()) {
-        dftk_set_error("tangent_cg_create: not available inside a batched multi-k call");
-        return DFTK_MI_EINVAL;
-    }
-    HIPCHK(hipSetDevice(b->device));
     std::unique_ptr<dftk_mi_tangent_cg> a(new dftk_mi_tangent_cg());
+    std::vector<PackedItem> items;
+    CHK(a->tab.build("tangent_cg_create", b, n_blocks, n_rows_h, n_cols_h, &items));
     a->b = b;
-    a->n_blocks = n_blocks;
-    a->rows.assign(n_rows_h, n_rows_h + n_blocks);
-    a->cols.assign(n_cols_h, n_cols_h + n_blocks);
     a->weight.assign(weight_h, weight_h + n_blocks);
-    std::vector<CgItem> items;
-    for (int i = 0; i < n_blocks; ++i)
-        for (int c = 0; c < a->cols[i]; ++c)
-            for (int64_t r0 = 0; r0 < a->rows[i]; r0 += NW_CH)
-                items.push_back(CgItem{i, c, (int)r0, (int)std::min<int64_t>(NW_CH, a->rows[i] - r0)});
-    if (items.size() > (size_t)INT32_MAX) {
-        dftk_set_error("tangent_cg_create: too many work items");
-        return DFTK_MI_EINVAL;
-    }
-    a->n_items = (int)items.size();
-    a->grid = std::min(a->n_items, NW_MAXG);
-    a->param_bytes = (size_t)n_blocks * sizeof(CgBlock);
-    bool ok = a->items.alloc(items.size() * sizeof(CgItem)) == hipSuccess &&
-              a->part.alloc(4 * (size_t)NW_MAXG * sizeof(double)) == hipSuccess;
-    for (int t = 0; t < NW_RING && ok; ++t)
-        ok = a->stage[t].alloc(a->param_bytes) == hipSuccess && a->params[t].alloc(a->param_bytes) == hipSuccess &&
-             hipEventCreateWithFlags(&a->ev[t].e, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
+    if (a->tab.items.alloc(items.size() * sizeof(PackedItem)) != hipSuccess ||
+        a->part.alloc(4 * (size_t)PACKED_MAXG * sizeof(double)) != hipSuccess ||
+        !a->ring.alloc((size_t)n_blocks * sizeof(CgBlock))) {
         dftk_set_error("tangent_cg_create: cannot allocate the tables of %d blocks", n_blocks);
         return DFTK_MI_EHIP;
     }
-    HIPCHK(hipMemsetAsync(a->part.get(), 0, 4 * (size_t)NW_MAXG * sizeof(double), b->stream));
-    HIPCHK(hipMemcpyAsync(a->items.get(), items.data(), items.size() * sizeof(CgItem), hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));       // (items leaves scope with the call)
+    HIPCHK(hipMemsetAsync(a->part.get(), 0, 4 * (size_t)PACKED_MAXG * sizeof(double), b->stream));
+    CHK(a->tab.upload(b, items));
     *out = a.release();
     return 0;
 }
 
-extern "C" int dftk_mi_tangent_cg_destroy(dftk_mi_tangent_cg* a) {
-    if (!a) return 0;
-    (void)hipSetDevice(a->b->device);
-    (void)hipStreamSynchronize(a->b->stream);
-    delete a;
-    return 0;
-}
+extern "C" int dftk_mi_tangent_cg_destroy(dftk_mi_tangent_cg* a) { return packed_destroy(a); }
 
 extern "C" int dftk_mi_tangent_cg_dot(dftk_mi_tangent_cg* a, int slot, const dftk_mi_cplx* const* a_d, const int64_t* lda_h,
                                       const dftk_mi_cplx* const* b_d, const int64_t* ldb_h) {
@@ -530,14 +440,13 @@ extern "C" int dftk_mi_tangent_cg_dot(dftk_mi_tangent_cg* a, int slot, const dft
         return DFTK_MI_EINVAL;
     }
     dftk_mi_basis* b = a->b;
-    HIPCHK(hipSetDevice(b->device));
     const CgBlock* blk_d = nullptr;
     CHK(cg_stage(a, [&](int i, CgBlock& k) {
         k.a = ccd(a_d[i]), k.lda = lda_h[i], k.c = ccd(b_d[i]), k.ldc = ldb_h[i];
     }, &blk_d));
     double* part = slot == DFTK_MI_CG_GAMMA ? a->gamma(a->cur ^ 1) : slot == DFTK_MI_CG_PC ? a->pc() : a->rr();
-    hipLaunchKernelGGL(k_cg_dot, dim3(a->grid), dim3(NW_NT), 0, b->stream, (const CgItem*)a->items.get(), a->n_items, blk_d,
-                       part);
+    hipLaunchKernelGGL(k_cg_dot, dim3(a->tab.grid), dim3(NW_NT), 0, b->stream, (const PackedItem*)a->tab.items.get(),
+                       a->tab.n_items, blk_d, part);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -549,14 +458,13 @@ extern "C" int dftk_mi_tangent_cg_update_xr(dftk_mi_tangent_cg* a, const dftk_mi
     const int64_t* ld[4] = {ldp_h, ldc_h, ldx_h, ldr_h};
     CHK(cg_check("tangent_cg_update_xr", a, 4, ptr, ld));
     dftk_mi_basis* b = a->b;
-    HIPCHK(hipSetDevice(b->device));
     const CgBlock* blk_d = nullptr;
     CHK(cg_stage(a, [&](int i, CgBlock& k) {
         k.a = ccd(p_d[i]), k.lda = ldp_h[i], k.c = ccd(c_d[i]), k.ldc = ldc_h[i];
         k.x = mcd(x_d[i]), k.ldx = ldx_h[i], k.r = mcd(r_d[i]), k.ldr = ldr_h[i];
     }, &blk_d));
-    hipLaunchKernelGGL(k_cg_update_xr, dim3(a->grid), dim3(NW_NT), 0, b->stream, (const CgItem*)a->items.get(), a->n_items,
-                       blk_d, (const double*)a->gamma(a->cur), (const double*)a->pc(), a->grid);
+    hipLaunchKernelGGL(k_cg_update_xr, dim3(a->tab.grid), dim3(NW_NT), 0, b->stream, (const PackedItem*)a->tab.items.get(),
+                       a->tab.n_items, blk_d, (const double*)a->gamma(a->cur), (const double*)a->pc(), a->tab.grid);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -567,13 +475,13 @@ extern "C" int dftk_mi_tangent_cg_update_p(dftk_mi_tangent_cg* a, const dftk_mi_
     const int64_t* ld[2] = {ldz_h, ldp_h};
     CHK(cg_check("tangent_cg_update_p", a, 2, ptr, ld));
     dftk_mi_basis* b = a->b;
-    HIPCHK(hipSetDevice(b->device));
     const CgBlock* blk_d = nullptr;
     CHK(cg_stage(a, [&](int i, CgBlock& k) {
         k.a = ccd(z_d[i]), k.lda = ldz_h[i], k.x = mcd(p_d[i]), k.ldx = ldp_h[i];
     }, &blk_d));
-    hipLaunchKernelGGL(k_cg_update_p, dim3(a->grid), dim3(NW_NT), 0, b->stream, (const CgItem*)a->items.get(), a->n_items,
-                       blk_d, (const double*)a->gamma(a->cur ^ 1), (const double*)a->gamma(a->cur), a->grid, first ? 1 : 0);
+    hipLaunchKernelGGL(k_cg_update_p, dim3(a->tab.grid), dim3(NW_NT), 0, b->stream, (const PackedItem*)a->tab.items.get(),
+                       a->tab.n_items, blk_d, (const double*)a->gamma(a->cur ^ 1), (const double*)a->gamma(a->cur), a->tab.grid,
+                       first ? 1 : 0);
     HIPCHK(hipGetLastError());
     a->cur ^= 1;                                   // the gamma of the last dot is the current one from here on
     return 0;
@@ -592,10 +500,10 @@ extern "C" int dftk_mi_tangent_cg_read(dftk_mi_tangent_cg* a, double* out3_h) {
     HIPCHK(hipSetDevice(b->device));
     double* land = reinterpret_cast<double*>(b->h_fetch.get());     // the landing zone: no device -> host blit
     hipLaunchKernelGGL(k_cg_read, dim3(1), dim3(NW_NT), 0, b->stream, (const double*)a->rr(), (const double*)a->gamma(a->cur),
-                       (const double*)a->pc(), a->grid, land);
+                       (const double*)a->pc(), a->tab.grid, land);
     HIPCHK(hipGetLastError());
     CHK(host_wait(b));
-    for (int t = 0; t < NW_RING; ++t) a->ev_pending[t] = false;     // the stream is idle: every staging buffer is free
+    a->ring.all_idle();                            // the stream is idle: every staging buffer is free
     out3_h[0] = land[0], out3_h[1] = land[1], out3_h[2] = land[2];
     return 0;
 }

@@ -22,6 +22,7 @@ import torch
 
 from . import _lib
 from .densities import compute_density
+from .packed import PackedHandle, mean_kin, packed_dot, rayleigh_ritz  # noqa: F401  (packed_dot: used here and by callers)
 from .terms import energy_hamiltonian
 
 ARMIJO_C1 = 1e-4            # LineSearches.BackTracking defaults: c_1, rho_hi, rho_lo, iterations
@@ -127,59 +128,31 @@ def retract_(basis, kpt, x):
     return x
 
 
-def packed_dot(a, b):
-    """Optim's inner product of two packed vectors, sum over blocks of Re(conj(a) b), as a 0-dim device tensor"""
-    return sum((x.real * y.real).sum() + (x.imag * y.imag).sum() for x, y in zip(a, b))
-
-
-class LbfgsNative:
+class LbfgsNative(PackedHandle):
     """The L-BFGS history behind the C ABI (``dftk_mi_lbfgs_*``) for packed vectors shaped like ``blocks`` (band-major
     tensors; only their shapes are read)."""
 
     def __init__(self, basis, shapes, memory=10):
-        self.basis = basis
-        self.shapes = [(int(nb), int(ng)) for nb, ng in shapes]
-        n = len(self.shapes)
-        rows = (C.c_int64 * n)(*[ng for _, ng in self.shapes])
-        cols = (C.c_int * n)(*[nb for nb, _ in self.shapes])
-        h = C.c_void_p()
-        _lib.check(basis.lib.dftk_mi_lbfgs_create(basis.handle, n, rows, cols, int(memory), C.byref(h)))
-        self.handle = h
-
-    def _tables(self, blocks):
-        n = len(self.shapes)
-        if len(blocks) != n or any(tuple(b.shape) != s for b, s in zip(blocks, self.shapes)):
-            raise ValueError("LbfgsNative: the blocks differ from those given at creation")
-        for b in blocks:
-            if not (b.is_cuda and b.dtype == torch.complex128 and b.stride(1) == 1):
-                raise TypeError("LbfgsNative: complex128 CUDA band-major blocks required")
-        return (C.c_void_p * n)(*[b.data_ptr() for b in blocks]), (C.c_int64 * n)(*[b.stride(0) for b in blocks])
+        super().__init__(basis, shapes, "dftk_mi_lbfgs_create", int(memory))
 
     def update(self, x, g):
         """-> (<s, y>, kept)"""
-        xp, xl = self._tables(x)
-        gp, gl = self._tables(g)
         sy, kept = C.c_double(0.0), C.c_int(0)
-        self.basis.pre_call()
-        _lib.check(self.basis.lib.dftk_mi_lbfgs_update(self.handle, xp, xl, gp, gl, C.byref(sy), C.byref(kept)))
-        self.basis.post_call(0)
+        self._call("dftk_mi_lbfgs_update", *self._tables(x, g), C.byref(sy), C.byref(kept))
         return float(sy.value), bool(kept.value)
 
     def direction(self, g, scale, kpoints=None, mean_kin=None):
         """d = -H g as new blocks; ``kpoints`` and ``mean_kin`` (one float64 array per block) switch the preconditioner on"""
         n = len(self.shapes)
         d = [torch.empty_like(b) for b in g]
-        gp, gl = self._tables(g)
-        dp, dl = self._tables(d)
+        gp, gl, dp, dl = self._tables(g, d)
         sc = (C.c_double * n)(*[float(s) for s in scale])
         kbs = mks = None
         if kpoints is not None:
             keep = [np.ascontiguousarray(m, dtype=np.float64) for m in mean_kin]
             kbs = (C.c_void_p * n)(*[k.handle.value for k in kpoints])
             mks = (C.c_void_p * n)(*[m.ctypes.data for m in keep])
-        self.basis.pre_call()
-        _lib.check(self.basis.lib.dftk_mi_lbfgs_direction(self.handle, gp, gl, kbs, mks, sc, dp, dl))
-        self.basis.post_call(0)
+        self._call("dftk_mi_lbfgs_direction", gp, gl, kbs, mks, sc, dp, dl)
         return d
 
     def reset(self):
@@ -188,17 +161,6 @@ class LbfgsNative:
     @property
     def history(self):
         return int(self.basis.lib.dftk_mi_lbfgs_history(self.handle))
-
-    def close(self):
-        if self.handle is not None:
-            self.basis.lib.dftk_mi_lbfgs_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def energy_gradient(basis, psi, occupation):
@@ -213,36 +175,6 @@ def energy_gradient(basis, psi, occupation):
         g *= 2.0 * filled * float(w)
         G.append(project_tangent_(basis, kpt, g, p))
     return dict(E=energies.total, G=G, rho=rho, energies=energies, ham=ham, psi=psi)
-
-
-def _mean_kin(basis, psi):
-    out = []
-    for kpt, p in zip(basis.kpoints, psi):
-        mk = np.zeros(p.shape[0])
-        basis.pre_call()
-        _lib.check(basis.lib.dftk_mi_tpa_precondprep(kpt.handle, p.shape[0], p.data_ptr(), p.stride(0), mk.ctypes.data))
-        out.append(mk)
-    return out
-
-
-def _rayleigh_ritz(basis, ham, psi):
-    """the final Rayleigh-Ritz of the reference (:181-188): eigenvalues of psi_k' H_k psi_k and psi_k times the vectors"""
-    from .refine import _overlaps, _zgemm
-    eigenvalues, out = [], []
-    for kpt, Hk, p in zip(basis.kpoints, ham, psi):
-        nb = p.shape[0]
-        M = _overlaps(basis, kpt, p, Hk @ p)
-        M = (0.5 * (M + M.conj().T)).contiguous()
-        V = torch.empty_like(M)
-        lam = np.zeros(nb)
-        basis.pre_call()
-        _lib.check(basis.lib.dftk_mi_heev(basis.lane_handles[kpt.lane], nb, M.data_ptr(), nb, lam.ctypes.data, V.data_ptr(), nb))
-        basis.post_call(kpt.lane)
-        q = torch.empty_like(p)
-        _zgemm(basis, kpt, b"N", kpt.n_G, nb, nb, 1.0, p, p.stride(0), V, nb, 0.0, q, q.stride(0))
-        eigenvalues.append(lam)
-        out.append(q)
-    return eigenvalues, out
 
 
 # ------------------------------------------------------------------------------------------ driver
@@ -285,7 +217,7 @@ def direct_minimization(basis, psi=None, tol=1e-6, is_converged=None, maxiter=10
             info = None
 
             def search_direction():
-                mk = _mean_kin(basis, cur["psi"])
+                mk = mean_kin(basis, cur["psi"])
                 d = lb.direction(cur["G"], basis.kweights, basis.kpoints, mk)
                 for kpt, dk, p in zip(basis.kpoints, d, cur["psi"]):
                     project_tangent_(basis, kpt, dk, p)
@@ -338,7 +270,7 @@ def direct_minimization(basis, psi=None, tol=1e-6, is_converged=None, maxiter=10
                 kept_log.append(kept)
                 n_iter += 1
 
-            eigenvalues, psi_rr = _rayleigh_ritz(basis, cur["ham"], cur["psi"])
+            eigenvalues, psi_rr = rayleigh_ritz(basis, cur["ham"], cur["psi"])
             basis.sync()
         finally:
             lb.close()

@@ -31,8 +31,8 @@ import torch
 from . import _lib
 from . import refine as _refine
 from .densities import compute_density
-from .direct_minimization import _mean_kin, _rayleigh_ritz
 from .direct_minimization import check_supported as _dm_check_supported
+from .packed import PackedHandle, mean_kin, rayleigh_ritz, sub_product
 from .response import _check_block, apply_kernel, compute_delta_rho, multiply_psi_by_potential
 from .symmetry import symmetrize_rho
 from .terms import energy_hamiltonian
@@ -80,7 +80,7 @@ class TangentSpace:
         self.rho = compute_density(basis, self.psi, self.occupation) if rho is None else rho
         self.ham = energy_hamiltonian(basis, self.psi, self.occupation, rho=self.rho)[1] if ham is None else ham
         self.Lambda = _refine.rayleigh_coefficients(self.ham, self.psi)
-        self.mean_kin = _mean_kin(basis, self.psi)
+        self.mean_kin = mean_kin(basis, self.psi)
         self.n_apply = 0
         nx, ny, nz = basis.fft_size
         need = sum(p.shape[0] for p in self.psi) * nx * ny * nz * 16
@@ -154,7 +154,7 @@ def apply_OmegaPlusK(ts, dpsi):
     out = []
     for kpt, Hk, dk, L in zip(basis.kpoints, ts.ham, d, ts.Lambda):
         Od = Hk @ dk
-        out.append(_refine._sub_product(basis, kpt, Od, dk, L))
+        out.append(sub_product(basis, kpt, Od, dk, L))
     if ts.psi_r is not None:
         dV = dV.to(torch.float64).contiguous()
         basis.pre_call()
@@ -173,65 +173,28 @@ def apply_OmegaPlusK(ts, dpsi):
 
 
 # ------------------------------------------------------------------------------------------ packed-vector CG
-class TangentCgNative:
+class TangentCgNative(PackedHandle):
     """The scalars of ``cg!`` behind the C ABI (``dftk_mi_tangent_cg_*``) for packed vectors shaped like ``shapes``
     (band-major ``(n_bands, n_G)``) with one weight per block."""
 
     def __init__(self, basis, shapes, weights):
-        self.basis = basis
-        self.shapes = [(int(nb), int(ng)) for nb, ng in shapes]
-        n = len(self.shapes)
-        rows = (C.c_int64 * n)(*[ng for _, ng in self.shapes])
-        cols = (C.c_int * n)(*[nb for nb, _ in self.shapes])
-        w = (C.c_double * n)(*[float(x) for x in weights])
-        h = C.c_void_p()
-        _lib.check(basis.lib.dftk_mi_tangent_cg_create(basis.handle, n, rows, cols, w, C.byref(h)))
-        self.handle = h
-
-    def _tables(self, blocks):
-        n = len(self.shapes)
-        if len(blocks) != n or any(tuple(b.shape) != s for b, s in zip(blocks, self.shapes)):
-            raise ValueError("TangentCgNative: the blocks differ from those given at creation")
-        for b in blocks:
-            if not (b.is_cuda and b.dtype == torch.complex128 and b.stride(1) == 1):
-                raise TypeError("TangentCgNative: complex128 CUDA band-major blocks required")
-        return (C.c_void_p * n)(*[b.data_ptr() for b in blocks]), (C.c_int64 * n)(*[b.stride(0) for b in blocks])
+        w = (C.c_double * len(shapes))(*[float(x) for x in weights])
+        super().__init__(basis, shapes, "dftk_mi_tangent_cg_create", w)
 
     def dot(self, slot, a, b):
-        ap, al = self._tables(a)
-        bp, bl = self._tables(b)
-        self.basis.pre_call()
-        _lib.check(self.basis.lib.dftk_mi_tangent_cg_dot(self.handle, int(slot), ap, al, bp, bl))
+        self._call("dftk_mi_tangent_cg_dot", int(slot), *self._tables(a, b), post=False)
 
     def update_xr(self, p, c, x, r):
-        tabs = [t for v in (p, c, x, r) for t in self._tables(v)]
-        self.basis.pre_call()
-        _lib.check(self.basis.lib.dftk_mi_tangent_cg_update_xr(self.handle, *tabs))
-        self.basis.post_call(0)
+        self._call("dftk_mi_tangent_cg_update_xr", *self._tables(p, c, x, r))
 
     def update_p(self, z, p, first=False):
-        zp, zl = self._tables(z)
-        pp, pl = self._tables(p)
-        self.basis.pre_call()
-        _lib.check(self.basis.lib.dftk_mi_tangent_cg_update_p(self.handle, zp, zl, pp, pl, 1 if first else 0))
-        self.basis.post_call(0)
+        self._call("dftk_mi_tangent_cg_update_p", *self._tables(z, p), 1 if first else 0)
 
     def read(self):
         """-> (<r, r>, gamma, <p, c>): the one host synchronisation of an iteration"""
         out = (C.c_double * 3)()
         _lib.check(self.basis.lib.dftk_mi_tangent_cg_read(self.handle, out))
         return float(out[0]), float(out[1]), float(out[2])
-
-    def close(self):
-        if self.handle is not None:
-            self.basis.lib.dftk_mi_tangent_cg_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def solve_OmegaPlusK_cg(basis, psi, dHext_psi, occupation, tol=1e-10, maxiter=100, miniter=1, callback=None,
@@ -365,7 +328,7 @@ def newton(basis, psi0, tol=1e-6, tol_cg=None, maxiter=20, callback=None, is_con
             converged = bool(is_converged(info))
             rho_in = rho
 
-        eigenvalues, psi_rr = _rayleigh_ritz(basis, ham, psi)
+        eigenvalues, psi_rr = rayleigh_ritz(basis, ham, psi)
         basis.sync()
 
     result = dict(basis=basis, ham=ham, energies=energies, converged=converged, rho=rho_in, psi=psi_rr,

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from .densities import compute_density
+from .packed import overlaps, sub_product
 from .response import (EPS, _check_block, apply_kernel, compute_delta_rho, multiply_psi_by_potential, occupied_empty_masks,
                        solve_OmegaPlusK_split)
 from .terms import _GGA_BITS, Energies, energy_hamiltonian, total_density
@@ -89,31 +90,9 @@ def _check_contains(basis, basis_ref):
 
 
 # ------------------------------------------------------------------------------------------ tangent space
-def _zgemm(basis, kpt, trans, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc):
-    basis.pre_call()
-    _lib.check(basis.lib.dftk_mi_zgemm(basis.lane_handles[kpt.lane], trans, m, n, k, _lib.cplx(alpha), A.data_ptr(), lda,
-                                       B.data_ptr(), ldb, _lib.cplx(beta), Cm.data_ptr(), ldc))
-    basis.post_call(kpt.lane)
-
-
-def _overlaps(basis, kpt, A, B):
-    """A' B for band-major blocks: an (n_B, n_A) tensor holding the column-major n_A x n_B matrix"""
-    S = torch.empty((B.shape[0], A.shape[0]), dtype=torch.complex128, device=A.device)
-    if A.shape[0] and B.shape[0]:
-        _zgemm(basis, kpt, b"C", A.shape[0], B.shape[0], kpt.n_G, 1.0, A, A.stride(0), B, B.stride(0), 0.0, S, A.shape[0])
-    return S
-
-
-def _sub_product(basis, kpt, Y, A, S):
-    """Y -= A S in place (A: (n_A, n_G) band-major, S as ``_overlaps`` returns it)"""
-    if A.shape[0] and Y.shape[0]:
-        _zgemm(basis, kpt, b"N", kpt.n_G, Y.shape[0], A.shape[0], -1.0, A, A.stride(0), S, A.shape[0], 1.0, Y, Y.stride(0))
-    return Y
-
-
 def proj_tangent_kpt_(basis, kpt, dpsik, psik):
     """``proj_tangent_kpt!`` (newton.jl:57-60): dpsik -= psik (psik' dpsik), two library zgemm calls."""
-    return _sub_product(basis, kpt, dpsik, psik, _overlaps(basis, kpt, psik, dpsik))
+    return sub_product(basis, kpt, dpsik, psik, overlaps(basis, kpt, psik, dpsik))
 
 
 def proj_tangent(basis, dpsi, psi):
@@ -139,7 +118,7 @@ def apply_Omega(dpsi, psi, ham, Lambda):
     out = []
     for kpt, Hk, d, p, L in zip(basis.kpoints, ham, proj_tangent(basis, dpsi, psi), psi, Lambda):
         Od = Hk @ d
-        _sub_product(basis, kpt, Od, d, L)
+        sub_product(basis, kpt, Od, d, L)
         out.append(proj_tangent_kpt_(basis, kpt, Od, p))
     return out
 
@@ -157,7 +136,7 @@ def apply_K(basis, dpsi, psi, rho, occupation):
 def rayleigh_coefficients(ham, psi):
     """Lambda_k = psi_k' H_k psi_k (refine.jl:147-150)"""
     basis = ham[0].basis
-    return [_overlaps(basis, kpt, p, Hk @ p.contiguous()) for kpt, Hk, p in zip(basis.kpoints, ham, psi)]
+    return [overlaps(basis, kpt, p, Hk @ p.contiguous()) for kpt, Hk, p in zip(basis.kpoints, ham, psi)]
 
 
 # ------------------------------------------------------------------------------------------ metric

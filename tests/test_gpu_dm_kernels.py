@@ -351,6 +351,88 @@ def test_launches_and_synchronisations(lib, bs):
     assert launches[1] == launches[3] == 2 * 3 + 1
 
 
+def test_more_items_than_workgroups(lib, bs):
+    """Blocks of 1025 x 400 and 2049 x 90 (NaN-padded): 800 + 270 = 1070 work items behind the 1024 workgroups of a launch, so
+    46 workgroups walk two items (``it += gridDim.x``) and the partial buffers are full (four partials per thread when the
+    next launch sums them).  Memory 2, three updates (two pairs) and a direction with the preconditioner on, against the
+    longdouble twin under the bounds of ``run_case``: the two-item walk adds <= 4 sequential additions per thread to an inner
+    product, which the 64 in front of both bounds covers (4 + 4 per thread, a wave tree of 6, the wave sums 2, then the
+    partials: under 32 roundings on the device)."""
+    shapes, memory, scale = [(1025, 400), (2049, 90)], 2, [0.25, 1.5]
+    assert sum(c * -(-r // 1024) for r, c in shapes) == 1070
+    rng = np.random.default_rng(7)
+    pairs = [kblock(lib, bs, r) for r, _ in shapes]
+    kbs, kin = [p[0] for p in pairs], [p[1] for p in pairs]
+    mks = [0.3 + 2.0 * rng.random(c) for _, c in shapes]
+    acc = Acc(lib, bs, shapes, memory)
+    ref, f64 = twin.LbfgsTwin(memory), twin.LbfgsTwin(memory, real=np.float64)
+    try:
+        for n_upd, (x, g) in enumerate(points(rng, shapes, 3), start=1):
+            xd = [padded(a, 3 + b) for b, a in enumerate(x)]
+            gd = [padded(a, 5 + b) for b, a in enumerate(g)]
+            torch.cuda.synchronize()
+            sy, kept = acc.update(xd, gd)
+            sy_ref, kept_ref = ref.update(x, g)
+            sy_64, _ = f64.update(x, g)
+            assert kept == int(kept_ref) and acc.history == len(ref.pairs) == n_upd - 1
+            if n_upd > 1:
+                s, y, _ = ref.pairs[-1]
+                floor = 64 * EPS * float(sum(np.abs(a.real * b.real + a.imag * b.imag).sum() for a, b in zip(s, y)))
+                bound = max(64 * abs(sy_64 - sy_ref), floor)
+                print(f"\nlbfgs 1070 items: <s, y> err / bound {abs(sy - sy_ref) / bound:.3g}", end="")
+                assert abs(sy - sy_ref) <= bound, (n_upd, sy, sy_ref, bound)
+        q = [crandn(rng, s) for s in shapes]
+        qd = [padded(a, 2 + b) for b, a in enumerate(q)]
+        dd = [padded(np.zeros(s, dtype=complex), 4 + b) for b, s in enumerate(shapes)]
+        torch.cuda.synchronize()
+        check(acc.direction(qd, scale, dd, kbs, mks))
+        bs.sync()
+        got = [unpad(t, s[0]) for t, s in zip(dd, shapes)]
+        want = ref.direction(q, scale, kin, mks)
+        w64 = f64.direction(q, scale, kin, mks)
+        err = max(float(np.abs(a - b).max()) for a, b in zip(got, want))
+        e64 = max(float(np.abs(a.astype(twin.CLD) - b).max()) for a, b in zip(w64, want))
+        bound = max(64 * e64, (2 * memory + 2) * EPS * max(ref.peak_q / min(scale), ref.peak_r))
+        print(f"\nlbfgs 1070 items: direction err / bound {err / bound:.3g}")
+        assert err <= bound, (err, bound)
+    finally:
+        acc.close()
+
+
+def test_ring_wraps_with_copies_still_queued(lib, bs):
+    """five ``direction`` calls in a row, five different g and mean kinetic energies, nothing waited for in between: the two
+    parameter buffers are each reused while earlier copies may still be queued.  Every d equals, bit for bit, the d of the
+    same call made alone (the stream idle before and after)."""
+    shapes, scale = [(1025, 3), (513, 5)], [0.25, 1.5]
+    rng = np.random.default_rng(8)
+    kbs = [kblock(lib, bs, r)[0] for r, _ in shapes]
+    acc = Acc(lib, bs, shapes, 2)
+    try:
+        for x, g in points(rng, shapes, 3):
+            acc.update([padded(a, 1) for a in x], [padded(a, 2) for a in g])
+        assert acc.history == 2
+        calls = [([padded(crandn(rng, s), 1 + b) for b, s in enumerate(shapes)], [0.3 + 2.0 * rng.random(c) for _, c in shapes])
+                 for _ in range(5)]
+        fresh = lambda: [padded(np.zeros(s, dtype=complex), 2 + b) for b, s in enumerate(shapes)]     # noqa: E731
+        row = [fresh() for _ in calls]
+        torch.cuda.synchronize()
+        bs.sync()
+        for (q, mk), d in zip(calls, row):
+            check(acc.direction(q, scale, d, kbs, mk))
+        bs.sync()
+        for (q, mk), d in zip(calls, row):
+            alone = fresh()
+            torch.cuda.synchronize()
+            check(acc.direction(q, scale, alone, kbs, mk))
+            bs.sync()
+            for a, b, s in zip(d, alone, shapes):
+                u, v = unpad(a, s[0]), unpad(b, s[0])
+                assert np.isfinite(u).all() and np.array_equal(u.view(np.float64).view(np.int64), v.view(np.float64).view(np.int64))
+        assert len({unpad(d[0], shapes[0][0]).tobytes() for d in row}) == 5       # the five calls are different calls
+    finally:
+        acc.close()
+
+
 # ------------------------------------------------------------------------------------------ the tangent projection
 @pytest.mark.parametrize("n,m", [(1, 1), (65, 3), (1025, 4), (4097, 33)])
 def test_stiefel_project_tangent(lib, bs, n, m):

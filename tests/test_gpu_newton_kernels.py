@@ -341,13 +341,13 @@ def vdiff(a, b):
     return max(float(np.abs(np.asarray(x).astype(CLD) - np.asarray(y).astype(CLD)).max()) for x, y in zip(a, b))
 
 
-def run_cg_case(lib, bs, rows, cols, n_blocks):
-    shapes = block_shapes(rows, cols, n_blocks)
+def run_cg_case(lib, bs, rows, cols, n_blocks, shapes=None, n_steps=3):
+    shapes = shapes or block_shapes(rows, cols, n_blocks)
     w = [0.25, 0.5, 1.5][:n_blocks]
     rng = np.random.default_rng(1000 * rows + 10 * cols + n_blocks)
     rnd = lambda: [crandn(rng, r, c) for r, c in shapes]                               # noqa: E731
     host = dict(x=rnd(), r=rnd(), z0=rnd())
-    steps = [dict(c=rnd(), z=rnd()) for _ in range(3)]
+    steps = [dict(c=rnd(), z=rnd()) for _ in range(n_steps)]
     worst = {}
 
     def note(key, err, bound):
@@ -463,6 +463,53 @@ def test_cg_pieces_against_the_longdouble_twin(lib, bs, rows, cols):
         for k, v in run_cg_case(lib, bs, rows, cols, n_blocks).items():
             worst[k] = max(worst.get(k, 0.0), v)
     print(f"\ntangent CG {rows} x {cols}, 1-3 blocks: error / bound " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+
+
+def test_cg_pieces_with_more_items_than_workgroups(lib, bs):
+    """Blocks of 1025 x 400 and 2049 x 90 (NaN-padded): 800 + 270 = 1070 work items behind the 1024 workgroups of a launch, so
+    46 workgroups walk two items (``it += gridDim.x``) and every partial buffer is full: ``sum_partials`` adds four partials
+    per thread.  ``dot`` into all three slots, ``update_xr``, ``update_p`` and ``read`` for one iteration against the
+    longdouble twin, under the bounds of ``run_cg_case``.  Their operation count at this shape: a term of an inner product
+    passes its product and the sum of the two products (2 roundings), <= 4 sequential additions per thread and item, the
+    weight, <= 2 additions over the items of the workgroup, the wave tree and the four wave sums (6 + 2), then <= 4
+    sequential additions over the 1024 partials and the same trees (4 + 6 + 2): 29 roundings, each at most eps times the sum
+    of the absolute terms -- within the 64 eps sum |terms| asserted there."""
+    shapes = [(1025, 400), (2049, 90)]
+    assert sum(c * -(-r // 1024) for r, c in shapes) == 1070
+    worst = run_cg_case(lib, bs, 1025, 400, 2, shapes=shapes, n_steps=1)
+    print("\ntangent CG, 1070 items on 1024 workgroups: error / bound " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+
+
+def test_cg_ring_wraps_with_copies_still_queued(lib, bs):
+    """2 x 8 + 1 = 17 ``dot`` calls into slot RR with 17 different operand pairs and no ``read`` between them: the ring of
+    eight parameter buffers wraps twice while copies may still be queued.  17 launches; the only host synchronisations are
+    waits the ring itself counted, and the first eight calls find their buffer free: at most 17 - 8.  The value read
+    afterwards equals, bit for bit, the one of the 17th dot issued alone on a fresh handle: no call saw the block table of
+    another."""
+    shapes, w = [(1025, 3), (513, 5)], [0.25, 1.5]
+    rng = np.random.default_rng(17)
+    vec = lambda pad: [padded(crandn(rng, r, c), pad + b) for b, (r, c) in enumerate(shapes)]     # noqa: E731
+    operands = [(vec(1), vec(2)) for _ in range(17)]
+    cg, fresh = Cg(lib, bs, shapes, w), Cg(lib, bs, shapes, w)
+    try:
+        torch.cuda.synchronize()
+        bs.sync()
+        l0, s0 = counts(lib)
+        for a, b in operands:
+            check(cg.dot(twin.RR, a, b))
+        l1, s1 = counts(lib)
+        assert l1 - l0 == 17 and 0 <= s1 - s0 <= 17 - 8, (l1 - l0, s1 - s0)
+        got = cg.read()
+        check(fresh.dot(twin.RR, *operands[-1]))
+        want = fresh.read()
+        assert np.float64(got[0]).view(np.int64) == np.float64(want[0]).view(np.int64), (got, want)
+        assert got[1:] == [0.0, 0.0] and np.isfinite(got[0]) and got[0] != 0.0
+        ref = twin.CgScalars(w).dot(twin.RR, *[[unpad(t, s[0]) for t, s in zip(v, shapes)] for v in operands[-1]])
+        bound = 64 * EPS * abs_terms(*[[unpad(t, s[0]) for t, s in zip(v, shapes)] for v in operands[-1]], w)
+        assert abs(got[0] - float(ref)) <= bound       # ... and it is the 17th inner product (the bound of run_cg_case)
+    finally:
+        cg.close()
+        fresh.close()
 
 
 def test_cg_refusals_leave_everything_untouched(lib, bs):

@@ -1427,6 +1427,21 @@ def test_lobpcg_handover_transition_table_on_the_host():
     assert "Sanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-3000:]
 
 
+def test_packed_item_table_on_the_host():
+    """``packed_items`` of csrc/packed.h -- the table of work items under the L-BFGS and CG handles -- through
+    tools/host_packed_check.cpp (no GPU; host code under AddressSanitizer and UBSan): for rows 1, 1023, 1024, 1025, 4097,
+    1, 3, 33 columns and 1 to 3 unequal blocks every (block, column, row) is covered by exactly one item, ``off`` is the
+    unpadded packed position, ``total``, ``total_cols`` and ``col0`` agree with the sizes; rows < 1, cols < 1 and rows above
+    INT32_MAX - 1024 are refused, in the first block or a later one."""
+    import subprocess
+    from dftk_jl_amd import _build
+    exe = _build.build_host_packed_check()
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, (res.returncode, res.stdout[-3000:], res.stderr[-3000:])
+    assert "host_packed_check OK" in res.stdout and "FAILED" not in res.stdout
+    assert "Sanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-3000:]
+
+
 def test_memory_statistics_and_plan_for_the_literal_4096_electron_cell():
     """``estimate_memory_usage`` (src/memory_usage.jl:35-87: psi_k, P_k, rho bytes and the 1 P + 2 psi + 6 psi_k + 12 rho
     peak) and the per-GPU plan of the plane-wave-sharded Gamma block: the headline 1000-electron cell fits one
